@@ -12,7 +12,7 @@ the CPU oracle and the line carries the PCM error (`parity`: the metric's second
 shards (weak scaling, no data-path collective); the only collective is the RCCL broadcast of the
 constant-table blob at start-up (plus the timing reduction and the checksum all-gather).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR]
 
 With --gpus N > 1 and no launcher environment (WORLD_SIZE unset) bench.py starts the N ranks itself
 (child processes, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, before anything touches a GPU) and
@@ -22,13 +22,18 @@ relays rank 0's line; under torch.distributed.run it is one of the ranks.  `--wo
 Prints ONE COMPACT JSON line on rank 0 (the contract keys, `roofline`, `parity`, `cpu_baseline`, and per other config
 {value, ms_per_step, kernel, kernel_ms, frac}: at most 4 KB -- contract_line()) and writes everything else to the
 sidecar `bench_detail.json` next to this script (and to gpurun_out/ when that directory exists): `other_configs` in full
-(the other GPU configs of BASELINE.json, 10 steps each, with their SQ issue models), `cpu_baselines` (the reference's
+(the other GPU configs of BASELINE.json, regions of --min-time-ms each, with their SQ issue models), `cpu_baselines` (the reference's
 scalar and SIMD builds, full path and its own bench_synth / bench_unvoiced recipes, one core and all cores), `host_path`
 (what a C host sees from host memory to host memory), `infinity_cache_assisted` (the same workload in the library's
 default alternating stream order; the headline itself is timed in a FIXED order, i.e. against HBM), `valu`, `copy_floor`.
-Nothing but the compact line goes to stdout.  The timed region is at least --steps steps and at
-least --min-time-ms (500 ms) of wall time: `steps_effective`; the warm-up ends with ~30 ms of untimed steps directly in front of it
-(`settle_steps`: past the load-onset transient of the power controller, profiles/r05/launch_series.txt).
+Nothing but the compact line goes to stdout.  The timed region is exactly --steps steps; without --steps it is sized to
+--min-time-ms (500 ms) of wall time.  `steps_effective` is the number of steps that were timed.  The warm-up ends with a fixed
+number of untimed steps directly in front of the timed region (`settle_steps`: about 30 ms at the headline rate, past the load-onset
+transient of the power controller, profiles/r05/launch_series.txt).
+
+--dump-outputs DIR (with --steps) writes what a caller of the timed path holds after the last timed step -- PCM, results, records,
+state, RNG state -- as DIR/<name>.npy (dump_outputs()).  Frames, seeds and the number of launches in front of that step depend on
+the arguments only, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import hashlib
@@ -68,6 +73,60 @@ WORKLOADS = {
     "ambe_soft_coded": (1, 65536, 1, "65,536 AMBE+2 3600x2450 streams x T=1, soft-decision frames (noisy observations of ENCODED voice frames)"),
 }
 CODEC_NAME = {0: "IMBE 7200x4400", 1: "AMBE+2 3600x2450", 2: "IMBE 7100x4400", 3: "AMBE 3600x2400"}
+
+# Untimed steps directly in front of every timed region: 150 steps of the headline workload (~30 ms), the same number of FRAMES for
+# every other shape.  A count, not a time, so that the state the last timed step starts from is the same from run to run.
+SETTLE_FRAMES = 150 * 65536
+SETTLE_STEPS_MAX = 1000   # small --streams batches are launch-bound: 1,000 launches are ~10 ms there
+MIN_STEPS = 10            # of a timed region that is sized by --min-time-ms
+# --dump-outputs: 65,536 frames of PCM as float32 are 42 MB, 512 streams of state as float64 8 MB: under 64 MB with everything else
+DUMP_FRAMES = 65536
+DUMP_STREAMS = 512
+
+
+def dump_sample(n, k):
+    """--dump-outputs: the rows kept of an output with n rows -- all of them, or k of them drawn once from a fixed seed (ascending)"""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.RandomState(0xD0).permutation(n)[:k])
+
+
+def fields_as_float64(a):
+    """A structured array [n] (PARMS / RNG layout) as float64 [n, values]: every field converted by its own type, in the struct's
+    order.  No field is wider than 48 significant bits, so the conversion is exact."""
+    return np.concatenate([a[f].reshape(a.shape[0], -1).astype(np.float64) for f in a.dtype.names], axis=1)
+
+
+def dump_outputs(dirname, dec, out, S, T, records=True):
+    """--dump-outputs: what a caller of the timed path holds once the last timed step has completed, as <dirname>/<name>.npy.
+      pcm16   [frames, 160] float32   int16 PCM of the step
+      results [frames, 5]   float32   mbe_process_result of the step
+      records [frames, 4]   float64   the parameter records the call returns (imbe_d / ambe_d words)
+      state   [streams, 3, 651] float64   {cur, prev, prev_enhanced} as the step left them, field by field
+      rng     [streams, 5]  float64   the per-stream RNG state as the step left it
+    frames / streams: all of them up to DUMP_FRAMES / DUMP_STREAMS, a fixed seeded sample (dump_sample) of a larger batch."""
+    import torch
+
+    from mbelib_neo_amd.layout import PARMS_DTYPE, RNG_DTYPE
+
+    torch.cuda.synchronize()
+    os.makedirs(dirname, exist_ok=True)
+    dev = out["pcm16"].device
+    fr = torch.from_numpy(dump_sample(S * T, DUMP_FRAMES)).to(dev)
+    st = torch.from_numpy(dump_sample(S, DUMP_STREAMS)).to(dev)
+    arrays = {
+        "pcm16": out["pcm16"][fr].cpu().numpy().astype(np.float32),
+        "results": out["results"][fr].cpu().numpy().astype(np.float32),
+    }
+    if records:
+        arrays["records"] = out["records"][fr].cpu().numpy().view(np.uint32).astype(np.float64)
+    dec.materialize()
+    state = dec.state.view(S, 3 * PARMS_DTYPE.itemsize)[st].cpu().numpy().view(PARMS_DTYPE).reshape(-1)
+    arrays["state"] = fields_as_float64(state).reshape(len(st), 3, -1)
+    arrays["rng"] = fields_as_float64(dec.rng.view(S, RNG_DTYPE.itemsize)[st].cpu().numpy().view(RNG_DTYPE).reshape(-1))
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 10**6
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def make_frames(name, codec, S, T, rank):
@@ -440,7 +499,7 @@ def parity_vs_oracle(name, codec, S, T, frames, seeds, launches, dec, out, step,
 
 
 def run_workload(name, S, T, steps, warmup, rank, first_stream, local_rank, blob, world, dist, args, use_dist=False, coll_device=None,
-                 alternate=False, min_time_s=None, serial=None, parity=False):
+                 alternate=False, min_time_s=None, serial=None, parity=False, dump_dir=None):
     """Returns the measurements of one workload: wall time of the timed steps (max over ranks), HIP-event time of the
     dominant kernel per step (mean, median, spread), frame mix.  The launches of a step are what mbx_process_batch issues;
     they are issued one by one here only so that the dominant kernel can be bracketed by events on the launch stream.
@@ -450,8 +509,9 @@ def run_workload(name, S, T, steps, warmup, rank, first_stream, local_rank, blob
     in between sees, and the timing the HBM roofline fraction is quoted on.  alternate = True is the library's default
     order for back-to-back launches (reported separately as `infinity_cache_assisted`).
 
-    The timed region is at least `steps` steps and at least `min_time_s` of wall time (steps_effective, the same on
-    every rank): a 20-step region of a 0.28 ms step is 5.6 ms, too short to resolve effects of a few per cent."""
+    The timed region is `steps` steps; steps = None: at least `min_time_s` of wall time and MIN_STEPS steps (steps_effective, the
+    same on every rank) -- a 20-step region of a 0.28 ms step is 5.6 ms, too short to resolve effects of a few per cent.
+    dump_dir: dump_outputs() after the last timed step."""
     import torch
 
     from mbelib_neo_amd import _native, decoder
@@ -583,14 +643,14 @@ def run_workload(name, S, T, steps, warmup, rank, first_stream, local_rank, blob
         L.mbx_debug_set_ablation(args.ablate)  # development build only (tools/); never in a reported run
     min_time_s = args.min_time_ms * 1e-3 if min_time_s is None else min_time_s
     steps_eff = steps
-    if min_time_s > 0:   # size the timed region from three untimed steps (part of the warm-up)
+    if steps is None:   # size the timed region from three untimed steps (part of the warm-up)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(3):
             step()
         torch.cuda.synchronize()
         est = (time.perf_counter() - t0) / 3
-        steps_eff = max(steps, int(np.ceil(min_time_s / max(est, 1e-6))))
+        steps_eff = max(MIN_STEPS, int(np.ceil(min_time_s / max(est, 1e-6))))
         if use_dist:
             t = torch.tensor([steps_eff], dtype=torch.int64, device=coll_device if coll_device is not None else torch.device("cuda", local_rank))
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -598,13 +658,11 @@ def run_workload(name, S, T, steps, warmup, rank, first_stream, local_rank, blob
     events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps_eff)]
     # Load-onset transient (profiles/r05/launch_series.txt): after an idle gap the first ~6 launches run at the steady rate, the next
     # ~100 up to 45 % slower (the power controller clamps, then relaxes), and only then the kernel time is what a decoder that runs tick
-    # after tick sees.  Building the events above IS such a gap, so the warm-up ends with `settle` more untimed steps (~30 ms of them)
-    # right in front of the timed region, and the timed region is long (--min-time-ms) against what the barrier's own gap re-triggers.
-    settle = 0
-    if min_time_s > 0:
-        settle = int(np.ceil(min(0.030, min_time_s) / max(est, 1e-6)))
-        for _ in range(settle):
-            step()
+    # after tick sees.  Building the events above IS such a gap, so the warm-up ends with `settle` more untimed steps (SETTLE_FRAMES of
+    # them) right in front of the timed region.
+    settle = min(SETTLE_STEPS_MAX, -(-SETTLE_FRAMES // n))
+    for _ in range(settle):
+        step()
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
@@ -626,6 +684,8 @@ def run_workload(name, S, T, steps, warmup, rank, first_stream, local_rank, blob
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, kernel_ms = float(t[0]), float(t[1])
     L.mbx_set_stream_order(previous_order)
+    if dump_dir:   # before anything below launches again
+        dump_outputs(dump_dir, dec, out, S, T, records=not overlap)   # (--overlap-front-end keeps its records in buffers of its own)
     hist = decoder.result_histogram(out["results"], stream)   # the last launch's tally of flags, formed on the device (mbx_result_histogram)
     pcm_digest = int(out["pcm16"].to(torch.int64).sum().item())
     parity_obj = None
@@ -832,7 +892,10 @@ def write_detail(detail):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="number of timed steps of the headline workload (steps_effective in the line); default: sized by --min-time-ms.  "
+                         "The region is timed on the host clock, first launch to synchronise: about 0.08 ms of it are not steps "
+                         "(2 %% of 20 headline steps, 0.2 %% of 200)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="imbe_voiced", choices=sorted(WORKLOADS))
     ap.add_argument("--streams", type=int, default=0, help="override streams per GPU")
@@ -852,8 +915,14 @@ def main():
     ap.add_argument("--ablate", type=int, default=0, help="timing-only stage mask (development build of the library only); results invalid")
     ap.add_argument("--dump-steps", default=None, help="diagnosis: write the event-bracketed time (ms) of every timed step, in order, to this file")
     ap.add_argument("--min-time-ms", type=float, default=500.0,
-                    help="the timed region is at least --steps steps AND at least this much wall time (steps_effective in the line)")
+                    help="least wall time of a timed region whose number of steps is not given: the headline's without --steps, the other configs' always")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the outputs of the last timed step of the headline workload to DIR/<name>.npy (rank 0's shard; needs --steps)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.steps is None:
+        ap.error("--dump-outputs needs --steps: a region sized by time ends on a step that differs from run to run")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # not under a launcher: become one, before anything touches a GPU
@@ -904,7 +973,7 @@ def main():
     first, count = shard_range(S * world, world, rank)  # weak scaling: S streams on every rank
     assert count == S
     m = run_workload(args.workload, S, T, args.steps, args.warmup, rank, first, local_rank, blob, world, dist, args, use_dist, coll_device,
-                     parity=(rank == 0 and not args.no_parity and not args.no_extras))
+                     parity=(rank == 0 and not args.no_parity and not args.no_extras), dump_dir=args.dump_outputs if rank == 0 else None)
     rank_values = [m["rank_value"]]
     if use_dist:   # what every rank measured on its own clock (the line's value is the max-over-ranks time)
         rv = torch.tensor([m["rank_value"]], dtype=torch.float64, device=coll_device)
@@ -917,7 +986,7 @@ def main():
         "value": m["value"],
         "unit": "frames/s",
         "n_gpus": world,
-        "steps": args.steps,
+        "steps": m["steps_effective"],
         "steps_effective": m["steps_effective"],
         "settle_steps": m["settle_steps"],   # untimed steps directly in front of the timed region, beyond --warmup
         "warmup": args.warmup,
@@ -985,14 +1054,14 @@ def main():
                     "NOT an HBM figure (part of the state comes out of the Infinity Cache), reported beside the headline only",
         }
     if extras and args.workload == "imbe_voiced":
-        # the other three GPU configs of BASELINE.json, driver-timed in the same line (10 steps each)
+        # the other three GPU configs of BASELINE.json, driver-timed in the same line (regions sized by --min-time-ms)
         line["other_configs"] = {}
         for other in ("imbe_voiced_resident", "ambe_fec", "ambe_fec_resident", "imbe_mixed", "ambe_stream"):
             oc, oS, oT, odesc = WORKLOADS[other]
-            om = run_workload(other, oS, oT, 10, 2, rank, 0, local_rank, blob, 1, dist, args)
+            om = run_workload(other, oS, oT, None, 2, rank, 0, local_rank, blob, 1, dist, args)
             orf = roofline_of(other, oS, oT, om)
             line["other_configs"][other] = {
-                "workload": odesc, "value": om["value"], "unit": "frames/s", "steps": 10, "steps_effective": om["steps_effective"],
+                "workload": odesc, "value": om["value"], "unit": "frames/s", "steps": om["steps_effective"], "steps_effective": om["steps_effective"],
                 "ms_per_step": om["ms_per_step"],
                 "kernel": om["kernel"], "kernel_ms": om["kernel_ms"], "kernel_ms_stats": om["kernel_ms_stats"],
                 "algorithmic_bytes_per_launch": om["alg_bytes"],

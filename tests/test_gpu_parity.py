@@ -1342,10 +1342,11 @@ def test_bench_rccl_code_path_runs_with_one_rank():
     assert line["n_gpus"] == 1 and line["value"] > 0 and "process group initialised" in line["config"]["parallelism"]
 
 
-def test_bench_default_line_keeps_its_contract():
+def test_bench_default_line_keeps_its_contract(tmp_path):
     """`python bench.py` (the driver's call, shortened by --min-time-ms): ONE JSON line with the contract's keys -- the metric string
     with both halves, whole-job value, roofline {bound, achieved, peak, unit, frac, traffic}, cpu_baseline {value, unit, cores, kind,
-    sample} and the parity object (no bound violated)."""
+    sample} and the parity object (no bound violated).  --steps IS the number of timed steps, and --dump-outputs leaves the last
+    timed step's outputs as float arrays of at most 64 MB."""
     import json
     import os
     import subprocess
@@ -1355,8 +1356,8 @@ def test_bench_default_line_keeps_its_contract():
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--min-time-ms", "20"], capture_output=True,
-                       text=True, timeout=900, env=env)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2", "--min-time-ms", "20",
+                        "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [x for x in r.stdout.splitlines() if x.strip()]
     assert len(lines) == 1 and lines[0].startswith("{"), lines[:3]
@@ -1369,6 +1370,7 @@ def test_bench_default_line_keeps_its_contract():
         set(v) == {"value", "ms_per_step", "kernel", "kernel_ms", "frac"} for v in d["other_configs"].values())
     assert "frames/sec" in d["metric"] and "PCM RMS error vs reference" in d["metric"]
     assert d["unit"] and d["n_gpus"] == 1 and d["steps"] == 5 and d["warmup"] == 2 and d["higher_is_better"] is True and d["scaling"] == "weak"
+    assert d["steps_effective"] == 5 and detail["roofline"]["kernel_ms_stats"]["launches"] == 5
     assert d["value"] > 1e7 and abs(d["ms_per_step"] * 1e-3 * d["value"] / d["config"]["frames_per_step"] - 1.0) < 0.02
     assert "vs_baseline" in d and d["dtype"] and "synthetic" in d["data"] and "workload" in d["config"] and "model" not in d["config"]
     rf = d["roofline"]
@@ -1380,6 +1382,38 @@ def test_bench_default_line_keeps_its_contract():
     assert "FAILED" not in par and par["rel_rms"] <= 1e-4 and par["results_exact"] and par["state_in_tolerance"] and par["streams_checked"] >= 256
     for oc in detail["other_configs"].values():   # the other configs' own parity legs, if they ran one, hold the same bounds
         assert "FAILED" not in (oc.get("parity") or {})
+    dump = {f[:-4]: np.load(tmp_path / "dump" / f) for f in os.listdir(tmp_path / "dump")}
+    assert set(dump) == {"pcm16", "results", "records", "state", "rng"} and sum(a.nbytes for a in dump.values()) <= 64e6
+    assert all(a.dtype in (np.float32, np.float64) for a in dump.values())
+    assert dump["pcm16"].shape == (65536, 160) and dump["results"].shape == (65536, 5) and dump["records"].shape == (65536, 4)
+    assert dump["state"].shape == (512, 3, 651) and dump["rng"].shape == (512, 5)
+    assert np.abs(dump["pcm16"]).max() > 1000 and (dump["pcm16"] == np.round(dump["pcm16"])).all()   # voiced speech, int16 values
+
+
+def test_bench_dumped_outputs_repeat_from_run_to_run(tmp_path):
+    """bench.py --dump-outputs with the same arguments twice: the same arrays, value for value -- frames, seeds and the number of
+    launches in front of the last timed step depend on the arguments only.  One T = 1 shape dumped whole and one whose frames and
+    streams are sampled."""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    for workload, frames in (("imbe_voiced", 65536), ("ambe_stream", 65536)):
+        for run in ("a", "b"):
+            r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", workload, "--steps", "3", "--warmup", "1",
+                                "--no-cpu-baseline", "--no-extras", "--dump-outputs", str(tmp_path / workload / run)],
+                               capture_output=True, text=True, timeout=900, env=env)
+            assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        names = sorted(os.listdir(tmp_path / workload / "a"))
+        assert names == sorted(os.listdir(tmp_path / workload / "b")) == ["pcm16.npy", "records.npy", "results.npy", "rng.npy", "state.npy"]
+        for f in names:
+            a, b = np.load(tmp_path / workload / "a" / f), np.load(tmp_path / workload / "b" / f)
+            assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=True), (workload, f)
+        assert np.load(tmp_path / workload / "a" / "pcm16.npy").shape == (frames, 160)
 
 
 def test_bench_two_ranks_self_launched_on_one_card():

@@ -238,55 +238,17 @@ def test_bench_self_launch_starts_ranks_and_relays_rank0(tmp_path):
 
 
 def test_program_written_against_the_reference_header_links(tmp_path):
-    """Drop-in at link level: a C program that includes the REFERENCE's own public header (where the reference tree is
-    present, i.e. in the authoring container; skipped elsewhere) and calls one function of every family links against
-    libmbe_neo_amd.so with no undefined symbol and no prototype conflict."""
+    """Drop-in at link level: a C program that includes the REFERENCE's own public header and calls one function of every family
+    (oracle/tools/api_host.c; oracle/Makefile compiles it with -Wall -Werror where the reference tree is present, so a prototype
+    conflict fails build(); skipped where that object was not built) links against libmbe_neo_amd.so with no undefined symbol."""
     import shim_lib
 
-    ref_inc = "/root/reference/include"
-    gen_inc = os.path.join(ROOT, "oracle", "_ref", "include")   # the generated one-line version.h (oracle/Makefile)
-    if not os.path.exists(os.path.join(ref_inc, "mbelib-neo", "mbelib.h")) or not os.path.exists(os.path.join(gen_inc, "mbelib-neo", "version.h")):
-        pytest.skip("reference tree not present here")
-    src = tmp_path / "host.c"
-    src.write_text(r'''
-#include <mbelib-neo/mbelib.h>
-int main(void) {
-    static mbe_parms cur, prev, enh;
-    static char imbe_fr[8][23], imbe7100_fr[7][24], ambe_fr[4][24], imbe_d[88], ambe_d[49];
-    static mbe_soft_bit soft_i[8][23], soft_a[4][24];
-    static short pcm[160];
-    static float pcmf[160];
-    mbe_process_result res;
-    long block = 0;
-    mbe_initMbeParms(&cur, &prev, &enh);
-    mbe_initProcessResult(&res);
-    mbe_setThreadRngSeed(1u);
-    int n = 0;
-    n += mbe_eccImbe7200x4400C0(imbe_fr) + mbe_demodulateImbe7200x4400Data(imbe_fr) + mbe_eccImbe7200x4400Data(imbe_fr, imbe_d);
-    n += mbe_decodeImbe4400Parms(imbe_d, &cur, &prev);
-    n += mbe_processImbe7200x4400Frame(pcm, &res, (const char(*)[23])imbe_fr, imbe_d, &cur, &prev, &enh);
-    n += mbe_processImbe7200x4400SoftFramef(pcmf, &res, (const mbe_soft_bit(*)[23])soft_i, imbe_d, &cur, &prev, &enh);
-    n += mbe_processImbe7100x4400Framef(pcmf, &res, (const char(*)[24])imbe7100_fr, imbe_d, &cur, &prev, &enh);
-    n += mbe_convertImbe7100to7200(imbe_d);
-    n += mbe_processAmbe3600x2450Frame(pcm, &res, (const char(*)[24])ambe_fr, ambe_d, &cur, &prev, &enh);
-    n += mbe_processAmbe3600x2450SoftFrame(pcm, &res, (const mbe_soft_bit(*)[24])soft_a, ambe_d, &cur, &prev, &enh);
-    n += mbe_processAmbe3600x2400Framef(pcmf, &res, (const char(*)[24])ambe_fr, ambe_d, &cur, &prev, &enh);
-    n += mbe_decodeAmbe2450Parms(ambe_d, &cur, &prev) + mbe_decodeAmbe2400Parms(ambe_d, &cur, &prev);
-    n += mbe_eccAmbe3600x2450C0(ambe_fr) + mbe_demodulateAmbe3600x2400Data(ambe_fr);
-    n += mbe_checkGolayBlock(&block) + mbe_golay2312(imbe_fr[0], imbe_fr[1]) + mbe_hamming1511(imbe_fr[4], imbe_fr[5]);
-    mbe_synthesizeSpeechf(pcmf, &cur, &prev);
-    mbe_spectralAmpEnhance(&cur);
-    mbe_applyAdaptiveSmoothing(&cur, &prev);
-    mbe_floattoshort(pcmf, pcm);
-    mbe_synthesizeComfortNoise(pcm);
-    mbe_synthesizeTonef(pcmf, ambe_d, &cur);
-    mbe_dumpImbe7200x4400Frame((const char(*)[23])imbe_fr);
-    return n + (mbe_versionString() != 0);
-}
-''')
+    obj = os.path.join(ROOT, "oracle", "_ref", "api_host.o")
+    if not os.path.exists(obj):
+        pytest.skip("oracle/_ref/api_host.o not built here (no reference tree)")
     exe = tmp_path / "host"
     libdir = os.path.dirname(shim_lib.PATH)
-    r = subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", ref_inc, "-I", gen_inc, str(src), "-o", str(exe), "-L", libdir, "-lmbe_neo_amd",
+    r = subprocess.run(["gcc", obj, "-o", str(exe), "-L", libdir, "-lmbe_neo_amd",
                         "-Wl,--no-undefined", "-Wl,--allow-shlib-undefined", "-Wl,-rpath," + libdir], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
 
@@ -462,6 +424,36 @@ def test_bench_contract_line_is_compact_and_complete():
     fat["other_configs"].update({f"extra{i}": fat["other_configs"]["ambe_fec"] for i in range(40)})
     thin = bench.contract_line(fat)
     assert len(json.dumps(thin)) <= 4096 and "other_configs" not in thin and thin["parity"]["FAILED"].startswith("xxx") and "roofline" in thin and "cpu_baseline" in thin
+
+
+def test_bench_dump_sample_and_struct_conversion():
+    """bench.py --dump-outputs, the host side: the rows kept of a large output are a fixed ascending sample (the same at every call),
+    a small output is kept whole, and a struct array becomes float64 field by field without losing a bit (a uint32 near 2^32, a
+    negative int32, the 48-bit seed)."""
+    import os
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    import mbelib_neo_amd  # noqa: F401
+    from mbelib_neo_amd.layout import init_state, rng_seeded
+
+    assert np.array_equal(bench.dump_sample(100, 512), np.arange(100))
+    rows = bench.dump_sample(1 << 20, bench.DUMP_FRAMES)
+    assert rows.shape == (65536,) and (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < (1 << 20)
+    assert np.array_equal(rows, bench.dump_sample(1 << 20, bench.DUMP_FRAMES)) and len(np.unique(rows // 128)) > 8000   # spread over the streams
+    assert bench.DUMP_FRAMES * (160 + 5) * 4 + bench.DUMP_FRAMES * 4 * 8 + bench.DUMP_STREAMS * (3 * 651 + 5) * 8 <= 64e6
+    st = init_state(4)
+    st["tonePhase"][:, 1] = 0xFFFFFFF1
+    st["Vl"][:, 2, 56] = -3
+    f = bench.fields_as_float64(st.reshape(-1)).reshape(4, 3, -1)
+    assert f.dtype == np.float64 and f.shape == (4, 3, 651)
+    assert (f[:, :, 0] == st["w0"].astype(np.float64)).all() and (f[:, 1, 288 + 1] == 0xFFFFFFF1).all() and (f[:, 2, 3 + 56] == -3).all()
+    assert (f[:, :, 554] == -1.0).all()   # noiseSeed, the 555th word of the struct
+    r = rng_seeded(np.arange(4) + (1 << 40))
+    fr = bench.fields_as_float64(r)
+    assert fr.shape == (4, 5) and (fr[:, 0].astype(np.uint64) == r["cn_seed48"]).all() and (fr[:, 2] == r["unvoiced_seed_state"]).all()
 
 
 def test_wire_permutation_from_a_callers_deinterleave_tables():

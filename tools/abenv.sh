@@ -19,7 +19,7 @@ for r in range(rounds):
                 env[k] = val
             if "MBX_HIP_LIBRARY" in env:
                 env["MBX_HIP_LIBRARY_ALLOW_OLDER"] = "1"
-            out = subprocess.run([sys.executable, "bench.py", "--workload", w, "--steps", "10", "--no-cpu-baseline", "--no-extras"],
+            out = subprocess.run([sys.executable, "bench.py", "--workload", w, "--no-cpu-baseline", "--no-extras"],
                                  env=env, capture_output=True, text=True)
             try:
                 d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -6,7 +6,7 @@ for r in range(4):
         env = dict(os.environ)
         if n != "product":
             env["MBX_HIP_LIBRARY"] = os.path.join(os.getcwd(), "mbelib-neo_amd", "variants", f"libmbx_hip_{n}.so"); env["MBX_HIP_LIBRARY_ALLOW_OLDER"] = "1"
-        out = subprocess.run([sys.executable, "bench.py", "--workload", wl, "--steps", "20", "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True)
+        out = subprocess.run([sys.executable, "bench.py", "--workload", wl, "--no-cpu-baseline", "--no-extras"], env=env, capture_output=True, text=True)
         d = json.loads(out.stdout.strip().splitlines()[-1])
         res.setdefault(n, []).append((d["ms_per_step"], d["roofline"]["kernel_ms"]))
 for n in names:

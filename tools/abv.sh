@@ -2,12 +2,13 @@
 # abv.sh <workload> <variant names...> -- GPU box: bench line of the product library and of each variant library
 w=$1; shift
 cd "$(dirname "$0")/.."
+export T=$(mktemp -d); trap 'rm -rf "$T"' EXIT   # one bench line per variant, read back by run()
 run() {  # label, env...
   label=$1; shift
-  env "$@" python bench.py --workload $w --steps 10 --no-cpu-baseline --no-extras > gpurun_out/abv_$label.log 2>&1
+  env "$@" python bench.py --workload $w --no-cpu-baseline --no-extras > $T/abv_$label.log 2>&1
   python - "$label" <<'PY'
-import json, sys
-f = "gpurun_out/abv_%s.log" % sys.argv[1]
+import json, os, sys
+f = os.path.join(os.environ["T"], "abv_%s.log" % sys.argv[1])
 try:
     d = json.loads(open(f).read().strip().splitlines()[-1])
     print(sys.argv[1], round(d["value"] / 1e6, 1), "M frames/s, kernel", round(d["roofline"]["kernel_ms"], 4), "ms")

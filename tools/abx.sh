@@ -15,7 +15,7 @@ for r in range(rounds):
             if n != "product":
                 env["MBX_HIP_LIBRARY"] = os.path.join(os.getcwd(), "mbelib-neo_amd", "variants", f"libmbx_hip_{n}.so")
                 env["MBX_HIP_LIBRARY_ALLOW_OLDER"] = "1"
-            out = subprocess.run([sys.executable, "bench.py", "--workload", w, "--steps", "10", "--no-cpu-baseline", "--no-extras"],
+            out = subprocess.run([sys.executable, "bench.py", "--workload", w, "--no-cpu-baseline", "--no-extras"],
                                  env=env, capture_output=True, text=True)
             try:
                 d = json.loads(out.stdout.strip().splitlines()[-1])

@@ -178,7 +178,7 @@ def main():
         out["counters_per_step"] = {k: sum(v) / len(v) for k, v in merged.items()}   # (= per dispatch where a step is one dispatch)
         out["kernel_ns_under_pmc"] = (sum(durs) / len(durs)) if durs else None       # the step's dispatches, durations added up
         if per_step > 1:   # the envelope of a sliced step must come from an UN-profiled run: the counter passes serialise the dispatches
-            r = subprocess.run(["python3", os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "2", "--min-time-ms", "300", "--no-cpu-baseline",
+            r = subprocess.run(["python3", os.path.join(ROOT, "bench.py"), "--warmup", "2", "--min-time-ms", "300", "--no-cpu-baseline",
                                 "--no-extras", "--workload", workload], capture_output=True, text=True, cwd="/tmp")
             try:
                 step_ns = json.loads(r.stdout.strip().splitlines()[-1])["roofline"]["kernel_ms"] * 1e6
