@@ -14,101 +14,7 @@
 
 #include "mbx.h"
 #include "mbx_device.h"
-
-namespace mbx {
-// kernels (mbx_fec.hip, mbx_stream.hip)
-__global__ void fec_imbe7200x4400_kernel(const uint8_t*, size_t, mbx_param_record*, DeviceTables);
-__global__ void fec_ambe3600x2450_kernel(const uint8_t*, size_t, mbx_param_record*, DeviceTables);
-__global__ void fec_imbe7100x4400_kernel(const uint8_t*, size_t, mbx_param_record*, DeviceTables);
-__global__ void floattoshort_kernel(const float*, int16_t*, size_t);
-__global__ void result_histogram_kernel(const mbe_process_result*, size_t, unsigned long long*);
-__global__ void stage_in_kernel(const uint8_t*, uint8_t*, size_t);
-__global__ void expand_imbe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
-__global__ void expand_ambe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
-__global__ void expand_ambe2400_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
-__global__ void imbe_stream_kernel(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                   int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void frame_server_kernel(mbx_frame_mailbox*, unsigned, mbe_parms*, mbx_stream_rng*, int16_t*, float*, mbe_process_result*,
-                                    mbx_param_record*, DeviceTables, FrameShadow);
-__global__ void imbe_stream_kernel_one(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                       int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe_stream_kernel_one(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                       int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe2400_stream_kernel_one(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                           int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void imbe_stream_kernel_one_fused(int, int, const uint8_t*, mbx_param_record*, mbe_parms*, mbx_stream_rng*, int16_t*, float*,
-                                             mbe_process_result*, DeviceTables);
-__global__ void imbe_stream_kernel_res1_fused(int, int, const uint8_t*, mbx_param_record*, mbe_parms*, mbx_stream_rng*, int16_t*, float*,
-                                              mbe_process_result*, DeviceTables);
-#ifdef MBX_EXP_PAIR
-__global__ void imbe_stream_kernel_lds_pairexp(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*, int16_t*, float*,
-                                               mbe_process_result*, DeviceTables);
-#endif
-__global__ void imbe_stream_kernel_lds_slice(int, int, int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*, int16_t*, float*,
-                                             mbe_process_result*, DeviceTables);
-__global__ void ambe_stream_kernel_lds_slice(int, int, int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*, int16_t*, float*,
-                                             mbe_process_result*, DeviceTables);
-__global__ void ambe2400_stream_kernel_lds_slice(int, int, int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*, int16_t*,
-                                                 float*, mbe_process_result*, DeviceTables);
-__global__ void imbe_one_launch_kernel(int, int, const uint8_t*, mbx_param_record*, FrameParams*, uint32_t*, uint32_t*, uint32_t, mbe_parms*,
-                                       mbx_stream_rng*, int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void imbe_one_launch_kernel_res(int, int, const uint8_t*, mbx_param_record*, FrameParams*, uint32_t*, uint32_t*, uint32_t, mbe_parms*,
-                                           mbx_stream_rng*, int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe_one_launch_kernel(int, const uint8_t*, mbx_param_record*, FrameParams*, uint32_t*, uint32_t*, uint32_t, mbe_parms*, mbx_stream_rng*,
-                                       int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe_one_launch_kernel_res(int, const uint8_t*, mbx_param_record*, FrameParams*, uint32_t*, uint32_t*, uint32_t, mbe_parms*,
-                                           mbx_stream_rng*, int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe2400_one_launch_kernel_res(int, const uint8_t*, mbx_param_record*, FrameParams*, uint32_t*, uint32_t*, uint32_t, mbe_parms*,
-                                               mbx_stream_rng*, int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe2400_one_launch_kernel(int, const uint8_t*, mbx_param_record*, FrameParams*, uint32_t*, uint32_t*, uint32_t, mbe_parms*,
-                                           mbx_stream_rng*, int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void imbe7100_stream_kernel_one_fused(int, int, const uint8_t*, mbx_param_record*, mbe_parms*, mbx_stream_rng*, int16_t*, float*,
-                                                 mbe_process_result*, DeviceTables);
-__global__ void imbe7100_stream_kernel_res1_fused(int, int, const uint8_t*, mbx_param_record*, mbe_parms*, mbx_stream_rng*, int16_t*, float*,
-                                                  mbe_process_result*, DeviceTables);
-__global__ void imbe_stream_kernel_res1(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                        int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe_stream_kernel_res1(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                        int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe2400_stream_kernel_res1(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                            int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void imbe_stream_kernel_res(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                       int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe_stream_kernel_res(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                       int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe2400_stream_kernel_res(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                           int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void imbe_stream_kernel_lds(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                       int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe_stream_kernel_lds(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                       int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe2400_stream_kernel_lds(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                           int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe_stream_kernel(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                   int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void ambe2400_stream_kernel(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbx_stream_rng*,
-                                   int16_t*, float*, mbe_process_result*, DeviceTables);
-__global__ void imbe_frame_kernel(int, const uint8_t*, mbx_param_record*, mbe_parms*, mbx_stream_rng*, int16_t*, float*,
-                                  mbe_process_result*, uint32_t*, uint32_t, DeviceTables, FrameShadow);
-__global__ void ambe_frame_kernel(const uint8_t*, mbx_param_record*, mbe_parms*, mbx_stream_rng*, int16_t*, float*, mbe_process_result*,
-                                  uint32_t*, uint32_t, DeviceTables, FrameShadow);
-__global__ void ambe2400_frame_kernel(const uint8_t*, mbx_param_record*, mbe_parms*, mbx_stream_rng*, int16_t*, float*,
-                                      mbe_process_result*, uint32_t*, uint32_t, DeviceTables, FrameShadow);
-__global__ void synth_speech_kernel(int, mbe_parms*, mbe_parms*, mbx_stream_rng*, float*, int16_t*, DeviceTables);
-__global__ void enhance_kernel(int, mbe_parms*);
-__global__ void smoothing_kernel(int, mbe_parms*, const mbe_parms*);
-__global__ void comfort_noise_kernel(int, mbx_stream_rng*, float*, int16_t*);
-__global__ void state_copy_kernel(int, mbe_parms*);
-__global__ void tone_kernel(int, const mbx_param_record*, const int32_t*, mbe_parms*, float*, int16_t*, int);
-__global__ void ecc_words_kernel(int, const uint32_t*, size_t, uint32_t*, int32_t*, DeviceTables);
-__global__ void pack_cells_kernel(int, const char*, size_t, uint8_t*, int32_t*);
-__global__ void fec_stage_kernel(int, int, const uint8_t*, size_t, uint8_t*, mbx_param_record*, DeviceTables);
-__global__ void decode_parms_kernel(int, int, const FrameParams*, mbe_parms*, mbe_parms*, int32_t*, DeviceTables);
-__global__ void fec_imbe7200x4400_soft_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
-__global__ void fec_ambe3600x2450_soft_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
-__global__ void fec_imbe7100x4400_soft_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
-__global__ void ecc_soft_words_kernel(int, const mbe_soft_bit*, size_t, uint32_t*, int32_t*, DeviceTables);
-}  // namespace mbx
+#include "mbx_kernels.h"
 
 namespace {
 
@@ -963,6 +869,84 @@ static int launch_expand(Context* c, int codec, const mbx_param_record* d_record
     return check_launch("expand_kernel");
 }
 
+// ---- the stream-stage kernel instances (mbx_stream.hip) ------------------------------------------------------------------------------
+// ONE table of what can run and ONE function that says what does (select_instance, below the switches it reads): the launchers
+// launch the entry it returns and report entry.name, mbx_batch_kernel_name / mbx_stream_kernel_name return the same entry's name.
+// A new instance: its declaration in mbx_kernels.h, its row here, its case in select_instance.
+using mbx::DeviceTables;
+using mbx::FrameParams;
+enum Family { kStreamArgs, kSliceArgs, kFusedArgs, kOneLaunchArgs, kOneLaunchLeadArgs };   // (one-launch: without / with the front blocks' lead)
+struct Instance {
+    const char* name;   // as the profiler prints it
+    Family      family;   // which argument list the kernel takes (mbx_kernels.h) = which member of the union is set
+    union {
+        void (*stream)(MBX_STREAM_PARAMS);
+        void (*slice)(MBX_SLICE_PARAMS);
+        void (*fused)(MBX_FUSED_PARAMS);
+        void (*one_launch)(int S, MBX_ONE_LAUNCH_PARAMS);
+        void (*one_launch_lead)(int S, int lead, MBX_ONE_LAUNCH_PARAMS);
+    };
+    // (the family follows from the kernel's type: a kernel whose parameter list is none of the families' does not compile here)
+    constexpr Instance(const char* n, void (*k)(MBX_STREAM_PARAMS)) : name(n), family(kStreamArgs), stream(k) {}
+    constexpr Instance(const char* n, void (*k)(MBX_SLICE_PARAMS)) : name(n), family(kSliceArgs), slice(k) {}
+    constexpr Instance(const char* n, void (*k)(MBX_FUSED_PARAMS)) : name(n), family(kFusedArgs), fused(k) {}
+    constexpr Instance(const char* n, void (*k)(int S, MBX_ONE_LAUNCH_PARAMS)) : name(n), family(kOneLaunchArgs), one_launch(k) {}
+    constexpr Instance(const char* n, void (*k)(int S, int lead, MBX_ONE_LAUNCH_PARAMS)) : name(n), family(kOneLaunchLeadArgs), one_launch_lead(k) {}
+};
+// rows of kInstances by their first entry; a row's columns: IMBE 7200x4400 | AMBE 3600x2450 | AMBE 3600x2400 (the two fused rows: IMBE
+// 7200x4400 | IMBE 7100x4400, the only codecs with a front end of their own inside the stream's wave)
+enum Row { kPlain = 0, kOne = 3, kLds = 6, kRes = 9, kRes1 = 12, kSlice = 15, kOneLaunch = 18, kOneLaunchRes = 21, kOneFused = 24, kRes1Fused = 26 };
+static const Instance kInstances[] = {
+    {"imbe_stream_kernel", mbx::imbe_stream_kernel},
+    {"ambe_stream_kernel", mbx::ambe_stream_kernel},
+    {"ambe2400_stream_kernel", mbx::ambe2400_stream_kernel},
+    {"imbe_stream_kernel_one", mbx::imbe_stream_kernel_one},
+    {"ambe_stream_kernel_one", mbx::ambe_stream_kernel_one},
+    {"ambe2400_stream_kernel_one", mbx::ambe2400_stream_kernel_one},
+    {"imbe_stream_kernel_lds", mbx::imbe_stream_kernel_lds},
+    {"ambe_stream_kernel_lds", mbx::ambe_stream_kernel_lds},
+    {"ambe2400_stream_kernel_lds", mbx::ambe2400_stream_kernel_lds},
+    {"imbe_stream_kernel_res", mbx::imbe_stream_kernel_res},
+    {"ambe_stream_kernel_res", mbx::ambe_stream_kernel_res},
+    {"ambe2400_stream_kernel_res", mbx::ambe2400_stream_kernel_res},
+    {"imbe_stream_kernel_res1", mbx::imbe_stream_kernel_res1},
+    {"ambe_stream_kernel_res1", mbx::ambe_stream_kernel_res1},
+    {"ambe2400_stream_kernel_res1", mbx::ambe2400_stream_kernel_res1},
+    {"imbe_stream_kernel_lds_slice", mbx::imbe_stream_kernel_lds_slice},
+    {"ambe_stream_kernel_lds_slice", mbx::ambe_stream_kernel_lds_slice},
+    {"ambe2400_stream_kernel_lds_slice", mbx::ambe2400_stream_kernel_lds_slice},
+    {"imbe_one_launch_kernel", mbx::imbe_one_launch_kernel},
+    {"ambe_one_launch_kernel", mbx::ambe_one_launch_kernel},
+    {"ambe2400_one_launch_kernel", mbx::ambe2400_one_launch_kernel},
+    {"imbe_one_launch_kernel_res", mbx::imbe_one_launch_kernel_res},
+    {"ambe_one_launch_kernel_res", mbx::ambe_one_launch_kernel_res},
+    {"ambe2400_one_launch_kernel_res", mbx::ambe2400_one_launch_kernel_res},
+    {"imbe_stream_kernel_one_fused", mbx::imbe_stream_kernel_one_fused},
+    {"imbe7100_stream_kernel_one_fused", mbx::imbe7100_stream_kernel_one_fused},
+    {"imbe_stream_kernel_res1_fused", mbx::imbe_stream_kernel_res1_fused},
+    {"imbe7100_stream_kernel_res1_fused", mbx::imbe7100_stream_kernel_res1_fused},
+};
+static_assert(sizeof(kInstances) / sizeof(kInstances[0]) == kRes1Fused + 2, "kInstances: Row names the first entry of every row");
+// what select_instance decides on
+struct Shape {
+    int  codec, S, T;
+    bool resident = false;    // the launch carries DeviceTables::resident
+    bool rows = false;        // ... and FrameParams rows written by an expand launch
+    bool sliced = false;      // try_sliced_launch issues it slice by slice
+    bool frames = false;      // the call has the wire frames (mbx_process_batch*): a T = 1 step may be ONE launch, and they are ...
+    bool aligned = false;     // ... 4-byte aligned (the IMBE front ends load dwords)
+    bool workspace = false;   // ... and the rows may go through the stream slot's own workspace and flag words (the one-launch forms)
+};
+static const Instance& select_instance(const Shape& q);
+// the tables of a launch: the context's + what this launch walks (`reverse`: see launch_stream)
+static mbx::DeviceTables launch_tables(const Context* c, bool reverse, const int32_t* d_stream_index, uint32_t* d_resident) {
+    mbx::DeviceTables tabs = c->tabs;
+    tabs.reverse = (reverse && reverse_enabled()) ? 1 : 0;
+    tabs.stream_map = d_stream_index;
+    tabs.resident = d_resident;
+    return tabs;
+}
+
 // ---- sliced launches (mbx_stream.hip, *_stream_kernel_lds_slice) ------------------------------------------------------------------
 // A launch of S streams x T frames is S workgroups of equal length; when S does not fill the device's resident wave slots evenly
 // the last round runs part-empty -- BASELINE configs[4]'s shard, 8,192 AMBE+2 streams on 5,120 slots, is 1.6 rounds: the second
@@ -1043,6 +1027,9 @@ static int try_sliced_launch(Context* c, StreamSlot& slot, mbx::DeviceTables tab
         (void)hipGetLastError();
         return 1;
     }
+    Shape q{codec, S, T};
+    q.sliced = true;
+    const Instance& e = select_instance(q);
     int result = 0;
     // Group 0 runs on the caller's stream itself -- its kernels are queued before the stream waits for the other groups --, so g
     // groups occupy g hardware queues, not g + 1, and one group needs no hand-over at all: 2.51 -> 2.42 ms on 8,192 x 128 AMBE+2
@@ -1078,15 +1065,9 @@ static int try_sliced_launch(Context* c, StreamSlot& slot, mbx::DeviceTables tab
         mbe_process_result* rs = d_results ? d_results + f0 : nullptr;
         for (int t0 = 0; t0 < T; t0 += Tc) {
             const int n = (T - t0) < Tc ? (T - t0) : Tc;
-            if (codec == MBX_CODEC_IMBE7200X4400) {
-                hipLaunchKernelGGL(mbx::imbe_stream_kernel_lds_slice, dim3((unsigned)Sg), dim3(64), 0, st, Sg, T, t0, n, rg, pg, sg, ng, p16, pf, rs, tg);
-            } else if (codec == MBX_CODEC_AMBE3600X2400) {
-                hipLaunchKernelGGL(mbx::ambe2400_stream_kernel_lds_slice, dim3((unsigned)Sg), dim3(64), 0, st, Sg, T, t0, n, rg, pg, sg, ng, p16, pf, rs, tg);
-            } else {
-                hipLaunchKernelGGL(mbx::ambe_stream_kernel_lds_slice, dim3((unsigned)Sg), dim3(64), 0, st, Sg, T, t0, n, rg, pg, sg, ng, p16, pf, rs, tg);
-            }
+            hipLaunchKernelGGL(e.slice, dim3((unsigned)Sg), dim3(64), 0, st, Sg, T, t0, n, rg, pg, sg, ng, p16, pf, rs, tg);
         }
-        const int lrc = check_launch("stream_kernel_lds_slice");
+        const int lrc = check_launch(e.name);
         if (lrc < 0) {
             result = lrc;
         }
@@ -1111,10 +1092,7 @@ static int launch_stream(Context* c, bool reverse, int codec, int S, int T, cons
                          const mbx::FrameParams* params, mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16,
                          float* d_pcmf, mbe_process_result* d_results, void* stream, const int32_t* d_stream_index = nullptr,
                          uint32_t* d_resident = nullptr, StreamSlot* slot = nullptr /* caller holds c->mu: time-sliced launches allowed */) {
-    mbx::DeviceTables tabs = c->tabs;
-    tabs.reverse = (reverse && reverse_enabled()) ? 1 : 0;
-    tabs.stream_map = d_stream_index;
-    tabs.resident = d_resident;
+    const mbx::DeviceTables tabs = launch_tables(c, reverse, d_stream_index, d_resident);
     // With several frames per stream prev_mp / prev_mp_enhanced stay in LDS for the whole launch (the *_lds instances,
     // four waves per SIMD) instead of being parked in their HBM slots every frame: mbx_stream.hip, ParkedState.
     // Resident state (d_resident) is understood by those instances only, whatever T is.
@@ -1125,79 +1103,13 @@ static int launch_stream(Context* c, bool reverse, int codec, int S, int T, cons
             return rc;
         }
     }
-    if (d_resident) {
-        if (codec == MBX_CODEC_IMBE7200X4400 && T == 1 && res1_enabled()) {
-            hipLaunchKernelGGL(mbx::imbe_stream_kernel_res1, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                               params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-        } else if (codec == MBX_CODEC_IMBE7200X4400) {
-            hipLaunchKernelGGL(mbx::imbe_stream_kernel_res, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                               params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-        } else if (T == 1 && params && res1_enabled()) {   // the AMBE codecs: one frame per stream on rows from the expand launch
-            auto* const k1 = codec == MBX_CODEC_AMBE3600X2400 ? mbx::ambe2400_stream_kernel_res1 : mbx::ambe_stream_kernel_res1;
-            hipLaunchKernelGGL(k1, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records, params, d_state, d_rng, d_pcm16, d_pcmf,
-                               d_results, tabs);
-        } else if (codec == MBX_CODEC_AMBE3600X2400) {
-            hipLaunchKernelGGL(mbx::ambe2400_stream_kernel_res, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                               params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-        } else {
-            hipLaunchKernelGGL(mbx::ambe_stream_kernel_res, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                               params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-        }
-        return check_launch("stream_kernel_res");
-    }
-    if (codec == MBX_CODEC_IMBE7200X4400) {
-        if (lds_resident) {
-#ifdef MBX_EXP_PAIR   // experiment builds only (mbx_stream.hip, imbe_stream_kernel_lds_pairexp)
-            if ((S & 1) == 0 && !tabs.stream_map) {
-                hipLaunchKernelGGL(mbx::imbe_stream_kernel_lds_pairexp, dim3((unsigned)S / 2), dim3(128), 0, (hipStream_t)stream, S, T, d_records,
-                                   params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-                return check_launch("imbe_stream_kernel_lds_pairexp");
-            }
-#endif
-            hipLaunchKernelGGL(mbx::imbe_stream_kernel_lds, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                               params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-            return check_launch("imbe_stream_kernel_lds");
-        }
-        if (T == 1) {
-            hipLaunchKernelGGL(mbx::imbe_stream_kernel_one, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                               params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-            return check_launch("imbe_stream_kernel_one");
-        }
-        hipLaunchKernelGGL(mbx::imbe_stream_kernel, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                           params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-        return check_launch("imbe_stream_kernel");
-    }
-    if (codec == MBX_CODEC_AMBE3600X2400) {
-        if (lds_resident) {
-            hipLaunchKernelGGL(mbx::ambe2400_stream_kernel_lds, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                               params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-            return check_launch("ambe2400_stream_kernel_lds");
-        }
-        if (T == 1) {
-            hipLaunchKernelGGL(mbx::ambe2400_stream_kernel_one, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                               params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-            return check_launch("ambe2400_stream_kernel_one");
-        }
-        hipLaunchKernelGGL(mbx::ambe2400_stream_kernel, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                           params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-        return check_launch("ambe2400_stream_kernel");
-    }
-    // (Long AMBE+2 launches used to need a second, register-padded instance to even out their rounds of waves -- config 5's
-    // shard is 8 waves per SIMD on 6 slots: 6 + 2.  The LDS-resident instance runs 16 waves per CU: 2 x 16, and
-    // 8,192 streams x T = 128 went from 3.51 ms to 3.15 ms.)
-    if (lds_resident) {
-        hipLaunchKernelGGL(mbx::ambe_stream_kernel_lds, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                           params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-        return check_launch("ambe_stream_kernel_lds");
-    }
-    if (T == 1) {
-        hipLaunchKernelGGL(mbx::ambe_stream_kernel_one, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                           params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-        return check_launch("ambe_stream_kernel_one");
-    }
-    hipLaunchKernelGGL(mbx::ambe_stream_kernel, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records,
-                       params, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-    return check_launch("ambe_stream_kernel");
+    Shape q{codec, S, T};
+    q.resident = d_resident != nullptr;
+    q.rows = params != nullptr;
+    const Instance& e = select_instance(q);
+    hipLaunchKernelGGL(e.stream, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records, params, d_state, d_rng, d_pcm16, d_pcmf,
+                       d_results, tabs);
+    return check_launch(e.name);
 }
 
 static bool stream_args_ok(int codec, int S, int T, const void* d_records, const void* d_state, const void* d_rng) {
@@ -1248,61 +1160,78 @@ static int front_lead_chunks() {
     return lead;
 }
 static bool ambe_codec(int codec) { return codec == MBX_CODEC_AMBE3600X2450 || codec == MBX_CODEC_AMBE3600X2400; }
-static bool fused_one_ok(int codec, int S, int T, const void* d_frames, bool resident = false) {
-    (void)resident;
-    if (T != 1 || S <= kSmallBatchFrames || fused_one_mode() == 0) {
-        return false;
+// THE selection: which instance runs for a launch of this shape under the switches above.  (A codec that is none of the four is
+// rejected before any launch; the names' functions answer for it as for AMBE 3600x2450, as they always have.)
+static const Instance& select_instance(const Shape& q) {
+    const bool imbe7100 = q.codec == MBX_CODEC_IMBE7100X4400;   // own front end, then the 7200x4400 column
+    const bool imbe = q.codec == MBX_CODEC_IMBE7200X4400 || imbe7100;
+    const int col = imbe ? 0 : (q.codec == MBX_CODEC_AMBE3600X2400 ? 2 : 1);
+    const int mode = fused_one_mode();
+    if (q.frames && q.T == 1 && q.S > kSmallBatchFrames && mode != 0) {   // the T = 1 step as one launch
+        if (ambe_codec(q.codec)) {   // 9-byte frames: byte loads, any alignment; no in-wave form: without a workspace the staged kernels
+            if (mode == 2 && q.workspace) {
+                return kInstances[(q.resident ? kOneLaunchRes : kOneLaunch) + col];
+            }
+        } else if (imbe && q.aligned) {
+            if (mode == 2 && !imbe7100 && q.workspace) {
+                return kInstances[(q.resident ? kOneLaunchRes : kOneLaunch) + col];
+            }
+            return kInstances[(q.resident ? kRes1Fused : kOneFused) + (imbe7100 ? 1 : 0)];
+        }
     }
-    if (ambe_codec(codec)) {
-        return fused_one_mode() == 2;   // 9-byte frames: byte loads, any alignment
+    if (q.sliced) {
+        return kInstances[kSlice + col];
     }
-    return (codec == MBX_CODEC_IMBE7200X4400 || codec == MBX_CODEC_IMBE7100X4400) && (reinterpret_cast<uintptr_t>(d_frames) & 3u) == 0;
+    if (q.resident) {   // understood by the *_res / *_res1 instances only, whatever T is and whatever MBX_NO_LDS_RESIDENT says
+        // (IMBE's one-frame instance expands a record itself; the AMBE ones read rows, and without rows the looped instance serves T = 1)
+        const bool one = q.T == 1 && res1_enabled() && (imbe || q.rows);
+        return kInstances[(one ? kRes1 : kRes) + col];
+    }
+    const bool lds = q.T >= kLdsResidentMinFrames && lds_resident_enabled();
+    // (Long AMBE+2 launches used to need a second, register-padded instance to even out their rounds of waves -- config 5's
+    // shard is 8 waves per SIMD on 6 slots: 6 + 2.  The LDS-resident instance runs 16 waves per CU: 2 x 16, and
+    // 8,192 streams x T = 128 went from 3.51 ms to 3.15 ms.)
+    return kInstances[(lds ? kLds : (q.T == 1 ? kOne : kPlain)) + col];
 }
-static bool one_launch_form(int codec) { return (codec == MBX_CODEC_IMBE7200X4400 || ambe_codec(codec)) && fused_one_mode() == 2; }
-static int launch_fused_one(Context* c, bool reverse, int codec, int S, const uint8_t* d_frames, mbx_param_record* d_records,
+static int launch_fused_one(Context* c, const Instance& e, bool reverse, int codec, int S, const uint8_t* d_frames, mbx_param_record* d_records,
                             mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
                             void* stream, const int32_t* d_stream_index, uint32_t* d_resident) {
-    mbx::DeviceTables tabs = c->tabs;
-    tabs.reverse = (reverse && reverse_enabled()) ? 1 : 0;
-    tabs.stream_map = d_stream_index;
-    tabs.resident = d_resident;
-    const bool v7100 = codec == MBX_CODEC_IMBE7100X4400;
-    auto* const kernel = d_resident ? (v7100 ? mbx::imbe7100_stream_kernel_res1_fused : mbx::imbe_stream_kernel_res1_fused)
-                                    : (v7100 ? mbx::imbe7100_stream_kernel_one_fused : mbx::imbe_stream_kernel_one_fused);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, codec, d_frames, d_records, d_state, d_rng, d_pcm16,
+    const mbx::DeviceTables tabs = launch_tables(c, reverse, d_stream_index, d_resident);
+    hipLaunchKernelGGL(e.fused, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, codec, d_frames, d_records, d_state, d_rng, d_pcm16,
                        d_pcmf, d_results, tabs);
-    return check_launch("imbe_stream_kernel_one_fused");
+    return check_launch(e.name);
 }
 // caller holds c->mu; the slot's workspace holds S rows and its flags
-static int launch_one_launch(Context* c, StreamSlot& slot, bool reverse, int codec, int S, const uint8_t* d_frames, mbx_param_record* d_records,
-                             mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
-                             void* stream, const int32_t* d_stream_index, uint32_t* d_resident) {
-    mbx::DeviceTables tabs = c->tabs;
-    tabs.reverse = (reverse && reverse_enabled()) ? 1 : 0;
-    tabs.stream_map = d_stream_index;
-    tabs.resident = d_resident;
+static int launch_one_launch(Context* c, const Instance& e, StreamSlot& slot, bool reverse, int S, const uint8_t* d_frames,
+                             mbx_param_record* d_records, mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf,
+                             mbe_process_result* d_results, void* stream, const int32_t* d_stream_index, uint32_t* d_resident) {
+    const mbx::DeviceTables tabs = launch_tables(c, reverse, d_stream_index, d_resident);
     if (++slot.epoch == 0u) {
         slot.epoch = 1u;
     }
     slot.exp_codec = -1;   // the rows of an earlier mbx_expand_records() are being replaced
     const unsigned chunks = (unsigned)((S + 7) / 8);
-    if (ambe_codec(codec)) {
-        auto* const akernel = d_resident ? (codec == MBX_CODEC_AMBE3600X2400 ? mbx::ambe2400_one_launch_kernel_res : mbx::ambe_one_launch_kernel_res)
-                                         : (codec == MBX_CODEC_AMBE3600X2400 ? mbx::ambe2400_one_launch_kernel : mbx::ambe_one_launch_kernel);
-        hipLaunchKernelGGL(akernel, dim3(9u * chunks), dim3(64), 0, (hipStream_t)stream, S, d_frames, d_records, slot.workspace, slot.flags,
-                           slot.flags + (slot.frames + 7) / 8, slot.epoch, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-        return check_launch("ambe_one_launch_kernel");
+    uint32_t* const fallbacks = slot.flags + (slot.frames + 7) / 8;
+    if (e.family == kOneLaunchLeadArgs) {
+        hipLaunchKernelGGL(e.one_launch_lead, dim3(9u * chunks), dim3(64), 0, (hipStream_t)stream, S, front_lead_chunks(), d_frames, d_records,
+                           slot.workspace, slot.flags, fallbacks, slot.epoch, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
+    } else {
+        hipLaunchKernelGGL(e.one_launch, dim3(9u * chunks), dim3(64), 0, (hipStream_t)stream, S, d_frames, d_records, slot.workspace, slot.flags,
+                           fallbacks, slot.epoch, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
     }
-    auto* const kernel = d_resident ? mbx::imbe_one_launch_kernel_res : mbx::imbe_one_launch_kernel;
-    hipLaunchKernelGGL(kernel, dim3(9u * chunks), dim3(64), 0, (hipStream_t)stream, S, front_lead_chunks(), d_frames, d_records, slot.workspace,
-                       slot.flags, slot.flags + (slot.frames + 7) / 8, slot.epoch, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
-    return check_launch("imbe_one_launch_kernel");
+    return check_launch(e.name);
 }
 // one fused launch if the shape allows it: returns 1 when it was issued (*rc = its status), 0 when the caller goes on with the stages
 static int try_fused_one(int codec, int S, int T, const uint8_t* d_frames, mbx_param_record* d_records, mbe_parms* d_state,
                          mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, void* stream,
                          const int32_t* d_stream_index, uint32_t* d_resident, int* rc, bool own_workspace = true) {
-    if (!fused_one_ok(codec, S, T, d_frames, d_resident != nullptr)) {
+    Shape q{codec, S, T};
+    q.resident = d_resident != nullptr;
+    q.frames = true;
+    q.aligned = (reinterpret_cast<uintptr_t>(d_frames) & 3u) == 0;
+    q.workspace = own_workspace;
+    const Instance& e = select_instance(q);
+    if (e.family == kStreamArgs) {   // no instance takes the frames of this shape: the staged kernels
         return 0;
     }
     int crc;
@@ -1317,7 +1246,7 @@ static int try_fused_one(int codec, int S, int T, const uint8_t* d_frames, mbx_p
     }
     std::lock_guard<std::mutex> lock(c->mu);
     StreamSlot& slot = c->slots[stream];
-    if (one_launch_form(codec) && own_workspace) {
+    if (e.family != kFusedArgs) {   // the one-launch forms
         // A launch that is being CAPTURED into a graph would be replayed with the same epoch, and a replay would find the flags of
         // the replay before it: captured launches take the staged kernels.
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -1331,14 +1260,11 @@ static int try_fused_one(int codec, int S, int T, const uint8_t* d_frames, mbx_p
             *rc = wrc;
             return 1;
         }
-        *rc = launch_one_launch(c, slot, (slot.launches++ & 1u) != 0u, codec, S, d_frames, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results,
+        *rc = launch_one_launch(c, e, slot, (slot.launches++ & 1u) != 0u, S, d_frames, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results,
                                 stream, d_stream_index, d_resident);
         return 1;
     }
-    if (ambe_codec(codec)) {   // (no in-wave form for the AMBE codecs: a caller-owned workspace or a captured launch takes the staged kernels)
-        return 0;
-    }
-    *rc = launch_fused_one(c, (slot.launches++ & 1u) != 0u, codec, S, d_frames, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream,
+    *rc = launch_fused_one(c, e, (slot.launches++ & 1u) != 0u, codec, S, d_frames, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream,
                            d_stream_index, d_resident);
     return 1;
 }
@@ -2004,44 +1930,22 @@ int mbx_launch_slices(int codec, int S, int T) {
     return choose_slice_frames(S, T, lds_kernel_waves_per_simd(sc) * c->simds);
 }
 
-// the dominant kernel of mbx_process_batch / _resident for a batch shape (frames 4-byte aligned, as device allocations are)
+// the dominant kernel of mbx_process_batch / _resident for a batch shape (frames 4-byte aligned, as device allocations are; a launch
+// on the stream slot's own workspace that is not being captured into a graph)
 const char* mbx_batch_kernel_name(int codec, int S, int T, int resident) {
-    if (fused_one_ok(codec, S, T, nullptr, resident != 0)) {
-        if (ambe_codec(codec)) {
-            return codec == MBX_CODEC_AMBE3600X2400 ? (resident ? "ambe2400_one_launch_kernel_res" : "ambe2400_one_launch_kernel")
-                                                    : (resident ? "ambe_one_launch_kernel_res" : "ambe_one_launch_kernel");
-        }
-        if (codec == MBX_CODEC_IMBE7100X4400) {
-            return resident ? "imbe7100_stream_kernel_res1_fused" : "imbe7100_stream_kernel_one_fused";
-        }
-        if (one_launch_form(codec)) {
-            return resident ? "imbe_one_launch_kernel_res" : "imbe_one_launch_kernel";
-        }
-        return resident ? "imbe_stream_kernel_res1_fused" : "imbe_stream_kernel_one_fused";
-    }
-    if (!resident && mbx_launch_slices(codec, S, T) > 0) {
-        return (codec == MBX_CODEC_IMBE7200X4400 || codec == MBX_CODEC_IMBE7100X4400) ? "imbe_stream_kernel_lds_slice"
-               : (codec == MBX_CODEC_AMBE3600X2400)                                    ? "ambe2400_stream_kernel_lds_slice"
-                                                                                        : "ambe_stream_kernel_lds_slice";
-    }
-    return mbx_stream_kernel_name(codec, resident ? -T : T);
+    Shape q{codec, S, T};
+    q.resident = resident != 0;
+    q.rows = true;
+    q.sliced = !resident && mbx_launch_slices(codec, S, T) > 0;
+    q.frames = q.aligned = q.workspace = true;
+    return select_instance(q).name;
 }
 
 const char* mbx_stream_kernel_name(int codec, int T) {
-    if (T < 0) {   // the instances of the resident launches (mbx_process_batch_resident) with -T frames per stream
-        const bool one = T == -1 && res1_enabled();
-        return (codec == MBX_CODEC_IMBE7200X4400 || codec == MBX_CODEC_IMBE7100X4400) ? (one ? "imbe_stream_kernel_res1" : "imbe_stream_kernel_res")
-               : (codec == MBX_CODEC_AMBE3600X2400)                                    ? (one ? "ambe2400_stream_kernel_res1" : "ambe2400_stream_kernel_res")
-                                                                                        : (one ? "ambe_stream_kernel_res1" : "ambe_stream_kernel_res");
-    }
-    const bool lds = T >= kLdsResidentMinFrames && lds_resident_enabled();
-    if (codec == MBX_CODEC_IMBE7200X4400 || codec == MBX_CODEC_IMBE7100X4400) {
-        return lds ? "imbe_stream_kernel_lds" : (T == 1 ? "imbe_stream_kernel_one" : "imbe_stream_kernel");
-    }
-    if (codec == MBX_CODEC_AMBE3600X2400) {
-        return lds ? "ambe2400_stream_kernel_lds" : (T == 1 ? "ambe2400_stream_kernel_one" : "ambe2400_stream_kernel");
-    }
-    return lds ? "ambe_stream_kernel_lds" : (T == 1 ? "ambe_stream_kernel_one" : "ambe_stream_kernel");
+    Shape q{codec, 0, T < 0 ? -T : T};
+    q.resident = T < 0;   // the instances of the resident launches (mbx_process_batch_resident) with -T frames per stream ...
+    q.rows = true;        // ... on rows from the expand launch wherever the shape has one
+    return select_instance(q).name;
 }
 
 // ---- host-buffer conveniences ------------------------------------------------------------

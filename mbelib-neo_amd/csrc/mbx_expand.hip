@@ -24,6 +24,7 @@
 #include "mbx_device.h"
 #include "mbx_expand_ambe.h"
 #include "mbx_expand_imbe.h"
+#include "mbx_kernels.h"
 
 namespace mbx {
 

@@ -12,6 +12,7 @@
 // Integer work only: results are bit-exact.
 #include "mbx_device.h"
 #include "mbx_fec_frame.h"
+#include "mbx_kernels.h"
 
 namespace mbx {
 

@@ -1,0 +1,99 @@
+// mbx_kernels.h -- every __global__ kernel of libmbx_hip.so, declared exactly once.
+// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_expand.hip, mbx_stream.hip, mbx_api.hip) and by the
+// one that launches it (mbx_api.hip), so a parameter list that drifts from its definition is a compile error (an unmatched
+// overload at the launch site or in the instance table), not an unresolved symbol when the library is loaded.
+// A new kernel: declare it here, define it, and -- a stream-stage instance -- give it its row in kInstances (mbx_api.hip).
+#pragma once
+#include "mbx_device.h"
+
+// The four argument families of the stream-stage instances, written once: the declarations below, the definitions
+// (mbx_stream.hip, MBX_*_KERNEL) and the launcher's function pointer types (mbx_api.hip, Instance) all take them from here.
+#define MBX_OUT_PARAMS                                                                                                     \
+    mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16, float* __restrict__ pcmf, \
+        mbe_process_result* __restrict__ results, DeviceTables tabs_in
+// stream: S streams x Tn frames of records (and their expanded rows, or nullptr)
+#define MBX_STREAM_PARAMS int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params, MBX_OUT_PARAMS
+// slice: frames t0 .. t0 + n - 1 of the `stride` frames every stream has in the batch arrays
+#define MBX_SLICE_PARAMS \
+    int S, int stride, int t0, int n, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params, MBX_OUT_PARAMS
+// fused: one wire frame per stream, the front end in the stream's own wave
+#define MBX_FUSED_PARAMS int S, int fec_codec, const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records, MBX_OUT_PARAMS
+// one-launch: front blocks and stream blocks in one grid; after `int S` (the AMBE codecs) or `int S, int lead` (IMBE)
+#define MBX_ONE_LAUNCH_PARAMS                                                                                                     \
+    const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records, FrameParams* __restrict__ rows, uint32_t* __restrict__ flags, \
+        uint32_t* __restrict__ fallbacks, uint32_t epoch, MBX_OUT_PARAMS
+
+namespace mbx {
+
+// ---- mbx_stream.hip: the stream-stage instances --------------------------------------------------------------------------------
+__global__ void imbe_stream_kernel(MBX_STREAM_PARAMS);
+__global__ void ambe_stream_kernel(MBX_STREAM_PARAMS);
+__global__ void ambe2400_stream_kernel(MBX_STREAM_PARAMS);
+__global__ void imbe_stream_kernel_one(MBX_STREAM_PARAMS);
+__global__ void ambe_stream_kernel_one(MBX_STREAM_PARAMS);
+__global__ void ambe2400_stream_kernel_one(MBX_STREAM_PARAMS);
+__global__ void imbe_stream_kernel_lds(MBX_STREAM_PARAMS);
+__global__ void ambe_stream_kernel_lds(MBX_STREAM_PARAMS);
+__global__ void ambe2400_stream_kernel_lds(MBX_STREAM_PARAMS);
+__global__ void imbe_stream_kernel_res(MBX_STREAM_PARAMS);
+__global__ void ambe_stream_kernel_res(MBX_STREAM_PARAMS);
+__global__ void ambe2400_stream_kernel_res(MBX_STREAM_PARAMS);
+__global__ void imbe_stream_kernel_res1(MBX_STREAM_PARAMS);
+__global__ void ambe_stream_kernel_res1(MBX_STREAM_PARAMS);
+__global__ void ambe2400_stream_kernel_res1(MBX_STREAM_PARAMS);
+__global__ void imbe_stream_kernel_lds_slice(MBX_SLICE_PARAMS);
+__global__ void ambe_stream_kernel_lds_slice(MBX_SLICE_PARAMS);
+__global__ void ambe2400_stream_kernel_lds_slice(MBX_SLICE_PARAMS);
+__global__ void imbe_stream_kernel_one_fused(MBX_FUSED_PARAMS);
+__global__ void imbe_stream_kernel_res1_fused(MBX_FUSED_PARAMS);
+__global__ void imbe7100_stream_kernel_one_fused(MBX_FUSED_PARAMS);
+__global__ void imbe7100_stream_kernel_res1_fused(MBX_FUSED_PARAMS);
+__global__ void imbe_one_launch_kernel(int S, int lead, MBX_ONE_LAUNCH_PARAMS);
+__global__ void imbe_one_launch_kernel_res(int S, int lead, MBX_ONE_LAUNCH_PARAMS);
+__global__ void ambe_one_launch_kernel(int S, MBX_ONE_LAUNCH_PARAMS);
+__global__ void ambe_one_launch_kernel_res(int S, MBX_ONE_LAUNCH_PARAMS);
+__global__ void ambe2400_one_launch_kernel(int S, MBX_ONE_LAUNCH_PARAMS);
+__global__ void ambe2400_one_launch_kernel_res(int S, MBX_ONE_LAUNCH_PARAMS);
+
+// ---- mbx_stream.hip: single-frame kernels, frame server, per-stage kernels -------------------------------------------------------
+__global__ void imbe_frame_kernel(int, const uint8_t*, mbx_param_record*, mbe_parms*, mbx_stream_rng*, int16_t*, float*, mbe_process_result*, uint32_t*,
+                                  uint32_t, DeviceTables, FrameShadow);
+__global__ void ambe_frame_kernel(const uint8_t*, mbx_param_record*, mbe_parms*, mbx_stream_rng*, int16_t*, float*, mbe_process_result*, uint32_t*,
+                                  uint32_t, DeviceTables, FrameShadow);
+__global__ void ambe2400_frame_kernel(const uint8_t*, mbx_param_record*, mbe_parms*, mbx_stream_rng*, int16_t*, float*, mbe_process_result*, uint32_t*,
+                                      uint32_t, DeviceTables, FrameShadow);
+__global__ void frame_server_kernel(mbx_frame_mailbox*, unsigned, mbe_parms*, mbx_stream_rng*, int16_t*, float*, mbe_process_result*,
+                                    mbx_param_record*, DeviceTables, FrameShadow);
+__global__ void synth_speech_kernel(int, mbe_parms*, mbe_parms*, mbx_stream_rng*, float*, int16_t*, DeviceTables);
+__global__ void tone_kernel(int, const mbx_param_record*, const int32_t*, mbe_parms*, float*, int16_t*, int);
+__global__ void enhance_kernel(int, mbe_parms*);
+__global__ void smoothing_kernel(int, mbe_parms*, const mbe_parms*);
+__global__ void comfort_noise_kernel(int, mbx_stream_rng*, float*, int16_t*);
+__global__ void decode_parms_kernel(int, int, const FrameParams*, mbe_parms*, mbe_parms*, int32_t*, DeviceTables);
+__global__ void state_copy_kernel(int, mbe_parms*);
+
+// ---- mbx_fec.hip ---------------------------------------------------------------------------------------------------------------
+__global__ void fec_imbe7200x4400_kernel(const uint8_t*, size_t, mbx_param_record*, DeviceTables);
+__global__ void fec_ambe3600x2450_kernel(const uint8_t*, size_t, mbx_param_record*, DeviceTables);
+__global__ void fec_imbe7100x4400_kernel(const uint8_t*, size_t, mbx_param_record*, DeviceTables);
+__global__ void stage_in_kernel(const uint8_t*, uint8_t*, size_t);
+__global__ void floattoshort_kernel(const float*, int16_t*, size_t);
+__global__ void result_histogram_kernel(const mbe_process_result*, size_t, unsigned long long*);
+__global__ void fec_stage_kernel(int, int, const uint8_t*, size_t, uint8_t*, mbx_param_record*, DeviceTables);
+__global__ void pack_cells_kernel(int, const char*, size_t, uint8_t*, int32_t*);
+__global__ void ecc_words_kernel(int, const uint32_t*, size_t, uint32_t*, int32_t*, DeviceTables);
+__global__ void fec_imbe7200x4400_soft_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
+__global__ void fec_ambe3600x2450_soft_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
+__global__ void fec_imbe7100x4400_soft_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
+__global__ void ecc_soft_words_kernel(int, const mbe_soft_bit*, size_t, uint32_t*, int32_t*, DeviceTables);
+
+// ---- mbx_expand.hip ------------------------------------------------------------------------------------------------------------
+__global__ void expand_imbe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
+__global__ void expand_ambe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
+__global__ void expand_ambe2400_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
+
+// ---- mbx_api.hip ---------------------------------------------------------------------------------------------------------------
+// (C linkage: defined inside the extern "C" block of the entry points, so the profiler prints the bare name)
+extern "C" __global__ void resident_materialize_kernel(int, const int32_t*, mbe_parms*, uint32_t*);
+
+}  // namespace mbx

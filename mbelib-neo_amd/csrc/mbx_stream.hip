@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "mbx_device.h"
+#include "mbx_kernels.h"
 #include "mbx_expand_ambe.h"
 // Development instrumentation (-DMBX_STAGE_TIMES, never in the product build; tools/stage_times.py): where the waves of a LAUNCH
 // spend their lives -- every wave adds the 100 MHz wall-clock time between consecutive marks of the one-frame IMBE body and of
@@ -85,9 +86,6 @@ namespace mbx { __device__ unsigned long long g_frame_stamps[16]; }
 // (and lose 1-6 % when a new wave's loads or a finishing wave's stores are given priority: tried, dropped); the AMBE bodies
 // lose 1-4 % with a raised priority in their front part or in the eight-frame expansion pass: not there.  Raising the rest of the
 // synthesiser (noise / phases, between bank and transform, overlap-add) as well costs 0.2-3.6 %: the point is the contrast.
-#ifndef MBX_AMBE_GATHER_STORES
-#define MBX_AMBE_GATHER_STORES 1   // gathered header stores in the one-frame AMBE instances too: 78 VGPRs = six waves, and still 1.7 % faster than seven waves with fourteen one-lane stores per struct (with a 16 B spill at seven: 2.4 % slower)
-#endif
 #ifndef MBX_PRIO_BANK
 #define MBX_PRIO_BANK 2
 #endif
@@ -97,27 +95,8 @@ namespace mbx { __device__ unsigned long long g_frame_stamps[16]; }
 #ifndef MBX_PRIO_FRONT_IMBE
 #define MBX_PRIO_FRONT_IMBE 3
 #endif
-#ifndef MBX_FLAT_LOADS
-#define MBX_FLAT_LOADS 1   // one-launch T = 1 kernels: unconditional struct loads (see load_parms_arrays)
-#endif
-#ifndef MBX_EARLY_NOISE
-#define MBX_EARLY_NOISE 1   // the next overlap's jump-ahead constants requested ahead of the voiced bank (synth_core)
-#endif
 #ifndef MBX_PRIO_FRONT_BLOCK
 #define MBX_PRIO_FRONT_BLOCK 3
-#endif
-#ifndef MBX_AMBE_EARLY_NOISE
-#define MBX_AMBE_EARLY_NOISE 0     // 1: the AMBE one-frame instances request the next overlap's jump-ahead constants ahead of the bank too (kEarly);
-                                   // off since round 6: its two registers across the bank are what kept those instances at six waves per SIMD
-#endif
-#ifndef MBX_RES_VIEW_FROM_CUR
-#define MBX_RES_VIEW_FROM_CUR 1    // 0 (A/B builds only): resident one-frame instances load prev_mp_enhanced's view separately (see enh_view_of)
-#endif
-#ifndef MBX_BANK_TRIM
-#define MBX_BANK_TRIM 1            // 0 (A/B builds only): the voiced bank's loop always starts at harmonic 1
-#endif
-#ifndef MBX_BANK_ALWAYS_DRIFT
-#define MBX_BANK_ALWAYS_DRIFT 0    // 1 (A/B builds only): the voiced bank always forms its first-order drift sums, as up to round 5
 #endif
 #ifndef MBX_PARK_N
 #define MBX_PARK_N 8   // how many per-lane values wait in LDS across the unvoiced transform pair (synth_core)
@@ -1318,7 +1297,7 @@ __device__ bool synth_core(float out[3], Parms& cur, Parms& prev, bool have_rm0,
     // bank, they are there when the bank is done -- an all-voiced frame then has no memory round trip between the bank and its
     // overlap-add (tools/stage_times.py: that round trip was 1.05 us of a one-frame wave's 20).  Two more registers across the bank.
     uint32_t q64_early = 0u, q128_early = 0u;
-    constexpr bool kEarlyNoise = MBX_EARLY_NOISE != 0 && kSnap && kEarly;
+    constexpr bool kEarlyNoise = kSnap && kEarly;
     if (kEarlyNoise && snap && !cold) {
         q64_early = lcg_req(lane + 64);
         q128_early = lcg_req(lane < 32 ? lane + 128 : 160);
@@ -1463,7 +1442,7 @@ __device__ bool synth_core(float out[3], Parms& cur, Parms& prev, bool have_rm0,
             // interleaved A/B (profiles/r06/ab_bank_variants.log): 65,536 x 16 IMBE -6.1 %, 8,192 x 128 AMBE+2 -5.5 %, 65,536 x 1 -2.1 / -1.6 %.
             // (Also tried there and NOT kept: running the loop on one model's half alone, in plain VOP2 instructions, when the other model
             // has no windowed-voiced harmonic -- 37 % of AMBE+2's random-bit frames: +0.9 ... +1.9 %.)
-            const bool need_drift = MBX_BANK_ALWAYS_DRIFT || !(wave_sum(drift_w) * (float)(kMidPrev * 7) < 0.125f);
+            const bool need_drift = !(wave_sum(drift_w) * (float)(kMidPrev * 7) < 0.125f);
             v2f Ec, Es;   // per-distance steps e^{i w0 k} (.x prev model, .y cur model); their error is amplified by l
             {
                 float c, d;
@@ -1489,7 +1468,7 @@ __device__ bool synth_core(float out[3], Parms& cur, Parms& prev, bool have_rm0,
             // squarings of the step (the same first-order error growth as the seven rotations they replace).
             const unsigned long long live = __ballot(wv_p || wv_c);   // != 0 here
             const int last = 63 - __clzll((long long)live);
-            const bool from8 = MBX_BANK_TRIM && (live & 0xfeULL) == 0ULL;
+            const bool from8 = (live & 0xfeULL) == 0ULL;
             const int first = from8 ? 8 : 1;
             v2f Qc0 = Ec, Qs0 = Es;   // harmonic 1
             if (from8) {
@@ -1957,9 +1936,6 @@ struct ParkedState {};   // kPark = false: nothing in LDS
 // 2,604 B of LDS less per wave: 5,200 B = five allocation granules instead of eight.
 struct ParkedPrevOnly {
     mbe_parms prev;
-#ifdef MBX_EXP_LDS_PAD
-    char pad[MBX_EXP_LDS_PAD];
-#endif
 };
 
 template <bool kPark>
@@ -2124,11 +2100,10 @@ __device__ __forceinline__ uint4 frame_record(int fec_codec, Wire wire, mbx_para
 // (mbx_front_imbe.h: FEC + expansion of eight frames by one wave), handed over through a flag word (FrontLink); should the row not
 // be there in time the wave runs the kFuse = 1 front end itself, so nothing here depends on the order in which blocks are dispatched.
 // A launch may hand a workgroup only a SLICE of its stream's frames (the time-sliced launches, *_stream_kernel_lds_sliced): frames
-// t0 .. t0 + Tn - 1 of the `stride` the stream has in this call, for the stream at position `pos` of the walk.
+// t0 .. t0 + Tn - 1 of the `stride` the stream has in this call.
 struct FrameSlice {
     int stride = 0;   // frames per stream in the batch arrays (0: Tn, the whole stream)
     int t0 = 0;       // first frame of the slice
-    int pos = -1;     // the workgroup's position among the streams (its blockIdx.x when < 0)
 };
 // INVARIANT of the hand-over: it uses RELAXED agent-scope atomics, a hand-written `s_waitcnt vmcnt(0)` between the
 // producer's row stores and its flag store, and compiler barriers -- no release / acquire pair.  That is sound ONLY because every word
@@ -2156,13 +2131,6 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
                  int fec_codec = 0, FrameShadow shadow = FrameShadow{}, FrontLink link = FrontLink{}, FrameSlice slice = FrameSlice{}) {
     using ScratchT = WaveScratchT<kPark ? 0 : MBX_PARK_N>;
     ScratchT* scratch_ptr;
-#ifdef MBX_EXP_PAIR   // EXPERIMENT (never the product build): two streams per 128-thread workgroup, see imbe_stream_kernel_lds_pairexp
-    __shared__ ScratchT scratch_pair[2];
-    __shared__ std::conditional_t<kPark, ParkedPrevOnly, ParkedState<false>> park_pair[2];
-    const int wave_in_group = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) & 1;
-    scratch_ptr = &scratch_pair[wave_in_group];
-    auto& park = park_pair[wave_in_group];
-#else
     if constexpr (kFuse == 3) {
         scratch_ptr = reinterpret_cast<ScratchT*>(link.lds);
     } else {
@@ -2170,10 +2138,9 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         scratch_ptr = &scratch_own;
     }
     __shared__ std::conditional_t<kPark, ParkedPrevOnly, ParkedState<false>> park;
-#endif
     ScratchT& scratch = *scratch_ptr;
     uint4 rec_in = make_uint4(0u, 0u, 0u, 0u);
-    const int bpos = (kFuse == 3) ? link.pos : (slice.pos >= 0 ? slice.pos : (int)blockIdx.x);
+    const int bpos = (kFuse == 3) ? link.pos : (int)blockIdx.x;
     if (bpos >= S) {
         return;
     }
@@ -2286,16 +2253,16 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         } else if (params) {   // the frame's FrameParams row is what the frame needs first: requested first (tools/stage_times.py: asked for
             row_first = params[fbase].v[lane_in];   // after the scalars of cur_mp had arrived, it cost 2.5 us of a wave's 22)
         }
-        constexpr bool kFlat = MBX_FLAT_LOADS && kFuse != 0;
+        constexpr bool kFlat = kFuse != 0;   // the fused and one-launch T = 1 instances: unconditional struct loads (see load_parms_arrays)
         const uint32_t h_cur = load_header(slot_cur, lane_in);
-        if constexpr (!(kRes && MBX_RES_VIEW_FROM_CUR)) {
+        if constexpr (!kRes) {
             h_prev_first = load_header(slot_prev, lane_in);
             h_enh_first = load_header(enh_src, lane_in);
         }
         load_rng(rng, &rngs[slot]);
         load_prev_arrays<kFlat>(prev_first, slot_prev, lane_in);
         load_parms_arrays<kFlat>(cur, slot_cur, lane_in);
-        if constexpr (kRes && MBX_RES_VIEW_FROM_CUR) {
+        if constexpr (kRes) {
             asm volatile("" ::: "memory");   // (everything above is requested before the flag is looked at)
             if (!elided1) {   // (elided: both come from cur_mp's registers where the frame loop starts, see enh_view_of / prev_header_of)
                 h_prev_first = load_header(slot_prev, lane_in);
@@ -2397,12 +2364,6 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
             lane &= 63;
         }
         const DeviceTables& tabs = ft;
-#if defined(MBX_EXP_PAIR) && MBX_EXP_PAIR > 0   // the rendezvous a paired transform would need: MBX_EXP_PAIR barriers per frame
-#pragma unroll
-        for (int bq = 0; bq < MBX_EXP_PAIR; ++bq) {
-            __builtin_amdgcn_s_barrier();
-        }
-#endif
         if constexpr (kPark && !kFrame) {
             __builtin_amdgcn_s_setprio(MBX_PRIO_FRONT_IMBE);
         }
@@ -2419,7 +2380,7 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
             load_prev_view_lds(prev, slot_prev, lane);
         } else if constexpr (kOne) {   // requested at the start, together with cur_mp
             prev = prev_first;
-            if (kRes && MBX_RES_VIEW_FROM_CUR && elided1) {   // cur_mp still holds what the last frame left: that IS prev_mp_enhanced
+            if (kRes && elided1) {   // cur_mp still holds what the last frame left: that IS prev_mp_enhanced
                 prev_header_of(prev, cur);
                 enh_view_of(enh, cur);
                 enh.w0 = cur.w0;
@@ -2600,50 +2561,6 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
     MBX_STAMP(8, true);
 }
 
-__global__ void __launch_bounds__(64, MBX_STREAM_WAVES_PER_SIMD)
-imbe_stream_kernel(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                   mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                   float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    imbe_stream_body<false>(S, Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
-// T = 1 (a tick of the per-tick API, BASELINE configs[1]): the HBM-slot body without a frame loop, every request of the frame
-// issued before the first wait.
-__global__ void __launch_bounds__(64, MBX_STREAM_WAVES_PER_SIMD)
-imbe_stream_kernel_one(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                       mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                       float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    imbe_stream_body<false, false, false, true>(S, Tn > 1 ? 1 : Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
-// The whole T = 1 step as ONE launch (kFuse): wire frames in, PCM / results / records / state out.
-// fec_codec: MBX_CODEC_IMBE7200X4400 or MBX_CODEC_IMBE7100X4400 (own front end, the same stream stage).
-__global__ void __launch_bounds__(64, MBX_STREAM_WAVES_PER_SIMD)
-imbe_stream_kernel_one_fused(int S, int fec_codec, const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records,
-                             mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                             float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    imbe_stream_body<false, false, false, true, 1>(S, 1, records, nullptr, state, rngs, pcm16, pcmf, results, tabs_in, frames, fec_codec);
-}
-__global__ void __launch_bounds__(64, MBX_STREAM_WAVES_PER_SIMD)
-imbe_stream_kernel_res1_fused(int S, int fec_codec, const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records,
-                              mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                              float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    imbe_stream_body<false, false, true, true, 1>(S, 1, records, nullptr, state, rngs, pcm16, pcmf, results, tabs_in, frames, fec_codec);
-}
-// IMBE 7100x4400 frames: own front end (whole, then the expansion's requests), the same stream stage
-__global__ void __launch_bounds__(64, MBX_STREAM_WAVES_PER_SIMD)
-imbe7100_stream_kernel_one_fused(int S, int fec_codec, const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records,
-                                 mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                                 float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    imbe_stream_body<false, false, false, true, 2>(S, 1, records, nullptr, state, rngs, pcm16, pcmf, results, tabs_in, frames, fec_codec);
-}
-__global__ void __launch_bounds__(64, MBX_STREAM_WAVES_PER_SIMD)
-imbe7100_stream_kernel_res1_fused(int S, int fec_codec, const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records,
-                                  mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                                  float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    imbe_stream_body<false, false, true, true, 2>(S, 1, records, nullptr, state, rngs, pcm16, pcmf, results, tabs_in, frames, fec_codec);
-}
-
 // ------------------------------------------------------------------------------------------
 // imbe_one_launch_kernel: the whole T = 1 step of the IMBE 7200x4400 codec as ONE launch whose grid holds two kinds of
 // one-wave workgroups: FRONT blocks (FEC + parameter expansion of eight frames each, mbx_front_imbe.h) and STREAM blocks
@@ -2734,33 +2651,6 @@ __device__ __forceinline__ void imbe_one_launch_body(int S, int lead, const uint
     link.pos = pos;
     imbe_stream_body<false, false, kRes, true, 3>(S, 1, records, rows, state, rngs, pcm16, pcmf, results, tabs_in, frames, MBX_CODEC_IMBE7200X4400,
                                                   FrameShadow{}, link);
-}
-
-__global__ void __launch_bounds__(64, MBX_STREAM_WAVES_PER_SIMD)
-imbe_one_launch_kernel(int S, int lead, const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records, FrameParams* __restrict__ rows,
-                       uint32_t* __restrict__ flags, uint32_t* __restrict__ fallbacks, uint32_t epoch, mbe_parms* __restrict__ state,
-                       mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16, float* __restrict__ pcmf,
-                       mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    imbe_one_launch_body<false>(S, lead, frames, records, rows, flags, fallbacks, epoch, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-__global__ void __launch_bounds__(64, MBX_STREAM_WAVES_PER_SIMD)
-imbe_one_launch_kernel_res(int S, int lead, const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records, FrameParams* __restrict__ rows,
-                           uint32_t* __restrict__ flags, uint32_t* __restrict__ fallbacks, uint32_t epoch, mbe_parms* __restrict__ state,
-                           mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16, float* __restrict__ pcmf,
-                           mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    imbe_one_launch_body<true>(S, lead, frames, records, rows, flags, fallbacks, epoch, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
-// T >= 4: prev_mp resident in LDS (see ParkedPrevOnly).  5,200 B of LDS per wave allow 25 waves per CU, so the register
-// file decides the occupancy: 79 VGPRs = six waves per SIMD.  Measured on configs[3] (65,536 x T=16) with padded LDS:
-// two waves per SIMD 5.15 ms, three 3.91, four (round 2) 3.40, five 2.86, six 2.76.
-#define MBX_LDS_KERNEL_ATTR(waves) __launch_bounds__(64, waves)
-// (MBX_IMBE_LDS_WAVES_PER_SIMD / MBX_AMBE_LDS_WAVES_PER_SIMD: mbx_device.h, shared with the launcher's slicing heuristic)
-__global__ void MBX_LDS_KERNEL_ATTR(MBX_IMBE_LDS_WAVES_PER_SIMD)
-imbe_stream_kernel_lds(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                       mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                       float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    imbe_stream_body<true>(S, Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3007,7 +2897,9 @@ __device__ void tone_dstar_frame(float out[3], int id1, Parms& cur, int lane, in
 // k2400: AMBE 3600x2400 (D-STAR) frame policy, ref src/ambe/ambe3600x2400.c:629-763 -- no erasure class, D-STAR
 // tones, repeats decided by the total error count alone.  The prediction (decode_ambe) is common.
 // kFuse = 3 (with kOne): the stream blocks of ambe_one_launch_kernel -- see imbe_stream_body and FrontLink
-template <bool k2400, bool kPark, bool kFrame = false, bool kRes = false, bool kOne = false, int kFuse = 0>   // kOne: see imbe_stream_body
+// kOne: see imbe_stream_body.  Its header stores are gathered here too (store_parms<kOne>): 78 VGPRs = six waves per SIMD, and still 1.7 %
+// faster than seven waves with fourteen one-lane stores per struct (with a 16 B spill at seven: 2.4 % slower).
+template <bool k2400, bool kPark, bool kFrame = false, bool kRes = false, bool kOne = false, int kFuse = 0>
 __device__ __forceinline__ void
 ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
                  mbe_parms* __restrict__ state,
@@ -3034,7 +2926,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
 #endif
     constexpr int kXRows = MBX_AMBE_XROWS, kXStride = 65;
     __shared__ float xrows[kPark ? kXRows : 1][kPark ? kXStride : 1];
-    const int bpos = (kFuse == 3) ? link.pos : (slice.pos >= 0 ? slice.pos : (int)blockIdx.x);
+    const int bpos = (kFuse == 3) ? link.pos : (int)blockIdx.x;
     if (bpos >= S) {
         return;
     }
@@ -3095,7 +2987,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
                 load_parms<kOne>(home, home_prev, lane_in);
                 load_parms<kOne>(cur, slot_cur, lane_in);
                 load_rng(rng, &rngs[slot]);
-                store_parms<kOne && MBX_AMBE_GATHER_STORES>(home, slot_prev, lane_in);
+                store_parms<kOne>(home, slot_prev, lane_in);
             }
             wave_lds_sync();
         } else {
@@ -3122,7 +3014,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
                 rec_in = frame_record(MBX_CODEC_AMBE3600X2450, wire_in, const_cast<mbx_param_record*>(records), tabs_in.t, lane_in);
             }
             set_parms_header(home, h_home);
-            store_parms<kOne && MBX_AMBE_GATHER_STORES>(home, slot_prev, lane_in);
+            store_parms<kOne>(home, slot_prev, lane_in);
         }
         set_enh_header(enh_keep, h_enh);
         set_parms_header(cur, h_cur);
@@ -3139,14 +3031,14 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         }
         const mbe_parms* const enh_src = elided ? slot_cur : slot_enh;
         const uint32_t h_cur = load_header(slot_cur, lane_in);
-        if constexpr (!(kRes && MBX_RES_VIEW_FROM_CUR)) {
+        if constexpr (!kRes) {
             h_prev_first = load_header(slot_prev, lane_in);
             h_enh_first = load_header(enh_src, lane_in);
         }
         load_rng(rng, &rngs[slot]);
         load_prev_arrays(prev_first, slot_prev, lane_in);
         load_parms_arrays(cur, slot_cur, lane_in);
-        if constexpr (kRes && MBX_RES_VIEW_FROM_CUR) {
+        if constexpr (kRes) {
             asm volatile("" ::: "memory");   // (everything above is requested before the flag is looked at)
             enh_from_cur = elided;
             if (!elided) {   // (elided: both come from cur_mp's registers where the frame loop starts, see enh_view_of / prev_header_of)
@@ -3272,7 +3164,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         } else if constexpr (kOne) {   // requested at the start, together with cur_mp
             prev = prev_first;
             scratch.x.fp[lane] = row_first;
-            if (kRes && MBX_RES_VIEW_FROM_CUR && enh_from_cur) {   // cur_mp still holds what the last frame left: that IS prev_mp_enhanced
+            if (kRes && enh_from_cur) {   // cur_mp still holds what the last frame left: that IS prev_mp_enhanced
                 prev_header_of(prev, cur);
                 enh_view_of(enh, cur);
                 enh.w0 = cur.w0;
@@ -3306,14 +3198,14 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
             if (fabsf(prev.mutingThreshold - MBE_MUTING_THRESHOLD_AMBE) > 1e-6f) {
                 init_ambe_parms(prev, lane);
                 cur = prev;
-                store_parms<kOne && MBX_AMBE_GATHER_STORES>(prev, slot_prev, lane);
+                store_parms<kOne>(prev, slot_prev, lane);
                 prev_partial = false;
                 if constexpr (kPark) {
                     keep_enh_view(prev);
                     enh = enh_keep;
                     synced = true;
                 } else {
-                    store_parms<kOne && MBX_AMBE_GATHER_STORES>(prev, slot_enh, lane);
+                    store_parms<kOne>(prev, slot_enh, lane);
                     elided = false;   // (all three structs have just been written whole)
                     slot_fence<kPark>();
                     load_enh_view(enh, slot_enh, lane);
@@ -3327,7 +3219,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
                 const int c0v_early = ((flags & MBE_PROCESS_FLAG_C0_VALID) != 0u) ? c0 : 0;
                 const bool keeps_enh = k2400 ? ((cls >= 7) && (cls <= 122) && (c0v_early < 2) && (total < 3)) : (cls == 7);
                 if (keeps_enh && synced) {
-                    store_parms<kOne && MBX_AMBE_GATHER_STORES>(cur, home_enh, lane);
+                    store_parms<kOne>(cur, home_enh, lane);
                     synced = false;
                 }
             }
@@ -3336,7 +3228,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
                 const int c0v_early = ((flags & MBE_PROCESS_FLAG_C0_VALID) != 0u) ? c0 : 0;
                 const bool keeps_enh = k2400 ? ((cls >= 7) && (cls <= 122) && (c0v_early < 2) && (total < 3)) : (cls == 7);
                 if (keeps_enh && elided) {
-                    store_parms<kOne && MBX_AMBE_GATHER_STORES>(cur, slot_enh, lane);
+                    store_parms<kOne>(cur, slot_enh, lane);
                     elided = false;
                 }
             }
@@ -3424,7 +3316,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         float out[3];
         float rm0 = 0.0f;
         if (action == kVoice) {
-            store_parms<kOne && MBX_AMBE_GATHER_STORES>(cur, slot_prev, lane);   // prev_mp := cur_mp
+            store_parms<kOne>(cur, slot_prev, lane);   // prev_mp := cur_mp
             prev_partial = false;
             cur.log2Ml = 0.0f;                   // read back from the snapshot after the synthesiser (see the IMBE kernel)
             cur.uw[0] = cur.uw[1] = cur.uw[2] = cur.uw[3] = 0.0f;
@@ -3432,7 +3324,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         } else if (action == kToneFallback) {
             // invalid tone id: run the synthesiser on a copy of the enhanced model.  `cur` is parked in
             // its slot meanwhile so that still only two structs are live.
-            store_parms<kOne && MBX_AMBE_GATHER_STORES>(cur, slot_cur, lane);
+            store_parms<kOne>(cur, slot_cur, lane);
             if constexpr (kPark) {
                 // The copy takes the LDS home of prev_mp for the duration (it is the synthesiser's snapshot), prev_mp waits in
                 // its HBM home.  prev_mp_enhanced is current in ITS home: this is a tone-class frame (see `synced`).
@@ -3454,7 +3346,9 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         }
         if (action == kVoice || action == kToneFallback) {
             const mbe_parms* snap = (kPark || action == kVoice) ? slot_prev : slot_enh;
-            const bool fresh = synth_core<true, kPark, ScratchT, kOne && MBX_AMBE_EARLY_NOISE>(out, cur, enh, action == kVoice, rm0, rng, scratch, tabs, lane, snap);
+            // (no kEarly, not even with kOne: the two registers the early noise request holds across the bank are what kept the one-frame AMBE
+            // instances at six waves per SIMD)
+            const bool fresh = synth_core<true, kPark, ScratchT>(out, cur, enh, action == kVoice, rm0, rng, scratch, tabs, lane, snap);
             {
                 slot_fence<kPark>();
                 const float* f = reinterpret_cast<const float*>(snap);
@@ -3478,7 +3372,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
                 if (action == kVoice) {
                     synced = true;
                 } else {
-                    store_parms<kOne && MBX_AMBE_GATHER_STORES>(cur, home_enh, lane);    // the replayed copy is NOT cur_mp: it goes to the home (synced stays false)
+                    store_parms<kOne>(cur, home_enh, lane);    // the replayed copy is NOT cur_mp: it goes to the home (synced stays false)
                     wave_lds_sync();
                     __threadfence_block();
                     copy_parms<kOne>(slot_prev, home_prev, lane);   // prev_mp returns to LDS
@@ -3487,7 +3381,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
             } else if (res1 && action == kVoice) {
                 elided = true;   // prev_mp_enhanced := cur_mp, not written
             } else {
-                store_parms<kOne && MBX_AMBE_GATHER_STORES>(cur, slot_enh, lane);   // (the replayed copy of an invalid tone is NOT cur_mp: it is stored)
+                store_parms<kOne>(cur, slot_enh, lane);   // (the replayed copy of an invalid tone is NOT cur_mp: it is stored)
             }
             if (action == kToneFallback) {
                 __threadfence_block();
@@ -3497,14 +3391,14 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
             tone_frame(out, tw, cur, lane, tabs.tones_off);
         } else if (action == kToneDstar) {
             tone_dstar_frame(out, bad, cur, lane, tabs.tones_off);
-            store_parms<kOne && MBX_AMBE_GATHER_STORES>(cur, slot_prev, lane);   // mbe_moveMbeParms(cur_mp, prev_mp)
+            store_parms<kOne>(cur, slot_prev, lane);   // mbe_moveMbeParms(cur_mp, prev_mp)
             prev_partial = false;
         } else {
             comfort_noise(out, rng, lane);
             if (action == kNoiseReinit) {   // mbe_initAmbeParms_common(cur, prev, prev_enhanced)
                 init_ambe_parms(cur, lane);
             }
-            store_parms<kOne && MBX_AMBE_GATHER_STORES>(cur, slot_prev, lane);
+            store_parms<kOne>(cur, slot_prev, lane);
             prev_partial = false;
             if constexpr (kPark) {
                 keep_enh_view(cur);
@@ -3512,7 +3406,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
             } else if (res1) {
                 elided = true;
             } else {
-                store_parms<kOne && MBX_AMBE_GATHER_STORES>(cur, slot_enh, lane);
+                store_parms<kOne>(cur, slot_enh, lane);
             }
         }
         if (t + 1 < Tn) {
@@ -3537,7 +3431,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         // the store form its address again from the SGPR pair: one v_lshl_add_u64 instead of a scratch round trip.
         mbe_parms* slot_cur_again = slot_cur;
         asm volatile("" : "+s"(slot_cur_again));
-        store_parms<kOne && MBX_AMBE_GATHER_STORES>(cur, slot_cur_again, lane_in);
+        store_parms<kOne>(cur, slot_cur_again, lane_in);
     }
     store_rng(rng, &rngs[slot], lane_in);
     if (res1 && lane_in == 0) {
@@ -3549,7 +3443,7 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
                 res[slot] = synced ? 1u : 0u;   // a resident launch leaves the struct elided while it equals cur_mp
             }
         } else if (synced) {
-            store_parms<kOne && MBX_AMBE_GATHER_STORES>(cur, home_enh, lane_in);
+            store_parms<kOne>(cur, home_enh, lane_in);
         }
         wave_lds_sync();
         if (!prev_partial) {
@@ -3557,9 +3451,9 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         }
         if constexpr (kFrame) {
             if (shadow.state) {   // the device copy of what has just gone to the caller; complete only if prev_mp_enhanced is cur_mp
-                store_parms<kOne && MBX_AMBE_GATHER_STORES, false>(cur, &shadow.state[0], lane_in);   // (a tone frame leaves prev_mp_enhanced at its pinned home alone: the next
+                store_parms<kOne, false>(cur, &shadow.state[0], lane_in);   // (a tone frame leaves prev_mp_enhanced at its pinned home alone: the next
                 if (synced) {                                  //  call then takes the state from the caller's structs again)
-                    store_parms<kOne && MBX_AMBE_GATHER_STORES, false>(cur, &shadow.state[2], lane_in);
+                    store_parms<kOne, false>(cur, &shadow.state[2], lane_in);
                 }
                 copy_parms(&shadow.state[1], slot_prev, lane_in);
                 store_rng(rng, shadow.rng, lane_in);
@@ -3699,30 +3593,6 @@ frame_server_kernel(mbx_frame_mailbox* mb, unsigned idle_ticks /* of the 100 MHz
     }
 }
 
-// mbe_synthesizeSpeechf for S independent (cur, prev) pairs.
-
-// T = 1: the HBM-slot bodies without a frame loop (see imbe_stream_kernel_one)
-#ifndef MBX_AMBE_ONE_WAVES_PER_SIMD
-#define MBX_AMBE_ONE_WAVES_PER_SIMD 7   // round 6: SEVEN waves (72 VGPRs, no scratch) once the one-frame AMBE instances stopped requesting the next
-#endif                                  // overlap's noise constants ahead of the bank (MBX_AMBE_EARLY_NOISE 0: two registers across the bank) and the
-                                        // interpolated branch stopped holding n^2 across its loop: 65,536 x 1 AMBE+2 -1.7 %, resident -2.5 %
-                                        // (profiles/r06/ab_ambe_seven_waves.log; round 5 forced seven with 44 B of scratch: +7.8 %)
-#ifndef MBX_AMBE_ONE_RES_WAVES_PER_SIMD
-#define MBX_AMBE_ONE_RES_WAVES_PER_SIMD 6   // ambe_one_launch_kernel_res alone still needs 12 B of scratch at seven (the transform pair's peak)
-#endif
-__global__ void __launch_bounds__(64, MBX_AMBE_ONE_WAVES_PER_SIMD)
-ambe_stream_kernel_one(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                       mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                       float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_stream_body<false, false, false, false, true>(S, Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-__global__ void __launch_bounds__(64, MBX_AMBE2400_WAVES_PER_SIMD)
-ambe2400_stream_kernel_one(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                           mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                           float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_stream_body<true, false, false, false, true>(S, Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
 // ambe_one_launch_kernel / ambe2400_one_launch_kernel: the T = 1 step of the AMBE codecs as ONE launch -- front blocks (the frame's
 // FEC by the first lane of its eight, then the eight-lane expansion of mbx_expand_ambe.h) and stream blocks in one grid, exactly as
 // imbe_one_launch_kernel (FrontLink; all front blocks first in the grid).
@@ -3795,162 +3665,8 @@ __device__ __forceinline__ void ambe_one_launch_body(int S, const uint8_t* __res
     ambe_stream_body<k2400, false, false, kRes, true, 3>(S, 1, records, rows, state, rngs, pcm16, pcmf, results, tabs_in, frames, FrameShadow{},
                                                          FrameSlice{}, link);
 }
-__global__ void __launch_bounds__(64, MBX_AMBE_ONE_WAVES_PER_SIMD)
-ambe_one_launch_kernel(int S, const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records, FrameParams* __restrict__ rows,
-                       uint32_t* __restrict__ flags, uint32_t* __restrict__ fallbacks, uint32_t epoch, mbe_parms* __restrict__ state,
-                       mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16, float* __restrict__ pcmf,
-                       mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_one_launch_body<false>(S, frames, records, rows, flags, fallbacks, epoch, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-__global__ void __launch_bounds__(64, MBX_AMBE_ONE_RES_WAVES_PER_SIMD)
-ambe_one_launch_kernel_res(int S, const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records, FrameParams* __restrict__ rows,
-                           uint32_t* __restrict__ flags, uint32_t* __restrict__ fallbacks, uint32_t epoch, mbe_parms* __restrict__ state,
-                           mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16, float* __restrict__ pcmf,
-                           mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_one_launch_body<false, true>(S, frames, records, rows, flags, fallbacks, epoch, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-__global__ void __launch_bounds__(64, MBX_AMBE2400_WAVES_PER_SIMD)
-ambe2400_one_launch_kernel_res(int S, const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records, FrameParams* __restrict__ rows,
-                               uint32_t* __restrict__ flags, uint32_t* __restrict__ fallbacks, uint32_t epoch, mbe_parms* __restrict__ state,
-                               mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16, float* __restrict__ pcmf,
-                               mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_one_launch_body<true, true>(S, frames, records, rows, flags, fallbacks, epoch, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-__global__ void __launch_bounds__(64, MBX_AMBE2400_WAVES_PER_SIMD)
-ambe2400_one_launch_kernel(int S, const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records, FrameParams* __restrict__ rows,
-                           uint32_t* __restrict__ flags, uint32_t* __restrict__ fallbacks, uint32_t epoch, mbe_parms* __restrict__ state,
-                           mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16, float* __restrict__ pcmf,
-                           mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_one_launch_body<true>(S, frames, records, rows, flags, fallbacks, epoch, state, rngs, pcm16, pcmf, results, tabs_in);
-}
 
-__global__ void __launch_bounds__(64, MBX_AMBE_WAVES_PER_SIMD)
-ambe_stream_kernel(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                   mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                   float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_stream_body<false, false>(S, Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
-__global__ void __launch_bounds__(64, MBX_AMBE2400_WAVES_PER_SIMD)
-ambe2400_stream_kernel(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                       mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                       float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_stream_body<true, false>(S, Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
-// T >= 4: prev_mp / prev_mp_enhanced resident in LDS (see the IMBE kernel)
-__global__ void MBX_LDS_KERNEL_ATTR(MBX_AMBE_LDS_WAVES_PER_SIMD)
-ambe_stream_kernel_lds(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                       mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                       float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_stream_body<false, true>(S, Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
-__global__ void MBX_LDS_KERNEL_ATTR(MBX_AMBE_LDS_WAVES_PER_SIMD)
-ambe2400_stream_kernel_lds(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                           mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                           float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_stream_body<true, true>(S, Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
-#ifdef MBX_EXP_PAIR
-// EXPERIMENT ("two streams per wave for the transform pair"): what does it cost two streams to share a
-// workgroup and meet at MBX_EXP_PAIR barriers per frame -- the rendezvous any pairing of their unvoiced transforms needs -- BEFORE
-// any of the pairing's arithmetic is saved?  Two waves per workgroup, wave w decodes stream 2 b + w with the unchanged body.
-// (An odd stream count would leave a wave without a partner at the barriers: the experiment runs even S only.)
-__global__ void __launch_bounds__(128, MBX_IMBE_LDS_WAVES_PER_SIMD)
-imbe_stream_kernel_lds_pairexp(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                               mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                               float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    FrameSlice sl;
-    sl.pos = 2 * (int)blockIdx.x + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (wave-uniform: say so)
-    imbe_stream_body<true>(S, Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in, nullptr, 0, FrameShadow{}, FrontLink{}, sl);
-}
-#endif
-
-// ------------------------------------------------------------------------------------------
-// Slice kernels (*_stream_kernel_lds_slice): the LDS-resident instances on a SLICE of every stream's frames -- frames t0 ..
-// t0 + n - 1 of the `stride` frames a stream has in the batch arrays.  A slice IS a launch of n frames per stream (state in from
-// HBM, state out to HBM); the launcher (mbx_api.hip, sliced_launch) cuts a launch whose stream count does not fill the device's
-// wave slots evenly into groups of streams x slices of frames and issues them on the caller's stream and two internal HIP streams (three groups), so that the slots one
-// group's slice leaves empty are taken by the other group's.
-// ------------------------------------------------------------------------------------------
-__global__ void MBX_LDS_KERNEL_ATTR(MBX_IMBE_LDS_WAVES_PER_SIMD)
-imbe_stream_kernel_lds_slice(int S, int stride, int t0, int n, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                             mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                             float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    FrameSlice sl;
-    sl.stride = stride;
-    sl.t0 = t0;
-    imbe_stream_body<true>(S, n, records, params, state, rngs, pcm16, pcmf, results, tabs_in, nullptr, 0, FrameShadow{}, FrontLink{}, sl);
-}
-__global__ void MBX_LDS_KERNEL_ATTR(MBX_AMBE_LDS_WAVES_PER_SIMD)
-ambe_stream_kernel_lds_slice(int S, int stride, int t0, int n, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                             mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                             float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    FrameSlice sl;
-    sl.stride = stride;
-    sl.t0 = t0;
-    ambe_stream_body<false, true>(S, n, records, params, state, rngs, pcm16, pcmf, results, tabs_in, nullptr, FrameShadow{}, sl);
-}
-__global__ void MBX_LDS_KERNEL_ATTR(MBX_AMBE_LDS_WAVES_PER_SIMD)
-ambe2400_stream_kernel_lds_slice(int S, int stride, int t0, int n, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                                 mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                                 float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    FrameSlice sl;
-    sl.stride = stride;
-    sl.t0 = t0;
-    ambe_stream_body<true, true>(S, n, records, params, state, rngs, pcm16, pcmf, results, tabs_in, nullptr, FrameShadow{}, sl);
-}
-
-// Resident state (DeviceTables::resident, mbx_process_batch_resident): the LDS-resident bodies with prev_mp_enhanced elided
-// while it equals cur_mp and prev_mp fetched lazily -- at every T, T = 1 included (sessions, queue mode).
-#ifndef MBX_IMBE_RES_WAVES_PER_SIMD
-#define MBX_IMBE_RES_WAVES_PER_SIMD MBX_IMBE_LDS_WAVES_PER_SIMD
-#endif
-__global__ void MBX_LDS_KERNEL_ATTR(MBX_IMBE_RES_WAVES_PER_SIMD)
-imbe_stream_kernel_res(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                       mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                       float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    imbe_stream_body<true, false, true>(S, Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
-// one frame per stream on resident state: the HBM-slot body (seven waves per SIMD, no LDS copy of prev_mp)
-__global__ void __launch_bounds__(64, MBX_STREAM_WAVES_PER_SIMD)
-imbe_stream_kernel_res1(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                        mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                        float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    imbe_stream_body<false, false, true, true>(S, Tn > 1 ? 1 : Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
-// one frame per stream on resident state: the HBM-slot bodies with the elision (see imbe_stream_kernel_res1)
-__global__ void __launch_bounds__(64, MBX_AMBE_ONE_WAVES_PER_SIMD)
-ambe_stream_kernel_res1(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                        mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                        float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_stream_body<false, false, false, true, true>(S, Tn > 1 ? 1 : Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-__global__ void __launch_bounds__(64, MBX_AMBE2400_WAVES_PER_SIMD)
-ambe2400_stream_kernel_res1(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                            mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                            float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_stream_body<true, false, false, true, true>(S, Tn > 1 ? 1 : Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
-__global__ void MBX_LDS_KERNEL_ATTR(MBX_AMBE_LDS_WAVES_PER_SIMD)
-ambe_stream_kernel_res(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                       mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                       float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_stream_body<false, true, false, true>(S, Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
-__global__ void MBX_LDS_KERNEL_ATTR(MBX_AMBE_LDS_WAVES_PER_SIMD)
-ambe2400_stream_kernel_res(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
-                           mbe_parms* __restrict__ state, mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16,
-                           float* __restrict__ pcmf, mbe_process_result* __restrict__ results, DeviceTables tabs_in) {
-    ambe_stream_body<true, true, false, true>(S, Tn, records, params, state, rngs, pcm16, pcmf, results, tabs_in);
-}
-
+// mbe_synthesizeSpeechf for S independent (cur, prev) pairs.
 __global__ void __launch_bounds__(64)
 synth_speech_kernel(int S, mbe_parms* __restrict__ curs, mbe_parms* __restrict__ prevs, mbx_stream_rng* __restrict__ rngs,
                     float* __restrict__ pcmf, int16_t* __restrict__ pcm16, DeviceTables tabs) {
@@ -4100,6 +3816,110 @@ state_copy_kernel(int S, mbe_parms* __restrict__ state) {
     store_parms<false, true>(b, &state[3 * (size_t)s + 1], lane);
     store_parms<false, true>(c, &state[3 * (size_t)s + 2], lane);
 }
+
+// ------------------------------------------------------------------------------------------
+// The stream-stage kernel instances: every __global__ entry of the stream bodies above, one block per argument family
+// (parameter lists: mbx_kernels.h; which instance a launch takes: mbx_api.hip, kInstances / select_instance).
+// One stream per 64-lane workgroup; the second number of the launch bounds is the instance's waves per SIMD.
+// ------------------------------------------------------------------------------------------
+// The body templates' arguments by name: imbe_stream_body<kPark, kFrame, kRes, kOne, kFuse>, ambe_stream_body<k2400, kPark, ...>
+constexpr bool kAmbe2450 = false, kAmbe2400 = true;   // k2400: AMBE+2 3600x2450 | AMBE 3600x2400 (D-STAR)
+constexpr bool kSlots = false, kLds = true;           // kPark: prev_mp parked in its HBM slot every frame | in LDS for the whole launch
+constexpr bool kBatch = false;                        // kFrame (true: the single-frame kernels above)
+constexpr bool kPlain = false, kResident = true;      // kRes: DeviceTables::resident honoured (prev_mp_enhanced elided while it equals cur_mp)
+constexpr bool kOneFrame = true;                      // kOne: no frame loop, every request of the frame issued before the first wait
+constexpr int kFrontImbe = 1, kFront7100 = 2;         // kFuse: the front end in the stream's own wave (3, front blocks: the *_one_launch_body)
+#define MBX_OUT_ARGS state, rngs, pcm16, pcmf, results, tabs_in
+#define MBX_STREAM_KERNEL(name, waves, ...) \
+    __global__ void __launch_bounds__(64, waves) name(MBX_STREAM_PARAMS) { __VA_ARGS__; }
+#define MBX_SLICE_KERNEL(name, waves, ...) \
+    __global__ void __launch_bounds__(64, waves) name(MBX_SLICE_PARAMS) { FrameSlice sl; sl.stride = stride; sl.t0 = t0; __VA_ARGS__; }
+#define MBX_FUSED_KERNEL(name, waves, ...) \
+    __global__ void __launch_bounds__(64, waves) name(MBX_FUSED_PARAMS) { __VA_ARGS__; }
+#define MBX_ONE_LAUNCH_KERNEL(name, waves, ...) \
+    __global__ void __launch_bounds__(64, waves) name(int S, MBX_ONE_LAUNCH_PARAMS) { __VA_ARGS__; }
+#define MBX_ONE_LAUNCH_LEAD_KERNEL(name, waves, ...) \
+    __global__ void __launch_bounds__(64, waves) name(int S, int lead, MBX_ONE_LAUNCH_PARAMS) { __VA_ARGS__; }
+
+// ---- stream family: S streams x Tn frames ----
+// one to three frames per stream: the HBM-slot bodies
+MBX_STREAM_KERNEL(imbe_stream_kernel, MBX_STREAM_WAVES_PER_SIMD, imbe_stream_body<kSlots>(S, Tn, records, params, MBX_OUT_ARGS))
+MBX_STREAM_KERNEL(ambe_stream_kernel, MBX_AMBE_WAVES_PER_SIMD, ambe_stream_body<kAmbe2450, kSlots>(S, Tn, records, params, MBX_OUT_ARGS))
+MBX_STREAM_KERNEL(ambe2400_stream_kernel, MBX_AMBE2400_WAVES_PER_SIMD, ambe_stream_body<kAmbe2400, kSlots>(S, Tn, records, params, MBX_OUT_ARGS))
+// T = 1 (a tick of the per-tick API, BASELINE configs[1]): the HBM-slot bodies without a frame loop, every request of the frame
+// issued before the first wait.
+#ifndef MBX_AMBE_ONE_WAVES_PER_SIMD
+#define MBX_AMBE_ONE_WAVES_PER_SIMD 7   // round 6: SEVEN waves (72 VGPRs, no scratch) once the one-frame AMBE instances stopped requesting the next
+#endif                                  // overlap's noise constants ahead of the bank (no kEarly: two registers across the bank) and the
+                                        // interpolated branch stopped holding n^2 across its loop: 65,536 x 1 AMBE+2 -1.7 %, resident -2.5 %
+                                        // (profiles/r06/ab_ambe_seven_waves.log; round 5 forced seven with 44 B of scratch: +7.8 %)
+MBX_STREAM_KERNEL(imbe_stream_kernel_one, MBX_STREAM_WAVES_PER_SIMD,
+                  imbe_stream_body<kSlots, kBatch, kPlain, kOneFrame>(S, Tn > 1 ? 1 : Tn, records, params, MBX_OUT_ARGS))
+MBX_STREAM_KERNEL(ambe_stream_kernel_one, MBX_AMBE_ONE_WAVES_PER_SIMD,
+                  ambe_stream_body<kAmbe2450, kSlots, kBatch, kPlain, kOneFrame>(S, Tn, records, params, MBX_OUT_ARGS))
+MBX_STREAM_KERNEL(ambe2400_stream_kernel_one, MBX_AMBE2400_WAVES_PER_SIMD,
+                  ambe_stream_body<kAmbe2400, kSlots, kBatch, kPlain, kOneFrame>(S, Tn, records, params, MBX_OUT_ARGS))
+// T >= 4: prev_mp resident in LDS (see ParkedPrevOnly).  5,200 B of LDS per wave allow 25 waves per CU, so the register
+// file decides the occupancy: 79 VGPRs = six waves per SIMD.  Measured on configs[3] (65,536 x T=16) with padded LDS:
+// two waves per SIMD 5.15 ms, three 3.91, four (round 2) 3.40, five 2.86, six 2.76.
+// (MBX_IMBE_LDS_WAVES_PER_SIMD / MBX_AMBE_LDS_WAVES_PER_SIMD: mbx_device.h, shared with the launcher's slicing heuristic)
+MBX_STREAM_KERNEL(imbe_stream_kernel_lds, MBX_IMBE_LDS_WAVES_PER_SIMD, imbe_stream_body<kLds>(S, Tn, records, params, MBX_OUT_ARGS))
+MBX_STREAM_KERNEL(ambe_stream_kernel_lds, MBX_AMBE_LDS_WAVES_PER_SIMD, ambe_stream_body<kAmbe2450, kLds>(S, Tn, records, params, MBX_OUT_ARGS))
+MBX_STREAM_KERNEL(ambe2400_stream_kernel_lds, MBX_AMBE_LDS_WAVES_PER_SIMD, ambe_stream_body<kAmbe2400, kLds>(S, Tn, records, params, MBX_OUT_ARGS))
+// Resident state (DeviceTables::resident, mbx_process_batch_resident): the LDS-resident bodies with prev_mp_enhanced elided
+// while it equals cur_mp and prev_mp fetched lazily -- at every T, T = 1 included (sessions, queue mode).
+#ifndef MBX_IMBE_RES_WAVES_PER_SIMD
+#define MBX_IMBE_RES_WAVES_PER_SIMD MBX_IMBE_LDS_WAVES_PER_SIMD
+#endif
+MBX_STREAM_KERNEL(imbe_stream_kernel_res, MBX_IMBE_RES_WAVES_PER_SIMD,
+                  imbe_stream_body<kLds, kBatch, kResident>(S, Tn, records, params, MBX_OUT_ARGS))
+MBX_STREAM_KERNEL(ambe_stream_kernel_res, MBX_AMBE_LDS_WAVES_PER_SIMD,
+                  ambe_stream_body<kAmbe2450, kLds, kBatch, kResident>(S, Tn, records, params, MBX_OUT_ARGS))
+MBX_STREAM_KERNEL(ambe2400_stream_kernel_res, MBX_AMBE_LDS_WAVES_PER_SIMD,
+                  ambe_stream_body<kAmbe2400, kLds, kBatch, kResident>(S, Tn, records, params, MBX_OUT_ARGS))
+// one frame per stream on resident state: the HBM-slot bodies with the elision (IMBE: seven waves per SIMD, no LDS copy of prev_mp)
+MBX_STREAM_KERNEL(imbe_stream_kernel_res1, MBX_STREAM_WAVES_PER_SIMD,
+                  imbe_stream_body<kSlots, kBatch, kResident, kOneFrame>(S, Tn > 1 ? 1 : Tn, records, params, MBX_OUT_ARGS))
+MBX_STREAM_KERNEL(ambe_stream_kernel_res1, MBX_AMBE_ONE_WAVES_PER_SIMD,
+                  ambe_stream_body<kAmbe2450, kSlots, kBatch, kResident, kOneFrame>(S, Tn > 1 ? 1 : Tn, records, params, MBX_OUT_ARGS))
+MBX_STREAM_KERNEL(ambe2400_stream_kernel_res1, MBX_AMBE2400_WAVES_PER_SIMD,
+                  ambe_stream_body<kAmbe2400, kSlots, kBatch, kResident, kOneFrame>(S, Tn > 1 ? 1 : Tn, records, params, MBX_OUT_ARGS))
+
+// ---- slice family (*_stream_kernel_lds_slice): the LDS-resident instances on a SLICE of every stream's frames -- frames t0 ..
+// t0 + n - 1 of the `stride` frames a stream has in the batch arrays.  A slice IS a launch of n frames per stream (state in from
+// HBM, state out to HBM); the launcher (mbx_api.hip, try_sliced_launch) cuts a launch whose stream count does not fill the device's
+// wave slots evenly into groups of streams x slices of frames and issues them on the caller's stream and two internal HIP streams
+// (three groups), so that the slots one group's slice leaves empty are taken by the other group's. ----
+MBX_SLICE_KERNEL(imbe_stream_kernel_lds_slice, MBX_IMBE_LDS_WAVES_PER_SIMD,
+                 imbe_stream_body<kLds>(S, n, records, params, MBX_OUT_ARGS, nullptr, 0, FrameShadow{}, FrontLink{}, sl))
+MBX_SLICE_KERNEL(ambe_stream_kernel_lds_slice, MBX_AMBE_LDS_WAVES_PER_SIMD,
+                 ambe_stream_body<kAmbe2450, kLds>(S, n, records, params, MBX_OUT_ARGS, nullptr, FrameShadow{}, sl))
+MBX_SLICE_KERNEL(ambe2400_stream_kernel_lds_slice, MBX_AMBE_LDS_WAVES_PER_SIMD,
+                 ambe_stream_body<kAmbe2400, kLds>(S, n, records, params, MBX_OUT_ARGS, nullptr, FrameShadow{}, sl))
+
+// ---- fused family: the whole T = 1 step as ONE launch with the front end in the stream's own wave (kFuse) -- wire frames in,
+// PCM / results / records / state out.  fec_codec: MBX_CODEC_IMBE7200X4400 or MBX_CODEC_IMBE7100X4400. ----
+MBX_FUSED_KERNEL(imbe_stream_kernel_one_fused, MBX_STREAM_WAVES_PER_SIMD,
+                 imbe_stream_body<kSlots, kBatch, kPlain, kOneFrame, kFrontImbe>(S, 1, records, nullptr, MBX_OUT_ARGS, frames, fec_codec))
+MBX_FUSED_KERNEL(imbe_stream_kernel_res1_fused, MBX_STREAM_WAVES_PER_SIMD,
+                 imbe_stream_body<kSlots, kBatch, kResident, kOneFrame, kFrontImbe>(S, 1, records, nullptr, MBX_OUT_ARGS, frames, fec_codec))
+// IMBE 7100x4400 frames: own front end (whole, then the expansion's requests), the same stream stage
+MBX_FUSED_KERNEL(imbe7100_stream_kernel_one_fused, MBX_STREAM_WAVES_PER_SIMD,
+                 imbe_stream_body<kSlots, kBatch, kPlain, kOneFrame, kFront7100>(S, 1, records, nullptr, MBX_OUT_ARGS, frames, fec_codec))
+MBX_FUSED_KERNEL(imbe7100_stream_kernel_res1_fused, MBX_STREAM_WAVES_PER_SIMD,
+                 imbe_stream_body<kSlots, kBatch, kResident, kOneFrame, kFront7100>(S, 1, records, nullptr, MBX_OUT_ARGS, frames, fec_codec))
+
+// ---- one-launch family: front blocks and stream blocks in one grid (imbe_one_launch_body / ambe_one_launch_body<k2400, kRes>) ----
+#ifndef MBX_AMBE_ONE_RES_WAVES_PER_SIMD
+#define MBX_AMBE_ONE_RES_WAVES_PER_SIMD 6   // ambe_one_launch_kernel_res alone still needs 12 B of scratch at seven (the transform pair's peak)
+#endif
+#define MBX_ONE_LAUNCH_ARGS frames, records, rows, flags, fallbacks, epoch, MBX_OUT_ARGS
+MBX_ONE_LAUNCH_LEAD_KERNEL(imbe_one_launch_kernel, MBX_STREAM_WAVES_PER_SIMD, imbe_one_launch_body<kPlain>(S, lead, MBX_ONE_LAUNCH_ARGS))
+MBX_ONE_LAUNCH_LEAD_KERNEL(imbe_one_launch_kernel_res, MBX_STREAM_WAVES_PER_SIMD, imbe_one_launch_body<kResident>(S, lead, MBX_ONE_LAUNCH_ARGS))
+MBX_ONE_LAUNCH_KERNEL(ambe_one_launch_kernel, MBX_AMBE_ONE_WAVES_PER_SIMD, ambe_one_launch_body<kAmbe2450>(S, MBX_ONE_LAUNCH_ARGS))
+MBX_ONE_LAUNCH_KERNEL(ambe_one_launch_kernel_res, MBX_AMBE_ONE_RES_WAVES_PER_SIMD, ambe_one_launch_body<kAmbe2450, kResident>(S, MBX_ONE_LAUNCH_ARGS))
+MBX_ONE_LAUNCH_KERNEL(ambe2400_one_launch_kernel, MBX_AMBE2400_WAVES_PER_SIMD, ambe_one_launch_body<kAmbe2400>(S, MBX_ONE_LAUNCH_ARGS))
+MBX_ONE_LAUNCH_KERNEL(ambe2400_one_launch_kernel_res, MBX_AMBE2400_WAVES_PER_SIMD, ambe_one_launch_body<kAmbe2400, kResident>(S, MBX_ONE_LAUNCH_ARGS))
 
 }  // namespace mbx
 

@@ -37,6 +37,34 @@ def test_cabi_library_exports_every_declared_symbol():
     assert "mbx_testing_" not in exported and "mbx_debug_set_" not in exported
 
 
+def test_every_kernel_is_declared_once_and_every_stream_instance_has_one_table_row():
+    csrc = os.path.join(ROOT, "mbelib-neo_amd", "csrc")
+    read = lambda name: open(os.path.join(csrc, name)).read()
+    header = read("mbx_kernels.h")
+    declared = re.findall(r"__global__\s+void\s+(\w+)\s*\(", header)
+    assert len(declared) == len(set(declared)), "a kernel is declared twice in mbx_kernels.h"
+    # definitions: written out (`__global__ void [__launch_bounds__(..)] name(`) or through a family macro (`MBX_*_KERNEL(name, ...)`)
+    plain = re.compile(r"^(?:extern \"C\" )?__global__\s+void\s+(?:__launch_bounds__\([^)]*\)\s*)?(\w+)\s*\(", re.M)
+    macro = re.compile(r"^MBX_\w+_KERNEL\((\w+),", re.M)
+    defined, instances = set(), set()
+    for src in sorted(f for f in os.listdir(csrc) if f.endswith(".hip")):
+        text = read(src)
+        defined |= set(plain.findall(text))
+        instances |= set(macro.findall(text))
+    assert len(instances) == 28 and not instances & defined
+    assert defined | instances == set(declared), sorted((defined | instances) ^ set(declared))
+    # the launcher: no prototype of its own, and every stream-stage instance exactly once in the instance table, under its own name
+    api = read("mbx_api.hip")
+    assert not re.search(r"__global__[^{;]*\)\s*;", api), "a kernel prototype in mbx_api.hip: declarations live in mbx_kernels.h"
+    table = api[api.index("kInstances[] = {"):]
+    table = table[:table.index("};")]
+    rows = re.findall(r'\{"(\w+)",\s*mbx::(\w+)\}', table)
+    assert all(name == fn for name, fn in rows), "a table row names another kernel than it launches"
+    assert sorted(name for name, _ in rows) == sorted(instances)
+    for name in instances:   # ... and nowhere else as a string: what ran and what is reported cannot disagree
+        assert api.count(f'"{name}"') == 1, name
+
+
 def test_launchers_fail_loudly_without_init_or_device():
     from mbelib_neo_amd import _native
 

@@ -17,15 +17,20 @@ CSRC = os.path.join(ROOT, "mbelib-neo_amd", "csrc")
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-def build(src, extra):
+def build(src, extra=(), line_info=True, root=ROOT):
+    """Device-only compile of <root>/mbelib-neo_amd/csrc/<src> with the product flags; returns the code object's disassembly
+    (with source-line marks, or as bare instruction text).  tools/isa_digest.py builds the same way."""
+    csrc = os.path.join(root, "mbelib-neo_amd", "csrc")
     o = f"/tmp/isa_lines_{os.getpid()}.o"
     elf = o[:-2] + ".elf"
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                           "-fno-fast-math", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-mllvm", "-disable-machine-licm",
-                           "-gline-tables-only", "--cuda-device-only", "-c", os.path.join(CSRC, src), "-o", o] + extra)
+                           "-fno-fast-math", "-I" + os.path.join(root, "include"), "-I" + csrc, "-mllvm", "-disable-machine-licm"]
+                          + (["-gline-tables-only"] if line_info else [])
+                          + ["--cuda-device-only", "-c", os.path.join(csrc, src), "-o", o] + list(extra))
     subprocess.check_call([LLVM + "/clang-offload-bundler", "--unbundle", "--type=o", "--input=" + o,
                            "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--output=" + elf])
-    text = subprocess.check_output([LLVM + "/llvm-objdump", "-d", "-l", elf], text=True)
+    text = subprocess.check_output([LLVM + "/llvm-objdump", "-d"] + (["-l"] if line_info else ["--no-show-raw-insn", "--no-leading-addr"])
+                                   + [elf], text=True)
     os.unlink(o)
     os.unlink(elf)
     return text
