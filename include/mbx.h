@@ -468,6 +468,13 @@ const char* mbx_batch_kernel_name(int codec, int S, int T, int resident);
  * expanded their own frame instead, since the workspace of `stream` was allocated (expected 0; results are the same either way).
  * Synchronises the stream.  -1: the stream has no workspace yet. */
 long long mbx_front_fallbacks(void* stream);
+/* what actually ran: the name of the stream-stage kernel instance of the last launch issued on `stream` in the calling thread's
+ * current device context -- a sliced launch reports its slice instance --, or NULL when none has been issued since mbx_init.
+ * Unlike the two functions above this does not predict from a shape: a caller workspace, frames that are not 4-byte aligned, a
+ * capture or AMBE without rows all show here.  Host side only; no synchronisation.  The string lives as long as the library.
+ * The record is kept per stream HANDLE for as long as the context lives (like the stream's workspace): a handle the runtime gives
+ * out again after hipStreamDestroy reports the earlier stream's last launch until it has launched itself. */
+const char* mbx_last_kernel_name(void* stream);
 /* (The fault-injection hook that FORCES that fall-back path is not part of this library: it exists only in the -DMBX_TESTING build,
  * libmbx_hip_testing.so -- `make -C mbelib-neo_amd/csrc testing` -- which tests/ load in a child process through MBX_HIP_LIBRARY.) */
 /* Sliced launches.  A launch of S streams x T >= 32 frames whose S does not fill the device's resident wave slots evenly (the

@@ -51,6 +51,8 @@ struct Context {
     int                simds = 0;            // 4 per CU
     size_t             reserve_frames = 0;   // mbx_reserve(): minimum workspace of every slot
     std::unordered_map<void*, StreamSlot> slots;
+    std::mutex         name_mu;              // guards last_kernel alone; a leaf lock (launch_stream runs with `mu` held and without)
+    std::unordered_map<void*, const char*> last_kernel;   // hipStream_t -> Instance::name of its last stream-stage launch (mbx_last_kernel_name)
 };
 Context    g_ctx[kMaxDevices];
 std::mutex g_init_mu;                        // serialises mbx_init() / mbx_shutdown()
@@ -123,6 +125,10 @@ void free_context(Context& c) {   // caller holds g_init_mu and c.mu
         release_side_streams(kv.second);
     }
     c.slots.clear();
+    {
+        std::lock_guard<std::mutex> lock(c.name_mu);
+        c.last_kernel.clear();
+    }
     c.d_blob = c.d_derived = nullptr;
     c.tabs = mbx::DeviceTables{};   // (every field zero: mbx_init sets what it needs)
     c.reserve_frames = 0;
@@ -938,6 +944,16 @@ struct Shape {
     bool workspace = false;   // ... and the rows may go through the stream slot's own workspace and flag words (the one-launch forms)
 };
 static const Instance& select_instance(const Shape& q);
+// every stream-stage launch ends here: what ran on `stream` (the caller's, also for the slices of a sliced launch) is written down
+// for mbx_last_kernel_name -- the table's own pointer, one store per launch, nothing on the device -- and the launch is checked
+static void record_launch(Context* c, void* stream, const Instance& e) {
+    std::lock_guard<std::mutex> lock(c->name_mu);
+    c->last_kernel[stream] = e.name;
+}
+static int launched(Context* c, void* stream, const Instance& e) {
+    record_launch(c, stream, e);
+    return check_launch(e.name);
+}
 // the tables of a launch: the context's + what this launch walks (`reverse`: see launch_stream)
 static mbx::DeviceTables launch_tables(const Context* c, bool reverse, const int32_t* d_stream_index, uint32_t* d_resident) {
     mbx::DeviceTables tabs = c->tabs;
@@ -1031,6 +1047,7 @@ static int try_sliced_launch(Context* c, StreamSlot& slot, mbx::DeviceTables tab
     q.sliced = true;
     const Instance& e = select_instance(q);
     int result = 0;
+    record_launch(c, stream, e);   // one record for the whole sliced launch, under the caller's stream
     // Group 0 runs on the caller's stream itself -- its kernels are queued before the stream waits for the other groups --, so g
     // groups occupy g hardware queues, not g + 1, and one group needs no hand-over at all: 2.51 -> 2.42 ms on 8,192 x 128 AMBE+2
     // (interleaved A/B; four groups are +26 % either way).  MBX_SLICE_OWN=0 puts every group on an internal stream (A/B timing; read once).
@@ -1109,7 +1126,7 @@ static int launch_stream(Context* c, bool reverse, int codec, int S, int T, cons
     const Instance& e = select_instance(q);
     hipLaunchKernelGGL(e.stream, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records, params, d_state, d_rng, d_pcm16, d_pcmf,
                        d_results, tabs);
-    return check_launch(e.name);
+    return launched(c, stream, e);
 }
 
 static bool stream_args_ok(int codec, int S, int T, const void* d_records, const void* d_state, const void* d_rng) {
@@ -1199,7 +1216,7 @@ static int launch_fused_one(Context* c, const Instance& e, bool reverse, int cod
     const mbx::DeviceTables tabs = launch_tables(c, reverse, d_stream_index, d_resident);
     hipLaunchKernelGGL(e.fused, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, codec, d_frames, d_records, d_state, d_rng, d_pcm16,
                        d_pcmf, d_results, tabs);
-    return check_launch(e.name);
+    return launched(c, stream, e);
 }
 // caller holds c->mu; the slot's workspace holds S rows and its flags
 static int launch_one_launch(Context* c, const Instance& e, StreamSlot& slot, bool reverse, int S, const uint8_t* d_frames,
@@ -1219,7 +1236,7 @@ static int launch_one_launch(Context* c, const Instance& e, StreamSlot& slot, bo
         hipLaunchKernelGGL(e.one_launch, dim3(9u * chunks), dim3(64), 0, (hipStream_t)stream, S, d_frames, d_records, slot.workspace, slot.flags,
                            fallbacks, slot.epoch, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
     }
-    return check_launch(e.name);
+    return launched(c, stream, e);
 }
 // one fused launch if the shape allows it: returns 1 when it was issued (*rc = its status), 0 when the caller goes on with the stages
 static int try_fused_one(int codec, int S, int T, const uint8_t* d_frames, mbx_param_record* d_records, mbe_parms* d_state,
@@ -1917,6 +1934,19 @@ long long mbx_front_fallbacks(void* stream) {
         return MBX_ENODEVICE;
     }
     return (long long)v;
+}
+
+// what ran, not what a shape predicts: the Instance::name of the last stream-stage launch issued on `stream` in the current device's
+// context (a sliced launch: its slice instance), or NULL when there has been none since mbx_init
+const char* mbx_last_kernel_name(void* stream) {
+    int crc;
+    Context* c = current_ctx(&crc);
+    if (!c) {
+        return nullptr;
+    }
+    std::lock_guard<std::mutex> lock(c->name_mu);
+    auto it = c->last_kernel.find(stream);
+    return it == c->last_kernel.end() ? nullptr : it->second;
 }
 
 // 0, or the slice length in frames a launch of this shape is cut into (mbx_process_records and the batch calls on top of it)

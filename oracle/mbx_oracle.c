@@ -14,6 +14,7 @@
 #include "mbx_oracle.h"
 
 #include <math.h>
+#include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -1908,25 +1909,32 @@ mbxo_comfort_noisef(float* out, mbx_stream_rng* rng) {
  * 256-point real FFT pair used by the unvoiced path (stands in for PFFFT; any correct
  * transform meets the tolerance).  Double precision, results rounded to float.
  * ===================================================================================== */
+/* twiddles and the bit-reversal permutation: filled once, under pthread_once, so that the first transforms of several
+ * threads (tests/oracle_lib.py runs ranges of streams on a thread pool) cannot meet a half-written table */
+static double g_fft_wr[128], g_fft_wi[128];
+static int g_fft_rev[256];
+static pthread_once_t g_fft_once = PTHREAD_ONCE_INIT;
+
+static void
+fft256_tables(void) {
+    for (int i = 0; i < 128; ++i) {
+        g_fft_wr[i] = cos(2.0 * M_PI * i / 256.0);
+        g_fft_wi[i] = -sin(2.0 * M_PI * i / 256.0);
+    }
+    for (int i = 0; i < 256; ++i) {
+        int r = 0;
+        for (int b = 0; b < 8; ++b) {
+            r |= ((i >> b) & 1) << (7 - b);
+        }
+        g_fft_rev[i] = r;
+    }
+}
+
 static void
 fft256(double* re, double* im, int inverse) {
-    static int ready = 0;
-    static double wr[128], wi[128];
-    static int rev[256];
-    if (!ready) {
-        for (int i = 0; i < 128; ++i) {
-            wr[i] = cos(2.0 * M_PI * i / 256.0);
-            wi[i] = -sin(2.0 * M_PI * i / 256.0);
-        }
-        for (int i = 0; i < 256; ++i) {
-            int r = 0;
-            for (int b = 0; b < 8; ++b) {
-                r |= ((i >> b) & 1) << (7 - b);
-            }
-            rev[i] = r;
-        }
-        ready = 1;
-    }
+    pthread_once(&g_fft_once, fft256_tables);
+    const double *wr = g_fft_wr, *wi = g_fft_wi;
+    const int* rev = g_fft_rev;
     for (int i = 0; i < 256; ++i) {
         if (rev[i] > i) {
             double t = re[i];
@@ -1980,8 +1988,8 @@ mbxo_set_fft_float(int on) {
     g_fft_float = on ? 1 : 0;
 }
 
-static float g_rtw[256]; /* FFTPACK's real-transform twiddles for n = 256 */
-static int g_rtw_ready = 0;
+static float g_rtw[256]; /* FFTPACK's real-transform twiddles for n = 256; filled once (pthread_once) */
+static pthread_once_t g_rtw_once = PTHREAD_ONCE_INIT;
 
 static void
 real_twiddles_256(void) {
@@ -2004,7 +2012,6 @@ real_twiddles_256(void) {
         }
         l1 = l2;
     }
-    g_rtw_ready = 1;
 }
 
 /* (ar + i ai) (wr - i wi) and (ar + i ai) (wr + i wi), in the library's operation order */
@@ -2137,9 +2144,7 @@ real_pass4_backward(int ido, int l1, const float* c, float* h, const float* w1, 
 /* forward: 256 real samples -> [X0.re, X128.re, X1.re, X1.im, ..., X127.re, X127.im] (the library's "ordered" layout) */
 static void
 real_fft256_forward(const float in[256], float out[256]) {
-    if (!g_rtw_ready) {
-        real_twiddles_256();
-    }
+    pthread_once(&g_rtw_once, real_twiddles_256);
     float a[256], b[256];
     /* (l1, ido, twiddle offset): 64,1,252 -> 16,4,240 -> 4,16,192 -> 1,64,0 */
     real_pass4_forward(1, 64, in, a, &g_rtw[252], &g_rtw[253], &g_rtw[254]);
@@ -2156,9 +2161,7 @@ real_fft256_forward(const float in[256], float out[256]) {
 /* backward of the above, unnormalised (backward(forward(x)) = 256 x) */
 static void
 real_fft256_backward(const float in[256], float out[256]) {
-    if (!g_rtw_ready) {
-        real_twiddles_256();
-    }
+    pthread_once(&g_rtw_once, real_twiddles_256);
     float a[256], b[256];
     a[0] = in[0];
     a[255] = in[1];

@@ -28,10 +28,19 @@
 extern "C" {
 #endif
 
-/* tables -------------------------------------------------------------------------- */
+/* tables and run-wide settings ------------------------------------------------------- */
+/* Threads.  mbxo_process_batch[_soft] and everything below them may run on several threads at once, each on its own
+ * streams (tests/oracle_lib.py: Oracle.process_batch splits a batch into contiguous ranges of streams), under this contract:
+ *   - mbxo_load_tables, mbxo_set_tones and mbxo_set_fft_float write file-scope settings that a run only reads; call them
+ *     BEFORE a run, never while another thread is inside the library;
+ *   - the FFT twiddle tables are filled once, under pthread_once, by whichever thread transforms first;
+ *   - the pre-clip peak pointer and the running peak are thread-local: mbxo_set_preclip_peaks binds the CALLING thread
+ *     only, and the batch driver indexes it by frame from ITS first stream, so a worker that decodes streams [a, b) of a
+ *     batch passes &peak[a * T];
+ *   - nothing else at file scope is written after load. */
 void mbxo_set_preclip_peaks(float* out); /* diagnostic: when non-NULL, mbxo_process_batch[_soft] writes per frame the largest |sample| before the soft clip (0 for frames that do not run the synthesiser); calling thread only */
-void mbxo_set_tones(int on); /* 0: the reference's NOTONES build (tone frames = silence, phases untouched); 1 (default): tones synthesised */
-void mbxo_set_fft_float(int on); /* 1: the unvoiced FFT as FFTPACK's float real transform (= the reference's PFFFT, bit for bit); 0 (default): double precision */
+void mbxo_set_tones(int on); /* 0: the reference's NOTONES build (tone frames = silence, phases untouched); 1 (default): tones synthesised.  Before a run. */
+void mbxo_set_fft_float(int on); /* 1: the unvoiced FFT as FFTPACK's float real transform (= the reference's PFFFT, bit for bit); 0 (default): double precision.  Before a run. */
 int mbxo_load_tables(const void* blob, size_t n); /* 0, or -1 on bad magic/size/checksum */
 
 /* frame packing (host side of the boundary) ---------------------------------------- */

@@ -1,0 +1,175 @@
+"""One oracle case per row of kInstances (mbelib-neo_amd/csrc/mbx_api.hip): every stream-stage kernel instance is run BY NAME --
+after each launch mbx_last_kernel_name must report the case's instance -- on the edge mix of its codec (tests/edge_mix.py) and
+held to the oracle on every stream: records, results and RNG state exact, PCM under the int16 bound of each frame's pre-clip
+peak, state in tolerance.  Shapes sit on the edges: S not a multiple of 8 or 64, 257 and 256 around the small-batch limit, T = 2, 3,
+4 (the LDS threshold) and 17 (AMBE expands eight frames at a time: two blocks and one), slices of 16, 16 and 8 frames over groups
+that do not divide S, more chunks than the front blocks' lead, an index into a larger pool; several launches on continuing state,
+so both walking directions and the hand-over of the state are under the oracle.
+
+Importable without a GPU (tests/test_host_logic.py holds CASES to the table).  Cases without switches run inside the GPU suite's
+process when its environment holds no MBX_* switch; a case with environment switches -- the library reads them once per process --
+and every case of a suite that itself runs under switches runs as `python tests/instance_cases.py <id>` in a fresh child with
+exactly the case's switches: exit status 0 = passed, 1 = a mismatch (printed)."""
+import os
+import sys
+from collections import namedtuple
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+# entry: batch = mbx_process_batch; batch_ws = mbx_process_batch_ws (caller workspace); batch_indexed = mbx_process_batch_indexed
+# (the batch's streams are every second slot, backwards, of a pool of 2 S + 3); resident = mbx_process_batch_resident; resident_indexed
+# = the same through that index; staged = mbx_fec_* + mbx_process_records
+Case = namedtuple("Case", "id name codec S T launches entry env")
+
+
+def _c(name, codec, S, T, launches, entry, env=None, tag=""):
+    return Case(name + ("-" + tag if tag else ""), name, codec, S, T, launches, entry, dict(env or {}))
+
+
+CASES = [
+    # T = 2, 3: the plain looped instances (state in its HBM slots every frame)
+    _c("imbe_stream_kernel", 0, 1003, 3, 2, "batch"),
+    _c("ambe_stream_kernel", 1, 1001, 2, 3, "batch"),
+    _c("ambe2400_stream_kernel", 3, 517, 3, 2, "batch_indexed"),
+    _c("imbe_stream_kernel", 2, 300, 2, 3, "batch", tag="imbe7100"),
+    # T = 1 behind the FEC (and expansion) launches: the staged calls, a small batch, a caller workspace
+    _c("imbe_stream_kernel_one", 0, 257, 1, 6, "staged"),
+    _c("imbe_stream_kernel_one", 0, 256, 1, 6, "batch", tag="small"),
+    _c("ambe_stream_kernel_one", 1, 1003, 1, 6, "batch_ws"),
+    _c("ambe2400_stream_kernel_one", 3, 257, 1, 6, "staged"),
+    # T >= 4: prev_mp / prev_mp_enhanced stay in LDS for the launch
+    _c("imbe_stream_kernel_lds", 0, 2051, 4, 2, "batch"),
+    _c("ambe_stream_kernel_lds", 1, 1001, 17, 2, "batch"),
+    _c("ambe2400_stream_kernel_lds", 3, 1003, 17, 2, "batch_indexed"),
+    # resident state, several frames and one
+    _c("imbe_stream_kernel_res", 0, 1001, 3, 2, "resident"),
+    _c("ambe_stream_kernel_res", 1, 1003, 17, 2, "resident_indexed"),
+    _c("ambe2400_stream_kernel_res", 3, 517, 4, 2, "resident"),
+    _c("imbe_stream_kernel_res1", 0, 256, 1, 6, "resident"),
+    _c("ambe_stream_kernel_res1", 1, 1003, 1, 6, "resident", env={"MBX_FUSE_ONE": "0"}),
+    _c("ambe2400_stream_kernel_res1", 3, 203, 1, 6, "resident_indexed"),
+    # sliced launches: three groups of streams that do not divide S.  Two cases with the slice length set by switch, T = 40 = slices
+    # of 16, 16 and a tail of 8; one sliced by the launcher's OWN rule, which needs more streams than the device has wave slots for
+    # the kernel -- 5,125 on the 5,120 of a whole MI355X (256 CUs x 4 SIMDs x 5 waves; on a partitioned device the launch would not be
+    # sliced and the name assertion says so) -- and T >= 32: T = 32 (16 + 16) keeps that case at 328,000 frames
+    _c("imbe_stream_kernel_lds_slice", 0, 1000, 40, 2, "batch", env={"MBX_SLICE": "16"}),
+    _c("ambe_stream_kernel_lds_slice", 1, 5125, 32, 2, "batch"),
+    _c("ambe2400_stream_kernel_lds_slice", 3, 1001, 40, 2, "batch", env={"MBX_SLICE": "16"}),
+    # the T = 1 step as ONE launch: front blocks and stream blocks in one grid (S = 257: the last chunk of eight holds one stream)
+    _c("imbe_one_launch_kernel", 0, 257, 1, 6, "batch"),
+    _c("imbe_one_launch_kernel", 0, 1003, 1, 6, "batch_indexed", env={"MBX_FRONT_LEAD": "64"}, tag="lead64"),   # 126 chunks, lead 64
+    _c("ambe_one_launch_kernel", 1, 4099, 1, 6, "batch"),
+    _c("ambe2400_one_launch_kernel", 3, 257, 1, 6, "batch"),
+    _c("imbe_one_launch_kernel_res", 0, 4099, 1, 6, "resident"),
+    _c("ambe_one_launch_kernel_res", 1, 257, 1, 6, "resident"),
+    _c("ambe2400_one_launch_kernel_res", 3, 1003, 1, 6, "resident_indexed"),
+    # ... and with the front end in the stream's own wave
+    _c("imbe_stream_kernel_one_fused", 0, 1003, 1, 6, "batch_ws"),
+    _c("imbe_stream_kernel_one_fused", 0, 257, 1, 6, "batch", env={"MBX_FUSE_ONE": "1"}, tag="switch"),
+    _c("imbe7100_stream_kernel_one_fused", 2, 1003, 1, 6, "batch"),
+    _c("imbe_stream_kernel_res1_fused", 0, 1003, 1, 6, "resident", env={"MBX_FUSE_ONE": "1"}),
+    _c("imbe7100_stream_kernel_res1_fused", 2, 257, 1, 6, "resident_indexed"),
+]
+BY_ID = {c.id: c for c in CASES}
+assert len(BY_ID) == len(CASES)
+
+
+def child_timeout(case):
+    """seconds a fresh process may take for a case: start-up of the runtime plus its frames at a cautious rate"""
+    return 180 + case.S * case.T * case.launches // 2000
+
+
+def run_case(case):
+    """Runs the case on the current device and compares with the oracle; raises AssertionError on the first mismatch.  The process's
+    environment must already hold case.env (the library reads its switches once)."""
+    import torch
+
+    import edge_mix
+    import oracle_lib
+    import parity
+    from mbelib_neo_amd import _native, decoder
+    from mbelib_neo_amd.layout import FRAME_BYTES, RECORD_DTYPE, RESULT_DTYPE
+
+    for k, v in case.env.items():
+        assert os.environ.get(k) == v, f"{case.id}: needs {k}={v} in the environment of a fresh process"
+    codec, S, T, n_launch = case.codec, case.S, case.T, case.launches
+    fb, Tt = FRAME_BYTES[codec], case.T * case.launches
+    frames = edge_mix.frames(codec, S, Tt, tag=sum(case.id.encode()) & 0xFFF)
+    seeds = np.arange(S) * 3 + 11
+    indexed = case.entry.endswith("_indexed")
+    resident = case.entry.startswith("resident")
+    pool = 2 * S + 3 if indexed else S
+    slots = np.arange(pool - 2, 0, -2)[:S] if indexed else np.arange(S)   # every second slot of the pool, walked backwards
+    assert len(slots) == S and len(set(slots.tolist())) == S
+    pool_seeds = np.full(pool, 999, dtype=np.int64)
+    pool_seeds[slots] = seeds
+    L = _native.lib()
+    dec = decoder.BatchDecoder(codec, pool, seeds=pool_seeds, resident=resident)
+    untouched_state, untouched_rng = dec.state_numpy().copy(), dec.rng_numpy().copy()
+    strm = torch.cuda.current_stream().cuda_stream
+    d_index = torch.from_numpy(slots.astype(np.int32)).cuda() if indexed else None
+    ws = torch.empty(int(L.mbx_workspace_bytes(S * T)), dtype=torch.uint8, device="cuda") if case.entry == "batch_ws" else None
+    got = {k: [] for k in ("records", "results", "pcm16", "pcmf")}
+    for k in range(n_launch):
+        part = np.ascontiguousarray(frames[:, k * T:(k + 1) * T])
+        if case.entry in ("batch", "staged") or (case.entry == "resident"):
+            out = dec.decode(part.reshape(-1, fb), T, want_float=True, staged=case.entry == "staged")
+        else:
+            d_frames = dec.to_device(part)
+            out = {"records": torch.empty((S * T, 4), dtype=torch.int32, device="cuda"), "results": torch.empty((S * T, 5), dtype=torch.int32, device="cuda"),
+                   "pcm16": torch.empty((S * T, 160), dtype=torch.int16, device="cuda"), "pcmf": torch.empty((S * T, 160), dtype=torch.float32, device="cuda")}
+            o = [out[x].data_ptr() for x in ("pcm16", "pcmf", "results", "records")]
+            if case.entry == "batch_ws":
+                rc = L.mbx_process_batch_ws(codec, S, T, d_frames.data_ptr(), dec.state.data_ptr(), dec.rng.data_ptr(), *o, ws.data_ptr(), ws.numel(), strm)
+            elif case.entry == "batch_indexed":
+                rc = L.mbx_process_batch_indexed(codec, S, T, d_index.data_ptr(), d_frames.data_ptr(), dec.state.data_ptr(), dec.rng.data_ptr(), *o, strm)
+            else:
+                assert case.entry == "resident_indexed", case.entry
+                rc = L.mbx_process_batch_resident(codec, S, T, d_index.data_ptr(), d_frames.data_ptr(), dec.state.data_ptr(), dec.resident.data_ptr(),
+                                                  dec.rng.data_ptr(), *o, strm)
+            _native.check(rc, case.entry)
+        ran = L.mbx_last_kernel_name(strm)
+        assert ran is not None and ran.decode() == case.name, f"{case.id}: launch {k} ran {ran!r}, the case is for {case.name}"
+        torch.cuda.synchronize()
+        for x in got:
+            got[x].append(out[x].cpu().numpy().reshape(S, T, -1))
+    got = {x: np.concatenate(v, axis=1) for x, v in got.items()}   # [S, Tt, ...]
+    state, rng = dec.state_numpy(), dec.rng_numpy()
+
+    o = oracle_lib.load()
+    ref = o.process_batch(codec, S, Tt, frames.reshape(S * Tt, fb), o.init_state(S), o.rng_seeded(seeds))
+    edge_mix.assert_classes(codec, ref)
+    what = case.id
+    parity.check_exact(ref["records"], np.ascontiguousarray(got["records"]).view(RECORD_DTYPE).reshape(-1), what + ": records", Tt)
+    with parity.located(Tt):
+        parity.check_results(ref["results"], np.ascontiguousarray(got["results"]).view(RESULT_DTYPE).reshape(-1), what + ": results")
+        m = parity.check_pcm(ref["pcmf"], got["pcmf"].reshape(-1, 160), ref["pcm16"], got["pcm16"].reshape(-1, 160), what=what + ": pcm", peak=ref["peak"])
+    parity.check_state(ref["state"], state[slots], what=what + ": state (rows are streams)")
+    parity.check_exact(ref["rng"], rng[slots], what + ": rng")
+    if indexed:   # the slots of the pool the index does not name are as they were
+        rest = np.setdiff1d(np.arange(pool), slots)
+        assert state[rest].tobytes() == untouched_state[rest].tobytes() and rng[rest].tobytes() == untouched_rng[rest].tobytes(), what + ": a slot outside the index changed"
+    return m
+
+
+def main():
+    case = BY_ID[sys.argv[1]]
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from mbelib_neo_amd import decoder
+
+    decoder.ensure_init(0)
+    try:
+        m = run_case(case)
+    except AssertionError as e:
+        print(f"MISMATCH {case.id}: {e}")
+        return 1
+    print(f"ok {case.id}: {m}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -3,6 +3,7 @@ __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module."
 import ctypes as C
 import os
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -16,6 +17,15 @@ sys.path.insert(0, ROOT)
 from mbelib_neo_amd.layout import PARMS_DTYPE, RECORD_DTYPE, RESULT_DTYPE, RNG_DTYPE, FRAME_BYTES, PARAM_BITS  # noqa: E402
 
 _vp = C.c_void_p
+SOFT_CELLS = {0: 184, 1: 96, 2: 168, 3: 96}   # (bit, reliability) pairs per soft-decision frame, by codec
+MAX_THREADS = 32             # Oracle.process_batch: most ranges of streams decoded side by side
+SMALL_BATCH_FRAMES = 16384   # ... and below this many frames ONE thread: a pool costs more than it saves there, and bench.py's
+                             # cpu_baseline leg times this function as "cores: 1" on batches of at most 8,192 frames
+
+
+def default_threads(frames):
+    """threads Oracle.process_batch uses for a batch of `frames` frames when the caller does not say"""
+    return 1 if frames < SMALL_BATCH_FRAMES else min(len(os.sched_getaffinity(0)), MAX_THREADS)
 
 
 class Oracle:
@@ -118,23 +128,23 @@ class Oracle:
         return out.value, errs
 
     def init_state(self, streams):
-        st = np.zeros((streams, 3), dtype=PARMS_DTYPE)
-        for s in range(streams):
-            self.h.mbxo_init_parms(st[s, 0:1].ctypes.data, st[s, 1:2].ctypes.data, st[s, 2:3].ctypes.data)
-        return st
+        """[streams, 3] (cur, prev, enh) as mbxo_init_parms leaves them: one call, repeated for every stream"""
+        one = np.zeros((1, 3), dtype=PARMS_DTYPE)
+        self.h.mbxo_init_parms(one[0, 0:1].ctypes.data, one[0, 1:2].ctypes.data, one[0, 2:3].ctypes.data)
+        return np.repeat(one, streams, axis=0)
 
     def rng_seeded(self, seeds):
         r = np.zeros(len(seeds), dtype=RNG_DTYPE)
+        base, step = r.ctypes.data, RNG_DTYPE.itemsize
         for i, s in enumerate(seeds):
-            self.h.mbxo_rng_default(r[i : i + 1].ctypes.data)
-            self.h.mbxo_rng_seed(r[i : i + 1].ctypes.data, int(s) & 0xFFFFFFFF)
+            self.h.mbxo_rng_default(base + i * step)
+            self.h.mbxo_rng_seed(base + i * step, int(s) & 0xFFFFFFFF)
         return r
 
     def rng_default(self, n):
-        r = np.zeros(n, dtype=RNG_DTYPE)
-        for i in range(n):
-            self.h.mbxo_rng_default(r[i : i + 1].ctypes.data)
-        return r
+        one = np.zeros(1, dtype=RNG_DTYPE)
+        self.h.mbxo_rng_default(one.ctypes.data)
+        return np.repeat(one, n)
 
     def pack(self, codec, cells):
         """cells: [n, 184|96] int8 -> (rc list, packed [n, 18|9])"""
@@ -219,8 +229,11 @@ class Oracle:
         assert self.h.mbxo_soft_bits_from_llr(llr.ctypes.data, out.ctypes.data, llr.size) == 0
         return out
 
-    def process_batch(self, codec, S, T, frames, state, rng, soft=False):
-        """frames: packed wire frames, or with soft=True uint8 [S*T, 184|96, 2] soft-decision frames"""
+    def process_batch(self, codec, S, T, frames, state, rng, soft=False, threads=None):
+        """frames: packed wire frames, or with soft=True uint8 [S*T, 184|96, 2] soft-decision frames.
+        threads: how many contiguous ranges of streams decode side by side (streams are independent, ctypes releases the GIL,
+        every range writes its own slices of the same arrays, so the result does not depend on it); None = one per CPU this
+        process may run on, at most MAX_THREADS, and one for batches below SMALL_BATCH_FRAMES frames."""
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
         state = np.ascontiguousarray(state).copy()
         rng = np.ascontiguousarray(rng).copy()
@@ -231,15 +244,30 @@ class Oracle:
         records = np.zeros(n, dtype=RECORD_DTYPE)
         peak = np.zeros(n, dtype=np.float32)   # largest |sample| before the soft clip, per frame (parity.int16_bound)
         fn = self.h.mbxo_process_batch_soft if soft else self.h.mbxo_process_batch
-        self.h.mbxo_set_preclip_peaks(peak.ctypes.data)
-        try:
-            rc = fn(
-                codec, S, T, frames.ctypes.data, state.ctypes.data, rng.ctypes.data, pcm16.ctypes.data, pcmf.ctypes.data,
-                results.ctypes.data, records.ctypes.data,
-            )
-        finally:
-            self.h.mbxo_set_preclip_peaks(None)
-        assert rc == 0
+        if threads is None:
+            threads = default_threads(n)
+        threads = max(1, min(int(threads), S))
+        frame_bytes = 2 * SOFT_CELLS[codec] if soft else FRAME_BYTES[codec]
+
+        def run(a, b):   # streams [a, b): every pointer moved to stream a, the peak pointer bound to THIS thread (mbx_oracle.h)
+            f = a * T
+            self.h.mbxo_set_preclip_peaks(peak.ctypes.data + f * 4)
+            try:
+                return fn(
+                    codec, b - a, T, frames.ctypes.data + f * frame_bytes, state.ctypes.data + a * 3 * PARMS_DTYPE.itemsize,
+                    rng.ctypes.data + a * RNG_DTYPE.itemsize, pcm16.ctypes.data + f * 320, pcmf.ctypes.data + f * 640,
+                    results.ctypes.data + f * RESULT_DTYPE.itemsize, records.ctypes.data + f * RECORD_DTYPE.itemsize,
+                )
+            finally:
+                self.h.mbxo_set_preclip_peaks(None)
+
+        if threads == 1:
+            rcs = [run(0, S)]
+        else:
+            cuts = [S * i // threads for i in range(threads + 1)]
+            with ThreadPoolExecutor(max_workers=threads) as pool:
+                rcs = list(pool.map(run, cuts[:-1], cuts[1:]))
+        assert all(rc == 0 for rc in rcs), rcs
         return {"pcm16": pcm16, "pcmf": pcmf, "results": results, "records": records, "state": state, "rng": rng, "peak": peak}
 
     def synthesize_speech(self, cur, prev, rng):

@@ -24,6 +24,9 @@ clipped frames; on those very frames the REFERENCE's own build for an FMA target
 oracle/Makefile `fma`) differs from its IEEE build by 8 to 55 LSB, and over 10.5 M samples by >= 7 LSB on 4,000 of them
 (oracle/tools/ref_simd_vs_scalar.py fma).  The oracle (and the HIP path) follow the IEEE build.
 """
+import contextlib
+import re
+
 import numpy as np
 
 from mbelib_neo_amd.layout import EXACT_FLOAT_FIELDS, FLOAT_FIELDS, INT_FIELDS
@@ -153,3 +156,61 @@ def check_state(ref, got, rel=STATE_REL_RMS, what="state"):
         assert r <= rel, f"{what}: float field {name} relative RMS {r:.3e} > {rel:.1e}"
         out[name] = r
     return out
+
+
+@contextlib.contextmanager
+def located(T, streams=None):
+    """`with parity.located(T, pick): parity.check_...(ref, got)` on batches laid out [stream, tick]: a failure that names a frame
+    ("frame 1234", "frames [7 8 9]") is raised again with the stream and the tick of each frame behind it -- frame f is tick f % T of
+    stream streams[f // T] (streams: the indices the compared rows were picked with; None = every stream, in order)."""
+    def where(f):
+        s = f // T
+        return f"{f} (stream {int(streams[s]) if streams is not None else s}, tick {f % T})"
+
+    try:
+        yield
+    except AssertionError as e:
+        msg = re.sub(r"frames \[([\d\s]+)\]", lambda m: "frames [" + ", ".join(where(int(x)) for x in m.group(1).split()) + "]", str(e))
+        msg = re.sub(r"frame (\d+)", lambda m: "frame " + where(int(m.group(1))), msg)
+        raise AssertionError(msg) from None
+
+
+def check_exact(ref, got, what, T=1, streams=None):
+    """byte-for-byte equality of two arrays with one row per frame (records, RNG state with T = 1, ...); names the first row that differs"""
+    ref, got = np.ascontiguousarray(ref), np.ascontiguousarray(got)
+    assert ref.dtype == got.dtype and ref.shape == got.shape, f"{what}: {ref.dtype}{ref.shape} against {got.dtype}{got.shape}"
+    if ref.tobytes() != got.tobytes():
+        rows = max(ref.shape[0], 1)
+        bad = np.nonzero((ref.reshape(rows, -1).view(np.uint8) != got.reshape(rows, -1).view(np.uint8)).any(axis=1))[0]
+        f = int(bad[0])
+        s = f // T
+        raise AssertionError(f"{what}: {bad.size} rows differ, first row {f} (stream {int(streams[s]) if streams is not None else s}, tick {f % T}): "
+                             f"ref={ref[f]} got={got[f]}")
+
+
+def check_state_blocks(ref, got, block=256, rel=STATE_REL_RMS, what="state"):
+    """check_state block by block of `block` streams (rows of ref / got), so that the float fields' relative-RMS bound meets every 256
+    streams on their own: over 65,536 streams at once one stream with a wrong float state is diluted 256-fold before it meets the
+    bound.  The failure names the block's streams."""
+    ref, got = np.asarray(ref), np.asarray(got)
+    assert ref.shape == got.shape, f"{what}: {ref.shape} against {got.shape}"
+    for a in range(0, ref.shape[0], block):
+        b = min(a + block, ref.shape[0])
+        check_state(ref[a:b], got[a:b], rel=rel, what=f"{what} (streams {a}..{b - 1}; indices within the block)")
+
+
+def check_pcm_located(ref_f, got_f, ref_s, got_s, T, streams=None, **kw):
+    """check_pcm (same arguments, same bounds) on a batch laid out [stream, tick]; a failure also names where the batch is worst --
+    the frame, stream and tick of the largest int16 difference and of the largest float error -- whichever bound it was that failed"""
+    try:
+        with located(T, streams):
+            return check_pcm(ref_f, got_f, ref_s, got_s, **kw)
+    except AssertionError as e:
+        def where(f):
+            s = f // T
+            return f"frame {f} (stream {int(streams[s]) if streams is not None else s}, tick {f % T})"
+
+        d = np.abs(np.asarray(ref_s, dtype=np.int32).reshape(-1, 160) - np.asarray(got_s, dtype=np.int32).reshape(-1, 160)).max(axis=1)
+        _, ratio, at = pcm_float_stats(ref_f, got_f)
+        raise AssertionError(f"{e}; largest int16 difference {int(d.max())} LSB in {where(int(d.argmax()))}; "
+                             f"largest float error {ratio:.3e} of the frame in {where(at)}") from None

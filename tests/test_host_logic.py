@@ -65,6 +65,45 @@ def test_every_kernel_is_declared_once_and_every_stream_instance_has_one_table_r
         assert api.count(f'"{name}"') == 1, name
 
 
+def test_every_table_row_has_an_oracle_case_and_every_case_switch_is_one_the_library_reads():
+    """tests/instance_cases.py is what runs each row of kInstances by name against the oracle (tests/test_gpu_instances.py): a row
+    without a case, a case for a row that is gone, or a case that asks for a switch nobody reads fails HERE, without a GPU."""
+    import instance_cases
+
+    api = open(os.path.join(ROOT, "mbelib-neo_amd", "csrc", "mbx_api.hip")).read()
+    table = api[api.index("kInstances[] = {"):]
+    rows = set(re.findall(r'\{"(\w+)",\s*mbx::\w+\}', table[:table.index("};")]))
+    covered = {c.name for c in instance_cases.CASES}
+    assert not rows - covered, f"kInstances rows without an oracle case in tests/instance_cases.py: {sorted(rows - covered)}"
+    assert not covered - rows, f"cases for instances that are not in kInstances: {sorted(covered - rows)}"
+    read = set(re.findall(r'getenv\("(MBX_\w+)"\)', api))
+    for c in instance_cases.CASES:
+        assert set(c.env) <= read, f"{c.id}: {sorted(set(c.env) - read)} is not read by mbx_api.hip"
+        assert c.launches >= 2 and c.S >= 2 and c.T >= 1 and c.S * c.T * c.launches <= 330_000, c.id
+        assert c.entry in ("batch", "batch_ws", "batch_indexed", "resident", "resident_indexed", "staged"), c.id
+        assert c.id == c.name or c.id.startswith(c.name + "-"), c.id
+    # the edges the cases are there for
+    shapes = {(c.S, c.T) for c in instance_cases.CASES}
+    assert {s for s, _ in shapes} >= {256, 257} and {t for _, t in shapes} >= {1, 2, 3, 4, 17, 40}
+    assert any(c.S % 8 and c.S % 3 and c.T == 40 for c in instance_cases.CASES)
+    assert any(c.env.get("MBX_FRONT_LEAD") and (c.S + 7) // 8 > int(c.env["MBX_FRONT_LEAD"]) for c in instance_cases.CASES)
+    assert any(c.entry.endswith("_indexed") for c in instance_cases.CASES)
+
+
+def test_the_edge_mix_holds_every_frame_class(oracle):
+    """the workload of the instance cases (tests/edge_mix.py), decoded by the oracle: repeats, a run of repeats to the mute, clean and
+    heavily damaged frames, frames above the soft clip, and for the AMBE codecs tone and erasure frames -- in as few as six frames"""
+    import edge_mix
+
+    for codec in range(4):
+        for S, T in ((200, 6), (257, 6), (301, 34)):
+            fr = edge_mix.frames(codec, S, T, tag=1)
+            assert fr.shape[:2] == (S, T) and (fr[2 + 3 * 1] [0] == 0).all() and (fr[2 + 3 * 1][1] == 0xFF).all()   # stream 5: all-zero, all-one
+            ref = oracle.process_batch(codec, S, T, fr.reshape(S * T, -1), oracle.init_state(S), oracle.rng_seeded(np.arange(S)))
+            edge_mix.assert_classes(codec, ref)
+            assert edge_mix.frames(codec, S, T, tag=1).tobytes() == fr.tobytes()   # seeded: the child processes build the same frames
+
+
 def test_launchers_fail_loudly_without_init_or_device():
     from mbelib_neo_amd import _native
 

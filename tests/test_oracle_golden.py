@@ -462,3 +462,91 @@ def test_tail_cases_fixture_is_pinned_and_shows_the_references_own_spread(oracle
     for codec in range(4):   # the histograms the cases were drawn from: >= 31 M samples per codec, nothing beyond 4 LSB
         h = fx[f"hist{codec}"]
         assert h.sum() >= 30_000_000 and h[5:].sum() == 0 and h[:2].sum() / h.sum() >= 0.99999
+
+
+def _same_bytes(a, b, what):
+    for k in a:
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), (what, k)
+
+
+@pytest.mark.parametrize("fft_float", [0, 1])
+@pytest.mark.parametrize("codec", [0, 1, 2, 3])
+def test_threaded_batch_gives_the_bytes_of_the_single_thread(oracle, codec, fft_float):
+    """Oracle.process_batch splits a batch into contiguous ranges of streams on a thread pool (the GPU suite compares every
+    stream of its full-shape launches with it).  1,000 random-bit streams x 6 frames -- every error bucket, repeats, mutes,
+    tone and erasure frames -- decoded on one thread and on seven (ranges of 142 and 143 streams): every returned array,
+    the pre-clip peaks included, is the same bytes, for every codec and both FFT forms."""
+    from mbelib_neo_amd import framegen
+
+    S, T = 1000, 6
+    frames = framegen.random_frames(codec, S * T, framegen.rng_for(900 + codec))
+    state, rng = oracle.init_state(S), oracle.rng_seeded(np.arange(S) * 7 + 1)
+    oracle.set_fft_float(fft_float)
+    try:
+        one = oracle.process_batch(codec, S, T, frames, state, rng, threads=1)
+        seven = oracle.process_batch(codec, S, T, frames, state, rng, threads=7)
+    finally:
+        oracle.set_fft_float(0)
+    assert one["peak"].max() > 0 and len(np.unique(one["results"]["flags"])) > 1   # the workload is not a trivial one
+    _same_bytes(one, seven, (codec, fft_float, "threads=7"))
+
+
+def test_default_stays_on_one_thread_for_the_batches_the_benchmark_times(oracle, monkeypatch):
+    """bench.py's cpu_baseline leg times Oracle.process_batch without a `threads` argument and reports it as one core: 4,096 x 1
+    (512 x 1 soft), 256 x 16 ... 64 x 128 = at most 8,192 frames.  For those the default is ONE thread, whatever the host has --
+    in the function that decides and in the calls that are made; the full-shape comparisons (>= 262,144 frames) get the pool."""
+    import concurrent.futures
+
+    from mbelib_neo_amd import framegen
+
+    monkeypatch.setattr(os, "sched_getaffinity", lambda pid: set(range(64)))
+    shapes = [(4096 if T == 1 else max(64, 4096 // T), T) for T in (1, 2, 4, 16, 40, 128)] + [(512, 1)]
+    for S, T in shapes:
+        assert oracle_lib.default_threads(S * T) == 1, (S, T)
+    assert oracle_lib.default_threads(65536 * 4) == oracle_lib.MAX_THREADS and oracle_lib.default_threads(8192 * 128) == oracle_lib.MAX_THREADS
+
+    def no_pool(*a, **k):
+        raise AssertionError("a thread pool for a batch the benchmark times as one core")
+
+    monkeypatch.setattr(oracle_lib, "ThreadPoolExecutor", no_pool)
+    assert concurrent.futures.ThreadPoolExecutor is not no_pool
+    for codec, S, T in ((0, 4096, 1), (0, 256, 16), (1, 64, 128)):
+        frames = framegen.random_frames(codec, S * T, framegen.rng_for(960 + T))
+        oracle.process_batch(codec, S, T, frames, oracle.init_state(S), oracle.rng_seeded(np.arange(S) + 1234))
+
+
+def test_default_thread_count_of_a_large_batch_gives_the_bytes_of_the_single_thread(oracle):
+    from mbelib_neo_amd import framegen
+
+    S, T = 2000, 10   # above SMALL_BATCH_FRAMES: the default is the pool
+    assert oracle_lib.default_threads(S * T) == min(len(os.sched_getaffinity(0)), oracle_lib.MAX_THREADS)
+    frames = framegen.random_frames(1, S * T, framegen.rng_for(970))
+    state, rng = oracle.init_state(S), oracle.rng_seeded(np.arange(S) + 3)
+    _same_bytes(oracle.process_batch(1, S, T, frames, state, rng, threads=1), oracle.process_batch(1, S, T, frames, state, rng), "threads=None")
+
+
+def test_threaded_soft_batch_gives_the_bytes_of_the_single_thread(oracle):
+    from mbelib_neo_amd import framegen
+
+    S, T = 1000, 6
+    soft = framegen.soft_frames(0, S * T, framegen.rng_for(950))
+    state, rng = oracle.init_state(S), oracle.rng_seeded(np.arange(S) + 77)
+    one = oracle.process_batch(0, S, T, soft, state, rng, soft=True, threads=1)
+    seven = oracle.process_batch(0, S, T, soft, state, rng, soft=True, threads=7)
+    assert one["peak"].max() > 0
+    _same_bytes(one, seven, "soft")
+
+
+def test_state_and_rng_builders_equal_one_call_per_stream(oracle):
+    """init_state / rng_default repeat one call's result; every stream's entry is what its own call writes"""
+    import ctypes as C
+
+    st = oracle.init_state(5)
+    own = np.zeros((1, 3), dtype=PARMS_DTYPE)
+    oracle.h.mbxo_init_parms(own[0, 0:1].ctypes.data, own[0, 1:2].ctypes.data, own[0, 2:3].ctypes.data)
+    assert st.shape == (5, 3) and all(st[i].tobytes() == own[0].tobytes() for i in range(5))
+    r = oracle.rng_seeded([0, 1, 0xFFFFFFFF])
+    for i, seed in enumerate([0, 1, 0xFFFFFFFF]):
+        one = oracle.rng_default(1)
+        oracle.h.mbxo_rng_seed(one.ctypes.data, C.c_uint32(seed))
+        assert r[i].tobytes() == one[0].tobytes()
