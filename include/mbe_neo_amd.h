@@ -174,8 +174,12 @@ int mbe_requiresAdaptiveSmoothing(const mbe_parms* mp);                         
  *                   mbe_flush();        // all queued frames run as a few batched launches; pcm / res / d are filled now
  *     mbe_batchEnd();                   // flush, bring the model state back to the host structs, leave queue mode
  *
- * Queued are the hard-decision mbe_process*Frame / mbe_process*Framef calls of the four codecs (every other function
- * keeps running synchronously).  A queued call validates its arguments and the frame bits exactly like the synchronous
+ * Queued are the hard-decision mbe_process*Frame / mbe_process*Framef calls of the four codecs and -- when the flag
+ * MBE_BATCH_QUEUE_SOFT is OR'ed into mbe_batchBegin's argument -- the eight mbe_process*SoftFrame / mbe_process*SoftFramef
+ * calls (every other function keeps running synchronously: mbe_decode*SoftFrame, the mbe_process*Data[f] calls; without
+ * the flag a soft call inside queue mode is synchronous as well).  A channel's pending frames share one codec and one
+ * input form: a channel that changes between hard and soft frames, or between codecs, runs what is queued first.  A
+ * queued call validates its arguments and the frame bits exactly like the synchronous
  * one (negative return, nothing queued, nothing written), then returns 0; its outputs -- aout_buf, *result (incl. the
  * total error count the synchronous call would have returned), imbe_d / ambe_d and the three mbe_parms -- are written by
  * mbe_flush(), so those pointers must stay valid until then.  A channel is identified by its cur_mp pointer; frames
@@ -191,6 +195,7 @@ int mbe_requiresAdaptiveSmoothing(const mbe_parms* mp);                         
  *                              channel first flushes and releases it, so mixing the two is safe, just slow. */
 #define MBE_BATCH_STATE_WRITEBACK 0
 #define MBE_BATCH_STATE_RESIDENT 1
+#define MBE_BATCH_QUEUE_SOFT 0x10            /* OR into state_mode: mbe_process*SoftFrame[f] calls are queued as well */
 int mbe_batchBegin(int state_mode);          /* 0, or MBE_STATUS_INVALID_ARGUMENT (bad mode, already in queue mode) */
 int mbe_flush(void);                         /* frames run (>= 0) */
 int mbe_batchPending(void);                  /* frames queued and not yet flushed by this thread */

@@ -203,11 +203,30 @@ int mbx_fec_stage(int codec, int stage, const void* d_in, size_t n, uint8_t* d_f
  *      mbe_golay2312Soft src/ecc/ecc.c:303-357, mbe_hamming1511Soft src/ecc/ecc.c:157-215,410-413 */
 int mbx_fec_soft(int codec, const mbe_soft_bit* d_soft /* n*184 | n*96 */, size_t n, mbx_param_record* d_records,
                  void* stream);
-/* ref: mbe_processImbe7200x4400SoftFrame[f] / mbe_processAmbe3600x2450SoftFrame[f]
- *      src/imbe/imbe7200x4400.c:950-980, src/ambe/ambe3600x2450.c:939-969: soft FEC, then mbx_process_records */
+/* Soft-decision batches: S streams x T frames of mbe_soft_bit cells in the reference's shapes ([8][23], [7][24] for codec 2,
+ * [4][24] for codecs 1 and 3), stream-major like wire frames.  A soft front launch (one wave per frame: the search of
+ * mbx_fec_soft, the record), then the stream stage as mbx_process_records runs it (the expand launch where
+ * mbx_uses_expand_launch(), the stream-stage instance mbx_last_kernel_name reports).
+ * Hard decisions must be 0/1: device input is the caller's to check (mbx_validate_soft_bits on the host).
+ * ref: mbe_processImbe7200x4400SoftFrame[f] / mbe_processImbe7100x4400SoftFrame[f] / mbe_processAmbe3600x2450SoftFrame[f] /
+ *      mbe_processAmbe3600x2400SoftFrame[f]  include/mbelib-neo/mbelib.h:437-447, 513-523;
+ *      src/imbe/imbe7200x4400.c:950-980, src/ambe/ambe3600x2450.c:939-969 */
 int mbx_process_batch_soft(int codec, int S, int T, const mbe_soft_bit* d_soft, mbe_parms* d_state, mbx_stream_rng* d_rng,
                            int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records,
                            void* stream);
+/* the same with a caller-owned workspace of mbx_workspace_bytes(S*T) bytes (cf. mbx_process_batch_ws): nothing is allocated or
+ * grown by the call, so it can be captured into a HIP graph.
+ * ref: as mbx_process_batch_soft, include/mbelib-neo/mbelib.h:437-447, 513-523 */
+int mbx_process_batch_soft_ws(int codec, int S, int T, const mbe_soft_bit* d_soft, mbe_parms* d_state, mbx_stream_rng* d_rng,
+                              int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records,
+                              void* d_workspace, size_t workspace_bytes, void* stream);
+/* the soft twin of mbx_process_batch_resident (below): batch row s of d_soft, records, PCM and results belongs to pool slot
+ * d_stream_index[s] (NULL: slot s); d_resident = the pool's elision words (NULL: the triplets stay in their ABI form, as with
+ * mbx_process_batch_indexed).  A pool may take hard and soft launches in any order.
+ * ref: as mbx_process_batch_soft, include/mbelib-neo/mbelib.h:437-447, 513-523; the state: include/mbelib-neo/mbelib.h:88-139 */
+int mbx_process_batch_soft_resident(int codec, int S, int T, const int32_t* d_stream_index, const mbe_soft_bit* d_soft,
+                                    mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16,
+                                    float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream);
 /* ref: mbe_golay2312Soft (kind 0, 23 soft bits per block) / mbe_hamming1511Soft (kind 1, 15 soft bits)
  *      include/mbelib-neo/mbelib.h:246, 260.  out[i] bit j = corrected cell j, errs[i] = the reference's return value */
 int mbx_ecc_soft_words(int kind, const mbe_soft_bit* d_in, size_t n, uint32_t* d_out, int32_t* d_errs, void* stream);
@@ -426,6 +445,14 @@ int mbx_session_submit(mbx_session* s, int T, const uint8_t* frames, int16_t* pc
  * others keep their state.  `records` (may be NULL) returns imbe_d / ambe_d + error context (mbx_unpack_records). */
 int mbx_session_submit_indexed(mbx_session* s, int n, int T, const int32_t* stream_index, const uint8_t* frames, int16_t* pcm16,
                                float* pcmf, mbe_process_result* results, mbx_param_record* records);
+/* Soft-decision submits: host mbe_soft_bit frames in the reference's shapes (184 / 168 / 96 cells per frame for codecs 0 / 2 /
+ * 1 and 3), staged like wire frames and run on the same resident state by mbx_process_batch_soft_resident: hard and soft submits
+ * may alternate in any order.  A hard decision > 1 anywhere returns MBE_STATUS_INVALID_BITS and queues nothing.  The session's
+ * soft buffers are allocated by the first soft submit.
+ * ref: mbe_process*SoftFrame[f] include/mbelib-neo/mbelib.h:437-447, 513-523; mbe_validate_soft_bits src/internal/mbe_result.h:31-42 */
+int mbx_session_submit_soft(mbx_session* s, int T, const mbe_soft_bit* soft, int16_t* pcm16, float* pcmf, mbe_process_result* results);
+int mbx_session_submit_soft_indexed(mbx_session* s, int n, int T, const int32_t* stream_index, const mbe_soft_bit* soft, int16_t* pcm16,
+                                    float* pcmf, mbe_process_result* results, mbx_param_record* records);
 /* every batch submitted so far is complete and its outputs are in the caller's buffers */
 int mbx_session_wait(mbx_session* s);
 /* state of streams [first, first + count): ref mbe_initMbeParms / mbe_setThreadRngSeed / direct access.  These wait. */

@@ -82,6 +82,8 @@ _SIGNATURES = {
     "mbx_fec_imbe7100x4400": (C.c_int, [_vp, _sz, _vp, _vp]),
     "mbx_fec_soft": (C.c_int, [C.c_int, _vp, _sz, _vp, _vp]),
     "mbx_process_batch_soft": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mbx_process_batch_soft_ws": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mbx_process_batch_soft_resident": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mbx_ecc_soft_words": (C.c_int, [C.c_int, _vp, _sz, _vp, _vp, _vp]),
     "mbx_validate_soft_bits": (C.c_int, [_vp, _sz]),
     "mbx_soft_bits_from_hard": (C.c_int, [_vp, _vp, _sz, C.c_uint8]),
@@ -94,6 +96,8 @@ _SIGNATURES = {
     "mbx_session_streams": (C.c_int, [_vp]),
     "mbx_session_submit": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
     "mbx_session_submit_indexed": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mbx_session_submit_soft": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp]),
+    "mbx_session_submit_soft_indexed": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mbx_session_wait": (C.c_int, [_vp]),
     "mbx_session_reset": (C.c_int, [_vp, C.c_int, C.c_int]),
     "mbx_session_seed": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),

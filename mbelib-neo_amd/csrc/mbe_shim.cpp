@@ -580,10 +580,11 @@ FrameShapeLite frame_shape_lite(int codec) {
 }
 
 // ==================================================================================================================
-// Queue mode (include/mbe_neo_amd.h): the hard-decision mbe_process*Frame[f] calls of a thread are recorded and run by
-// mbe_flush() as batched launches -- one mbx_process_batch_indexed() per (codec, frames-per-channel) group -- over a
-// pool of channel states that lives on the device.  Host work per queued frame: validation + packing (what the
-// synchronous call does on the host as well) and a 64-byte queue entry.
+// Queue mode (include/mbe_neo_amd.h): the hard-decision mbe_process*Frame[f] calls of a thread -- and, with
+// MBE_BATCH_QUEUE_SOFT, its mbe_process*SoftFrame[f] calls -- are recorded and run by mbe_flush() as batched launches,
+// one per (codec, input form, frames-per-channel) group, over a pool of channel states that lives on the device.  Host
+// work per queued frame: validation + packing (what the synchronous call does on the host as well) and a queue entry;
+// a soft frame's cells (up to 368 B) go into the thread's cell arena, the entry keeps their offset.
 // ==================================================================================================================
 struct QEntry {
     void*               aout;
@@ -592,12 +593,14 @@ struct QEntry {
     int                 channel;      // index into Batch::channels
     uint8_t             codec;
     uint8_t             want_short;
-    uint8_t             frame[MBX_IMBE_FRAME_BYTES];
+    uint8_t             frame[MBX_IMBE_FRAME_BYTES];   // hard-decision entry: the packed wire frame
+    size_t              soft_at;                       // soft entry: first cell in Batch::soft_cells
 };
 
 struct QChannel {
     mbe_parms *cur, *prev, *enh;
     int  codec = -1;       // codec of the frames pending for this channel (one codec per channel and flush)
+    bool soft = false;     // ... and their input form (one per channel and flush as well)
     int  pending = 0;
     int  first = -1;       // per-flush scratch: position of the channel inside its group
     int  slot = -1;        // where its state lives in the device pool (resident mode: = channel index; write-back: per flush)
@@ -654,8 +657,11 @@ struct PinArr {   // grow-only pinned host array
 
 struct Batch {
     bool active = false;
+    bool queue_soft = false;                              // MBE_BATCH_QUEUE_SOFT: mbe_process*SoftFrame[f] queue as well
     int  mode = MBE_BATCH_STATE_WRITEBACK;
     std::vector<QEntry>   q;
+    std::vector<mbe_soft_bit> soft_cells;                 // cells of the queued soft frames, in call order; gathered into
+                                                          // h_frames (pinned, group order) by the flush like packed frames
     std::vector<QChannel> channels;                       // pool slot = index
     std::unordered_map<const mbe_parms*, int> index;      // cur_mp -> channel
     std::unordered_map<const mbe_parms*, int> aux;        // prev_mp / prev_mp_enhanced -> channel (direct use of either struct)
@@ -694,6 +700,11 @@ Batch& batch() {
 
 size_t frame_bytes_of(int codec) {
     return (codec == MBX_CODEC_AMBE3600X2450 || codec == MBX_CODEC_AMBE3600X2400) ? MBX_AMBE_FRAME_BYTES : MBX_IMBE_FRAME_BYTES;
+}
+
+// one frame as the batch launchers take it: packed wire bytes, or the reference's array of soft cells
+size_t input_bytes_of(int codec, bool soft) {
+    return soft ? (size_t)frame_shape_lite(codec).ncell * sizeof(mbe_soft_bit) : frame_bytes_of(codec);
 }
 
 // grow the device pool to `n` channels, keeping what is resident
@@ -848,6 +859,7 @@ int flush_batch(Batch& b) {
     // ---- groups of channels with the same codec and the same number of pending frames ----
     struct Group {
         int    codec, T;
+        bool   soft;
         size_t nch = 0, row0 = 0, byte0 = 0;    // channels, first batch row, byte offset of its frames
         std::vector<int> members;
     };
@@ -858,11 +870,11 @@ int flush_batch(Batch& b) {
         if (ch.pending == 0) {
             continue;
         }
-        const uint64_t key = ((uint64_t)ch.codec << 32) | (uint32_t)ch.pending;
+        const uint64_t key = ((uint64_t)ch.codec << 33) | ((uint64_t)ch.soft << 32) | (uint32_t)ch.pending;
         auto it = group_of.find(key);
         if (it == group_of.end()) {
             it = group_of.emplace(key, groups.size()).first;
-            groups.push_back(Group{ch.codec, ch.pending});
+            groups.push_back(Group{ch.codec, ch.pending, ch.soft});
         }
         Group& g = groups[it->second];
         ch.first = (int)g.nch++;
@@ -873,7 +885,7 @@ int flush_batch(Batch& b) {
         g.row0 = rows;
         g.byte0 = bytes;
         rows += g.nch * (size_t)g.T;
-        bytes += (g.nch * (size_t)g.T * frame_bytes_of(g.codec) + 15u) & ~(size_t)15u;   // frame arrays start 16-byte aligned
+        bytes += (g.nch * (size_t)g.T * input_bytes_of(g.codec, g.soft) + 15u) & ~(size_t)15u;   // frame arrays start 16-byte aligned
     }
     // row of every queue entry: group row0 + position of the channel * T + (how many of the channel's frames came before)
     std::vector<size_t> row_of(n);
@@ -892,8 +904,8 @@ int flush_batch(Batch& b) {
         const Group& g = groups[group_idx[(size_t)qe.channel]];
         const size_t local = (size_t)b.channels[(size_t)qe.channel].first * (size_t)g.T + (size_t)seen[(size_t)qe.channel]++;
         row_of[e] = g.row0 + local;
-        const size_t fb = frame_bytes_of(g.codec);
-        memcpy(b.h_frames.p + g.byte0 + local * fb, qe.frame, fb);
+        const size_t fb = input_bytes_of(g.codec, g.soft);
+        memcpy(b.h_frames.p + g.byte0 + local * fb, g.soft ? static_cast<const void*>(&b.soft_cells[qe.soft_at]) : static_cast<const void*>(qe.frame), fb);
         any_short |= qe.want_short != 0;
         any_float |= qe.want_short == 0;
     }
@@ -947,7 +959,14 @@ int flush_batch(Batch& b) {
     const double tr1 = g_trace_flush ? trace_now() : 0.0;
     for (size_t gi = 0; gi < groups.size(); ++gi) {
         const Group& g = groups[gi];
-        if (b.mode == MBE_BATCH_STATE_RESIDENT) {   // the pool owns the state between flushes: no prev_mp_enhanced traffic, lazy prev_mp
+        if (g.soft) {   // soft cells in: the soft twin of both launchers (no elision words in write-back mode)
+            must(mbx_process_batch_soft_resident(g.codec, (int)g.nch, g.T, k_index + index_off[gi],
+                                                 reinterpret_cast<const mbe_soft_bit*>(k_frames + g.byte0), b.d_state.p,
+                                                 b.mode == MBE_BATCH_STATE_RESIDENT ? b.d_elided.p : nullptr, b.d_rng.p,
+                                                 k_pcm16 ? k_pcm16 + g.row0 * 160 : nullptr, k_pcmf ? k_pcmf + g.row0 * 160 : nullptr,
+                                                 k_results + g.row0, k_records + g.row0, s.stream),
+                 "mbx_process_batch_soft_resident");
+        } else if (b.mode == MBE_BATCH_STATE_RESIDENT) {   // the pool owns the state between flushes: no prev_mp_enhanced traffic, lazy prev_mp
             must(mbx_process_batch_resident(g.codec, (int)g.nch, g.T, k_index + index_off[gi], k_frames + g.byte0, b.d_state.p,
                                             b.d_elided.p, b.d_rng.p, k_pcm16 ? k_pcm16 + g.row0 * 160 : nullptr,
                                             k_pcmf ? k_pcmf + g.row0 * 160 : nullptr, k_results + g.row0, k_records + g.row0, s.stream),
@@ -1037,6 +1056,7 @@ int flush_batch(Batch& b) {
     }
     s.npending = 0;
     b.q.clear();
+    b.soft_cells.clear();
     for (QChannel& ch : b.channels) {
         ch.pending = 0;
         ch.codec = -1;
@@ -1108,14 +1128,14 @@ void sync_channel_for_direct_use(const mbe_parms* any) {
     }
 }
 
-// the queued form of mbe_process*Frame[f]
+// the queued form of mbe_process*Frame[f] (cells) and mbe_process*SoftFrame[f] (soft: the frame's cells, `cells` unused)
 int queue_frame(int codec, float* aout_f, short* aout_s, mbe_process_result* result, const char* cells, char* bits_out,
-                mbe_parms* cur, mbe_parms* prev, mbe_parms* enh) {
+                mbe_parms* cur, mbe_parms* prev, mbe_parms* enh, const mbe_soft_bit* soft = nullptr) {
     const FrameShapeLite sh = frame_shape_lite(codec);
     if (!bits_out || (!aout_f && !aout_s) || !cur || !prev || !enh) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    int rc = validate_bits(cells, (size_t)sh.ncell);
+    int rc = soft ? mbx_validate_soft_bits(soft, (size_t)sh.ncell) : validate_bits(cells, (size_t)sh.ncell);
     if (rc < 0) {
         return rc;
     }
@@ -1139,13 +1159,14 @@ int queue_frame(int codec, float* aout_f, short* aout_s, mbe_process_result* res
         if (ch.prev != prev || ch.enh != enh) {
             return MBE_STATUS_INVALID_ARGUMENT;   // a channel is its three structs; they cannot change while it is queued / resident
         }
-        if (ch.pending && ch.codec != codec) {    // one codec per channel and flush: run what is queued first
+        if (ch.pending && (ch.codec != codec || ch.soft != (soft != nullptr))) {   // one codec and one input form per channel and flush: run what is queued first
             (void)flush_batch(b);
-            return queue_frame(codec, aout_f, aout_s, result, cells, bits_out, cur, prev, enh);
+            return queue_frame(codec, aout_f, aout_s, result, cells, bits_out, cur, prev, enh, soft);
         }
     }
     QChannel& ch = b.channels[(size_t)c];
     ch.codec = codec;
+    ch.soft = soft != nullptr;
     ch.pending++;
     b.q.emplace_back();
     QEntry& qe = b.q.back();
@@ -1155,6 +1176,11 @@ int queue_frame(int codec, float* aout_f, short* aout_s, mbe_process_result* res
     qe.bits_out = bits_out;
     qe.channel = c;
     qe.codec = (uint8_t)codec;
+    if (soft) {
+        qe.soft_at = b.soft_cells.size();
+        b.soft_cells.insert(b.soft_cells.end(), soft, soft + sh.ncell);
+        return 0;
+    }
     rc = (codec == MBX_CODEC_IMBE7200X4400)   ? mbx_pack_imbe7200x4400(cells, 1, qe.frame)
          : (codec == MBX_CODEC_IMBE7100X4400) ? mbx_pack_imbe7100x4400(cells, 1, qe.frame)
                                               : mbx_pack_ambe3600x2450(cells, 1, qe.frame);
@@ -1167,6 +1193,24 @@ int queue_frame(int codec, float* aout_f, short* aout_s, mbe_process_result* res
 }
 
 bool queueing() { return batch().active; }
+
+// mbe_process*SoftFrame[f] inside queue mode with MBE_BATCH_QUEUE_SOFT.  Only a call the synchronous path would run to the end
+// is queued: with a NULL argument that path reports its own status after writing what the reference writes, so it keeps the call.
+bool queue_soft_call(const void* aout, const void* cells, const char* bits_out, const mbe_parms* cur, const mbe_parms* prev,
+                     const mbe_parms* enh) {
+    const Batch& b = batch();
+    return b.active && b.queue_soft && aout && cells && bits_out && cur && prev && enh;
+}
+
+// the queued soft call: a refused frame leaves *result cleared, as the synchronous call does; a queued one writes nothing before the flush
+int queue_soft_frame(int codec, float* aout_f, short* aout_s, mbe_process_result* result, const mbe_soft_bit* cells, char* bits_out,
+                     mbe_parms* cur, mbe_parms* prev, mbe_parms* enh) {
+    const int rc = queue_frame(codec, aout_f, aout_s, result, nullptr, bits_out, cur, prev, enh, cells);
+    if (rc < 0 && result) {
+        memset(result, 0, sizeof(*result));
+    }
+    return rc;
+}
 
 // mbe_process*Frame[f], synchronous: frame decode + parameter processing as ONE launch of one wavefront (mbx_process_frame:
 // FEC by lane 0, then the LDS-resident stream body) on the caller's structs copied into the thread's pinned block; the
@@ -1541,11 +1585,16 @@ int mbe_decodeAmbe3600x2450SoftFrame(const mbe_soft_bit ambe_fr[4][24], char amb
 // ---- queue mode (include/mbe_neo_amd.h) -----------------------------------------------------------------------------
 int mbe_batchBegin(int state_mode) {
     Batch& b = batch();
+    const bool queue_soft = state_mode >= 0 && (state_mode & MBE_BATCH_QUEUE_SOFT) != 0;
+    if (queue_soft) {
+        state_mode &= ~MBE_BATCH_QUEUE_SOFT;
+    }
     if (b.active || (state_mode != MBE_BATCH_STATE_WRITEBACK && state_mode != MBE_BATCH_STATE_RESIDENT)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     (void)slot();   // the thread's device scratch and stream exist from here on
     b.active = true;
+    b.queue_soft = queue_soft;
     b.mode = state_mode;
     return 0;
 }
@@ -1784,6 +1833,9 @@ int mbe_decodeImbe7100x4400SoftFrame(const mbe_soft_bit imbe_fr[7][24], char imb
 
 int mbe_processImbe7100x4400SoftFramef(float* aout_buf, mbe_process_result* result, const mbe_soft_bit imbe_fr[7][24],
                                        char imbe_d[88], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
+    if (queue_soft_call(aout_buf, imbe_fr, imbe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
+        return queue_soft_frame(MBX_CODEC_IMBE7100X4400, aout_buf, nullptr, result, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    }
     mbe_process_result local;
     if (!result) {
         result = &local;
@@ -1797,6 +1849,9 @@ int mbe_processImbe7100x4400SoftFramef(float* aout_buf, mbe_process_result* resu
 
 int mbe_processImbe7100x4400SoftFrame(short* aout_buf, mbe_process_result* result, const mbe_soft_bit imbe_fr[7][24],
                                       char imbe_d[88], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
+    if (queue_soft_call(aout_buf, imbe_fr, imbe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
+        return queue_soft_frame(MBX_CODEC_IMBE7100X4400, nullptr, aout_buf, result, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    }
     if (!aout_buf) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
@@ -1854,6 +1909,9 @@ int mbe_processAmbe3600x2400Frame(short* aout_buf, mbe_process_result* result, c
 
 int mbe_processAmbe3600x2400SoftFramef(float* aout_buf, mbe_process_result* result, const mbe_soft_bit ambe_fr[4][24],
                                        char ambe_d[49], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
+    if (queue_soft_call(aout_buf, ambe_fr, ambe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
+        return queue_soft_frame(MBX_CODEC_AMBE3600X2400, aout_buf, nullptr, result, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    }
     mbe_process_result local;
     if (!result) {
         result = &local;
@@ -1867,6 +1925,9 @@ int mbe_processAmbe3600x2400SoftFramef(float* aout_buf, mbe_process_result* resu
 
 int mbe_processAmbe3600x2400SoftFrame(short* aout_buf, mbe_process_result* result, const mbe_soft_bit ambe_fr[4][24],
                                       char ambe_d[49], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
+    if (queue_soft_call(aout_buf, ambe_fr, ambe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
+        return queue_soft_frame(MBX_CODEC_AMBE3600X2400, nullptr, aout_buf, result, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    }
     if (!aout_buf) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
@@ -1884,6 +1945,9 @@ int mbe_processAmbe3600x2400SoftFrame(short* aout_buf, mbe_process_result* resul
 // ---- soft frames -> PCM: ref src/imbe/imbe7200x4400.c:950-980, src/ambe/ambe3600x2450.c:939-969 --------
 int mbe_processImbe7200x4400SoftFramef(float* aout_buf, mbe_process_result* result, const mbe_soft_bit imbe_fr[8][23],
                                        char imbe_d[88], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
+    if (queue_soft_call(aout_buf, imbe_fr, imbe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
+        return queue_soft_frame(MBX_CODEC_IMBE7200X4400, aout_buf, nullptr, result, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    }
     mbe_process_result local;
     if (!result) {
         result = &local;
@@ -1897,6 +1961,9 @@ int mbe_processImbe7200x4400SoftFramef(float* aout_buf, mbe_process_result* resu
 
 int mbe_processImbe7200x4400SoftFrame(short* aout_buf, mbe_process_result* result, const mbe_soft_bit imbe_fr[8][23],
                                       char imbe_d[88], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
+    if (queue_soft_call(aout_buf, imbe_fr, imbe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
+        return queue_soft_frame(MBX_CODEC_IMBE7200X4400, nullptr, aout_buf, result, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    }
     if (!aout_buf) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
@@ -1913,6 +1980,9 @@ int mbe_processImbe7200x4400SoftFrame(short* aout_buf, mbe_process_result* resul
 
 int mbe_processAmbe3600x2450SoftFramef(float* aout_buf, mbe_process_result* result, const mbe_soft_bit ambe_fr[4][24],
                                        char ambe_d[49], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
+    if (queue_soft_call(aout_buf, ambe_fr, ambe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
+        return queue_soft_frame(MBX_CODEC_AMBE3600X2450, aout_buf, nullptr, result, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    }
     mbe_process_result local;
     if (!result) {
         result = &local;
@@ -1926,6 +1996,9 @@ int mbe_processAmbe3600x2450SoftFramef(float* aout_buf, mbe_process_result* resu
 
 int mbe_processAmbe3600x2450SoftFrame(short* aout_buf, mbe_process_result* result, const mbe_soft_bit ambe_fr[4][24],
                                       char ambe_d[49], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
+    if (queue_soft_call(aout_buf, ambe_fr, ambe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
+        return queue_soft_frame(MBX_CODEC_AMBE3600X2450, nullptr, aout_buf, result, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    }
     if (!aout_buf) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }

@@ -781,6 +781,19 @@ int mbx_fec_imbe7100x4400(const uint8_t* d_frames, size_t n, mbx_param_record* d
     return check_launch("fec_imbe7100x4400_kernel");
 }
 
+// the front of a soft batch step: n <= 2^31-1 frames -> records, one wavefront per frame (mbx_soft_front.hip)
+static int launch_soft_front(Context* c, int codec, const mbe_soft_bit* d_soft, size_t n, mbx_param_record* d_records, void* stream) {
+    const dim3 grid((unsigned)n), block(64);
+    if (codec == MBX_CODEC_IMBE7200X4400) {
+        hipLaunchKernelGGL(mbx::soft_front_imbe_kernel, grid, block, 0, (hipStream_t)stream, d_soft, n, d_records, c->tabs);
+    } else if (codec == MBX_CODEC_IMBE7100X4400) {
+        hipLaunchKernelGGL(mbx::soft_front_imbe7100_kernel, grid, block, 0, (hipStream_t)stream, d_soft, n, d_records, c->tabs);
+    } else {   // both AMBE codecs: the same cells, the same search
+        hipLaunchKernelGGL(mbx::soft_front_ambe_kernel, grid, block, 0, (hipStream_t)stream, d_soft, n, d_records, c->tabs);
+    }
+    return check_launch("soft_front_kernel");
+}
+
 int mbx_fec_soft(int codec, const mbe_soft_bit* d_soft, size_t n, mbx_param_record* d_records, void* stream) {
     REQUIRE_CTX(c);
     if (!d_soft || !d_records || codec < MBX_CODEC_IMBE7200X4400 || codec > MBX_CODEC_AMBE3600X2400) {
@@ -1700,20 +1713,79 @@ int mbx_resident_materialize(int n, const int32_t* d_stream_index, mbe_parms* d_
     return check_launch("resident_materialize_kernel");
 }
 
+// ---- soft-decision batches ------------------------------------------------------------------------------------------------------
+// A soft front launch (mbx_soft_front.hip: one wave per frame, soft cells -> record), then the stream stage exactly as for records
+// from anywhere else: the expand launch where the stream stage reads rows, and the instance launch_stream() picks for the shape.
+// Codec 2 records come out in 7200x4400 order; codec 3 frames are searched as AMBE cells and expanded by the 3600x2400 rules.
+// caller_ws: the rows go to d_workspace (nothing of the stream's slot is touched: the launches can be captured into a graph);
+// otherwise to the stream's own workspace, grown under the lock that also covers both launches
+static int soft_batch(int codec, int S, int T, const int32_t* d_stream_index, const mbe_soft_bit* d_soft, mbe_parms* d_state,
+                      uint32_t* d_resident, mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
+                      mbx_param_record* d_records, bool caller_ws, void* d_workspace, size_t workspace_bytes, void* stream) {
+    REQUIRE_CTX(c);
+    if (!d_soft || !d_records || !d_state || !d_rng || S < 0 || T < 0 || codec < MBX_CODEC_IMBE7200X4400
+        || codec > MBX_CODEC_AMBE3600X2400) {
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (S == 0 || T == 0) {
+        return 0;
+    }
+    const size_t n = (size_t)S * (size_t)T;
+    if (n > 0x7fffffffu) {
+        return fail(MBE_STATUS_INVALID_ARGUMENT, "soft batch: more than 2^31-1 frames in one launch");
+    }
+    const int stream_codec = codec == MBX_CODEC_IMBE7100X4400 ? MBX_CODEC_IMBE7200X4400 : codec;
+    const bool rows = needs_workspace(stream_codec, S, T);
+    auto step = [&](unsigned order, mbx::FrameParams* ws, StreamSlot* slot) {   // front, then expand (where needed) + stream with the workspace at ws
+        const int rc = launch_soft_front(c, codec, d_soft, n, d_records, stream);
+        if (rc < 0) {
+            return rc;
+        }
+        return run_stream_stage(c, order, stream_codec, S, T, d_records, ws, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream,
+                                d_stream_index, d_resident, slot);
+    };
+    if (caller_ws) {
+        if (rows && (!d_workspace || workspace_bytes < mbx_workspace_bytes(n))) {
+            return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_process_batch_soft_ws: workspace missing or smaller than mbx_workspace_bytes(S*T)");
+        }
+        unsigned order;
+        {
+            std::lock_guard<std::mutex> lock(c->mu);
+            order = c->slots[stream].launches++;
+        }
+        return step(order, static_cast<mbx::FrameParams*>(d_workspace), nullptr);
+    }
+    std::lock_guard<std::mutex> lock(c->mu);
+    StreamSlot& slot = c->slots[stream];
+    if (rows) {
+        const int rc = ensure_workspace(c, slot, n, stream);
+        if (rc < 0) {
+            return rc;
+        }
+        slot.exp_codec = -1;   // the rows are about to be replaced
+    }
+    return step(slot.launches++, slot.workspace, &slot);
+}
+
 int mbx_process_batch_soft(int codec, int S, int T, const mbe_soft_bit* d_soft, mbe_parms* d_state, mbx_stream_rng* d_rng,
                            int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records,
                            void* stream) {
-    if (!d_soft || !d_records || S < 0 || T < 0) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    int rc = mbx_fec_soft(codec, d_soft, (size_t)S * (size_t)T, d_records, stream);
-    if (rc < 0) {
-        return rc;
-    }
-    if (codec == MBX_CODEC_IMBE7100X4400) {   // the records are in 7200x4400 order
-        codec = MBX_CODEC_IMBE7200X4400;
-    }
-    return mbx_process_records(codec, S, T, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream);
+    return soft_batch(codec, S, T, nullptr, d_soft, d_state, nullptr, d_rng, d_pcm16, d_pcmf, d_results, d_records, false, nullptr, 0,
+                      stream);
+}
+
+int mbx_process_batch_soft_ws(int codec, int S, int T, const mbe_soft_bit* d_soft, mbe_parms* d_state, mbx_stream_rng* d_rng,
+                              int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records,
+                              void* d_workspace, size_t workspace_bytes, void* stream) {
+    return soft_batch(codec, S, T, nullptr, d_soft, d_state, nullptr, d_rng, d_pcm16, d_pcmf, d_results, d_records, true, d_workspace,
+                      workspace_bytes, stream);
+}
+
+int mbx_process_batch_soft_resident(int codec, int S, int T, const int32_t* d_stream_index, const mbe_soft_bit* d_soft,
+                                    mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16,
+                                    float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
+    return soft_batch(codec, S, T, d_stream_index, d_soft, d_state_pool, d_resident, d_rng_pool, d_pcm16, d_pcmf, d_results, d_records,
+                      false, nullptr, 0, stream);
 }
 
 int mbx_synthesize_speech(int S, mbe_parms* d_cur, mbe_parms* d_prev, mbx_stream_rng* d_rng, float* d_pcmf,

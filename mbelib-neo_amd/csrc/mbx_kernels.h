@@ -1,5 +1,5 @@
 // mbx_kernels.h -- every __global__ kernel of libmbx_hip.so, declared exactly once.
-// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_expand.hip, mbx_stream.hip, mbx_api.hip) and by the
+// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_expand.hip, mbx_stream.hip, mbx_api.hip) and by the
 // one that launches it (mbx_api.hip), so a parameter list that drifts from its definition is a compile error (an unmatched
 // overload at the launch site or in the instance table), not an unresolved symbol when the library is loaded.
 // A new kernel: declare it here, define it, and -- a stream-stage instance -- give it its row in kInstances (mbx_api.hip).
@@ -86,6 +86,11 @@ __global__ void fec_imbe7200x4400_soft_kernel(const mbe_soft_bit*, size_t, mbx_p
 __global__ void fec_ambe3600x2450_soft_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
 __global__ void fec_imbe7100x4400_soft_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
 __global__ void ecc_soft_words_kernel(int, const mbe_soft_bit*, size_t, uint32_t*, int32_t*, DeviceTables);
+
+// ---- mbx_soft_front.hip: the front of a soft batch step, soft frames -> records, one wave per frame ---------------------------------
+__global__ void soft_front_imbe_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
+__global__ void soft_front_imbe7100_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
+__global__ void soft_front_ambe_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
 
 // ---- mbx_expand.hip ------------------------------------------------------------------------------------------------------------
 __global__ void expand_imbe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);

@@ -65,6 +65,7 @@ struct CopyOut {   // a staged output still to be handed to the caller's pageabl
 
 struct Slot {
     uint8_t*            d_frames = nullptr;
+    mbe_soft_bit*       d_soft = nullptr;   // soft frames, allocated (as h_soft) by the slot's first soft submit
     mbx_param_record*   d_records = nullptr;
     int16_t*            d_pcm16 = nullptr;
     float*              d_pcmf = nullptr;
@@ -73,6 +74,7 @@ struct Slot {
     void*               d_workspace = nullptr;
     // pinned staging, allocated on first need
     uint8_t*            h_in = nullptr;
+    uint8_t*            h_soft = nullptr;
     int32_t*            h_index = nullptr;
     int16_t*            h_pcm16 = nullptr;
     float*              h_pcmf = nullptr;
@@ -93,6 +95,7 @@ struct mbx_session {
     size_t   max_frames = 0;
     unsigned outputs = 0;
     size_t   frame_bytes = 0;
+    size_t   soft_bytes = 0;      // one frame of mbe_soft_bit cells in the reference's shape
     mbe_parms*      d_state = nullptr;   // [streams][3]
     mbx_stream_rng* d_rng = nullptr;     // [streams]
     uint32_t*       d_resident = nullptr;   // [streams]: prev_mp_enhanced of the stream is elided (mbx_process_batch_resident, include/mbx.h)
@@ -160,10 +163,11 @@ bool range_ok(const mbx_session* s, int first, int count) {
     return s && first >= 0 && count >= 0 && (long long)first + count <= s->streams;
 }
 
-int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const uint8_t* frames, int16_t* pcm16, float* pcmf,
+// `soft`: frames are mbe_soft_bit cells (soft_bytes per frame) instead of wire frames (frame_bytes)
+int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
             mbe_process_result* results, mbx_param_record* records);
 
-int submit(mbx_session* s, int n, int T, const int32_t* index, const uint8_t* frames, int16_t* pcm16, float* pcmf,
+int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
            mbe_process_result* results, mbx_param_record* records) {
     if (!s || !frames || n < 0 || T < 0 || n > s->streams || (size_t)n * (size_t)T > s->max_frames) {
         return MBE_STATUS_INVALID_ARGUMENT;
@@ -174,6 +178,12 @@ int submit(mbx_session* s, int n, int T, const int32_t* index, const uint8_t* fr
     }
     if (n == 0 || T == 0) {
         return 0;
+    }
+    if (soft) {   // a hard decision > 1 is refused before anything is queued (ref mbe_validate_soft_bits, src/internal/mbe_result.h:31-42)
+        const int rc = mbx_validate_soft_bits(static_cast<const mbe_soft_bit*>(frames), (size_t)n * (size_t)T * (s->soft_bytes / sizeof(mbe_soft_bit)));
+        if (rc < 0) {
+            return rc;
+        }
     }
     if (index) {   // every row must name its own stream: two rows on one stream would race on its state
         s->seen.assign((size_t)s->streams, 0);
@@ -193,7 +203,7 @@ int submit(mbx_session* s, int n, int T, const int32_t* index, const uint8_t* fr
     }
     // From here on work is queued on the three streams against this slot's buffers.  If anything fails halfway the slot is
     // NOT marked busy, so before the error goes back the streams are drained: the next submit may reuse the slot at once.
-    rc = enqueue(s, sl, n, T, index, frames, pcm16, pcmf, results, records);
+    rc = enqueue(s, sl, n, T, index, frames, soft, pcm16, pcmf, results, records);
     if (rc < 0) {
         (void)hipStreamSynchronize(s->s_comp);
         (void)hipStreamSynchronize(s->s_out);
@@ -206,29 +216,28 @@ int submit(mbx_session* s, int n, int T, const int32_t* index, const uint8_t* fr
     return 0;
 }
 
-int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const uint8_t* frames, int16_t* pcm16, float* pcmf,
+int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
             mbe_process_result* results, mbx_param_record* records) {
     int rc = 0;
     const size_t nf = (size_t)n * (size_t)T;
     // ---- in ----
-    const uint8_t* src = frames;
-    if (!is_pinned(frames)) {
-        rc = pinned(sl.h_in, s->max_frames * s->frame_bytes);
-        if (rc < 0) {
-            return rc;
-        }
-        memcpy(sl.h_in, frames, nf * s->frame_bytes);
-        src = sl.h_in;
+    // Soft frames are 368 / 336 / 192 B each against 18 / 9: their device buffer and their pinned staging belong to the slot's
+    // first soft submit, so a session that never sees one pays for neither.
+    const size_t in_bytes = soft ? s->soft_bytes : s->frame_bytes;
+    uint8_t*& stage = soft ? sl.h_soft : sl.h_in;
+    if (soft && !sl.d_soft) {
+        S_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_soft), s->max_frames * s->soft_bytes));
     }
+    const uint8_t* src = static_cast<const uint8_t*>(frames);
     // The frames (and the stream index) are fetched by a kernel on the COMPUTE stream, not by a DMA copy: see stage_in_kernel
     // (mbx_fec.hip).  A pinned buffer that is not 16-byte aligned goes through the slot's own pinned staging like a pageable one.
-    if (reinterpret_cast<uintptr_t>(src) & 15u) {
-        rc = pinned(sl.h_in, s->max_frames * s->frame_bytes);
+    if (!is_pinned(frames) || (reinterpret_cast<uintptr_t>(src) & 15u)) {
+        rc = pinned(stage, s->max_frames * in_bytes);
         if (rc < 0) {
             return rc;
         }
-        memcpy(sl.h_in, frames, nf * s->frame_bytes);
-        src = sl.h_in;
+        memcpy(stage, frames, nf * in_bytes);
+        src = stage;
     }
     const void* dev_view = src;   // what the GPU dereferences: the same address for hipHostMalloc memory, possibly another one for
     void* mapped = nullptr;       // memory the host registered itself (hipHostRegister)
@@ -237,7 +246,7 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
     } else {
         (void)hipGetLastError();
     }
-    rc = mbx_stage_in(sl.d_frames, dev_view, nf * s->frame_bytes, s->s_comp);
+    rc = mbx_stage_in(soft ? static_cast<void*>(sl.d_soft) : static_cast<void*>(sl.d_frames), dev_view, nf * in_bytes, s->s_comp);
     if (rc < 0) {
         return rc;
     }
@@ -256,7 +265,10 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
     int16_t* d16 = pcm16 ? sl.d_pcm16 : nullptr;
     float*   dfl = pcmf ? sl.d_pcmf : nullptr;
     mbe_process_result* dres = results ? sl.d_results : nullptr;
-    if (s->d_resident) {   // the session owns the state between submits: the resident form (no prev_mp_enhanced traffic, lazy prev_mp)
+    if (soft) {   // the soft twin of the resident launcher takes every form: index or none, resident words or plain triplets
+        rc = mbx_process_batch_soft_resident(s->codec, n, T, index ? sl.d_index : nullptr, sl.d_soft, s->d_state, s->d_resident, s->d_rng,
+                                             d16, dfl, dres, sl.d_records, s->s_comp);
+    } else if (s->d_resident) {   // the session owns the state between submits: the resident form (no prev_mp_enhanced traffic, lazy prev_mp)
         rc = mbx_process_batch_resident(s->codec, n, T, index ? sl.d_index : nullptr, sl.d_frames, s->d_state, s->d_resident, s->d_rng,
                                         d16, dfl, dres, sl.d_records, s->s_comp);
     } else if (index) {
@@ -334,6 +346,9 @@ int mbx_session_create(mbx_session** out, int codec, int streams, size_t max_fra
     s->max_frames = max_frames_per_submit;
     s->outputs = outputs ? outputs : MBX_SESSION_PCM16;
     s->frame_bytes = (codec == MBX_CODEC_AMBE3600X2450 || codec == MBX_CODEC_AMBE3600X2400) ? MBX_AMBE_FRAME_BYTES : MBX_IMBE_FRAME_BYTES;
+    s->soft_bytes = sizeof(mbe_soft_bit) * (codec == MBX_CODEC_IMBE7200X4400   ? (size_t)MBX_IMBE_SOFT_BITS
+                                            : codec == MBX_CODEC_IMBE7100X4400 ? (size_t)MBX_IMBE7100_SOFT_BITS
+                                                                               : (size_t)MBX_AMBE_SOFT_BITS);
     *out = s;
     auto bail = [&](int rc) {
         mbx_session_destroy(s);
@@ -401,6 +416,7 @@ int mbx_session_destroy(mbx_session* s) {
     }
     for (Slot& sl : s->slot) {
         (void)hipFree(sl.d_frames);
+        (void)hipFree(sl.d_soft);
         (void)hipFree(sl.d_records);
         (void)hipFree(sl.d_pcm16);
         (void)hipFree(sl.d_pcmf);
@@ -408,6 +424,7 @@ int mbx_session_destroy(mbx_session* s) {
         (void)hipFree(sl.d_index);
         (void)hipFree(sl.d_workspace);
         (void)hipHostFree(sl.h_in);
+        (void)hipHostFree(sl.h_soft);
         (void)hipHostFree(sl.h_index);
         (void)hipHostFree(sl.h_pcm16);
         (void)hipHostFree(sl.h_pcmf);
@@ -528,7 +545,7 @@ int mbx_session_seed(mbx_session* s, int first, int count, const uint32_t* seeds
 }
 
 int mbx_session_submit(mbx_session* s, int T, const uint8_t* frames, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
-    return submit(s, s ? s->streams : 0, T, nullptr, frames, pcm16, pcmf, results, nullptr);
+    return submit(s, s ? s->streams : 0, T, nullptr, frames, false, pcm16, pcmf, results, nullptr);
 }
 
 int mbx_session_submit_indexed(mbx_session* s, int n, int T, const int32_t* stream_index, const uint8_t* frames, int16_t* pcm16,
@@ -536,7 +553,19 @@ int mbx_session_submit_indexed(mbx_session* s, int n, int T, const int32_t* stre
     if (!stream_index) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    return submit(s, n, T, stream_index, frames, pcm16, pcmf, results, records);
+    return submit(s, n, T, stream_index, frames, false, pcm16, pcmf, results, records);
+}
+
+int mbx_session_submit_soft(mbx_session* s, int T, const mbe_soft_bit* soft, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
+    return submit(s, s ? s->streams : 0, T, nullptr, soft, true, pcm16, pcmf, results, nullptr);
+}
+
+int mbx_session_submit_soft_indexed(mbx_session* s, int n, int T, const int32_t* stream_index, const mbe_soft_bit* soft, int16_t* pcm16,
+                                    float* pcmf, mbe_process_result* results, mbx_param_record* records) {
+    if (!stream_index) {
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    return submit(s, n, T, stream_index, soft, true, pcm16, pcmf, results, records);
 }
 
 }  // extern "C"

@@ -111,13 +111,49 @@ class BatchDecoder:
             _native.check(fn(d_frames.data_ptr(), n, rec.data_ptr(), torch.cuda.current_stream().cuda_stream), "mbx_fec")
         return rec
 
-    def make_outputs(self, T, want_pcm16=True, want_float=False, want_results=True):
+    def make_outputs(self, T, want_pcm16=True, want_float=False, want_results=True, streams=None):
         torch = _torch()
-        n = self.streams * T
+        n = (self.streams if streams is None else int(streams)) * T
         out = {"records": torch.empty((n, 4), dtype=torch.int32, device=self.device)}
         out["pcm16"] = torch.empty((n, 160), dtype=torch.int16, device=self.device) if want_pcm16 else None
         out["pcmf"] = torch.empty((n, 160), dtype=torch.float32, device=self.device) if want_float else None
         out["results"] = torch.empty((n, 5), dtype=torch.int32, device=self.device) if want_results else None
+        return out
+
+    def decode_soft(self, soft, T, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None):
+        """Soft-decision frames: `soft` = torch tensor (or array) uint8 [n*T, cells, 2] = (bit, reliability), cells = 184 / 96 /
+        168 / 96 for codecs 0..3, stream-major.  Runs mbx_process_batch_soft_resident on this decoder's state, resident or not.
+        stream_index (int32 tensor [n]): batch row i belongs to stream stream_index[i] of this decoder (no stream twice); without
+        it n = streams.  Hard decisions must be 0/1 (checked here only for host arrays).  Hard and soft calls may alternate."""
+        torch = _torch()
+        if isinstance(soft, np.ndarray):
+            soft = _soft_array(self.codec, soft, soft.size // (SOFT_CELLS[self.codec] * 2))
+            if soft.reshape(-1, 2)[:, 0].max(initial=0) > 1:
+                raise ValueError("soft frames: a hard decision is not 0 or 1")
+        d_soft = self.to_device(soft)
+        if d_soft.dtype != torch.uint8 or not d_soft.is_contiguous():
+            raise ValueError("soft frames must be a contiguous uint8 tensor")
+        n = self.streams if stream_index is None else int(stream_index.numel())
+        if d_soft.numel() != n * int(T) * SOFT_CELLS[self.codec] * 2:
+            raise ValueError("soft must hold n*T frames of SOFT_CELLS[codec] (bit, reliability) pairs")
+        if stream_index is not None:
+            if stream_index.dtype != torch.int32 or stream_index.device != self.device:
+                raise ValueError("stream_index must be an int32 tensor on the decoder's device")
+            if n and (int(torch.unique(stream_index).numel()) != n or int(stream_index.min()) < 0 or int(stream_index.max()) >= self.streams):
+                raise ValueError("stream_index: out of range, or a stream listed twice (two rows would race on one state)")
+        if out is None:
+            out = self.make_outputs(T, want_pcm16, want_float, want_results, streams=n)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        with torch.cuda.device(self.device):
+            rc = _native.lib().mbx_process_batch_soft_resident(
+                self.codec, n, int(T), ptr(stream_index), d_soft.data_ptr(), self.state.data_ptr(), ptr(self.resident),
+                self.rng.data_ptr(), ptr(out["pcm16"]), ptr(out["pcmf"]), ptr(out["results"]), out["records"].data_ptr(),
+                torch.cuda.current_stream().cuda_stream,
+            )
+        _native.check(rc, "mbx_process_batch_soft_resident")
         return out
 
     def decode(self, frames, T, want_pcm16=True, want_float=False, want_results=True, out=None, staged=False):
