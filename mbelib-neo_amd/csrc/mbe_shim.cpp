@@ -26,6 +26,7 @@
 
 #include "mbe_neo_amd.h"
 #include "mbx.h"
+#include "mbx_codec.h"
 
 namespace {
 
@@ -416,36 +417,49 @@ mbx_param_record make_record(const char* bits, int nbits, const mbe_process_resu
     return rec;
 }
 
-int decode_frame(int codec, const char* cells, int ncell, int nbits, char* bits_out, mbe_process_result* result) {
+// The shim links against the launcher's public ABI only: the packer and the FEC launch of a codec's front end (mbx_codec.h:
+// CodecShape::front) are picked here, once.  `codec`: one of the four.
+int pack_one(int codec, const char* cells, uint8_t* packed) {
+    switch (mbx::kCodecs[codec].front) {
+        case MBX_CODEC_IMBE7200X4400: return mbx_pack_imbe7200x4400(cells, 1, packed);
+        case MBX_CODEC_IMBE7100X4400: return mbx_pack_imbe7100x4400(cells, 1, packed);
+        default: return mbx_pack_ambe3600x2450(cells, 1, packed);
+    }
+}
+int fec_one(int codec, const uint8_t* d_frame, mbx_param_record* d_rec, void* stream) {
+    switch (mbx::kCodecs[codec].front) {
+        case MBX_CODEC_IMBE7200X4400: return mbx_fec_imbe7200x4400(d_frame, 1, d_rec, stream);
+        case MBX_CODEC_IMBE7100X4400: return mbx_fec_imbe7100x4400(d_frame, 1, d_rec, stream);
+        default: return mbx_fec_ambe3600x2450(d_frame, 1, d_rec, stream);
+    }
+}
+
+// mbe_decode*Frame
+int decode_frame(int codec, const char* cells, char* bits_out, mbe_process_result* result) {
+    const mbx::CodecShape& sh = mbx::kCodecs[codec];
     if (result) {
         memset(result, 0, sizeof(*result));
     }
     if (!bits_out) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    int rc = validate_bits(cells, (size_t)ncell);
+    int rc = validate_bits(cells, (size_t)sh.cells);
     if (rc < 0) {
         return rc;
     }
     uint8_t packed[MBX_IMBE_FRAME_BYTES];
-    rc = (codec == MBX_CODEC_IMBE7200X4400)   ? mbx_pack_imbe7200x4400(cells, 1, packed)
-         : (codec == MBX_CODEC_IMBE7100X4400) ? mbx_pack_imbe7100x4400(cells, 1, packed)
-                                              : mbx_pack_ambe3600x2450(cells, 1, packed);
+    rc = pack_one(codec, cells, packed);
     if (rc < 0) {
         return rc;
     }
     Slot& s = slot();
-    const size_t fb = (codec == MBX_CODEC_AMBE3600X2450) ? MBX_AMBE_FRAME_BYTES : MBX_IMBE_FRAME_BYTES;
-    s.up(s.frame, packed, fb);
-    must((codec == MBX_CODEC_IMBE7200X4400)   ? mbx_fec_imbe7200x4400(s.frame, 1, s.rec, s.stream)
-         : (codec == MBX_CODEC_IMBE7100X4400) ? mbx_fec_imbe7100x4400(s.frame, 1, s.rec, s.stream)
-                                              : mbx_fec_ambe3600x2450(s.frame, 1, s.rec, s.stream),
-         "mbx_fec");
+    s.up(s.frame, packed, (size_t)sh.frame_bytes);
+    must(fec_one(codec, s.frame, s.rec, s.stream), "mbx_fec");
     mbx_param_record rec;
     s.down(&rec, s.rec, sizeof(rec));
     s.sync();
     mbe_process_result r;
-    mbx_unpack_records(&rec, 1, nbits, bits_out, &r);
+    mbx_unpack_records(&rec, 1, sh.data_bits, bits_out, &r);
     if (result) {
         *result = r;
     }
@@ -455,8 +469,9 @@ int decode_frame(int codec, const char* cells, int ncell, int nbits, char* bits_
 void sync_channel_for_direct_use(const mbe_parms* cur);   // queue mode, further down
 
 // mbe_process*Dataf: ref src/imbe/imbe7200x4400.c:858-909, src/ambe/ambe3600x2450.c:851-898
-int process_data(int codec, float* aout_f, short* aout_s, mbe_process_result* result, const char* bits, int nbits,
-                 mbe_parms* cur, mbe_parms* prev, mbe_parms* enh) {
+int process_data(int codec, float* aout_f, short* aout_s, mbe_process_result* result, const char* bits, mbe_parms* cur, mbe_parms* prev,
+                 mbe_parms* enh) {
+    const int nbits = mbx::kCodecs[codec].data_bits;
     mbe_process_result local;
     if (!result) {
         memset(&local, 0, sizeof(local));
@@ -545,7 +560,8 @@ int ecc_soft_word(int kind, const mbe_soft_bit* in, uint32_t* out) {
 }
 
 // mbe_decode*SoftFrame: ref src/imbe/imbe7200x4400.c:746-778, src/ambe/ambe3600x2450.c:684-714
-int decode_soft_frame(int codec, const mbe_soft_bit* cells, int ncell, int nbits, char* bits_out, mbe_process_result* result) {
+int decode_soft_frame(int codec, const mbe_soft_bit* cells, char* bits_out, mbe_process_result* result) {
+    const int ncell = mbx::kCodecs[codec].cells, nbits = mbx::kCodecs[codec].data_bits;
     if (result) {
         memset(result, 0, sizeof(*result));
     }
@@ -570,14 +586,6 @@ int decode_soft_frame(int codec, const mbe_soft_bit* cells, int ncell, int nbits
     return r.total_errors;
 }
 
-
-struct FrameShapeLite {
-    int ncell, nbits;
-};
-FrameShapeLite frame_shape_lite(int codec) {
-    return codec == MBX_CODEC_IMBE7200X4400 ? FrameShapeLite{184, 88}
-           : codec == MBX_CODEC_IMBE7100X4400 ? FrameShapeLite{168, 88} : FrameShapeLite{96, 49};
-}
 
 // ==================================================================================================================
 // Queue mode (include/mbe_neo_amd.h): the hard-decision mbe_process*Frame[f] calls of a thread -- and, with
@@ -698,13 +706,9 @@ Batch& batch() {
     return *holder.p;
 }
 
-size_t frame_bytes_of(int codec) {
-    return (codec == MBX_CODEC_AMBE3600X2450 || codec == MBX_CODEC_AMBE3600X2400) ? MBX_AMBE_FRAME_BYTES : MBX_IMBE_FRAME_BYTES;
-}
-
 // one frame as the batch launchers take it: packed wire bytes, or the reference's array of soft cells
 size_t input_bytes_of(int codec, bool soft) {
-    return soft ? (size_t)frame_shape_lite(codec).ncell * sizeof(mbe_soft_bit) : frame_bytes_of(codec);
+    return soft ? (size_t)mbx::kCodecs[codec].cells * sizeof(mbe_soft_bit) : (size_t)mbx::kCodecs[codec].frame_bytes;
 }
 
 // grow the device pool to `n` channels, keeping what is resident
@@ -1025,8 +1029,7 @@ int flush_batch(Batch& b) {
         if (qe.result) {
             *qe.result = b.h_results.p[r];
         }
-        const int nbits = (qe.codec == MBX_CODEC_AMBE3600X2450 || qe.codec == MBX_CODEC_AMBE3600X2400) ? 49 : 88;
-        unpack_bits_fast(b.h_records.p[r], nbits, qe.bits_out);
+        unpack_bits_fast(b.h_records.p[r], mbx::kCodecs[qe.codec].data_bits, qe.bits_out);
     }
     for (int k = 0; k < kChunks; ++k) {   // PCM, chunk by chunk
         const size_t r0 = (size_t)k * per_chunk, r1 = r0 + per_chunk < rows ? r0 + per_chunk : rows;
@@ -1131,11 +1134,11 @@ void sync_channel_for_direct_use(const mbe_parms* any) {
 // the queued form of mbe_process*Frame[f] (cells) and mbe_process*SoftFrame[f] (soft: the frame's cells, `cells` unused)
 int queue_frame(int codec, float* aout_f, short* aout_s, mbe_process_result* result, const char* cells, char* bits_out,
                 mbe_parms* cur, mbe_parms* prev, mbe_parms* enh, const mbe_soft_bit* soft = nullptr) {
-    const FrameShapeLite sh = frame_shape_lite(codec);
+    const size_t ncell = (size_t)mbx::kCodecs[codec].cells;
     if (!bits_out || (!aout_f && !aout_s) || !cur || !prev || !enh) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    int rc = soft ? mbx_validate_soft_bits(soft, (size_t)sh.ncell) : validate_bits(cells, (size_t)sh.ncell);
+    int rc = soft ? mbx_validate_soft_bits(soft, ncell) : validate_bits(cells, ncell);
     if (rc < 0) {
         return rc;
     }
@@ -1178,12 +1181,10 @@ int queue_frame(int codec, float* aout_f, short* aout_s, mbe_process_result* res
     qe.codec = (uint8_t)codec;
     if (soft) {
         qe.soft_at = b.soft_cells.size();
-        b.soft_cells.insert(b.soft_cells.end(), soft, soft + sh.ncell);
+        b.soft_cells.insert(b.soft_cells.end(), soft, soft + ncell);
         return 0;
     }
-    rc = (codec == MBX_CODEC_IMBE7200X4400)   ? mbx_pack_imbe7200x4400(cells, 1, qe.frame)
-         : (codec == MBX_CODEC_IMBE7100X4400) ? mbx_pack_imbe7100x4400(cells, 1, qe.frame)
-                                              : mbx_pack_ambe3600x2450(cells, 1, qe.frame);
+    rc = pack_one(codec, cells, qe.frame);
     if (rc < 0) {
         b.q.pop_back();
         ch.pending--;
@@ -1220,29 +1221,26 @@ int queue_soft_frame(int codec, float* aout_f, short* aout_s, mbe_process_result
 // reports only AFTER the frame decode has written imbe_d / result take the two-call path below, which does the same.
 int process_frame(int codec, float* aout_f, short* aout_s, mbe_process_result* result, const char* cells, char* bits_out,
                   mbe_parms* cur, mbe_parms* prev, mbe_parms* enh) {
-    const FrameShapeLite sh = frame_shape_lite(codec);
-    const int fec_codec = codec == MBX_CODEC_AMBE3600X2400 ? MBX_CODEC_AMBE3600X2450 : codec;   // shared AMBE front end
+    const mbx::CodecShape& sh = mbx::kCodecs[codec];
     if (!bits_out || (!aout_f && !aout_s) || !cur || !prev || !enh) {
         mbe_process_result local;
         mbe_process_result* r = result ? result : &local;
-        const int rc = decode_frame(fec_codec, cells, sh.ncell, sh.nbits, bits_out, r);
+        const int rc = decode_frame(sh.front, cells, bits_out, r);
         if (rc < 0) {
             return rc;
         }
-        return process_data(codec, aout_f, aout_s, r, bits_out, sh.nbits, cur, prev, enh);
+        return process_data(codec, aout_f, aout_s, r, bits_out, cur, prev, enh);
     }
     if (result) {
         memset(result, 0, sizeof(*result));
     }
-    int rc = validate_bits(cells, (size_t)sh.ncell);
+    int rc = validate_bits(cells, (size_t)sh.cells);
     if (rc < 0) {
         return rc;
     }
     sync_channel_for_direct_use(cur);
     Slot& s = slot();
-    rc = (codec == MBX_CODEC_IMBE7200X4400)   ? mbx_pack_imbe7200x4400(cells, 1, s.frame)
-         : (codec == MBX_CODEC_IMBE7100X4400) ? mbx_pack_imbe7100x4400(cells, 1, s.frame)
-                                              : mbx_pack_ambe3600x2450(cells, 1, s.frame);
+    rc = pack_one(codec, cells, s.frame);
     if (rc < 0) {
         return rc;
     }
@@ -1279,12 +1277,39 @@ int process_frame(int codec, float* aout_f, short* aout_s, mbe_process_result* r
     *prev = s.state[1];
     *enh = s.state[2];
     t_rng.r = *s.rng;
-    mbx_unpack_records(s.rec, 1, sh.nbits, bits_out, nullptr);
+    mbx_unpack_records(s.rec, 1, sh.data_bits, bits_out, nullptr);
     const int total = s.res->total_errors;
     if (result) {
         *result = *s.res;
     }
     return total;
+}
+
+// The sixteen mbe_process*Frame[f] / mbe_process*SoftFrame[f] exports: a float form passes aout_f, a short form aout_s -- after it has
+// refused a NULL buffer, before anything is written; a float form's NULL buffer is reported by the calls below, after the frame
+// decode has cleared *result and written the parameter bits, as in the reference.
+int hard_frame_call(int codec, float* aout_f, short* aout_s, mbe_process_result* result, const char* cells, char* bits_out, mbe_parms* cur,
+                    mbe_parms* prev, mbe_parms* enh) {
+    return queueing() ? queue_frame(codec, aout_f, aout_s, result, cells, bits_out, cur, prev, enh)
+                      : process_frame(codec, aout_f, aout_s, result, cells, bits_out, cur, prev, enh);
+}
+
+// soft frames, ref src/imbe/imbe7200x4400.c:950-980, src/ambe/ambe3600x2450.c:939-969: mbe_decode*SoftFrame of the codec's front
+// end, then mbe_process*Data[f] of its stream stage
+int soft_frame_call(int codec, float* aout_f, short* aout_s, mbe_process_result* result, const mbe_soft_bit* cells, char* bits_out,
+                    mbe_parms* cur, mbe_parms* prev, mbe_parms* enh) {
+    if (queue_soft_call(aout_s ? static_cast<const void*>(aout_s) : aout_f, cells, bits_out, cur, prev, enh)) {
+        return queue_soft_frame(codec, aout_f, aout_s, result, cells, bits_out, cur, prev, enh);
+    }
+    mbe_process_result local;
+    if (!result) {
+        result = &local;
+    }
+    const int rc = decode_soft_frame(mbx::kCodecs[codec].front, cells, bits_out, result);
+    if (rc < 0) {
+        return rc;
+    }
+    return process_data(mbx::kCodecs[codec].stream, aout_f, aout_s, result, bits_out, cur, prev, enh);
 }
 
 }  // namespace
@@ -1432,26 +1457,20 @@ int mbe_7100x4400hamming1511(const char* in, char* out) {
 }
 
 int mbe_decodeImbe7100x4400Frame(const char imbe_fr[7][24], char imbe_d[88], mbe_process_result* result) {
-    return decode_frame(MBX_CODEC_IMBE7100X4400, reinterpret_cast<const char*>(imbe_fr), 168, 88, imbe_d, result);
+    return decode_frame(MBX_CODEC_IMBE7100X4400, reinterpret_cast<const char*>(imbe_fr), imbe_d, result);
 }
 
 int mbe_processImbe7100x4400Framef(float* aout_buf, mbe_process_result* result, const char imbe_fr[7][24], char imbe_d[88],
                                    mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (queueing()) {
-        return queue_frame(MBX_CODEC_IMBE7100X4400, aout_buf, nullptr, result, reinterpret_cast<const char*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    return process_frame(MBX_CODEC_IMBE7100X4400, aout_buf, nullptr, result, reinterpret_cast<const char*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return hard_frame_call(MBX_CODEC_IMBE7100X4400, aout_buf, nullptr, result, reinterpret_cast<const char*>(imbe_fr), imbe_d, cur_mp, prev_mp,
+                           prev_mp_enhanced);
 }
 
 int mbe_processImbe7100x4400Frame(short* aout_buf, mbe_process_result* result, const char imbe_fr[7][24], char imbe_d[88],
                                   mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (!aout_buf) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (queueing()) {
-        return queue_frame(MBX_CODEC_IMBE7100X4400, nullptr, aout_buf, result, reinterpret_cast<const char*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    return process_frame(MBX_CODEC_IMBE7100X4400, nullptr, aout_buf, result, reinterpret_cast<const char*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return aout_buf ? hard_frame_call(MBX_CODEC_IMBE7100X4400, nullptr, aout_buf, result, reinterpret_cast<const char*>(imbe_fr), imbe_d, cur_mp, prev_mp,
+                                      prev_mp_enhanced)
+                    : MBE_STATUS_INVALID_ARGUMENT;
 }
 
 // ---- tones and the status trace: ref src/core/mbelib.c:68-104 (format documented in mbelib.h:195-202), :745-856 ----
@@ -1574,11 +1593,11 @@ int mbe_hamming1511Soft(const mbe_soft_bit* in, char* out) {
 }
 
 int mbe_decodeImbe7200x4400SoftFrame(const mbe_soft_bit imbe_fr[8][23], char imbe_d[88], mbe_process_result* result) {
-    return decode_soft_frame(MBX_CODEC_IMBE7200X4400, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), 184, 88, imbe_d, result);
+    return decode_soft_frame(MBX_CODEC_IMBE7200X4400, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, result);
 }
 
 int mbe_decodeAmbe3600x2450SoftFrame(const mbe_soft_bit ambe_fr[4][24], char ambe_d[49], mbe_process_result* result) {
-    return decode_soft_frame(MBX_CODEC_AMBE3600X2450, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), 96, 49, ambe_d, result);
+    return decode_soft_frame(MBX_CODEC_AMBE3600X2450, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, result);
 }
 
 
@@ -1649,17 +1668,17 @@ int mbe_batchEnd(void) {
 
 // ---- frame decode ---------------------------------------------------------------------------
 int mbe_decodeImbe7200x4400Frame(const char imbe_fr[8][23], char imbe_d[88], mbe_process_result* result) {
-    return decode_frame(MBX_CODEC_IMBE7200X4400, reinterpret_cast<const char*>(imbe_fr), 184, 88, imbe_d, result);
+    return decode_frame(MBX_CODEC_IMBE7200X4400, reinterpret_cast<const char*>(imbe_fr), imbe_d, result);
 }
 
 int mbe_decodeAmbe3600x2450Frame(const char ambe_fr[4][24], char ambe_d[49], mbe_process_result* result) {
-    return decode_frame(MBX_CODEC_AMBE3600X2450, reinterpret_cast<const char*>(ambe_fr), 96, 49, ambe_d, result);
+    return decode_frame(MBX_CODEC_AMBE3600X2450, reinterpret_cast<const char*>(ambe_fr), ambe_d, result);
 }
 
 // ---- parameters -> PCM ------------------------------------------------------------------------
 int mbe_processImbe4400Dataf(float* aout_buf, mbe_process_result* result, const char imbe_d[88], mbe_parms* cur_mp,
                              mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    return process_data(MBX_CODEC_IMBE7200X4400, aout_buf, nullptr, result, imbe_d, 88, cur_mp, prev_mp, prev_mp_enhanced);
+    return process_data(MBX_CODEC_IMBE7200X4400, aout_buf, nullptr, result, imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
 }
 
 int mbe_processImbe4400Data(short* aout_buf, mbe_process_result* result, const char imbe_d[88], mbe_parms* cur_mp,
@@ -1667,12 +1686,12 @@ int mbe_processImbe4400Data(short* aout_buf, mbe_process_result* result, const c
     if (!aout_buf) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    return process_data(MBX_CODEC_IMBE7200X4400, nullptr, aout_buf, result, imbe_d, 88, cur_mp, prev_mp, prev_mp_enhanced);
+    return process_data(MBX_CODEC_IMBE7200X4400, nullptr, aout_buf, result, imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
 }
 
 int mbe_processAmbe2450Dataf(float* aout_buf, mbe_process_result* result, const char ambe_d[49], mbe_parms* cur_mp,
                              mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    return process_data(MBX_CODEC_AMBE3600X2450, aout_buf, nullptr, result, ambe_d, 49, cur_mp, prev_mp, prev_mp_enhanced);
+    return process_data(MBX_CODEC_AMBE3600X2450, aout_buf, nullptr, result, ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
 }
 
 int mbe_processAmbe2450Data(short* aout_buf, mbe_process_result* result, const char ambe_d[49], mbe_parms* cur_mp,
@@ -1680,46 +1699,34 @@ int mbe_processAmbe2450Data(short* aout_buf, mbe_process_result* result, const c
     if (!aout_buf) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    return process_data(MBX_CODEC_AMBE3600X2450, nullptr, aout_buf, result, ambe_d, 49, cur_mp, prev_mp, prev_mp_enhanced);
+    return process_data(MBX_CODEC_AMBE3600X2450, nullptr, aout_buf, result, ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
 }
 
 // ---- frames -> PCM: ref src/imbe/imbe7200x4400.c:935-1001, src/ambe/ambe3600x2450.c:924-990 ------
 int mbe_processImbe7200x4400Framef(float* aout_buf, mbe_process_result* result, const char imbe_fr[8][23], char imbe_d[88],
                                    mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (queueing()) {
-        return queue_frame(MBX_CODEC_IMBE7200X4400, aout_buf, nullptr, result, reinterpret_cast<const char*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    return process_frame(MBX_CODEC_IMBE7200X4400, aout_buf, nullptr, result, reinterpret_cast<const char*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return hard_frame_call(MBX_CODEC_IMBE7200X4400, aout_buf, nullptr, result, reinterpret_cast<const char*>(imbe_fr), imbe_d, cur_mp, prev_mp,
+                           prev_mp_enhanced);
 }
 
 int mbe_processImbe7200x4400Frame(short* aout_buf, mbe_process_result* result, const char imbe_fr[8][23], char imbe_d[88],
                                   mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (!aout_buf) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (queueing()) {
-        return queue_frame(MBX_CODEC_IMBE7200X4400, nullptr, aout_buf, result, reinterpret_cast<const char*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    return process_frame(MBX_CODEC_IMBE7200X4400, nullptr, aout_buf, result, reinterpret_cast<const char*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return aout_buf ? hard_frame_call(MBX_CODEC_IMBE7200X4400, nullptr, aout_buf, result, reinterpret_cast<const char*>(imbe_fr), imbe_d, cur_mp, prev_mp,
+                                      prev_mp_enhanced)
+                    : MBE_STATUS_INVALID_ARGUMENT;
 }
 
 int mbe_processAmbe3600x2450Framef(float* aout_buf, mbe_process_result* result, const char ambe_fr[4][24], char ambe_d[49],
                                    mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (queueing()) {
-        return queue_frame(MBX_CODEC_AMBE3600X2450, aout_buf, nullptr, result, reinterpret_cast<const char*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    return process_frame(MBX_CODEC_AMBE3600X2450, aout_buf, nullptr, result, reinterpret_cast<const char*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return hard_frame_call(MBX_CODEC_AMBE3600X2450, aout_buf, nullptr, result, reinterpret_cast<const char*>(ambe_fr), ambe_d, cur_mp, prev_mp,
+                           prev_mp_enhanced);
 }
 
 int mbe_processAmbe3600x2450Frame(short* aout_buf, mbe_process_result* result, const char ambe_fr[4][24], char ambe_d[49],
                                   mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (!aout_buf) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (queueing()) {
-        return queue_frame(MBX_CODEC_AMBE3600X2450, nullptr, aout_buf, result, reinterpret_cast<const char*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    return process_frame(MBX_CODEC_AMBE3600X2450, nullptr, aout_buf, result, reinterpret_cast<const char*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return aout_buf ? hard_frame_call(MBX_CODEC_AMBE3600X2450, nullptr, aout_buf, result, reinterpret_cast<const char*>(ambe_fr), ambe_d, cur_mp, prev_mp,
+                                      prev_mp_enhanced)
+                    : MBE_STATUS_INVALID_ARGUMENT;
 }
 
 // ---- synthesis pieces --------------------------------------------------------------------------
@@ -1828,56 +1835,34 @@ int mbe_7100x4400hamming1511Soft(const mbe_soft_bit* in, char* out) {
 }
 
 int mbe_decodeImbe7100x4400SoftFrame(const mbe_soft_bit imbe_fr[7][24], char imbe_d[88], mbe_process_result* result) {
-    return decode_soft_frame(MBX_CODEC_IMBE7100X4400, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), 168, 88, imbe_d, result);
+    return decode_soft_frame(MBX_CODEC_IMBE7100X4400, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, result);
 }
 
 int mbe_processImbe7100x4400SoftFramef(float* aout_buf, mbe_process_result* result, const mbe_soft_bit imbe_fr[7][24],
                                        char imbe_d[88], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (queue_soft_call(aout_buf, imbe_fr, imbe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
-        return queue_soft_frame(MBX_CODEC_IMBE7100X4400, aout_buf, nullptr, result, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    mbe_process_result local;
-    if (!result) {
-        result = &local;
-    }
-    const int rc = mbe_decodeImbe7100x4400SoftFrame(imbe_fr, imbe_d, result);
-    if (rc < 0) {
-        return rc;
-    }
-    return mbe_processImbe4400Dataf(aout_buf, result, imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return soft_frame_call(MBX_CODEC_IMBE7100X4400, aout_buf, nullptr, result, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, cur_mp, prev_mp,
+                           prev_mp_enhanced);
 }
 
 int mbe_processImbe7100x4400SoftFrame(short* aout_buf, mbe_process_result* result, const mbe_soft_bit imbe_fr[7][24],
                                       char imbe_d[88], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (queue_soft_call(aout_buf, imbe_fr, imbe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
-        return queue_soft_frame(MBX_CODEC_IMBE7100X4400, nullptr, aout_buf, result, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    if (!aout_buf) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    mbe_process_result local;
-    if (!result) {
-        result = &local;
-    }
-    const int rc = mbe_decodeImbe7100x4400SoftFrame(imbe_fr, imbe_d, result);
-    if (rc < 0) {
-        return rc;
-    }
-    return mbe_processImbe4400Data(aout_buf, result, imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return aout_buf ? soft_frame_call(MBX_CODEC_IMBE7100X4400, nullptr, aout_buf, result, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, cur_mp, prev_mp,
+                                      prev_mp_enhanced)
+                    : MBE_STATUS_INVALID_ARGUMENT;
 }
 
 // ---- AMBE 3600x2400 (D-STAR): ref src/ambe/ambe3600x2400.c:563-627 (frame decode = the AMBE+2 one), :733-852 --
 int mbe_decodeAmbe3600x2400Frame(const char ambe_fr[4][24], char ambe_d[49], mbe_process_result* result) {
-    return decode_frame(MBX_CODEC_AMBE3600X2450, reinterpret_cast<const char*>(ambe_fr), 96, 49, ambe_d, result);
+    return decode_frame(MBX_CODEC_AMBE3600X2450, reinterpret_cast<const char*>(ambe_fr), ambe_d, result);
 }
 
 int mbe_decodeAmbe3600x2400SoftFrame(const mbe_soft_bit ambe_fr[4][24], char ambe_d[49], mbe_process_result* result) {
-    return decode_soft_frame(MBX_CODEC_AMBE3600X2450, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), 96, 49, ambe_d, result);
+    return decode_soft_frame(MBX_CODEC_AMBE3600X2450, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, result);
 }
 
 int mbe_processAmbe2400Dataf(float* aout_buf, mbe_process_result* result, const char ambe_d[49], mbe_parms* cur_mp,
                              mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    return process_data(MBX_CODEC_AMBE3600X2400, aout_buf, nullptr, result, ambe_d, 49, cur_mp, prev_mp, prev_mp_enhanced);
+    return process_data(MBX_CODEC_AMBE3600X2400, aout_buf, nullptr, result, ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
 }
 
 int mbe_processAmbe2400Data(short* aout_buf, mbe_process_result* result, const char ambe_d[49], mbe_parms* cur_mp,
@@ -1885,132 +1870,60 @@ int mbe_processAmbe2400Data(short* aout_buf, mbe_process_result* result, const c
     if (!aout_buf) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    return process_data(MBX_CODEC_AMBE3600X2400, nullptr, aout_buf, result, ambe_d, 49, cur_mp, prev_mp, prev_mp_enhanced);
+    return process_data(MBX_CODEC_AMBE3600X2400, nullptr, aout_buf, result, ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
 }
 
 int mbe_processAmbe3600x2400Framef(float* aout_buf, mbe_process_result* result, const char ambe_fr[4][24], char ambe_d[49],
                                    mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (queueing()) {
-        return queue_frame(MBX_CODEC_AMBE3600X2400, aout_buf, nullptr, result, reinterpret_cast<const char*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    return process_frame(MBX_CODEC_AMBE3600X2400, aout_buf, nullptr, result, reinterpret_cast<const char*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return hard_frame_call(MBX_CODEC_AMBE3600X2400, aout_buf, nullptr, result, reinterpret_cast<const char*>(ambe_fr), ambe_d, cur_mp, prev_mp,
+                           prev_mp_enhanced);
 }
 
 int mbe_processAmbe3600x2400Frame(short* aout_buf, mbe_process_result* result, const char ambe_fr[4][24], char ambe_d[49],
                                   mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (!aout_buf) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (queueing()) {
-        return queue_frame(MBX_CODEC_AMBE3600X2400, nullptr, aout_buf, result, reinterpret_cast<const char*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    return process_frame(MBX_CODEC_AMBE3600X2400, nullptr, aout_buf, result, reinterpret_cast<const char*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return aout_buf ? hard_frame_call(MBX_CODEC_AMBE3600X2400, nullptr, aout_buf, result, reinterpret_cast<const char*>(ambe_fr), ambe_d, cur_mp, prev_mp,
+                                      prev_mp_enhanced)
+                    : MBE_STATUS_INVALID_ARGUMENT;
 }
 
 int mbe_processAmbe3600x2400SoftFramef(float* aout_buf, mbe_process_result* result, const mbe_soft_bit ambe_fr[4][24],
                                        char ambe_d[49], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (queue_soft_call(aout_buf, ambe_fr, ambe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
-        return queue_soft_frame(MBX_CODEC_AMBE3600X2400, aout_buf, nullptr, result, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    mbe_process_result local;
-    if (!result) {
-        result = &local;
-    }
-    const int rc = mbe_decodeAmbe3600x2400SoftFrame(ambe_fr, ambe_d, result);
-    if (rc < 0) {
-        return rc;
-    }
-    return mbe_processAmbe2400Dataf(aout_buf, result, ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return soft_frame_call(MBX_CODEC_AMBE3600X2400, aout_buf, nullptr, result, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, cur_mp, prev_mp,
+                           prev_mp_enhanced);
 }
 
 int mbe_processAmbe3600x2400SoftFrame(short* aout_buf, mbe_process_result* result, const mbe_soft_bit ambe_fr[4][24],
                                       char ambe_d[49], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (queue_soft_call(aout_buf, ambe_fr, ambe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
-        return queue_soft_frame(MBX_CODEC_AMBE3600X2400, nullptr, aout_buf, result, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    if (!aout_buf) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    mbe_process_result local;
-    if (!result) {
-        result = &local;
-    }
-    const int rc = mbe_decodeAmbe3600x2400SoftFrame(ambe_fr, ambe_d, result);
-    if (rc < 0) {
-        return rc;
-    }
-    return mbe_processAmbe2400Data(aout_buf, result, ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return aout_buf ? soft_frame_call(MBX_CODEC_AMBE3600X2400, nullptr, aout_buf, result, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, cur_mp, prev_mp,
+                                      prev_mp_enhanced)
+                    : MBE_STATUS_INVALID_ARGUMENT;
 }
 
 // ---- soft frames -> PCM: ref src/imbe/imbe7200x4400.c:950-980, src/ambe/ambe3600x2450.c:939-969 --------
 int mbe_processImbe7200x4400SoftFramef(float* aout_buf, mbe_process_result* result, const mbe_soft_bit imbe_fr[8][23],
                                        char imbe_d[88], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (queue_soft_call(aout_buf, imbe_fr, imbe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
-        return queue_soft_frame(MBX_CODEC_IMBE7200X4400, aout_buf, nullptr, result, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    mbe_process_result local;
-    if (!result) {
-        result = &local;
-    }
-    const int rc = mbe_decodeImbe7200x4400SoftFrame(imbe_fr, imbe_d, result);
-    if (rc < 0) {
-        return rc;
-    }
-    return mbe_processImbe4400Dataf(aout_buf, result, imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return soft_frame_call(MBX_CODEC_IMBE7200X4400, aout_buf, nullptr, result, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, cur_mp, prev_mp,
+                           prev_mp_enhanced);
 }
 
 int mbe_processImbe7200x4400SoftFrame(short* aout_buf, mbe_process_result* result, const mbe_soft_bit imbe_fr[8][23],
                                       char imbe_d[88], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (queue_soft_call(aout_buf, imbe_fr, imbe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
-        return queue_soft_frame(MBX_CODEC_IMBE7200X4400, nullptr, aout_buf, result, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    if (!aout_buf) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    mbe_process_result local;
-    if (!result) {
-        result = &local;
-    }
-    const int rc = mbe_decodeImbe7200x4400SoftFrame(imbe_fr, imbe_d, result);
-    if (rc < 0) {
-        return rc;
-    }
-    return mbe_processImbe4400Data(aout_buf, result, imbe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return aout_buf ? soft_frame_call(MBX_CODEC_IMBE7200X4400, nullptr, aout_buf, result, reinterpret_cast<const mbe_soft_bit*>(imbe_fr), imbe_d, cur_mp, prev_mp,
+                                      prev_mp_enhanced)
+                    : MBE_STATUS_INVALID_ARGUMENT;
 }
 
 int mbe_processAmbe3600x2450SoftFramef(float* aout_buf, mbe_process_result* result, const mbe_soft_bit ambe_fr[4][24],
                                        char ambe_d[49], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (queue_soft_call(aout_buf, ambe_fr, ambe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
-        return queue_soft_frame(MBX_CODEC_AMBE3600X2450, aout_buf, nullptr, result, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    mbe_process_result local;
-    if (!result) {
-        result = &local;
-    }
-    const int rc = mbe_decodeAmbe3600x2450SoftFrame(ambe_fr, ambe_d, result);
-    if (rc < 0) {
-        return rc;
-    }
-    return mbe_processAmbe2450Dataf(aout_buf, result, ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return soft_frame_call(MBX_CODEC_AMBE3600X2450, aout_buf, nullptr, result, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, cur_mp, prev_mp,
+                           prev_mp_enhanced);
 }
 
 int mbe_processAmbe3600x2450SoftFrame(short* aout_buf, mbe_process_result* result, const mbe_soft_bit ambe_fr[4][24],
                                       char ambe_d[49], mbe_parms* cur_mp, mbe_parms* prev_mp, mbe_parms* prev_mp_enhanced) {
-    if (queue_soft_call(aout_buf, ambe_fr, ambe_d, cur_mp, prev_mp, prev_mp_enhanced)) {
-        return queue_soft_frame(MBX_CODEC_AMBE3600X2450, nullptr, aout_buf, result, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
-    }
-    if (!aout_buf) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    mbe_process_result local;
-    if (!result) {
-        result = &local;
-    }
-    const int rc = mbe_decodeAmbe3600x2450SoftFrame(ambe_fr, ambe_d, result);
-    if (rc < 0) {
-        return rc;
-    }
-    return mbe_processAmbe2450Data(aout_buf, result, ambe_d, cur_mp, prev_mp, prev_mp_enhanced);
+    return aout_buf ? soft_frame_call(MBX_CODEC_AMBE3600X2450, nullptr, aout_buf, result, reinterpret_cast<const mbe_soft_bit*>(ambe_fr), ambe_d, cur_mp, prev_mp,
+                                      prev_mp_enhanced)
+                    : MBE_STATUS_INVALID_ARGUMENT;
 }
 
 }  // extern "C"
@@ -2022,27 +1935,9 @@ int mbe_processAmbe3600x2450SoftFrame(short* aout_buf, mbe_process_result* resul
 // ==================================================================================================================
 namespace {
 
-struct FrameShape {
-    int rows, stride, ncell, nbits, fbytes;
-    int width[8];
-    int first[8];   // first cell of each row that is on the wire (IMBE 7100x4400 C0 has cells 0..18, AMBE rows start at 0)
-};
-const FrameShape kShape[4] = {
-    {8, 23, 184, 88, MBX_IMBE_FRAME_BYTES, {23, 23, 23, 23, 15, 15, 15, 7}, {0, 0, 0, 0, 0, 0, 0, 0}},      // IMBE 7200x4400
-    {4, 24, 96, 49, MBX_AMBE_FRAME_BYTES, {24, 23, 11, 14, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}},           // AMBE 3600x2450
-    {7, 24, 168, 88, MBX_IMBE7100_FRAME_BYTES, {19, 24, 23, 23, 15, 15, 23, 0}, {0, 0, 0, 0, 0, 0, 0, 0}},   // IMBE 7100x4400
-    {4, 24, 96, 49, MBX_AMBE_FRAME_BYTES, {24, 23, 11, 14, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}},           // AMBE 3600x2400
-};
-
-int pack_cells(int codec, const char* cells, uint8_t* packed) {
-    return (codec == MBX_CODEC_IMBE7200X4400)   ? mbx_pack_imbe7200x4400(cells, 1, packed)
-           : (codec == MBX_CODEC_IMBE7100X4400) ? mbx_pack_imbe7100x4400(cells, 1, packed)
-                                                : mbx_pack_ambe3600x2450(cells, 1, packed);
-}
-
 // rows [r0, r1] of a packed frame back into the caller's cell array (the other cells are left alone, like the reference)
 void unpack_rows(int codec, const uint8_t* packed, char* cells, int r0, int r1) {
-    const FrameShape& sh = kShape[codec];
+    const mbx::CodecShape& sh = mbx::kCodecs[codec];
     int pos = 0;
     for (int r = 0; r < sh.rows; ++r) {
         for (int j = sh.width[r] - 1; j >= 0; --j, ++pos) {
@@ -2055,21 +1950,21 @@ void unpack_rows(int codec, const uint8_t* packed, char* cells, int r0, int r1) 
 
 // stage 1 (C0 ECC) or 2 (demodulation), in place; returns the reference's return value
 int frame_stage(int codec, int stage, char* cells) {
-    const FrameShape& sh = kShape[codec];
-    int rc = validate_bits(cells, (size_t)sh.ncell);
+    const mbx::CodecShape& sh = mbx::kCodecs[codec];
+    int rc = validate_bits(cells, (size_t)sh.cells);
     if (rc < 0) {
         return rc;
     }
     uint8_t packed[MBX_IMBE_FRAME_BYTES], back[MBX_IMBE_FRAME_BYTES];
-    rc = pack_cells(codec, cells, packed);
+    rc = pack_one(codec, cells, packed);
     if (rc < 0) {
         return rc;
     }
     Slot& s = slot();
-    s.up(s.frame, packed, (size_t)sh.fbytes);
+    s.up(s.frame, packed, (size_t)sh.frame_bytes);
     must(mbx_fec_stage(codec, stage, s.frame, 1, s.frame_out, s.rec, s.stream), "mbx_fec_stage");
     mbx_param_record rec;
-    s.down(back, s.frame_out, (size_t)sh.fbytes);
+    s.down(back, s.frame_out, (size_t)sh.frame_bytes);
     s.down(&rec, s.rec, sizeof(rec));
     s.sync();
     if (stage == MBX_STAGE_C0) {
@@ -2088,31 +1983,32 @@ int frame_stage(int codec, int stage, char* cells) {
 }
 
 int frame_data_ecc(int codec, char* cells, char* bits_out) {
-    const FrameShape& sh = kShape[codec];
+    const mbx::CodecShape& sh = mbx::kCodecs[codec];
     if (!bits_out) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    int rc = validate_bits(cells, (size_t)sh.ncell);
+    int rc = validate_bits(cells, (size_t)sh.cells);
     if (rc < 0) {
         return rc;
     }
     uint8_t packed[MBX_IMBE_FRAME_BYTES];
-    rc = pack_cells(codec, cells, packed);
+    rc = pack_one(codec, cells, packed);
     if (rc < 0) {
         return rc;
     }
     Slot& s = slot();
-    s.up(s.frame, packed, (size_t)sh.fbytes);
+    s.up(s.frame, packed, (size_t)sh.frame_bytes);
     must(mbx_fec_stage(codec, MBX_STAGE_DATA, s.frame, 1, nullptr, s.rec, s.stream), "mbx_fec_stage");
     mbx_param_record rec;
     s.down(&rec, s.rec, sizeof(rec));
     s.sync();
-    mbx_unpack_records(&rec, 1, sh.nbits, bits_out, nullptr);
+    mbx_unpack_records(&rec, 1, sh.data_bits, bits_out, nullptr);
     return (int)(rec.w[3] & 0xffu);
 }
 
 // mbe_decode*Parms: parameter decode alone (expand + prediction), both structs updated like the reference
-int decode_parms(int codec, const char* bits, int nbits, mbe_parms* cur, mbe_parms* prev) {
+int decode_parms(int codec, const char* bits, mbe_parms* cur, mbe_parms* prev) {
+    const int nbits = mbx::kCodecs[codec].data_bits;
     if (!cur || !prev) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
@@ -2181,17 +2077,17 @@ extern "C" {
 int mbe_eccImbe7200x4400C0(char imbe_fr[8][23]) { return frame_stage(MBX_CODEC_IMBE7200X4400, MBX_STAGE_C0, reinterpret_cast<char*>(imbe_fr)); }
 int mbe_demodulateImbe7200x4400Data(char imbe[8][23]) { return frame_stage(MBX_CODEC_IMBE7200X4400, MBX_STAGE_DEMODULATE, reinterpret_cast<char*>(imbe)); }
 int mbe_eccImbe7200x4400Data(char imbe_fr[8][23], char* imbe_d) { return frame_data_ecc(MBX_CODEC_IMBE7200X4400, reinterpret_cast<char*>(imbe_fr), imbe_d); }
-int mbe_decodeImbe4400Parms(const char* imbe_d, mbe_parms* cur_mp, mbe_parms* prev_mp) { return decode_parms(MBX_CODEC_IMBE7200X4400, imbe_d, 88, cur_mp, prev_mp); }
+int mbe_decodeImbe4400Parms(const char* imbe_d, mbe_parms* cur_mp, mbe_parms* prev_mp) { return decode_parms(MBX_CODEC_IMBE7200X4400, imbe_d, cur_mp, prev_mp); }
 
 int mbe_eccAmbe3600x2450C0(char ambe_fr[4][24]) { return frame_stage(MBX_CODEC_AMBE3600X2450, MBX_STAGE_C0, reinterpret_cast<char*>(ambe_fr)); }
 int mbe_demodulateAmbe3600x2450Data(char ambe_fr[4][24]) { return frame_stage(MBX_CODEC_AMBE3600X2450, MBX_STAGE_DEMODULATE, reinterpret_cast<char*>(ambe_fr)); }
 int mbe_eccAmbe3600x2450Data(char ambe_fr[4][24], char* ambe_d) { return frame_data_ecc(MBX_CODEC_AMBE3600X2450, reinterpret_cast<char*>(ambe_fr), ambe_d); }
-int mbe_decodeAmbe2450Parms(const char* ambe_d, mbe_parms* cur_mp, mbe_parms* prev_mp) { return decode_parms(MBX_CODEC_AMBE3600X2450, ambe_d, 49, cur_mp, prev_mp); }
+int mbe_decodeAmbe2450Parms(const char* ambe_d, mbe_parms* cur_mp, mbe_parms* prev_mp) { return decode_parms(MBX_CODEC_AMBE3600X2450, ambe_d, cur_mp, prev_mp); }
 
 int mbe_eccAmbe3600x2400C0(char ambe_fr[4][24]) { return frame_stage(MBX_CODEC_AMBE3600X2400, MBX_STAGE_C0, reinterpret_cast<char*>(ambe_fr)); }
 int mbe_demodulateAmbe3600x2400Data(char ambe_fr[4][24]) { return frame_stage(MBX_CODEC_AMBE3600X2400, MBX_STAGE_DEMODULATE, reinterpret_cast<char*>(ambe_fr)); }
 int mbe_eccAmbe3600x2400Data(char ambe_fr[4][24], char* ambe_d) { return frame_data_ecc(MBX_CODEC_AMBE3600X2400, reinterpret_cast<char*>(ambe_fr), ambe_d); }
-int mbe_decodeAmbe2400Parms(const char* ambe_d, mbe_parms* cur_mp, mbe_parms* prev_mp) { return decode_parms(MBX_CODEC_AMBE3600X2400, ambe_d, 49, cur_mp, prev_mp); }
+int mbe_decodeAmbe2400Parms(const char* ambe_d, mbe_parms* cur_mp, mbe_parms* prev_mp) { return decode_parms(MBX_CODEC_AMBE3600X2400, ambe_d, cur_mp, prev_mp); }
 
 int mbe_eccImbe7100x4400C0(char imbe_fr[7][24]) { return frame_stage(MBX_CODEC_IMBE7100X4400, MBX_STAGE_C0, reinterpret_cast<char*>(imbe_fr)); }
 int mbe_demodulateImbe7100x4400Data(char imbe[7][24]) { return frame_stage(MBX_CODEC_IMBE7100X4400, MBX_STAGE_DEMODULATE, reinterpret_cast<char*>(imbe)); }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "mbx.h"
+#include "mbx_codec.h"
 #include "mbx_device.h"
 #include "mbx_kernels.h"
 
@@ -540,28 +541,17 @@ uint32_t mbx_table_checksum(void) {
 
 // Where cell [row][col] of the reference's frame array sits in the packed wire frame: bit index from the frame's first bit (bit 7 of
 // byte 0 = index 0), -1 for a cell the codec does not use.  The row widths are the packers' (pack_rows: row after row, inside a row
-// from the highest cell down to cell 0).
-static const int* wire_row_widths(int codec, int* rows) {
-    static const int imbe7200[8] = {23, 23, 23, 23, 15, 15, 15, 7}, imbe7100[7] = {19, 24, 23, 23, 15, 15, 23}, ambe[4] = {24, 23, 11, 14};
-    switch (codec) {
-        case MBX_CODEC_IMBE7200X4400: *rows = 8; return imbe7200;
-        case MBX_CODEC_IMBE7100X4400: *rows = 7; return imbe7100;
-        case MBX_CODEC_AMBE3600X2450:
-        case MBX_CODEC_AMBE3600X2400: *rows = 4; return ambe;
-        default: *rows = 0; return nullptr;
-    }
-}
+// from the highest cell down to cell 0), declared in mbx_codec.h.
 int mbx_wire_bit_of_cell(int codec, int row, int col) {
-    int rows = 0;
-    const int* w = wire_row_widths(codec, &rows);
-    if (!w || row < 0 || row >= rows || col < 0 || col >= w[row]) {
+    const mbx::CodecShape* sh = mbx::codec_shape(codec);
+    if (!sh || row < 0 || row >= sh->rows || col < 0 || col >= sh->width[row]) {
         return -1;
     }
     int pos = 0;
     for (int r = 0; r < row; ++r) {
-        pos += w[r];
+        pos += sh->width[r];
     }
-    return pos + (w[row] - 1 - col);
+    return pos + (sh->width[row] - 1 - col);
 }
 
 // Folds a caller's deinterleave schedule into one table: the caller knows, for each of the n channel bits of a voice burst in the order
@@ -569,14 +559,13 @@ int mbx_wire_bit_of_cell(int codec, int row, int col) {
 // goes in the packed wire frame.  Refuses a schedule that is not a bijection onto the codec's cells (a wrong table is caught here,
 // once, not as noise in the audio).
 int mbx_wire_permutation(int codec, const int* cell_row, const int* cell_col, int n, int* wire_bit) {
-    int rows = 0;
-    const int* w = wire_row_widths(codec, &rows);
-    if (!w || !cell_row || !cell_col || !wire_bit) {
+    const mbx::CodecShape* sh = mbx::codec_shape(codec);
+    if (!sh || !cell_row || !cell_col || !wire_bit) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     int total = 0;
-    for (int r = 0; r < rows; ++r) {
-        total += w[r];
+    for (int r = 0; r < sh->rows; ++r) {
+        total += sh->width[r];
     }
     if (n != total) {
         return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_wire_permutation: the schedule must name every channel bit of the codec once");
@@ -593,9 +582,8 @@ int mbx_wire_permutation(int codec, const int* cell_row, const int* cell_col, in
     return 0;
 }
 
-int mbx_pack_imbe7200x4400(const char* frames, size_t n, uint8_t* packed) {
-    static const int width[8] = {23, 23, 23, 23, 15, 15, 15, 7};
-    int rc = validate_bits(frames, n * 184u);
+static int pack_frames(const mbx::CodecShape& sh, const char* frames, size_t n, uint8_t* packed) {
+    int rc = validate_bits(frames, n * (size_t)sh.cells);
     if (rc < 0) {
         return rc;
     }
@@ -603,40 +591,13 @@ int mbx_pack_imbe7200x4400(const char* frames, size_t n, uint8_t* packed) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     for (size_t i = 0; i < n; ++i) {
-        pack_rows(frames + i * 184u, 8, 23, width, packed + i * MBX_IMBE_FRAME_BYTES, MBX_IMBE_FRAME_BYTES);
+        pack_rows(frames + i * (size_t)sh.cells, sh.rows, sh.stride, sh.width, packed + i * (size_t)sh.frame_bytes, sh.frame_bytes);
     }
     return 0;
 }
-
-int mbx_pack_imbe7100x4400(const char* frames, size_t n, uint8_t* packed) {
-    static const int width[7] = {19, 24, 23, 23, 15, 15, 23};
-    int rc = validate_bits(frames, n * 168u);
-    if (rc < 0) {
-        return rc;
-    }
-    if (!packed) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    for (size_t i = 0; i < n; ++i) {
-        pack_rows(frames + i * 168u, 7, 24, width, packed + i * MBX_IMBE7100_FRAME_BYTES, MBX_IMBE7100_FRAME_BYTES);
-    }
-    return 0;
-}
-
-int mbx_pack_ambe3600x2450(const char* frames, size_t n, uint8_t* packed) {
-    static const int width[4] = {24, 23, 11, 14};
-    int rc = validate_bits(frames, n * 96u);
-    if (rc < 0) {
-        return rc;
-    }
-    if (!packed) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    for (size_t i = 0; i < n; ++i) {
-        pack_rows(frames + i * 96u, 4, 24, width, packed + i * MBX_AMBE_FRAME_BYTES, MBX_AMBE_FRAME_BYTES);
-    }
-    return 0;
-}
+int mbx_pack_imbe7200x4400(const char* frames, size_t n, uint8_t* packed) { return pack_frames(mbx::kCodecs[MBX_CODEC_IMBE7200X4400], frames, n, packed); }
+int mbx_pack_imbe7100x4400(const char* frames, size_t n, uint8_t* packed) { return pack_frames(mbx::kCodecs[MBX_CODEC_IMBE7100X4400], frames, n, packed); }
+int mbx_pack_ambe3600x2450(const char* frames, size_t n, uint8_t* packed) { return pack_frames(mbx::kCodecs[MBX_CODEC_AMBE3600X2450], frames, n, packed); }
 
 void mbx_unpack_records(const mbx_param_record* rec, size_t n, int nbits, char* bits, mbe_process_result* results) {
     for (size_t i = 0; i < n; ++i) {
@@ -739,85 +700,6 @@ int mbx_release_stream(void* stream) {
 
 size_t mbx_workspace_bytes(size_t max_frames) { return max_frames * sizeof(mbx::FrameParams); }
 
-int mbx_fec_imbe7200x4400(const uint8_t* d_frames, size_t n, mbx_param_record* d_records, void* stream) {
-    REQUIRE_CTX(c);
-    if (!d_frames || !d_records) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (n == 0) {
-        return 0;
-    }
-    const unsigned grid = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(mbx::fec_imbe7200x4400_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_frames, n,
-                       d_records, c->tabs);
-    return check_launch("fec_imbe7200x4400_kernel");
-}
-
-int mbx_fec_ambe3600x2450(const uint8_t* d_frames, size_t n, mbx_param_record* d_records, void* stream) {
-    REQUIRE_CTX(c);
-    if (!d_frames || !d_records) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (n == 0) {
-        return 0;
-    }
-    const unsigned grid = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(mbx::fec_ambe3600x2450_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_frames, n,
-                       d_records, c->tabs);
-    return check_launch("fec_ambe3600x2450_kernel");
-}
-
-int mbx_fec_imbe7100x4400(const uint8_t* d_frames, size_t n, mbx_param_record* d_records, void* stream) {
-    REQUIRE_CTX(c);
-    if (!d_frames || !d_records) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (n == 0) {
-        return 0;
-    }
-    const unsigned grid = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(mbx::fec_imbe7100x4400_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_frames, n,
-                       d_records, c->tabs);
-    return check_launch("fec_imbe7100x4400_kernel");
-}
-
-// the front of a soft batch step: n <= 2^31-1 frames -> records, one wavefront per frame (mbx_soft_front.hip)
-static int launch_soft_front(Context* c, int codec, const mbe_soft_bit* d_soft, size_t n, mbx_param_record* d_records, void* stream) {
-    const dim3 grid((unsigned)n), block(64);
-    if (codec == MBX_CODEC_IMBE7200X4400) {
-        hipLaunchKernelGGL(mbx::soft_front_imbe_kernel, grid, block, 0, (hipStream_t)stream, d_soft, n, d_records, c->tabs);
-    } else if (codec == MBX_CODEC_IMBE7100X4400) {
-        hipLaunchKernelGGL(mbx::soft_front_imbe7100_kernel, grid, block, 0, (hipStream_t)stream, d_soft, n, d_records, c->tabs);
-    } else {   // both AMBE codecs: the same cells, the same search
-        hipLaunchKernelGGL(mbx::soft_front_ambe_kernel, grid, block, 0, (hipStream_t)stream, d_soft, n, d_records, c->tabs);
-    }
-    return check_launch("soft_front_kernel");
-}
-
-int mbx_fec_soft(int codec, const mbe_soft_bit* d_soft, size_t n, mbx_param_record* d_records, void* stream) {
-    REQUIRE_CTX(c);
-    if (!d_soft || !d_records || codec < MBX_CODEC_IMBE7200X4400 || codec > MBX_CODEC_AMBE3600X2400) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (n == 0) {
-        return 0;
-    }
-    if (n > 0x7fffffffu) {
-        return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_fec_soft: more than 2^31-1 frames in one launch");
-    }
-    if (codec == MBX_CODEC_IMBE7200X4400) {   // one wavefront per frame
-        hipLaunchKernelGGL(mbx::fec_imbe7200x4400_soft_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, d_soft, n,
-                           d_records, c->tabs);
-    } else if (codec == MBX_CODEC_IMBE7100X4400) {
-        hipLaunchKernelGGL(mbx::fec_imbe7100x4400_soft_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, d_soft, n,
-                           d_records, c->tabs);
-    } else {
-        hipLaunchKernelGGL(mbx::fec_ambe3600x2450_soft_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, d_soft, n,
-                           d_records, c->tabs);
-    }
-    return check_launch("fec_soft_kernel");
-}
-
 int mbx_ecc_soft_words(int kind, const mbe_soft_bit* d_in, size_t n, uint32_t* d_out, int32_t* d_errs, void* stream) {
     REQUIRE_CTX(c);
     if (!d_in || !d_out || kind < 0 || kind > 2 || n > 0x7fffffffu) {
@@ -869,23 +751,6 @@ int mbx_soft_bits_from_llr(const int16_t* llr, mbe_soft_bit* soft, size_t count)
         soft[i].reliability = (uint8_t)(mag > 255 ? 255 : mag);
     }
     return 0;
-}
-
-static bool expand_codec_ok(int codec) {
-    return codec == MBX_CODEC_IMBE7200X4400 || codec == MBX_CODEC_AMBE3600X2450 || codec == MBX_CODEC_AMBE3600X2400;
-}
-
-// frame-parallel half of the parameter decode: records -> FrameParams rows at `out`
-static int launch_expand(Context* c, int codec, const mbx_param_record* d_records, size_t n, mbx::FrameParams* out, void* stream) {
-    const unsigned egrid = (unsigned)((n + 31) / 32);   // 8 frames per wave, 4 waves per workgroup (mbx_expand.hip)
-    if (codec == MBX_CODEC_IMBE7200X4400) {
-        hipLaunchKernelGGL(mbx::expand_imbe_kernel, dim3(egrid), dim3(256), 0, (hipStream_t)stream, d_records, n, out, c->tabs);
-    } else if (codec == MBX_CODEC_AMBE3600X2400) {
-        hipLaunchKernelGGL(mbx::expand_ambe2400_kernel, dim3(egrid), dim3(256), 0, (hipStream_t)stream, d_records, n, out, c->tabs);
-    } else {
-        hipLaunchKernelGGL(mbx::expand_ambe_kernel, dim3(egrid), dim3(256), 0, (hipStream_t)stream, d_records, n, out, c->tabs);
-    }
-    return check_launch("expand_kernel");
 }
 
 // ---- the stream-stage kernel instances (mbx_stream.hip) ------------------------------------------------------------------------------
@@ -946,6 +811,87 @@ static const Instance kInstances[] = {
     {"imbe7100_stream_kernel_res1_fused", mbx::imbe7100_stream_kernel_res1_fused},
 };
 static_assert(sizeof(kInstances) / sizeof(kInstances[0]) == kRes1Fused + 2, "kInstances: Row names the first entry of every row");
+// What the launcher knows of a codec beyond its shape (mbx_codec.h), keyed the same way, every kernel named once.  A codec's frames
+// go through the FEC kernels of the row CodecShape::front names and the expand kernel and kInstances column of the row
+// CodecShape::stream names: a row that is nobody's front end has no FEC kernels, one that is nobody's stream stage no expand kernel.
+// A new codec: its shape in mbx_codec.h, its row here.
+using FecKernel = void (*)(const uint8_t*, size_t, mbx_param_record*, DeviceTables);
+using SoftFecKernel = void (*)(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
+using ExpandKernel = void (*)(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
+struct CodecKernels {
+    FecKernel     fec;            // hard FEC: packed frames -> records, one frame per thread
+    const char*   fec_name;
+    SoftFecKernel fec_soft;       // soft FEC alone (mbx_fec_soft) ...
+    SoftFecKernel soft_front;     // ... and as the front of a soft batch step (mbx_soft_front.hip); both one wavefront per frame
+    ExpandKernel  expand;         // records -> FrameParams rows
+    int           column;         // of the stream stage in the three-column rows of kInstances
+    int           lds_waves;      // resident waves per SIMD of the kernel a long launch takes (the kernels' own launch bounds: mbx_device.h)
+    int           fused_column;   // the IMBE codecs -- a front end inside the stream's wave, a stream kernel that expands a record itself --:
+                                  // their column in the two fused rows; -1: an AMBE codec
+};
+static const CodecKernels kCodecKernels[4] = {
+    {mbx::fec_imbe7200x4400_kernel, "fec_imbe7200x4400_kernel", mbx::fec_imbe7200x4400_soft_kernel, mbx::soft_front_imbe_kernel,
+     mbx::expand_imbe_kernel, 0, MBX_IMBE_LDS_WAVES_PER_SIMD, 0},
+    {mbx::fec_ambe3600x2450_kernel, "fec_ambe3600x2450_kernel", mbx::fec_ambe3600x2450_soft_kernel, mbx::soft_front_ambe_kernel,
+     mbx::expand_ambe_kernel, 1, MBX_AMBE_LDS_WAVES_PER_SIMD, -1},
+    {mbx::fec_imbe7100x4400_kernel, "fec_imbe7100x4400_kernel", mbx::fec_imbe7100x4400_soft_kernel, mbx::soft_front_imbe7100_kernel,
+     nullptr, -1, 0, 1},
+    {nullptr, nullptr, nullptr, nullptr, mbx::expand_ambe2400_kernel, 2, MBX_AMBE_LDS_WAVES_PER_SIMD, -1},
+};
+// the row of the stream stage a codec's frames end in (a codec that is none of the four is rejected before any launch; the names'
+// functions answer for it as for AMBE 3600x2450, as they always have)
+static const CodecKernels& stream_kernels(int codec) {
+    const mbx::CodecShape* sh = mbx::codec_shape(codec);
+    return kCodecKernels[sh ? sh->stream : MBX_CODEC_AMBE3600X2450];
+}
+static bool imbe_codec(int codec) { return mbx::codec_shape(codec) && kCodecKernels[codec].fused_column >= 0; }
+
+// FEC stage of hard-decision frames of `codec` (one of the four): n frames -> records
+static int launch_fec(Context* c, int codec, const uint8_t* d_frames, size_t n, mbx_param_record* d_records, void* stream) {
+    const CodecKernels& k = kCodecKernels[mbx::kCodecs[codec].front];
+    hipLaunchKernelGGL(k.fec, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d_frames, n, d_records, c->tabs);
+    return check_launch(k.fec_name);
+}
+static int fec_export(int codec, const uint8_t* d_frames, size_t n, mbx_param_record* d_records, void* stream) {
+    REQUIRE_CTX(c);
+    if (!d_frames || !d_records) {
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    return n == 0 ? 0 : launch_fec(c, codec, d_frames, n, d_records, stream);
+}
+int mbx_fec_imbe7200x4400(const uint8_t* d_frames, size_t n, mbx_param_record* d_records, void* stream) { return fec_export(MBX_CODEC_IMBE7200X4400, d_frames, n, d_records, stream); }
+int mbx_fec_ambe3600x2450(const uint8_t* d_frames, size_t n, mbx_param_record* d_records, void* stream) { return fec_export(MBX_CODEC_AMBE3600X2450, d_frames, n, d_records, stream); }
+int mbx_fec_imbe7100x4400(const uint8_t* d_frames, size_t n, mbx_param_record* d_records, void* stream) { return fec_export(MBX_CODEC_IMBE7100X4400, d_frames, n, d_records, stream); }
+
+// soft frames of `codec` (one of the four), n <= 2^31-1 of them, -> records, one wavefront per frame: the front of a soft batch step
+// (mbx_soft_front.hip), or the FEC-only kernel behind mbx_fec_soft
+static int launch_soft_fec(Context* c, int codec, bool front, const mbe_soft_bit* d_soft, size_t n, mbx_param_record* d_records, void* stream) {
+    const CodecKernels& k = kCodecKernels[mbx::kCodecs[codec].front];
+    const SoftFecKernel kernel = front ? k.soft_front : k.fec_soft;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, d_soft, n, d_records, c->tabs);
+    return check_launch(front ? "soft_front_kernel" : "fec_soft_kernel");
+}
+
+int mbx_fec_soft(int codec, const mbe_soft_bit* d_soft, size_t n, mbx_param_record* d_records, void* stream) {
+    REQUIRE_CTX(c);
+    if (!d_soft || !d_records || !mbx::codec_shape(codec)) {
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (n == 0) {
+        return 0;
+    }
+    if (n > 0x7fffffffu) {
+        return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_fec_soft: more than 2^31-1 frames in one launch");
+    }
+    return launch_soft_fec(c, codec, false, d_soft, n, d_records, stream);
+}
+
+// frame-parallel half of the parameter decode: records of a codec with a stream stage of its own -> FrameParams rows at `out`
+static int launch_expand(Context* c, int codec, const mbx_param_record* d_records, size_t n, mbx::FrameParams* out, void* stream) {
+    const unsigned egrid = (unsigned)((n + 31) / 32);   // 8 frames per wave, 4 waves per workgroup (mbx_expand.hip)
+    hipLaunchKernelGGL(kCodecKernels[codec].expand, dim3(egrid), dim3(256), 0, (hipStream_t)stream, d_records, n, out, c->tabs);
+    return check_launch("expand_kernel");
+}
 // what select_instance decides on
 struct Shape {
     int  codec, S, T;
@@ -967,12 +913,27 @@ static int launched(Context* c, void* stream, const Instance& e) {
     record_launch(c, stream, e);
     return check_launch(e.name);
 }
+// What every launcher of a batch step passes on.  `codec` is the call's own: a launcher asks the codec tables for the codec of the
+// stage it launches (a 7100x4400 step has a front end of its own and streams as 7200x4400).
+struct BatchCall {
+    int                 codec, S, T;
+    mbx_param_record*   records;        // S*T, stream-major: written by the front launch of a step that has one, only read otherwise
+    mbe_parms*          state;          // three structs per stream, or per slot of the pool `stream_index` names
+    mbx_stream_rng*     rng;
+    int16_t*            pcm16;          // S*T*160 samples each, or nullptr
+    float*              pcmf;
+    mbe_process_result* results;        // S*T, or nullptr
+    void*               stream;
+    const int32_t*      stream_index;   // row of the batch -> slot of state / rng, or nullptr: identity
+    uint32_t*           resident;       // elision words of resident state, or nullptr: plain triplets
+};
+static bool call_args_ok(const BatchCall& b) { return b.records && b.state && b.rng && b.S >= 0 && b.T >= 0; }
 // the tables of a launch: the context's + what this launch walks (`reverse`: see launch_stream)
-static mbx::DeviceTables launch_tables(const Context* c, bool reverse, const int32_t* d_stream_index, uint32_t* d_resident) {
+static mbx::DeviceTables launch_tables(const Context* c, bool reverse, const BatchCall& b) {
     mbx::DeviceTables tabs = c->tabs;
     tabs.reverse = (reverse && reverse_enabled()) ? 1 : 0;
-    tabs.stream_map = d_stream_index;
-    tabs.resident = d_resident;
+    tabs.stream_map = b.stream_index;
+    tabs.resident = b.resident;
     return tabs;
 }
 
@@ -1017,15 +978,12 @@ static int choose_slice_frames(int S, int T, int slots) {
     const double plain = (double)((S + slots - 1) / slots);
     return (plain >= 1.06 * ideal) ? Tc : 0;   // what the part-empty last round costs must be worth the extra launches
 }
-// resident waves per SIMD of the kernel a long launch of `codec` takes (the kernels' own launch bounds: mbx_device.h)
-static int lds_kernel_waves_per_simd(int codec) {
-    return (codec == MBX_CODEC_IMBE7200X4400) ? MBX_IMBE_LDS_WAVES_PER_SIMD : MBX_AMBE_LDS_WAVES_PER_SIMD;
-}
 // caller holds c->mu.  0: issued (*rc); 1: not applicable (take the plain launch)
-static int try_sliced_launch(Context* c, StreamSlot& slot, mbx::DeviceTables tabs, int codec, int S, int T, const mbx_param_record* d_records,
-                             const mbx::FrameParams* params, mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf,
-                             mbe_process_result* d_results, void* stream, int* rc) {
-    const int Tc = choose_slice_frames(S, T, lds_kernel_waves_per_simd(codec) * c->simds);
+static int try_sliced_launch(Context* c, StreamSlot& slot, const mbx::DeviceTables& tabs, const BatchCall& b, const mbx::FrameParams* params,
+                             int* rc) {
+    const int S = b.S, T = b.T;
+    void* const stream = b.stream;
+    const int Tc = choose_slice_frames(S, T, stream_kernels(b.codec).lds_waves * c->simds);
     if (Tc <= 0) {
         return 1;
     }
@@ -1056,7 +1014,7 @@ static int try_sliced_launch(Context* c, StreamSlot& slot, mbx::DeviceTables tab
         (void)hipGetLastError();
         return 1;
     }
-    Shape q{codec, S, T};
+    Shape q{b.codec, S, T};
     q.sliced = true;
     const Instance& e = select_instance(q);
     int result = 0;
@@ -1085,17 +1043,20 @@ static int try_sliced_launch(Context* c, StreamSlot& slot, mbx::DeviceTables tab
             tg.stream_map += s0;
         }
         const size_t f0 = (size_t)s0 * (size_t)T;
-        const mbx_param_record* rg = d_records + f0;
+        BatchCall part = b;   // this group's rows of the batch
+        part.records += f0;
         const mbx::FrameParams* pg = params ? params + f0 : nullptr;
-        // (state and RNG state are addressed through the stream map when there is one: then only the batch rows are offset)
-        mbe_parms* sg = tabs.stream_map ? d_state : d_state + 3 * (size_t)s0;
-        mbx_stream_rng* ng = tabs.stream_map ? d_rng : d_rng + s0;
-        int16_t* p16 = d_pcm16 ? d_pcm16 + f0 * 160 : nullptr;
-        float* pf = d_pcmf ? d_pcmf + f0 * 160 : nullptr;
-        mbe_process_result* rs = d_results ? d_results + f0 : nullptr;
+        if (!tabs.stream_map) {   // (state and RNG state are addressed through the stream map when there is one: then only the batch rows are offset)
+            part.state += 3 * (size_t)s0;
+            part.rng += s0;
+        }
+        part.pcm16 = b.pcm16 ? b.pcm16 + f0 * 160 : nullptr;
+        part.pcmf = b.pcmf ? b.pcmf + f0 * 160 : nullptr;
+        part.results = b.results ? b.results + f0 : nullptr;
         for (int t0 = 0; t0 < T; t0 += Tc) {
             const int n = (T - t0) < Tc ? (T - t0) : Tc;
-            hipLaunchKernelGGL(e.slice, dim3((unsigned)Sg), dim3(64), 0, st, Sg, T, t0, n, rg, pg, sg, ng, p16, pf, rs, tg);
+            hipLaunchKernelGGL(e.slice, dim3((unsigned)Sg), dim3(64), 0, st, Sg, T, t0, n, part.records, pg, part.state, part.rng, part.pcm16, part.pcmf, part.results,
+                               tg);
         }
         const int lrc = check_launch(e.name);
         if (lrc < 0) {
@@ -1118,32 +1079,26 @@ static int try_sliced_launch(Context* c, StreamSlot& slot, mbx::DeviceTables tab
 // order every launch finds none of it there, while a launch that starts where the previous one ended finds its last
 // quarter-gigabyte.  The results do not depend on the order.  The alternation is kept per (device, hipStream_t) slot
 // and per session -- whoever re-walks the same state -- not process-wide.
-static int launch_stream(Context* c, bool reverse, int codec, int S, int T, const mbx_param_record* d_records,
-                         const mbx::FrameParams* params, mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16,
-                         float* d_pcmf, mbe_process_result* d_results, void* stream, const int32_t* d_stream_index = nullptr,
-                         uint32_t* d_resident = nullptr, StreamSlot* slot = nullptr /* caller holds c->mu: time-sliced launches allowed */) {
-    const mbx::DeviceTables tabs = launch_tables(c, reverse, d_stream_index, d_resident);
+// `slot` (the caller holds c->mu) or nullptr: with it the launch may be issued slice by slice.
+static int launch_stream(Context* c, bool reverse, const BatchCall& b, const mbx::FrameParams* params, StreamSlot* slot) {
+    const mbx::DeviceTables tabs = launch_tables(c, reverse, b);
     // With several frames per stream prev_mp / prev_mp_enhanced stay in LDS for the whole launch (the *_lds instances,
     // four waves per SIMD) instead of being parked in their HBM slots every frame: mbx_stream.hip, ParkedState.
     // Resident state (d_resident) is understood by those instances only, whatever T is.
-    const bool lds_resident = T >= kLdsResidentMinFrames && lds_resident_enabled();
-    if (slot && lds_resident && !d_resident) {
+    const bool lds_resident = b.T >= kLdsResidentMinFrames && lds_resident_enabled();
+    if (slot && lds_resident && !b.resident) {
         int rc = 0;
-        if (try_sliced_launch(c, *slot, tabs, codec, S, T, d_records, params, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, &rc) == 0) {
+        if (try_sliced_launch(c, *slot, tabs, b, params, &rc) == 0) {
             return rc;
         }
     }
-    Shape q{codec, S, T};
-    q.resident = d_resident != nullptr;
+    Shape q{b.codec, b.S, b.T};
+    q.resident = b.resident != nullptr;
     q.rows = params != nullptr;
     const Instance& e = select_instance(q);
-    hipLaunchKernelGGL(e.stream, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, T, d_records, params, d_state, d_rng, d_pcm16, d_pcmf,
-                       d_results, tabs);
-    return launched(c, stream, e);
-}
-
-static bool stream_args_ok(int codec, int S, int T, const void* d_records, const void* d_state, const void* d_rng) {
-    return d_records && d_state && d_rng && S >= 0 && T >= 0 && expand_codec_ok(codec);
+    hipLaunchKernelGGL(e.stream, dim3((unsigned)b.S), dim3(64), 0, (hipStream_t)b.stream, b.S, b.T, b.records, params, b.state, b.rng, b.pcm16,
+                       b.pcmf, b.results, tabs);
+    return launched(c, b.stream, e);
 }
 
 // IMBE with several frames per stream: the stream kernel expands the records itself, which saves the workspace round
@@ -1155,7 +1110,7 @@ static bool stream_args_ok(int codec, int S, int T, const void* d_records, const
 // last few per cent of kernel efficiency, and the IMBE stream kernel expands the record itself.
 constexpr int kSmallBatchFrames = 256;
 static bool needs_workspace(int codec, int S, int T) {
-    if (codec == MBX_CODEC_IMBE7200X4400) {
+    if (imbe_codec(codec)) {
         return T == 1 && S > kSmallBatchFrames;
     }
     // AMBE codecs: the LDS-resident instances (T >= 4) expand eight frames of their stream at a time into LDS rows;
@@ -1189,16 +1144,16 @@ static int front_lead_chunks() {
     }();
     return lead;
 }
-static bool ambe_codec(int codec) { return codec == MBX_CODEC_AMBE3600X2450 || codec == MBX_CODEC_AMBE3600X2400; }
-// THE selection: which instance runs for a launch of this shape under the switches above.  (A codec that is none of the four is
-// rejected before any launch; the names' functions answer for it as for AMBE 3600x2450, as they always have.)
+// THE selection: which instance runs for a launch of this shape under the switches above.  (A codec that is none of the four:
+// see stream_kernels.)
 static const Instance& select_instance(const Shape& q) {
-    const bool imbe7100 = q.codec == MBX_CODEC_IMBE7100X4400;   // own front end, then the 7200x4400 column
-    const bool imbe = q.codec == MBX_CODEC_IMBE7200X4400 || imbe7100;
-    const int col = imbe ? 0 : (q.codec == MBX_CODEC_AMBE3600X2400 ? 2 : 1);
+    const mbx::CodecShape* sh = mbx::codec_shape(q.codec);
+    const bool imbe7100 = sh && sh->stream != q.codec;   // own front end, then the 7200x4400 column
+    const bool imbe = imbe_codec(q.codec);
+    const int col = stream_kernels(q.codec).column;
     const int mode = fused_one_mode();
     if (q.frames && q.T == 1 && q.S > kSmallBatchFrames && mode != 0) {   // the T = 1 step as one launch
-        if (ambe_codec(q.codec)) {   // 9-byte frames: byte loads, any alignment; no in-wave form: without a workspace the staged kernels
+        if (sh && !imbe) {   // AMBE, 9-byte frames: byte loads, any alignment; no in-wave form: without a workspace the staged kernels
             if (mode == 2 && q.workspace) {
                 return kInstances[(q.resident ? kOneLaunchRes : kOneLaunch) + col];
             }
@@ -1206,7 +1161,7 @@ static const Instance& select_instance(const Shape& q) {
             if (mode == 2 && !imbe7100 && q.workspace) {
                 return kInstances[(q.resident ? kOneLaunchRes : kOneLaunch) + col];
             }
-            return kInstances[(q.resident ? kRes1Fused : kOneFused) + (imbe7100 ? 1 : 0)];
+            return kInstances[(q.resident ? kRes1Fused : kOneFused) + kCodecKernels[q.codec].fused_column];
         }
     }
     if (q.sliced) {
@@ -1223,40 +1178,36 @@ static const Instance& select_instance(const Shape& q) {
     // 8,192 streams x T = 128 went from 3.51 ms to 3.15 ms.)
     return kInstances[(lds ? kLds : (q.T == 1 ? kOne : kPlain)) + col];
 }
-static int launch_fused_one(Context* c, const Instance& e, bool reverse, int codec, int S, const uint8_t* d_frames, mbx_param_record* d_records,
-                            mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
-                            void* stream, const int32_t* d_stream_index, uint32_t* d_resident) {
-    const mbx::DeviceTables tabs = launch_tables(c, reverse, d_stream_index, d_resident);
-    hipLaunchKernelGGL(e.fused, dim3((unsigned)S), dim3(64), 0, (hipStream_t)stream, S, codec, d_frames, d_records, d_state, d_rng, d_pcm16,
-                       d_pcmf, d_results, tabs);
-    return launched(c, stream, e);
+static int launch_fused_one(Context* c, const Instance& e, bool reverse, const BatchCall& b, const uint8_t* d_frames) {
+    const mbx::DeviceTables tabs = launch_tables(c, reverse, b);
+    hipLaunchKernelGGL(e.fused, dim3((unsigned)b.S), dim3(64), 0, (hipStream_t)b.stream, b.S, b.codec, d_frames, b.records, b.state, b.rng, b.pcm16,
+                       b.pcmf, b.results, tabs);
+    return launched(c, b.stream, e);
 }
 // caller holds c->mu; the slot's workspace holds S rows and its flags
-static int launch_one_launch(Context* c, const Instance& e, StreamSlot& slot, bool reverse, int S, const uint8_t* d_frames,
-                             mbx_param_record* d_records, mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf,
-                             mbe_process_result* d_results, void* stream, const int32_t* d_stream_index, uint32_t* d_resident) {
-    const mbx::DeviceTables tabs = launch_tables(c, reverse, d_stream_index, d_resident);
+static int launch_one_launch(Context* c, const Instance& e, StreamSlot& slot, bool reverse, const BatchCall& b, const uint8_t* d_frames) {
+    const mbx::DeviceTables tabs = launch_tables(c, reverse, b);
     if (++slot.epoch == 0u) {
         slot.epoch = 1u;
     }
     slot.exp_codec = -1;   // the rows of an earlier mbx_expand_records() are being replaced
-    const unsigned chunks = (unsigned)((S + 7) / 8);
+    const unsigned chunks = (unsigned)((b.S + 7) / 8);
     uint32_t* const fallbacks = slot.flags + (slot.frames + 7) / 8;
     if (e.family == kOneLaunchLeadArgs) {
-        hipLaunchKernelGGL(e.one_launch_lead, dim3(9u * chunks), dim3(64), 0, (hipStream_t)stream, S, front_lead_chunks(), d_frames, d_records,
-                           slot.workspace, slot.flags, fallbacks, slot.epoch, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
+        hipLaunchKernelGGL(e.one_launch_lead, dim3(9u * chunks), dim3(64), 0, (hipStream_t)b.stream, b.S, front_lead_chunks(), d_frames, b.records,
+                           slot.workspace, slot.flags, fallbacks, slot.epoch, b.state, b.rng, b.pcm16, b.pcmf, b.results, tabs);
     } else {
-        hipLaunchKernelGGL(e.one_launch, dim3(9u * chunks), dim3(64), 0, (hipStream_t)stream, S, d_frames, d_records, slot.workspace, slot.flags,
-                           fallbacks, slot.epoch, d_state, d_rng, d_pcm16, d_pcmf, d_results, tabs);
+        hipLaunchKernelGGL(e.one_launch, dim3(9u * chunks), dim3(64), 0, (hipStream_t)b.stream, b.S, d_frames, b.records, slot.workspace, slot.flags,
+                           fallbacks, slot.epoch, b.state, b.rng, b.pcm16, b.pcmf, b.results, tabs);
     }
-    return launched(c, stream, e);
+    return launched(c, b.stream, e);
 }
-// one fused launch if the shape allows it: returns 1 when it was issued (*rc = its status), 0 when the caller goes on with the stages
-static int try_fused_one(int codec, int S, int T, const uint8_t* d_frames, mbx_param_record* d_records, mbe_parms* d_state,
-                         mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, void* stream,
-                         const int32_t* d_stream_index, uint32_t* d_resident, int* rc, bool own_workspace = true) {
-    Shape q{codec, S, T};
-    q.resident = d_resident != nullptr;
+// The one-launch forms of a hard-frame step.  Caller holds c->mu; `own_workspace`: the rows may go through the slot's workspace and
+// flag words.  Returns 1 when a launch was issued (*rc = its status; the slot's launch counter has been bumped), 0 when the
+// caller goes on with the stages.
+static int try_fused_one(Context* c, StreamSlot& slot, const BatchCall& b, const uint8_t* d_frames, bool own_workspace, int* rc) {
+    Shape q{b.codec, b.S, b.T};
+    q.resident = b.resident != nullptr;
     q.frames = true;
     q.aligned = (reinterpret_cast<uintptr_t>(d_frames) & 3u) == 0;
     q.workspace = own_workspace;
@@ -1264,64 +1215,30 @@ static int try_fused_one(int codec, int S, int T, const uint8_t* d_frames, mbx_p
     if (e.family == kStreamArgs) {   // no instance takes the frames of this shape: the staged kernels
         return 0;
     }
-    int crc;
-    Context* c = current_ctx(&crc);
-    if (!c) {
-        *rc = crc;
-        return 1;
-    }
-    if (!d_state || !d_rng) {
-        *rc = MBE_STATUS_INVALID_ARGUMENT;
-        return 1;
-    }
-    std::lock_guard<std::mutex> lock(c->mu);
-    StreamSlot& slot = c->slots[stream];
-    if (e.family != kFusedArgs) {   // the one-launch forms
+    if (e.family != kFusedArgs) {   // rows handed over through the slot's workspace
         // A launch that is being CAPTURED into a graph would be replayed with the same epoch, and a replay would find the flags of
         // the replay before it: captured launches take the staged kernels.
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        const bool capturing = stream && hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+        const bool capturing = b.stream && hipStreamIsCapturing((hipStream_t)b.stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
         (void)hipGetLastError();
         if (capturing) {
             return 0;
         }
-        const int wrc = ensure_workspace(c, slot, (size_t)S, stream);
-        if (wrc < 0) {
-            *rc = wrc;
-            return 1;
+        *rc = ensure_workspace(c, slot, (size_t)b.S, b.stream);
+        if (*rc >= 0) {
+            *rc = launch_one_launch(c, e, slot, (slot.launches++ & 1u) != 0u, b, d_frames);
         }
-        *rc = launch_one_launch(c, e, slot, (slot.launches++ & 1u) != 0u, S, d_frames, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results,
-                                stream, d_stream_index, d_resident);
         return 1;
     }
-    *rc = launch_fused_one(c, e, (slot.launches++ & 1u) != 0u, codec, S, d_frames, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream,
-                           d_stream_index, d_resident);
+    *rc = launch_fused_one(c, e, (slot.launches++ & 1u) != 0u, b, d_frames);
     return 1;
 }
 
-extern "C" int mbx_uses_expand_launch(int codec, int S, int T) { return needs_workspace(codec == MBX_CODEC_IMBE7100X4400 ? MBX_CODEC_IMBE7200X4400 : codec, S, T) ? 1 : 0; }
-
-// expand (where needed) + stream kernel with the workspace at `ws` (nullptr when none is needed); `order` = the launch
-// counter that decides the walking direction
-static int run_stream_stage(Context* c, unsigned order, int codec, int S, int T, const mbx_param_record* d_records,
-                            mbx::FrameParams* ws, mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf,
-                            mbe_process_result* d_results, void* stream, const int32_t* d_stream_index = nullptr,
-                            uint32_t* d_resident = nullptr, StreamSlot* slot = nullptr) {
-    if (needs_workspace(codec, S, T)) {
-        int rc = launch_expand(c, codec, d_records, (size_t)S * (size_t)T, ws, stream);
-        if (rc < 0) {
-            return rc;
-        }
-    } else {
-        ws = nullptr;
-    }
-    return launch_stream(c, (order & 1u) != 0u, codec, S, T, d_records, ws, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream,
-                         d_stream_index, d_resident, slot);
-}
+extern "C" int mbx_uses_expand_launch(int codec, int S, int T) { return needs_workspace(codec, S, T) ? 1 : 0; }
 
 int mbx_expand_records(int codec, const mbx_param_record* d_records, size_t n, void* stream) {
     REQUIRE_CTX(c);
-    if (!d_records || !expand_codec_ok(codec)) {
+    if (!d_records || !mbx::codec_streams(codec)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     if (n == 0) {
@@ -1340,9 +1257,6 @@ int mbx_expand_records(int codec, const mbx_param_record* d_records, size_t n, v
     return rc;
 }
 
-static int stream_expanded(int codec, int S, int T, const mbx_param_record* d_records, mbe_parms* d_state, uint32_t* d_resident,
-                           mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, void* stream);
-
 // The two halves with a CALLER-OWNED workspace, so that they can run on DIFFERENT streams: the frame-parallel front end
 // (FEC + expansion) of batch k + 1 does not depend on the stream stage of batch k, only on the frames -- a host that decodes
 // batch after batch (recorded traffic, many sites) MAY let them overlap and order them with events of its own.  Measured on
@@ -1351,7 +1265,7 @@ static int stream_expanded(int codec, int S, int T, const mbx_param_record* d_re
 int mbx_expand_records_ws(int codec, const mbx_param_record* d_records, size_t n, void* d_workspace, size_t workspace_bytes,
                           void* stream) {
     REQUIRE_CTX(c);
-    if (!d_records || !expand_codec_ok(codec) || !d_workspace || workspace_bytes < mbx_workspace_bytes(n)) {
+    if (!d_records || !mbx::codec_streams(codec) || !d_workspace || workspace_bytes < mbx_workspace_bytes(n)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     if (n == 0) {
@@ -1360,12 +1274,13 @@ int mbx_expand_records_ws(int codec, const mbx_param_record* d_records, size_t n
     return launch_expand(c, codec, d_records, n, static_cast<mbx::FrameParams*>(d_workspace), stream);
 }
 
+// (the records of these calls are read, never written: a BatchCall holds the pointer a front launch would write through)
 int mbx_stream_expanded_ws(int codec, int S, int T, const mbx_param_record* d_records, mbe_parms* d_state, uint32_t* d_resident,
                            mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
                            const void* d_workspace, size_t workspace_bytes, void* stream) {
     REQUIRE_CTX(c);
-    if (!stream_args_ok(codec, S, T, d_records, d_state, d_rng) || !d_workspace
-        || workspace_bytes < mbx_workspace_bytes((size_t)S * (size_t)T)) {
+    const BatchCall b{codec, S, T, const_cast<mbx_param_record*>(d_records), d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, d_resident};
+    if (!call_args_ok(b) || !mbx::codec_streams(codec) || !d_workspace || workspace_bytes < mbx_workspace_bytes((size_t)S * (size_t)T)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     if (S == 0 || T == 0) {
@@ -1376,14 +1291,31 @@ int mbx_stream_expanded_ws(int codec, int S, int T, const mbx_param_record* d_re
         std::lock_guard<std::mutex> lock(c->mu);
         order = c->slots[stream].launches++;
     }
-    return launch_stream(c, (order & 1u) != 0u, codec, S, T, d_records, static_cast<const mbx::FrameParams*>(d_workspace), d_state,
-                         d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, d_resident);
+    return launch_stream(c, (order & 1u) != 0u, b, static_cast<const mbx::FrameParams*>(d_workspace), nullptr);
+}
+
+// the stream stage on the rows the last mbx_expand_records() left in the stream's own workspace
+static int stream_expanded(const BatchCall& b) {
+    REQUIRE_CTX(c);
+    if (!call_args_ok(b) || !mbx::codec_streams(b.codec)) {
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (b.S == 0 || b.T == 0) {
+        return 0;
+    }
+    std::lock_guard<std::mutex> lock(c->mu);
+    StreamSlot& slot = c->slots[b.stream];
+    if (slot.exp_codec != b.codec || slot.exp_n != (size_t)b.S * (size_t)b.T || slot.exp_records != b.records) {
+        return fail(MBE_STATUS_INVALID_ARGUMENT,
+                    "mbx_stream_expanded: the last mbx_expand_records() on this stream was not for this codec / batch / record array");
+    }
+    return launch_stream(c, (slot.launches++ & 1u) != 0u, b, slot.workspace, nullptr);
 }
 
 int mbx_stream_expanded(int codec, int S, int T, const mbx_param_record* d_records, mbe_parms* d_state,
                         mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
                         void* stream) {
-    return stream_expanded(codec, S, T, d_records, d_state, nullptr, d_rng, d_pcm16, d_pcmf, d_results, stream);
+    return stream_expanded({codec, S, T, const_cast<mbx_param_record*>(d_records), d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, nullptr});
 }
 
 // the same on resident state (mbx_process_batch_resident): bench.py brackets the stream kernel alone with it
@@ -1393,108 +1325,124 @@ int mbx_stream_expanded_resident(int codec, int S, int T, const mbx_param_record
     if (!d_resident) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    return stream_expanded(codec, S, T, d_records, d_state, d_resident, d_rng, d_pcm16, d_pcmf, d_results, stream);
+    return stream_expanded({codec, S, T, const_cast<mbx_param_record*>(d_records), d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, d_resident});
 }
 
-static int stream_expanded(int codec, int S, int T, const mbx_param_record* d_records, mbe_parms* d_state, uint32_t* d_resident,
-                           mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, void* stream) {
-    REQUIRE_CTX(c);
-    if (!stream_args_ok(codec, S, T, d_records, d_state, d_rng)) {
+// ---- the batch step ------------------------------------------------------------------------------------------------------------
+// Every batch entry point ends here: it makes the checks that are its own, fills the record and says what the step starts from
+// and whose workspace the FrameParams rows go to.
+//   kRecords: the records are there;  kFrames: packed hard frames, a FEC launch in front -- or the whole T = 1 step as ONE launch
+//   (try_fused_one);  kSoft: soft cells, a soft front launch (one wave per frame) in front.  Codec 2 records come out in 7200x4400
+//   order; codec 3 frames take the AMBE front end and are expanded by the 3600x2400 rules.
+//   caller_ws == nullptr: the stream slot's own workspace, grown here under c->mu, which is then held to the last launch -- the
+//   workspace cannot be grown (freed) by another thread between the launches of this call, and two threads that share one
+//   hipStream_t cannot interleave their steps.  The front launch is issued inside the lock as well.
+//   caller_ws: the caller's rows.  Nothing of the slot is touched but its launch counter, c->mu is held only to read and bump it
+//   (and across the in-wave fused launch of a T = 1 IMBE step, which needs no rows), the launch is never sliced and never one
+//   that needs the slot's flag words: the step can be captured into a graph.
+// The slot goes to launch_stream (sliced launches allowed) whenever the workspace is the slot's own, with resident state too:
+// launch_stream slices only without b.resident, so a resident step is never sliced either way.
+// The launch counter is bumped once per step: by the one-launch form when it issues, otherwise here.
+enum InputKind { kRecords, kFrames, kSoft };
+struct CallerWorkspace {
+    void*  p;
+    size_t bytes;
+};
+// the staged launches of a step: the front launch (where the step has one), expand (where the stream stage reads rows: to `ws`) and the
+// stream kernel; `order` = the launch counter that decides the walking direction; `slot`: see launch_stream
+static int run_stages(Context* c, unsigned order, const BatchCall& b, InputKind kind, const void* d_input, mbx::FrameParams* ws, StreamSlot* slot) {
+    const size_t n = (size_t)b.S * (size_t)b.T;
+    int rc = 0;
+    if (kind == kFrames) {
+        rc = launch_fec(c, b.codec, static_cast<const uint8_t*>(d_input), n, b.records, b.stream);
+    } else if (kind == kSoft) {
+        rc = launch_soft_fec(c, b.codec, true, static_cast<const mbe_soft_bit*>(d_input), n, b.records, b.stream);
+    }
+    if (rc >= 0 && needs_workspace(b.codec, b.S, b.T)) {
+        rc = launch_expand(c, mbx::kCodecs[b.codec].stream, b.records, n, ws, b.stream);
+    } else {
+        ws = nullptr;
+    }
+    return rc < 0 ? rc : launch_stream(c, (order & 1u) != 0u, b, ws, slot);
+}
+static int run_batch(Context* c, const char* who, const BatchCall& b, InputKind kind, const void* d_input, const CallerWorkspace* caller_ws) {
+    const mbx::CodecShape* sh = mbx::codec_shape(b.codec);
+    if (!d_input || !call_args_ok(b) || (kind == kRecords && !mbx::codec_streams(b.codec)) || (kind == kSoft && !sh)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    if (S == 0 || T == 0) {
+    if (b.S == 0 || b.T == 0) {
         return 0;
     }
-    std::lock_guard<std::mutex> lock(c->mu);
-    StreamSlot& slot = c->slots[stream];
-    if (slot.exp_codec != codec || slot.exp_n != (size_t)S * (size_t)T || slot.exp_records != d_records) {
-        return fail(MBE_STATUS_INVALID_ARGUMENT,
-                    "mbx_stream_expanded: the last mbx_expand_records() on this stream was not for this codec / batch / record array");
+    if (!sh) {   // (a hard-frame step has always come to its codec only here, after the empty batch)
+        return MBE_STATUS_INVALID_ARGUMENT;
     }
-    return launch_stream(c, (slot.launches++ & 1u) != 0u, codec, S, T, d_records, slot.workspace, d_state, d_rng, d_pcm16, d_pcmf,
-                         d_results, stream, nullptr, d_resident);
+    const size_t n = (size_t)b.S * (size_t)b.T;
+    char text[128];
+    if (kind == kSoft && n > 0x7fffffffu) {
+        snprintf(text, sizeof(text), "%s: more than 2^31-1 frames in one launch", who);
+        return fail(MBE_STATUS_INVALID_ARGUMENT, text);
+    }
+    const uint8_t* const d_frames = kind == kFrames ? static_cast<const uint8_t*>(d_input) : nullptr;
+    const bool rows = needs_workspace(b.codec, b.S, b.T);
+    int rc = 0;
+    if (caller_ws) {
+        unsigned order;
+        {
+            std::lock_guard<std::mutex> lock(c->mu);
+            StreamSlot& slot = c->slots[b.stream];
+            if (d_frames && try_fused_one(c, slot, b, d_frames, false, &rc)) {
+                return rc;
+            }
+            if (rows && (!caller_ws->p || caller_ws->bytes < mbx_workspace_bytes(n))) {
+                snprintf(text, sizeof(text), "%s: workspace missing or smaller than mbx_workspace_bytes(S*T)", who);
+                return fail(MBE_STATUS_INVALID_ARGUMENT, text);
+            }
+            order = slot.launches++;
+        }
+        return run_stages(c, order, b, kind, d_input, static_cast<mbx::FrameParams*>(caller_ws->p), nullptr);
+    }
+    std::lock_guard<std::mutex> lock(c->mu);
+    StreamSlot& slot = c->slots[b.stream];
+    if (d_frames && try_fused_one(c, slot, b, d_frames, true, &rc)) {
+        return rc;
+    }
+    if (rows) {
+        rc = ensure_workspace(c, slot, n, b.stream);
+        if (rc < 0) {
+            return rc;
+        }
+        slot.exp_codec = -1;   // the rows are about to be replaced
+    }
+    return run_stages(c, slot.launches++, b, kind, d_input, slot.workspace, &slot);
 }
 
 int mbx_process_records(int codec, int S, int T, const mbx_param_record* d_records, mbe_parms* d_state,
                         mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
                         void* stream) {
     REQUIRE_CTX(c);
-    if (!stream_args_ok(codec, S, T, d_records, d_state, d_rng)) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (S == 0 || T == 0) {
-        return 0;
-    }
-    // The lock is held across the launches of this call: the workspace of `stream` cannot be grown (freed) by another
-    // thread between the expand launch and the stream launch, and two threads that share one hipStream_t cannot
-    // interleave their expand / stream pairs.
-    std::lock_guard<std::mutex> lock(c->mu);
-    StreamSlot& slot = c->slots[stream];
-    if (needs_workspace(codec, S, T)) {
-        int rc = ensure_workspace(c, slot, (size_t)S * (size_t)T, stream);
-        if (rc < 0) {
-            return rc;
-        }
-        slot.exp_codec = -1;   // the rows are about to be replaced
-    }
-    return run_stream_stage(c, slot.launches++, codec, S, T, d_records, slot.workspace, d_state, d_rng, d_pcm16, d_pcmf, d_results,
-                            stream, nullptr, nullptr, &slot);
+    const BatchCall b{codec, S, T, const_cast<mbx_param_record*>(d_records), d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, nullptr};
+    return run_batch(c, "mbx_process_records", b, kRecords, d_records, nullptr);
 }
 
 int mbx_process_records_ws(int codec, int S, int T, const mbx_param_record* d_records, mbe_parms* d_state,
                            mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
                            void* d_workspace, size_t workspace_bytes, void* stream) {
     REQUIRE_CTX(c);
-    if (!stream_args_ok(codec, S, T, d_records, d_state, d_rng)) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (S == 0 || T == 0) {
-        return 0;
-    }
-    if (needs_workspace(codec, S, T) && (!d_workspace || workspace_bytes < mbx_workspace_bytes((size_t)S * (size_t)T))) {
-        return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_process_records_ws: workspace missing or smaller than mbx_workspace_bytes(S*T)");
-    }
-    unsigned order;
-    {
-        std::lock_guard<std::mutex> lock(c->mu);
-        order = c->slots[stream].launches++;
-    }
-    return run_stream_stage(c, order, codec, S, T, d_records, static_cast<mbx::FrameParams*>(d_workspace), d_state, d_rng, d_pcm16,
-                            d_pcmf, d_results, stream);
+    const BatchCall b{codec, S, T, const_cast<mbx_param_record*>(d_records), d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, nullptr};
+    const CallerWorkspace ws{d_workspace, workspace_bytes};
+    return run_batch(c, "mbx_process_records_ws", b, kRecords, d_records, &ws);
 }
 
-// FEC stage of a hard-decision batch; *stream_codec = the codec of the stream stage that follows
-static int launch_fec(int codec, const uint8_t* d_frames, size_t n, mbx_param_record* d_records, void* stream, int* stream_codec) {
-    *stream_codec = codec;
-    if (codec == MBX_CODEC_IMBE7200X4400) {
-        return mbx_fec_imbe7200x4400(d_frames, n, d_records, stream);
-    }
-    if (codec == MBX_CODEC_IMBE7100X4400) {   // own front end; the records are in 7200x4400 order
-        *stream_codec = MBX_CODEC_IMBE7200X4400;
-        return mbx_fec_imbe7100x4400(d_frames, n, d_records, stream);
-    }
-    if (codec == MBX_CODEC_AMBE3600X2450 || codec == MBX_CODEC_AMBE3600X2400) {   // shared AMBE FEC front end
-        return mbx_fec_ambe3600x2450(d_frames, n, d_records, stream);
-    }
-    return MBE_STATUS_INVALID_ARGUMENT;
-}
-
+// (mbx_process_batch and its _ws form refuse what they can before they ask for a context; the other batch calls ask first)
 int mbx_process_batch(int codec, int S, int T, const uint8_t* d_frames, mbe_parms* d_state, mbx_stream_rng* d_rng,
                       int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records,
                       void* stream) {
-    if (!d_frames || !d_records || S < 0 || T < 0) {
+    if (!d_frames || !d_records || S < 0 || T < 0 || !mbx::codec_shape(codec)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    int stream_codec;
-    int rc;
-    if (try_fused_one(codec, S, T, d_frames, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, nullptr, &rc)) {
-        return rc;
-    }
-    rc = launch_fec(codec, d_frames, (size_t)S * (size_t)T, d_records, stream, &stream_codec);
-    if (rc < 0) {
-        return rc;
-    }
-    return mbx_process_records(stream_codec, S, T, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream);
+    REQUIRE_CTX(c);
+    const BatchCall b{codec, S, T, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, nullptr};
+    return run_batch(c, "mbx_process_batch", b, kFrames, d_frames, nullptr);
 }
 
 int mbx_stage_in(void* d_dst, const void* pinned_src, size_t bytes, void* stream) {
@@ -1513,33 +1461,31 @@ int mbx_stage_in(void* d_dst, const void* pinned_src, size_t bytes, void* stream
     return check_launch("stage_in_kernel");
 }
 
-static int launch_frame(int codec, const uint8_t* d_frame, mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf,
-                        mbe_process_result* d_result, mbx_param_record* d_record, uint32_t* d_done, uint32_t token, void* stream,
-                        const mbx::FrameShadow& shadow) {
+// one frame of one stream (b.S = b.T = 1) as one launch of one wavefront
+static int launch_frame(const BatchCall& b, const uint8_t* d_frame, uint32_t* d_done, uint32_t token, const mbx::FrameShadow& shadow) {
     REQUIRE_CTX(c);
-    if (!d_frame || !d_state || !d_rng || !d_record || codec < MBX_CODEC_IMBE7200X4400 || codec > MBX_CODEC_AMBE3600X2400) {
+    if (!d_frame || !call_args_ok(b) || !mbx::codec_shape(b.codec)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    mbx::DeviceTables tabs = c->tabs;
-    tabs.reverse = 0;
-    tabs.stream_map = nullptr;
-    tabs.resident = nullptr;
-    if (codec == MBX_CODEC_IMBE7200X4400 || codec == MBX_CODEC_IMBE7100X4400) {
-        hipLaunchKernelGGL(mbx::imbe_frame_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, codec, d_frame, d_record, d_state, d_rng,
-                           d_pcm16, d_pcmf, d_result, d_done, token, tabs, shadow);
-    } else if (codec == MBX_CODEC_AMBE3600X2400) {
-        hipLaunchKernelGGL(mbx::ambe2400_frame_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_frame, d_record, d_state, d_rng,
-                           d_pcm16, d_pcmf, d_result, d_done, token, tabs, shadow);
+    const mbx::DeviceTables tabs = launch_tables(c, false, b);
+    const hipStream_t stream = (hipStream_t)b.stream;
+    if (imbe_codec(b.codec)) {
+        hipLaunchKernelGGL(mbx::imbe_frame_kernel, dim3(1), dim3(64), 0, stream, b.codec, d_frame, b.records, b.state, b.rng, b.pcm16, b.pcmf,
+                           b.results, d_done, token, tabs, shadow);
+    } else if (b.codec == MBX_CODEC_AMBE3600X2400) {
+        hipLaunchKernelGGL(mbx::ambe2400_frame_kernel, dim3(1), dim3(64), 0, stream, d_frame, b.records, b.state, b.rng, b.pcm16, b.pcmf,
+                           b.results, d_done, token, tabs, shadow);
     } else {
-        hipLaunchKernelGGL(mbx::ambe_frame_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_frame, d_record, d_state, d_rng, d_pcm16,
-                           d_pcmf, d_result, d_done, token, tabs, shadow);
+        hipLaunchKernelGGL(mbx::ambe_frame_kernel, dim3(1), dim3(64), 0, stream, d_frame, b.records, b.state, b.rng, b.pcm16, b.pcmf, b.results,
+                           d_done, token, tabs, shadow);
     }
     return check_launch("frame_kernel");
 }
 
 int mbx_process_frame(int codec, const uint8_t* d_frame, mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf,
                       mbe_process_result* d_result, mbx_param_record* d_record, uint32_t* d_done, uint32_t token, void* stream) {
-    return launch_frame(codec, d_frame, d_state, d_rng, d_pcm16, d_pcmf, d_result, d_record, d_done, token, stream, mbx::FrameShadow{});
+    return launch_frame({codec, 1, 1, d_record, d_state, d_rng, d_pcm16, d_pcmf, d_result, stream, nullptr, nullptr}, d_frame, d_done, token,
+                        mbx::FrameShadow{});
 }
 
 int mbx_process_frame_shadow(int codec, const uint8_t* d_frame, mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf,
@@ -1554,12 +1500,12 @@ int mbx_process_frame_shadow(int codec, const uint8_t* d_frame, mbe_parms* d_sta
     shadow.rng = d_shadow_rng;
     shadow.ok = d_shadow_ok;
     shadow.use = use_shadow ? 1u : 0u;
-    if (h_frame) {   // the frame's bytes travel with the launch
-        const size_t nb = (codec == MBX_CODEC_IMBE7200X4400 || codec == MBX_CODEC_IMBE7100X4400) ? 18u : 9u;
-        memcpy(shadow.frame_words, h_frame, nb);
+    const mbx::CodecShape* sh = mbx::codec_shape(codec);
+    if (h_frame && sh) {   // the frame's bytes travel with the launch (no such codec: launch_frame refuses the call)
+        memcpy(shadow.frame_words, h_frame, (size_t)sh->frame_bytes);
         shadow.have_frame = 1u;
     }
-    return launch_frame(codec, d_frame, d_state, d_rng, d_pcm16, d_pcmf, d_result, d_record, d_done, token, stream, shadow);
+    return launch_frame({codec, 1, 1, d_record, d_state, d_rng, d_pcm16, d_pcmf, d_result, stream, nullptr, nullptr}, d_frame, d_done, token, shadow);
 }
 
 int mbx_frame_server_start(mbx_frame_mailbox* mailbox, unsigned idle_us, mbe_parms* d_state, mbx_stream_rng* d_rng, int16_t* d_pcm16,
@@ -1586,53 +1532,24 @@ int mbx_frame_server_start(mbx_frame_mailbox* mailbox, unsigned idle_us, mbe_par
 int mbx_process_batch_ws(int codec, int S, int T, const uint8_t* d_frames, mbe_parms* d_state, mbx_stream_rng* d_rng,
                          int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records,
                          void* d_workspace, size_t workspace_bytes, void* stream) {
-    if (!d_frames || !d_records || S < 0 || T < 0) {
+    if (!d_frames || !d_records || S < 0 || T < 0 || !mbx::codec_shape(codec)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    int stream_codec;
-    int rc;
-    if (try_fused_one(codec, S, T, d_frames, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, nullptr, &rc, false)) {
-        return rc;   // (the form that needs no workspace: the caller's has no flag words)
-    }
-    rc = launch_fec(codec, d_frames, (size_t)S * (size_t)T, d_records, stream, &stream_codec);
-    if (rc < 0) {
-        return rc;
-    }
-    return mbx_process_records_ws(stream_codec, S, T, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, d_workspace,
-                                  workspace_bytes, stream);
+    REQUIRE_CTX(c);
+    const BatchCall b{codec, S, T, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, nullptr};
+    const CallerWorkspace ws{d_workspace, workspace_bytes};
+    return run_batch(c, "mbx_process_batch_ws", b, kFrames, d_frames, &ws);
 }
 
 int mbx_process_batch_indexed(int codec, int S, int T, const int32_t* d_stream_index, const uint8_t* d_frames,
                               mbe_parms* d_state_pool, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf,
                               mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
     REQUIRE_CTX(c);
-    if (!d_frames || !d_records || !d_stream_index || !d_state_pool || !d_rng_pool || S < 0 || T < 0) {
+    if (!d_stream_index) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    if (S == 0 || T == 0) {
-        return 0;
-    }
-    int stream_codec;
-    int rc;
-    if (try_fused_one(codec, S, T, d_frames, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index, nullptr,
-                      &rc)) {
-        return rc;
-    }
-    rc = launch_fec(codec, d_frames, (size_t)S * (size_t)T, d_records, stream, &stream_codec);
-    if (rc < 0) {
-        return rc;
-    }
-    std::lock_guard<std::mutex> lock(c->mu);
-    StreamSlot& slot = c->slots[stream];
-    if (needs_workspace(stream_codec, S, T)) {
-        rc = ensure_workspace(c, slot, (size_t)S * (size_t)T, stream);
-        if (rc < 0) {
-            return rc;
-        }
-        slot.exp_codec = -1;
-    }
-    return run_stream_stage(c, slot.launches++, stream_codec, S, T, d_records, slot.workspace, d_state_pool, d_rng_pool, d_pcm16,
-                            d_pcmf, d_results, stream, d_stream_index, nullptr, &slot);
+    const BatchCall b{codec, S, T, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index, nullptr};
+    return run_batch(c, "mbx_process_batch_indexed", b, kFrames, d_frames, nullptr);
 }
 
 // ---- resident state (sessions, queue mode) ------------------------------------------------------------------------------
@@ -1647,33 +1564,11 @@ int mbx_process_batch_resident(int codec, int S, int T, const int32_t* d_stream_
                                mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16,
                                float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
     REQUIRE_CTX(c);
-    if (!d_frames || !d_records || !d_state_pool || !d_resident || !d_rng_pool || S < 0 || T < 0) {
+    if (!d_resident) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    if (S == 0 || T == 0) {
-        return 0;
-    }
-    int stream_codec;
-    int rc;
-    if (try_fused_one(codec, S, T, d_frames, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index,
-                      d_resident, &rc)) {
-        return rc;
-    }
-    rc = launch_fec(codec, d_frames, (size_t)S * (size_t)T, d_records, stream, &stream_codec);
-    if (rc < 0) {
-        return rc;
-    }
-    std::lock_guard<std::mutex> lock(c->mu);
-    StreamSlot& slot = c->slots[stream];
-    if (needs_workspace(stream_codec, S, T)) {
-        rc = ensure_workspace(c, slot, (size_t)S * (size_t)T, stream);
-        if (rc < 0) {
-            return rc;
-        }
-        slot.exp_codec = -1;
-    }
-    return run_stream_stage(c, slot.launches++, stream_codec, S, T, d_records, slot.workspace, d_state_pool, d_rng_pool, d_pcm16,
-                            d_pcmf, d_results, stream, d_stream_index, d_resident);
+    const BatchCall b{codec, S, T, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index, d_resident};
+    return run_batch(c, "mbx_process_batch_resident", b, kFrames, d_frames, nullptr);
 }
 
 namespace mbx {
@@ -1713,79 +1608,31 @@ int mbx_resident_materialize(int n, const int32_t* d_stream_index, mbe_parms* d_
     return check_launch("resident_materialize_kernel");
 }
 
-// ---- soft-decision batches ------------------------------------------------------------------------------------------------------
-// A soft front launch (mbx_soft_front.hip: one wave per frame, soft cells -> record), then the stream stage exactly as for records
-// from anywhere else: the expand launch where the stream stage reads rows, and the instance launch_stream() picks for the shape.
-// Codec 2 records come out in 7200x4400 order; codec 3 frames are searched as AMBE cells and expanded by the 3600x2400 rules.
-// caller_ws: the rows go to d_workspace (nothing of the stream's slot is touched: the launches can be captured into a graph);
-// otherwise to the stream's own workspace, grown under the lock that also covers both launches
-static int soft_batch(int codec, int S, int T, const int32_t* d_stream_index, const mbe_soft_bit* d_soft, mbe_parms* d_state,
-                      uint32_t* d_resident, mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
-                      mbx_param_record* d_records, bool caller_ws, void* d_workspace, size_t workspace_bytes, void* stream) {
-    REQUIRE_CTX(c);
-    if (!d_soft || !d_records || !d_state || !d_rng || S < 0 || T < 0 || codec < MBX_CODEC_IMBE7200X4400
-        || codec > MBX_CODEC_AMBE3600X2400) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (S == 0 || T == 0) {
-        return 0;
-    }
-    const size_t n = (size_t)S * (size_t)T;
-    if (n > 0x7fffffffu) {
-        return fail(MBE_STATUS_INVALID_ARGUMENT, "soft batch: more than 2^31-1 frames in one launch");
-    }
-    const int stream_codec = codec == MBX_CODEC_IMBE7100X4400 ? MBX_CODEC_IMBE7200X4400 : codec;
-    const bool rows = needs_workspace(stream_codec, S, T);
-    auto step = [&](unsigned order, mbx::FrameParams* ws, StreamSlot* slot) {   // front, then expand (where needed) + stream with the workspace at ws
-        const int rc = launch_soft_front(c, codec, d_soft, n, d_records, stream);
-        if (rc < 0) {
-            return rc;
-        }
-        return run_stream_stage(c, order, stream_codec, S, T, d_records, ws, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream,
-                                d_stream_index, d_resident, slot);
-    };
-    if (caller_ws) {
-        if (rows && (!d_workspace || workspace_bytes < mbx_workspace_bytes(n))) {
-            return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_process_batch_soft_ws: workspace missing or smaller than mbx_workspace_bytes(S*T)");
-        }
-        unsigned order;
-        {
-            std::lock_guard<std::mutex> lock(c->mu);
-            order = c->slots[stream].launches++;
-        }
-        return step(order, static_cast<mbx::FrameParams*>(d_workspace), nullptr);
-    }
-    std::lock_guard<std::mutex> lock(c->mu);
-    StreamSlot& slot = c->slots[stream];
-    if (rows) {
-        const int rc = ensure_workspace(c, slot, n, stream);
-        if (rc < 0) {
-            return rc;
-        }
-        slot.exp_codec = -1;   // the rows are about to be replaced
-    }
-    return step(slot.launches++, slot.workspace, &slot);
-}
-
+// ---- soft-decision batches: run_batch with kSoft ------------------------------------------------------------------------------------
 int mbx_process_batch_soft(int codec, int S, int T, const mbe_soft_bit* d_soft, mbe_parms* d_state, mbx_stream_rng* d_rng,
                            int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records,
                            void* stream) {
-    return soft_batch(codec, S, T, nullptr, d_soft, d_state, nullptr, d_rng, d_pcm16, d_pcmf, d_results, d_records, false, nullptr, 0,
-                      stream);
+    REQUIRE_CTX(c);
+    const BatchCall b{codec, S, T, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, nullptr};
+    return run_batch(c, "mbx_process_batch_soft", b, kSoft, d_soft, nullptr);
 }
 
 int mbx_process_batch_soft_ws(int codec, int S, int T, const mbe_soft_bit* d_soft, mbe_parms* d_state, mbx_stream_rng* d_rng,
                               int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records,
                               void* d_workspace, size_t workspace_bytes, void* stream) {
-    return soft_batch(codec, S, T, nullptr, d_soft, d_state, nullptr, d_rng, d_pcm16, d_pcmf, d_results, d_records, true, d_workspace,
-                      workspace_bytes, stream);
+    REQUIRE_CTX(c);
+    const BatchCall b{codec, S, T, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, nullptr};
+    const CallerWorkspace ws{d_workspace, workspace_bytes};
+    return run_batch(c, "mbx_process_batch_soft_ws", b, kSoft, d_soft, &ws);
 }
 
+// (index NULL = identity, d_resident NULL = plain triplets: nothing here that is this export's own to refuse)
 int mbx_process_batch_soft_resident(int codec, int S, int T, const int32_t* d_stream_index, const mbe_soft_bit* d_soft,
                                     mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16,
                                     float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
-    return soft_batch(codec, S, T, d_stream_index, d_soft, d_state_pool, d_resident, d_rng_pool, d_pcm16, d_pcmf, d_results, d_records,
-                      false, nullptr, 0, stream);
+    REQUIRE_CTX(c);
+    const BatchCall b{codec, S, T, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index, d_resident};
+    return run_batch(c, "mbx_process_batch_soft_resident", b, kSoft, d_soft, nullptr);
 }
 
 int mbx_synthesize_speech(int S, mbe_parms* d_cur, mbe_parms* d_prev, mbx_stream_rng* d_rng, float* d_pcmf,
@@ -1919,7 +1766,7 @@ void mbx_debug_set_ablation(int mask) {
 int mbx_pack_cells(int codec, const char* d_cells, size_t n, uint8_t* d_packed, int32_t* d_status, void* stream) {
     REQUIRE_CTX(c);
     (void)c;
-    if (!d_cells || !d_packed || codec < MBX_CODEC_IMBE7200X4400 || codec > MBX_CODEC_AMBE3600X2400) {
+    if (!d_cells || !d_packed || !mbx::codec_shape(codec)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     if (n == 0) {
@@ -1932,7 +1779,7 @@ int mbx_pack_cells(int codec, const char* d_cells, size_t n, uint8_t* d_packed, 
 
 int mbx_fec_stage(int codec, int stage, const void* d_in, size_t n, uint8_t* d_frames_out, mbx_param_record* d_out, void* stream) {
     REQUIRE_CTX(c);
-    if (!d_in || codec < MBX_CODEC_IMBE7200X4400 || codec > MBX_CODEC_AMBE3600X2400
+    if (!d_in || !mbx::codec_shape(codec)
         || !(stage == MBX_STAGE_C0 || stage == MBX_STAGE_DEMODULATE || stage == MBX_STAGE_DATA || stage == MBX_STAGE_CONVERT7100)
         || ((stage == MBX_STAGE_DATA || stage == MBX_STAGE_CONVERT7100) && !d_out)
         || ((stage == MBX_STAGE_C0 || stage == MBX_STAGE_DEMODULATE) && !d_frames_out)) {
@@ -1949,7 +1796,7 @@ int mbx_fec_stage(int codec, int stage, const void* d_in, size_t n, uint8_t* d_f
 int mbx_decode_parms(int codec, const mbx_param_record* d_records, size_t n, mbe_parms* d_cur, mbe_parms* d_prev, int32_t* d_rc,
                      void* stream) {
     REQUIRE_CTX(c);
-    if (!d_records || !d_cur || !d_prev || !d_rc || !expand_codec_ok(codec) || n > 0x7fffffffu) {
+    if (!d_records || !d_cur || !d_prev || !d_rc || !mbx::codec_streams(codec) || n > 0x7fffffffu) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     if (n == 0) {
@@ -2028,8 +1875,7 @@ int mbx_launch_slices(int codec, int S, int T) {
     if (!c || !(T >= kLdsResidentMinFrames && lds_resident_enabled())) {
         return 0;
     }
-    const int sc = codec == MBX_CODEC_IMBE7100X4400 ? MBX_CODEC_IMBE7200X4400 : codec;
-    return choose_slice_frames(S, T, lds_kernel_waves_per_simd(sc) * c->simds);
+    return choose_slice_frames(S, T, stream_kernels(codec).lds_waves * c->simds);
 }
 
 // the dominant kernel of mbx_process_batch / _resident for a batch shape (frames 4-byte aligned, as device allocations are; a launch
@@ -2055,19 +1901,16 @@ const char* mbx_stream_kernel_name(int codec, int T) {
 
 int mbx_fec_host(int codec, const uint8_t* frames, size_t n, mbx_param_record* records) {
     REQUIRE_CTX(c);
-    if (!frames || !records) {
+    const mbx::CodecShape* sh = mbx::codec_shape(codec);
+    if (!frames || !records || !sh) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    const size_t fb = (codec == MBX_CODEC_AMBE3600X2450 || codec == MBX_CODEC_AMBE3600X2400) ? MBX_AMBE_FRAME_BYTES : MBX_IMBE_FRAME_BYTES;
+    const size_t fb = (size_t)sh->frame_bytes;
     DevBuf df, dr;
     HIP_TRY(df.alloc(n * fb));
     HIP_TRY(dr.alloc(n * sizeof(mbx_param_record)));
     HIP_TRY(hipMemcpy(df.p, frames, n * fb, hipMemcpyHostToDevice));
-    int rc = (codec == MBX_CODEC_IMBE7200X4400)   ? mbx_fec_imbe7200x4400(df.as<uint8_t>(), n, dr.as<mbx_param_record>(), nullptr)
-             : (codec == MBX_CODEC_IMBE7100X4400) ? mbx_fec_imbe7100x4400(df.as<uint8_t>(), n, dr.as<mbx_param_record>(), nullptr)
-             : (codec == MBX_CODEC_AMBE3600X2450 || codec == MBX_CODEC_AMBE3600X2400)
-                 ? mbx_fec_ambe3600x2450(df.as<uint8_t>(), n, dr.as<mbx_param_record>(), nullptr)
-                 : MBE_STATUS_INVALID_ARGUMENT;
+    const int rc = n == 0 ? 0 : launch_fec(c, codec, df.as<uint8_t>(), n, dr.as<mbx_param_record>(), nullptr);
     if (rc < 0) {
         return rc;
     }
@@ -2075,14 +1918,10 @@ int mbx_fec_host(int codec, const uint8_t* frames, size_t n, mbx_param_record* r
     return 0;
 }
 
-static size_t soft_cells(int codec) {
-    return codec == MBX_CODEC_IMBE7200X4400 ? MBX_IMBE_SOFT_BITS : (codec == MBX_CODEC_IMBE7100X4400 ? MBX_IMBE7100_SOFT_BITS : MBX_AMBE_SOFT_BITS);   // both AMBE codecs: 96
-}
-
-// frames in (hard: packed bytes, soft: mbe_soft_bit arrays), everything else as mbx_process_batch
-static int process_batch_host_impl(int codec, int S, int T, const void* frames, size_t frame_bytes, bool soft, mbe_parms* state,
-                                   mbx_stream_rng* rng, int16_t* pcm16, float* pcmf, mbe_process_result* results,
-                                   mbx_param_record* records) {
+// `h`: a batch call whose pointers are HOST buffers (records / pcm16 / pcmf / results may be NULL: not wanted); frames in (hard: packed
+// bytes, soft: mbe_soft_bit arrays), everything else as mbx_process_batch
+static int process_batch_host_impl(const BatchCall& h, const void* frames, size_t frame_bytes, bool soft) {
+    const int codec = h.codec, S = h.S, T = h.T;
     const size_t n = (size_t)S * (size_t)T;
     DevBuf df, ds, dg, d16, dfl, dres, drec;
     HIP_TRY(df.alloc(n * frame_bytes));
@@ -2093,31 +1932,31 @@ static int process_batch_host_impl(int codec, int S, int T, const void* frames, 
     HIP_TRY(dres.alloc(n * sizeof(mbe_process_result)));
     HIP_TRY(drec.alloc(n * sizeof(mbx_param_record)));
     HIP_TRY(hipMemcpy(df.p, frames, n * frame_bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(ds.p, state, (size_t)S * 3 * sizeof(mbe_parms), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dg.p, rng, (size_t)S * sizeof(mbx_stream_rng), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ds.p, h.state, (size_t)S * 3 * sizeof(mbe_parms), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dg.p, h.rng, (size_t)S * sizeof(mbx_stream_rng), hipMemcpyHostToDevice));
     int rc = soft ? mbx_process_batch_soft(codec, S, T, df.as<mbe_soft_bit>(), ds.as<mbe_parms>(), dg.as<mbx_stream_rng>(),
-                                           pcm16 ? d16.as<int16_t>() : nullptr, pcmf ? dfl.as<float>() : nullptr,
-                                           results ? dres.as<mbe_process_result>() : nullptr, drec.as<mbx_param_record>(), nullptr)
+                                           h.pcm16 ? d16.as<int16_t>() : nullptr, h.pcmf ? dfl.as<float>() : nullptr,
+                                           h.results ? dres.as<mbe_process_result>() : nullptr, drec.as<mbx_param_record>(), nullptr)
                   : mbx_process_batch(codec, S, T, df.as<uint8_t>(), ds.as<mbe_parms>(), dg.as<mbx_stream_rng>(),
-                                      pcm16 ? d16.as<int16_t>() : nullptr, pcmf ? dfl.as<float>() : nullptr,
-                                      results ? dres.as<mbe_process_result>() : nullptr, drec.as<mbx_param_record>(), nullptr);
+                                      h.pcm16 ? d16.as<int16_t>() : nullptr, h.pcmf ? dfl.as<float>() : nullptr,
+                                      h.results ? dres.as<mbe_process_result>() : nullptr, drec.as<mbx_param_record>(), nullptr);
     if (rc < 0) {
         return rc;
     }
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(state, ds.p, (size_t)S * 3 * sizeof(mbe_parms), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rng, dg.p, (size_t)S * sizeof(mbx_stream_rng), hipMemcpyDeviceToHost));
-    if (pcm16) {
-        HIP_TRY(hipMemcpy(pcm16, d16.p, n * 160 * sizeof(int16_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h.state, ds.p, (size_t)S * 3 * sizeof(mbe_parms), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h.rng, dg.p, (size_t)S * sizeof(mbx_stream_rng), hipMemcpyDeviceToHost));
+    if (h.pcm16) {
+        HIP_TRY(hipMemcpy(h.pcm16, d16.p, n * 160 * sizeof(int16_t), hipMemcpyDeviceToHost));
     }
-    if (pcmf) {
-        HIP_TRY(hipMemcpy(pcmf, dfl.p, n * 160 * sizeof(float), hipMemcpyDeviceToHost));
+    if (h.pcmf) {
+        HIP_TRY(hipMemcpy(h.pcmf, dfl.p, n * 160 * sizeof(float), hipMemcpyDeviceToHost));
     }
-    if (results) {
-        HIP_TRY(hipMemcpy(results, dres.p, n * sizeof(mbe_process_result), hipMemcpyDeviceToHost));
+    if (h.results) {
+        HIP_TRY(hipMemcpy(h.results, dres.p, n * sizeof(mbe_process_result), hipMemcpyDeviceToHost));
     }
-    if (records) {
-        HIP_TRY(hipMemcpy(records, drec.p, n * sizeof(mbx_param_record), hipMemcpyDeviceToHost));
+    if (h.records) {
+        HIP_TRY(hipMemcpy(h.records, drec.p, n * sizeof(mbx_param_record), hipMemcpyDeviceToHost));
     }
     return 0;
 }
@@ -2125,34 +1964,37 @@ static int process_batch_host_impl(int codec, int S, int T, const void* frames, 
 int mbx_process_batch_host(int codec, int S, int T, const uint8_t* frames, mbe_parms* state, mbx_stream_rng* rng,
                            int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records) {
     REQUIRE_CTX(c);
-    if (!frames || !state || !rng || S < 0 || T < 0) {
+    const mbx::CodecShape* sh = mbx::codec_shape(codec);
+    if (!frames || !state || !rng || S < 0 || T < 0 || !sh) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    const size_t fb = (codec == MBX_CODEC_AMBE3600X2450 || codec == MBX_CODEC_AMBE3600X2400) ? MBX_AMBE_FRAME_BYTES : MBX_IMBE_FRAME_BYTES;
-    return process_batch_host_impl(codec, S, T, frames, fb, false, state, rng, pcm16, pcmf, results, records);
+    return process_batch_host_impl({codec, S, T, records, state, rng, pcm16, pcmf, results, nullptr, nullptr, nullptr}, frames,
+                                   (size_t)sh->frame_bytes, false);
 }
 
 int mbx_process_batch_soft_host(int codec, int S, int T, const mbe_soft_bit* soft, mbe_parms* state, mbx_stream_rng* rng,
                                 int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records) {
     REQUIRE_CTX(c);
-    if (!soft || !state || !rng || S < 0 || T < 0) {
+    const mbx::CodecShape* sh = mbx::codec_shape(codec);
+    if (!soft || !state || !rng || S < 0 || T < 0 || !sh) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    const size_t cells = soft_cells(codec);
+    const size_t cells = (size_t)sh->cells;
     int rc = mbx_validate_soft_bits(soft, (size_t)S * (size_t)T * cells);
     if (rc < 0) {
         return rc;
     }
-    return process_batch_host_impl(codec, S, T, soft, cells * sizeof(mbe_soft_bit), true, state, rng, pcm16, pcmf, results,
-                                   records);
+    return process_batch_host_impl({codec, S, T, records, state, rng, pcm16, pcmf, results, nullptr, nullptr, nullptr}, soft,
+                                   cells * sizeof(mbe_soft_bit), true);
 }
 
 int mbx_fec_soft_host(int codec, const mbe_soft_bit* soft, size_t n, mbx_param_record* records) {
     REQUIRE_CTX(c);
-    if (!soft || !records) {
+    const mbx::CodecShape* sh = mbx::codec_shape(codec);
+    if (!soft || !records || !sh) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    const size_t cells = soft_cells(codec);
+    const size_t cells = (size_t)sh->cells;
     int rc = mbx_validate_soft_bits(soft, n * cells);
     if (rc < 0) {
         return rc;

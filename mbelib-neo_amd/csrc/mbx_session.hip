@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "mbx.h"
+#include "mbx_codec.h"
 
 void mbx_set_error_text(const char* text);   // mbx_api.hip: the per-thread text behind mbx_last_error()
 
@@ -326,7 +327,8 @@ void mbx_host_free(void* p) {
 }
 
 int mbx_session_create(mbx_session** out, int codec, int streams, size_t max_frames_per_submit, unsigned outputs) {
-    if (!out || streams <= 0 || max_frames_per_submit == 0 || codec < MBX_CODEC_IMBE7200X4400 || codec > MBX_CODEC_AMBE3600X2400
+    const mbx::CodecShape* shape = mbx::codec_shape(codec);
+    if (!out || streams <= 0 || max_frames_per_submit == 0 || !shape
         || (outputs & ~(MBX_SESSION_PCM16 | MBX_SESSION_PCMF | MBX_SESSION_RESULTS)) != 0u) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
@@ -345,10 +347,8 @@ int mbx_session_create(mbx_session** out, int codec, int streams, size_t max_fra
     s->streams = streams;
     s->max_frames = max_frames_per_submit;
     s->outputs = outputs ? outputs : MBX_SESSION_PCM16;
-    s->frame_bytes = (codec == MBX_CODEC_AMBE3600X2450 || codec == MBX_CODEC_AMBE3600X2400) ? MBX_AMBE_FRAME_BYTES : MBX_IMBE_FRAME_BYTES;
-    s->soft_bytes = sizeof(mbe_soft_bit) * (codec == MBX_CODEC_IMBE7200X4400   ? (size_t)MBX_IMBE_SOFT_BITS
-                                            : codec == MBX_CODEC_IMBE7100X4400 ? (size_t)MBX_IMBE7100_SOFT_BITS
-                                                                               : (size_t)MBX_AMBE_SOFT_BITS);
+    s->frame_bytes = (size_t)shape->frame_bytes;
+    s->soft_bytes = sizeof(mbe_soft_bit) * (size_t)shape->cells;
     *out = s;
     auto bail = [&](int rc) {
         mbx_session_destroy(s);

@@ -90,6 +90,50 @@ def test_every_table_row_has_an_oracle_case_and_every_case_switch_is_one_the_lib
     assert any(c.entry.endswith("_indexed") for c in instance_cases.CASES)
 
 
+def test_the_codec_table_is_the_only_place_the_frame_shapes_are_written(oracle):
+    """csrc/mbx_codec.h declares what a codec is, once, for the launcher, the sessions and the mbe_* shim.  Each of the three
+    row-width lists occurs in it exactly once and in no other host source of csrc/ (the device kernels of mbx_fec.hip unpack the
+    rows with widths of their own: device code does not read the host table), and what the table says is what
+    mbelib-neo_amd/layout.py says -- asked of the library through mbx_wire_bit_of_cell and the packers, not by parsing C."""
+    from mbelib_neo_amd import _native
+    from mbelib_neo_amd.layout import FRAME_BYTES, FRAME_CELLS, PARAM_BITS, ROW_WIDTHS
+
+    csrc = os.path.join(ROOT, "mbelib-neo_amd", "csrc")
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".cpp"))}
+    for f in ("mbx_api.hip", "mbx_session.hip", "mbe_shim.cpp"):
+        assert '#include "mbx_codec.h"' in sources[f], f
+    lists = {tuple(w) for w in ROW_WIDTHS.values()}
+    assert len(lists) == 3
+    for widths in lists:
+        pat = re.compile(r",\s*".join(str(w) for w in widths) + r"\s*\}")
+        found = {f: len(pat.findall(text)) for f, text in sources.items() if pat.search(text)}
+        device = {f: n for f, n in found.items() if f == "mbx_fec.hip"}
+        assert found == {"mbx_codec.h": 1, **device}, (widths, found)
+    try:
+        L = _native.lib()
+    except _native.NativeLibraryError as e:
+        pytest.skip(str(e))
+    packers = {0: L.mbx_pack_imbe7200x4400, 1: L.mbx_pack_ambe3600x2450, 2: L.mbx_pack_imbe7100x4400, 3: L.mbx_pack_ambe3600x2450}
+    rng = np.random.default_rng(11)
+    for codec in (0, 1, 2, 3):
+        rows, stride = FRAME_CELLS[codec]
+        widths = ROW_WIDTHS[codec]
+        assert FRAME_BYTES[codec] == (sum(widths) + 7) // 8 and PARAM_BITS[codec] == {0: 88, 1: 49, 2: 88, 3: 49}[codec]
+        # rows, stride and widths: cell (r, j) is on the wire iff j < widths[r], at the position layout.py's widths give it
+        pos = 0
+        for r in range(rows + 1):
+            for j in range(stride + 1):
+                on_wire = r < rows and j < widths[r]
+                assert L.mbx_wire_bit_of_cell(codec, r, j) == (pos + widths[r] - 1 - j if on_wire else -1), (codec, r, j)
+            pos += widths[r] if r < rows else 0
+        # cells per frame and packed frame bytes: frame i of a batch is read at i * rows * stride and written at i * FRAME_BYTES
+        cells = rng.integers(0, 2, size=(5, rows, stride), dtype=np.int8)
+        _, ref = oracle.pack(codec, cells.reshape(5, rows * stride))
+        flat = np.full(5 * FRAME_BYTES[codec] + 4, 0x55, dtype=np.uint8)
+        assert packers[codec](cells.ctypes.data, 5, flat.ctypes.data) == 0
+        assert np.array_equal(flat[:5 * FRAME_BYTES[codec]].reshape(5, -1), ref) and (flat[5 * FRAME_BYTES[codec]:] == 0x55).all()
+
+
 def test_the_edge_mix_holds_every_frame_class(oracle):
     """the workload of the instance cases (tests/edge_mix.py), decoded by the oracle: repeats, a run of repeats to the mute, clean and
     heavily damaged frames, frames above the soft clip, and for the AMBE codecs tone and erasure frames -- in as few as six frames"""
