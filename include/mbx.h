@@ -227,6 +227,28 @@ int mbx_process_batch_soft_ws(int codec, int S, int T, const mbe_soft_bit* d_sof
 int mbx_process_batch_soft_resident(int codec, int S, int T, const int32_t* d_stream_index, const mbe_soft_bit* d_soft,
                                     mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16,
                                     float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream);
+/* Ragged batches: every stream brings a frame count of its own.  Stream row i of the batch owns rows
+ * [d_frame_offset[i], d_frame_offset[i + 1]) of d_frames / d_soft, d_records, d_results, d_pcm16 and d_pcmf (x 160), in time order;
+ * d_frame_offset holds S + 1 ascending int32 offsets ON THE DEVICE, [0] = 0, [S] = total_frames (the host's copy of it: the size of
+ * every batch array).  With all counts equal to T this is the stream-major layout of the calls above.  A stream with count 0 is not
+ * touched: state, RNG state and elision word keep their bytes.  d_stream_index: row i belongs to pool slot d_stream_index[i] (NULL:
+ * slot i; no slot twice); d_resident: the pool's elision words (NULL: the ABI triplets are whole after the launch).
+ * One step = one front launch over total_frames, one expand launch, ONE stream-stage launch (*_stream_kernel_ragged[_res], as
+ * mbx_last_kernel_name reports) -- in front of it, with more streams than the device has resident wave slots, a one-workgroup launch
+ * that orders the streams longest first (time only: every stream computes what a launch of its own count would; MBX_RAGGED_ORDER=0
+ * in the environment leaves them in grid order).  A linear chain on `stream`: no internal streams, no events, no host
+ * synchronisation.  The rows and the order words go through the stream's workspace: total_frames + (S + 63) / 64 frames of it, which
+ * a caller who captures the step reserves with mbx_reserve_stream() first.  S == 0 or total_frames == 0: returns 0, nothing launched.
+ * Offsets that break the contract are clamped on the device to [0, total_frames]: wrong PCM for their streams, never an access
+ * outside the arrays.  Results are bit-identical to one mbx_process_batch_resident / _indexed call per distinct count.
+ * ref: a caller's loop over streams of different lengths around mbe_process*Frame[f]  include/mbelib-neo/mbelib.h:429, 505, 564, 352
+ *      (hard) and mbe_process*SoftFrame[f]  include/mbelib-neo/mbelib.h:437-447, 513-523 (soft); the state: include/mbelib-neo/mbelib.h:88-139 */
+int mbx_process_batch_ragged(int codec, int S, const int32_t* d_frame_offset, size_t total_frames, const int32_t* d_stream_index,
+                             const uint8_t* d_frames, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool,
+                             int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream);
+int mbx_process_batch_soft_ragged(int codec, int S, const int32_t* d_frame_offset, size_t total_frames, const int32_t* d_stream_index,
+                                  const mbe_soft_bit* d_soft, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool,
+                                  int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream);
 /* ref: mbe_golay2312Soft (kind 0, 23 soft bits per block) / mbe_hamming1511Soft (kind 1, 15 soft bits)
  *      include/mbelib-neo/mbelib.h:246, 260.  out[i] bit j = corrected cell j, errs[i] = the reference's return value */
 int mbx_ecc_soft_words(int kind, const mbe_soft_bit* d_in, size_t n, uint32_t* d_out, int32_t* d_errs, void* stream);

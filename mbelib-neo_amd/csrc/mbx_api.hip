@@ -811,6 +811,22 @@ static const Instance kInstances[] = {
     {"imbe7100_stream_kernel_res1_fused", mbx::imbe7100_stream_kernel_res1_fused},
 };
 static_assert(sizeof(kInstances) / sizeof(kInstances[0]) == kRes1Fused + 2, "kInstances: Row names the first entry of every row");
+// The ragged stream-stage kernels (mbx_process_batch_ragged: a frame count per stream).  A table of their own: a ragged call has no
+// shape to select by -- one kernel per codec column (as in kInstances) and state form, whatever the counts are.
+struct RaggedKernel {
+    const char* name;
+    void (*kernel)(MBX_RAGGED_PARAMS);
+};
+static const RaggedKernel kRagged[2][3] = {
+    // ABI triplets
+    {{"imbe_stream_kernel_ragged", mbx::imbe_stream_kernel_ragged},
+     {"ambe_stream_kernel_ragged", mbx::ambe_stream_kernel_ragged},
+     {"ambe2400_stream_kernel_ragged", mbx::ambe2400_stream_kernel_ragged}},
+    // resident state
+    {{"imbe_stream_kernel_ragged_res", mbx::imbe_stream_kernel_ragged_res},
+     {"ambe_stream_kernel_ragged_res", mbx::ambe_stream_kernel_ragged_res},
+     {"ambe2400_stream_kernel_ragged_res", mbx::ambe2400_stream_kernel_ragged_res}},
+};
 // What the launcher knows of a codec beyond its shape (mbx_codec.h), keyed the same way, every kernel named once.  A codec's frames
 // go through the FEC kernels of the row CodecShape::front names and the expand kernel and kInstances column of the row
 // CodecShape::stream names: a row that is nobody's front end has no FEC kernels, one that is nobody's stream stage no expand kernel.
@@ -905,10 +921,11 @@ struct Shape {
 static const Instance& select_instance(const Shape& q);
 // every stream-stage launch ends here: what ran on `stream` (the caller's, also for the slices of a sliced launch) is written down
 // for mbx_last_kernel_name -- the table's own pointer, one store per launch, nothing on the device -- and the launch is checked
-static void record_launch(Context* c, void* stream, const Instance& e) {
+static void record_launch(Context* c, void* stream, const char* name) {
     std::lock_guard<std::mutex> lock(c->name_mu);
-    c->last_kernel[stream] = e.name;
+    c->last_kernel[stream] = name;
 }
+static void record_launch(Context* c, void* stream, const Instance& e) { record_launch(c, stream, e.name); }
 static int launched(Context* c, void* stream, const Instance& e) {
     record_launch(c, stream, e);
     return check_launch(e.name);
@@ -926,8 +943,12 @@ struct BatchCall {
     void*               stream;
     const int32_t*      stream_index;   // row of the batch -> slot of state / rng, or nullptr: identity
     uint32_t*           resident;       // elision words of resident state, or nullptr: plain triplets
+    // a RAGGED step (mbx_process_batch_ragged): stream row i owns batch rows frame_offset[i] .. frame_offset[i + 1] - 1; T is unused
+    const int32_t*      frame_offset = nullptr;   // S + 1 offsets on the device, or nullptr: S x T, stream-major
+    size_t              total = 0;                // the host's copy of frame_offset[S]: rows of every batch array
 };
 static bool call_args_ok(const BatchCall& b) { return b.records && b.state && b.rng && b.S >= 0 && b.T >= 0; }
+static size_t batch_rows(const BatchCall& b) { return b.frame_offset ? b.total : (size_t)b.S * (size_t)b.T; }
 // the tables of a launch: the context's + what this launch walks (`reverse`: see launch_stream)
 static mbx::DeviceTables launch_tables(const Context* c, bool reverse, const BatchCall& b) {
     mbx::DeviceTables tabs = c->tabs;
@@ -1099,6 +1120,38 @@ static int launch_stream(Context* c, bool reverse, const BatchCall& b, const mbx
     hipLaunchKernelGGL(e.stream, dim3((unsigned)b.S), dim3(64), 0, (hipStream_t)b.stream, b.S, b.T, b.records, params, b.state, b.rng, b.pcm16,
                        b.pcmf, b.results, tabs);
     return launched(c, b.stream, e);
+}
+
+// The stream stage of a ragged step: ONE launch of S one-wave workgroups whose frame loops run frame_offset[s + 1] - frame_offset[s]
+// times, on the rows of the expand launch.  `order_ws`: S words behind the rows (the step's own workspace).
+// Workgroups are dispatched in grid order; with more streams than resident wave slots the launch ends when the last-dispatched long
+// stream does, so the streams are taken longest first: ragged_order_kernel, in front of the stream kernel on the same stream, writes
+// the order.  With S within the slots every stream starts at once and no order is made.  MBX_RAGGED_ORDER=0: no order kernel, grid
+// order (A/B timing and the byte test; read once).
+static bool ragged_order_enabled() {
+    static const bool on = [] {
+        const char* e = getenv("MBX_RAGGED_ORDER");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+static int launch_ragged(Context* c, const BatchCall& b, const mbx::FrameParams* params, int32_t* order_ws) {
+    const CodecKernels& k = stream_kernels(b.codec);
+    const int32_t* order = nullptr;
+    if (ragged_order_enabled() && b.S > k.lds_waves * c->simds) {
+        // (one workgroup of the 1,024 threads the kernel strides by: mbx_stream.hip, kOrderThreads)
+        hipLaunchKernelGGL(mbx::ragged_order_kernel, dim3(1), dim3(1024), 0, (hipStream_t)b.stream, b.S, b.frame_offset, order_ws);
+        const int rc = check_launch("ragged_order_kernel");
+        if (rc < 0) {
+            return rc;
+        }
+        order = order_ws;
+    }
+    const RaggedKernel& e = kRagged[b.resident ? 1 : 0][k.column];
+    hipLaunchKernelGGL(e.kernel, dim3((unsigned)b.S), dim3(64), 0, (hipStream_t)b.stream, b.S, (int)b.total, b.frame_offset, order, b.records, params,
+                       b.state, b.rng, b.pcm16, b.pcmf, b.results, launch_tables(c, false, b));
+    record_launch(c, b.stream, e.name);
+    return check_launch(e.name);
 }
 
 // IMBE with several frames per stream: the stream kernel expands the records itself, which saves the workspace round
@@ -1351,36 +1404,55 @@ struct CallerWorkspace {
 // the staged launches of a step: the front launch (where the step has one), expand (where the stream stage reads rows: to `ws`) and the
 // stream kernel; `order` = the launch counter that decides the walking direction; `slot`: see launch_stream
 static int run_stages(Context* c, unsigned order, const BatchCall& b, InputKind kind, const void* d_input, mbx::FrameParams* ws, StreamSlot* slot) {
-    const size_t n = (size_t)b.S * (size_t)b.T;
+    const size_t n = batch_rows(b);
     int rc = 0;
     if (kind == kFrames) {
         rc = launch_fec(c, b.codec, static_cast<const uint8_t*>(d_input), n, b.records, b.stream);
     } else if (kind == kSoft) {
         rc = launch_soft_fec(c, b.codec, true, static_cast<const mbe_soft_bit*>(d_input), n, b.records, b.stream);
     }
-    if (rc >= 0 && needs_workspace(b.codec, b.S, b.T)) {
+    if (rc >= 0 && (b.frame_offset || needs_workspace(b.codec, b.S, b.T))) {
         rc = launch_expand(c, mbx::kCodecs[b.codec].stream, b.records, n, ws, b.stream);
     } else {
         ws = nullptr;
     }
-    return rc < 0 ? rc : launch_stream(c, (order & 1u) != 0u, b, ws, slot);
+    if (rc < 0) {
+        return rc;
+    }
+    if (b.frame_offset) {   // (the order words: behind the rows, see run_batch)
+        return launch_ragged(c, b, ws, reinterpret_cast<int32_t*>(ws + n));
+    }
+    return launch_stream(c, (order & 1u) != 0u, b, ws, slot);
 }
 static int run_batch(Context* c, const char* who, const BatchCall& b, InputKind kind, const void* d_input, const CallerWorkspace* caller_ws) {
     const mbx::CodecShape* sh = mbx::codec_shape(b.codec);
     if (!d_input || !call_args_ok(b) || (kind == kRecords && !mbx::codec_streams(b.codec)) || (kind == kSoft && !sh)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    if (b.S == 0 || b.T == 0) {
+    const size_t n = batch_rows(b);
+    if (b.S == 0 || n == 0) {
         return 0;
     }
     if (!sh) {   // (a hard-frame step has always come to its codec only here, after the empty batch)
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    const size_t n = (size_t)b.S * (size_t)b.T;
     char text[128];
-    if (kind == kSoft && n > 0x7fffffffu) {
+    if ((kind == kSoft || b.frame_offset) && n > 0x7fffffffu) {   // (ragged offsets are int32_t)
         snprintf(text, sizeof(text), "%s: more than 2^31-1 frames in one launch", who);
         return fail(MBE_STATUS_INVALID_ARGUMENT, text);
+    }
+    if (b.frame_offset) {
+        // A ragged step: front launch over all rows, expansion, (order,) one ragged stream kernel -- a linear chain on the caller's
+        // stream, no one-launch form, never sliced.  The slot's workspace holds the rows and, behind them, S order words.
+        std::lock_guard<std::mutex> lock(c->mu);
+        StreamSlot& slot = c->slots[b.stream];
+        const int wrc = ensure_workspace(c, slot, n + ((size_t)b.S + 63) / 64, b.stream);
+        if (wrc < 0) {
+            return wrc;
+        }
+        slot.exp_codec = -1;   // the rows are about to be replaced
+        slot.launches++;
+        return run_stages(c, 0u, b, kind, d_input, slot.workspace, nullptr);
     }
     const uint8_t* const d_frames = kind == kFrames ? static_cast<const uint8_t*>(d_input) : nullptr;
     const bool rows = needs_workspace(b.codec, b.S, b.T);
@@ -1633,6 +1705,38 @@ int mbx_process_batch_soft_resident(int codec, int S, int T, const int32_t* d_st
     REQUIRE_CTX(c);
     const BatchCall b{codec, S, T, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index, d_resident};
     return run_batch(c, "mbx_process_batch_soft_resident", b, kSoft, d_soft, nullptr);
+}
+
+// ---- ragged batches: run_batch with BatchCall::frame_offset ---------------------------------------------------------------------------
+// (what can be refused without a device is refused before one is asked for, as mbx_process_batch does)
+static int process_batch_ragged(const char* who, InputKind kind, int codec, int S, const int32_t* d_frame_offset, size_t total_frames,
+                                const int32_t* d_stream_index, const void* d_input, mbe_parms* d_state_pool, uint32_t* d_resident,
+                                mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
+                                mbx_param_record* d_records, void* stream) {
+    const bool empty = S == 0 || total_frames == 0;   // (a batch without frames has no frame and no record array to name)
+    if (!d_frame_offset || !d_state_pool || !d_rng_pool || S < 0 || !mbx::codec_shape(codec) || (!empty && (!d_input || !d_records))) {
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    REQUIRE_CTX(c);
+    if (empty) {
+        return 0;
+    }
+    BatchCall b{codec, S, 0, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index, d_resident};
+    b.frame_offset = d_frame_offset;
+    b.total = total_frames;
+    return run_batch(c, who, b, kind, d_input, nullptr);
+}
+int mbx_process_batch_ragged(int codec, int S, const int32_t* d_frame_offset, size_t total_frames, const int32_t* d_stream_index,
+                             const uint8_t* d_frames, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool,
+                             int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
+    return process_batch_ragged("mbx_process_batch_ragged", kFrames, codec, S, d_frame_offset, total_frames, d_stream_index, d_frames, d_state_pool,
+                                d_resident, d_rng_pool, d_pcm16, d_pcmf, d_results, d_records, stream);
+}
+int mbx_process_batch_soft_ragged(int codec, int S, const int32_t* d_frame_offset, size_t total_frames, const int32_t* d_stream_index,
+                                  const mbe_soft_bit* d_soft, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool,
+                                  int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
+    return process_batch_ragged("mbx_process_batch_soft_ragged", kSoft, codec, S, d_frame_offset, total_frames, d_stream_index, d_soft, d_state_pool,
+                                d_resident, d_rng_pool, d_pcm16, d_pcmf, d_results, d_records, stream);
 }
 
 int mbx_synthesize_speech(int S, mbe_parms* d_cur, mbe_parms* d_prev, mbx_stream_rng* d_rng, float* d_pcmf,

@@ -22,6 +22,11 @@
 #define MBX_ONE_LAUNCH_PARAMS                                                                                                     \
     const uint8_t* __restrict__ frames, mbx_param_record* __restrict__ records, FrameParams* __restrict__ rows, uint32_t* __restrict__ flags, \
         uint32_t* __restrict__ fallbacks, uint32_t epoch, MBX_OUT_PARAMS
+// ragged (a family of its own, outside the instance table): stream row s owns batch rows frame_offset[s] .. frame_offset[s + 1] - 1 of
+// the `total` the arrays hold; workgroup b takes row order[b] (nullptr: row b)
+#define MBX_RAGGED_PARAMS                                                                                                           \
+    int S, int total, const int32_t* __restrict__ frame_offset, const int32_t* __restrict__ order, const mbx_param_record* __restrict__ records, \
+        const FrameParams* __restrict__ params, MBX_OUT_PARAMS
 
 namespace mbx {
 
@@ -54,6 +59,15 @@ __global__ void ambe_one_launch_kernel(int S, MBX_ONE_LAUNCH_PARAMS);
 __global__ void ambe_one_launch_kernel_res(int S, MBX_ONE_LAUNCH_PARAMS);
 __global__ void ambe2400_one_launch_kernel(int S, MBX_ONE_LAUNCH_PARAMS);
 __global__ void ambe2400_one_launch_kernel_res(int S, MBX_ONE_LAUNCH_PARAMS);
+
+// ---- mbx_stream.hip: the ragged stream-stage kernels (mbx_api.hip, kRagged) and the kernel that orders their workgroups ----------------------
+__global__ void imbe_stream_kernel_ragged(MBX_RAGGED_PARAMS);
+__global__ void ambe_stream_kernel_ragged(MBX_RAGGED_PARAMS);
+__global__ void ambe2400_stream_kernel_ragged(MBX_RAGGED_PARAMS);
+__global__ void imbe_stream_kernel_ragged_res(MBX_RAGGED_PARAMS);
+__global__ void ambe_stream_kernel_ragged_res(MBX_RAGGED_PARAMS);
+__global__ void ambe2400_stream_kernel_ragged_res(MBX_RAGGED_PARAMS);
+__global__ void ragged_order_kernel(int, const int32_t*, int32_t*);
 
 // ---- mbx_stream.hip: single-frame kernels, frame server, per-stage kernels -------------------------------------------------------
 __global__ void imbe_frame_kernel(int, const uint8_t*, mbx_param_record*, mbe_parms*, mbx_stream_rng*, int16_t*, float*, mbe_process_result*, uint32_t*,

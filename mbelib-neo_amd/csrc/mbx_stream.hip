@@ -2101,10 +2101,38 @@ __device__ __forceinline__ uint4 frame_record(int fec_codec, Wire wire, mbx_para
 // be there in time the wave runs the kFuse = 1 front end itself, so nothing here depends on the order in which blocks are dispatched.
 // A launch may hand a workgroup only a SLICE of its stream's frames (the time-sliced launches, *_stream_kernel_lds_sliced): frames
 // t0 .. t0 + Tn - 1 of the `stride` the stream has in this call.
+// A RAGGED launch (*_stream_kernel_ragged[_res]) gives every stream a frame count of its own: stream row s owns batch rows
+// frame_offset[s] .. frame_offset[s + 1] - 1, and `Tn` of the body becomes that difference.
 struct FrameSlice {
     int stride = 0;   // frames per stream in the batch arrays (0: Tn, the whole stream)
     int t0 = 0;       // first frame of the slice
+    const int32_t* frame_offset = nullptr;   // ragged: S + 1 ascending batch rows, [0] = 0, [S] = total (nullptr: S x Tn, as above)
+    const int32_t* order = nullptr;          // ragged: workgroup b takes stream row order[b] (ragged_order_kernel; nullptr: as `reverse` says)
+    int total = 0;                           // ragged: rows of the batch arrays -- what the offsets are clamped to
 };
+// The stream row a workgroup takes, the batch row of its first frame and the number of its frames.  All three are wave-uniform and stay
+// in SGPRs (block index, kernel arguments, scalar loads), so every branch on them is a scalar branch.  A ragged launch reads its
+// offsets from device memory the host has never seen: whatever they hold, row + n <= total, so an offset array that breaks the
+// contract costs its streams their PCM and nobody an out-of-bounds access.
+struct StreamRows {
+    int    s;
+    size_t fbase;
+    int    Tn;
+};
+__device__ __forceinline__ StreamRows stream_rows(int bpos, int S, int Tn, int reverse, const FrameSlice& slice) {
+    int s = reverse ? (S - 1 - bpos) : bpos;
+    if (slice.frame_offset) {
+        if (slice.order) {
+            s = uni(slice.order[bpos]);
+            s = s < 0 ? 0 : (s >= S ? S - 1 : s);
+        }
+        int lo = uni(slice.frame_offset[s]), hi = uni(slice.frame_offset[s + 1]);
+        lo = lo < 0 ? 0 : (lo > slice.total ? slice.total : lo);
+        hi = hi < lo ? lo : (hi > slice.total ? slice.total : hi);
+        return {s, (size_t)lo, hi - lo};
+    }
+    return {s, (size_t)s * (size_t)(slice.stride ? slice.stride : Tn) + (size_t)slice.t0, Tn};
+}
 // INVARIANT of the hand-over: it uses RELAXED agent-scope atomics, a hand-written `s_waitcnt vmcnt(0)` between the
 // producer's row stores and its flag store, and compiler barriers -- no release / acquire pair.  That is sound ONLY because every word
 // that crosses (the 64 dwords of a FrameParams row, the flag, an AMBE record) is written with an sc1 (write-through) atomic store and
@@ -2144,8 +2172,13 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
     if (bpos >= S) {
         return;
     }
-    const int s = tabs_in.reverse ? (S - 1 - bpos) : bpos;
-    const size_t fbase = (size_t)s * (size_t)(slice.stride ? slice.stride : Tn) + (size_t)slice.t0;   // the batch index of the slice's first frame
+    const StreamRows rows = stream_rows(bpos, S, Tn, tabs_in.reverse, slice);
+    const int s = rows.s;
+    const size_t fbase = rows.fbase;   // the batch index of the slice's first frame
+    Tn = rows.Tn;
+    if (slice.frame_offset && Tn == 0) {   // a stream without frames in a ragged batch: nothing of its slot is read or written
+        return;
+    }
     const int lane_in = lane_id();
     MBX_STAMP(0, false);
     if constexpr (kOne) { MBX_TS(0); }
@@ -2930,8 +2963,13 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
     if (bpos >= S) {
         return;
     }
-    const int s = tabs_in.reverse ? (S - 1 - bpos) : bpos;
-    const size_t fbase = (size_t)s * (size_t)(slice.stride ? slice.stride : Tn) + (size_t)slice.t0;   // the batch index of the slice's first frame
+    const StreamRows rows = stream_rows(bpos, S, Tn, tabs_in.reverse, slice);
+    const int s = rows.s;
+    const size_t fbase = rows.fbase;   // the batch index of the slice's first frame
+    Tn = rows.Tn;
+    if (slice.frame_offset && Tn == 0) {   // a stream without frames in a ragged batch: nothing of its slot is read or written
+        return;
+    }
     const int lane_in = lane_id();
     Wire wire_in = {};
     if constexpr (kFrame) {
@@ -3896,6 +3934,91 @@ MBX_SLICE_KERNEL(ambe_stream_kernel_lds_slice, MBX_AMBE_LDS_WAVES_PER_SIMD,
                  ambe_stream_body<kAmbe2450, kLds>(S, n, records, params, MBX_OUT_ARGS, nullptr, FrameShadow{}, sl))
 MBX_SLICE_KERNEL(ambe2400_stream_kernel_lds_slice, MBX_AMBE_LDS_WAVES_PER_SIMD,
                  ambe_stream_body<kAmbe2400, kLds>(S, n, records, params, MBX_OUT_ARGS, nullptr, FrameShadow{}, sl))
+
+// ---- ragged family (*_stream_kernel_ragged, *_ragged_res): stream row s brings frame_offset[s + 1] - frame_offset[s] >= 0 frames, the
+// rows of the batch arrays from frame_offset[s] on (stream_rows).  The LDS-parked bodies, which take any wave-uniform frame count
+// >= 1: on ABI triplets (the *_lds twins) and on resident state (the *_res twins), with their twins' launch bounds.  A stream without
+// frames returns before its first state request.  Written out, not table instances: they are no answer of select_instance -- a
+// ragged call has one stream kernel per codec and state form (mbx_api.hip, kRagged). ----
+#define MBX_RAGGED_SLICE ragged_slice(total, frame_offset, order)
+__device__ __forceinline__ FrameSlice ragged_slice(int total, const int32_t* frame_offset, const int32_t* order) {
+    FrameSlice sl;
+    sl.frame_offset = frame_offset;
+    sl.order = order;
+    sl.total = total;
+    return sl;
+}
+__global__ void __launch_bounds__(64, MBX_IMBE_LDS_WAVES_PER_SIMD)
+imbe_stream_kernel_ragged(MBX_RAGGED_PARAMS) {
+    imbe_stream_body<kLds>(S, 0, records, params, MBX_OUT_ARGS, nullptr, 0, FrameShadow{}, FrontLink{}, MBX_RAGGED_SLICE);
+}
+__global__ void __launch_bounds__(64, MBX_AMBE_LDS_WAVES_PER_SIMD)
+ambe_stream_kernel_ragged(MBX_RAGGED_PARAMS) {
+    ambe_stream_body<kAmbe2450, kLds>(S, 0, records, params, MBX_OUT_ARGS, nullptr, FrameShadow{}, MBX_RAGGED_SLICE);
+}
+__global__ void __launch_bounds__(64, MBX_AMBE_LDS_WAVES_PER_SIMD)
+ambe2400_stream_kernel_ragged(MBX_RAGGED_PARAMS) {
+    ambe_stream_body<kAmbe2400, kLds>(S, 0, records, params, MBX_OUT_ARGS, nullptr, FrameShadow{}, MBX_RAGGED_SLICE);
+}
+__global__ void __launch_bounds__(64, MBX_IMBE_RES_WAVES_PER_SIMD)
+imbe_stream_kernel_ragged_res(MBX_RAGGED_PARAMS) {
+    imbe_stream_body<kLds, kBatch, kResident>(S, 0, records, params, MBX_OUT_ARGS, nullptr, 0, FrameShadow{}, FrontLink{}, MBX_RAGGED_SLICE);
+}
+__global__ void __launch_bounds__(64, MBX_AMBE_LDS_WAVES_PER_SIMD)
+ambe_stream_kernel_ragged_res(MBX_RAGGED_PARAMS) {
+    ambe_stream_body<kAmbe2450, kLds, kBatch, kResident>(S, 0, records, params, MBX_OUT_ARGS, nullptr, FrameShadow{}, MBX_RAGGED_SLICE);
+}
+__global__ void __launch_bounds__(64, MBX_AMBE_LDS_WAVES_PER_SIMD)
+ambe2400_stream_kernel_ragged_res(MBX_RAGGED_PARAMS) {
+    ambe_stream_body<kAmbe2400, kLds, kBatch, kResident>(S, 0, records, params, MBX_OUT_ARGS, nullptr, FrameShadow{}, MBX_RAGGED_SLICE);
+}
+
+// order[0 .. S) := the stream rows of a ragged batch by frame count, longest first: a counting sort on min(count, 255), ties in any
+// order.  Workgroups are dispatched in grid order and a stream is one workgroup, so the ragged kernels then start their long streams
+// first (longest processing time first) and the launch ends near max(longest stream, work / wave slots) instead of wherever a long
+// stream that was dispatched last happens to end.  The order decides WHEN a stream runs, never what it computes.  One workgroup:
+// S counts are a few passes over S words, next to a stream stage of at least S frames.
+constexpr int kOrderBins = 256, kOrderThreads = 1024;
+__global__ void __launch_bounds__(kOrderThreads)
+ragged_order_kernel(int S, const int32_t* __restrict__ frame_offset, int32_t* __restrict__ order) {
+    __shared__ uint32_t bin[kOrderBins];   // bin k: the streams of min(count, 255) == 255 - k
+    const int tid = (int)threadIdx.x;
+    if (tid < kOrderBins) {
+        bin[tid] = 0u;
+    }
+    __syncthreads();
+    auto bin_of = [&](int i) -> int {
+        const long long n = (long long)frame_offset[i + 1] - (long long)frame_offset[i];
+        return (kOrderBins - 1) - (int)(n < 0 ? 0 : (n > kOrderBins - 1 ? kOrderBins - 1 : n));
+    };
+    for (int i = tid; i < S; i += kOrderThreads) {
+        atomicAdd(&bin[bin_of(i)], 1u);
+    }
+    __syncthreads();
+    if (tid < 64) {   // bin[k] := the streams in bins < k (four bins per lane, a wave-wide scan of the lanes' sums)
+        uint32_t v[4], sum = 0u;
+        for (int k = 0; k < 4; ++k) {
+            v[k] = bin[4 * tid + k];
+            sum += v[k];
+        }
+        uint32_t incl = sum;
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d, 64);
+            if (tid >= d) {
+                incl += up;
+            }
+        }
+        uint32_t base = incl - sum;
+        for (int k = 0; k < 4; ++k) {
+            bin[4 * tid + k] = base;
+            base += v[k];
+        }
+    }
+    __syncthreads();
+    for (int i = tid; i < S; i += kOrderThreads) {
+        order[atomicAdd(&bin[bin_of(i)], 1u)] = i;   // (< S: the bins hold S streams in all)
+    }
+}
 
 // ---- fused family: the whole T = 1 step as ONE launch with the front end in the stream's own wave (kFuse) -- wire frames in,
 // PCM / results / records / state out.  fec_codec: MBX_CODEC_IMBE7200X4400 or MBX_CODEC_IMBE7100X4400. ----

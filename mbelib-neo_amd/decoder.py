@@ -111,9 +111,10 @@ class BatchDecoder:
             _native.check(fn(d_frames.data_ptr(), n, rec.data_ptr(), torch.cuda.current_stream().cuda_stream), "mbx_fec")
         return rec
 
-    def make_outputs(self, T, want_pcm16=True, want_float=False, want_results=True, streams=None):
+    def make_outputs(self, T, want_pcm16=True, want_float=False, want_results=True, streams=None, total=None):
+        """Output tensors of a launch of `streams` (default: all) x T frames, or -- total given: a ragged launch -- of `total` frames."""
         torch = _torch()
-        n = (self.streams if streams is None else int(streams)) * T
+        n = (self.streams if streams is None else int(streams)) * T if total is None else int(total)
         out = {"records": torch.empty((n, 4), dtype=torch.int32, device=self.device)}
         out["pcm16"] = torch.empty((n, 160), dtype=torch.int16, device=self.device) if want_pcm16 else None
         out["pcmf"] = torch.empty((n, 160), dtype=torch.float32, device=self.device) if want_float else None
@@ -154,6 +155,55 @@ class BatchDecoder:
                 torch.cuda.current_stream().cuda_stream,
             )
         _native.check(rc, "mbx_process_batch_soft_resident")
+        return out
+
+    def decode_ragged(self, frames, counts, soft=False, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None):
+        """A frame count per stream: row i of the batch brings counts[i] >= 0 frames (host sequence or array), its rows of `frames`
+        and of every output are offsets[i] .. offsets[i + 1] - 1 with offsets = [0, cumsum(counts)], in time order.  One
+        mbx_process_batch_ragged / _soft_ragged call on this decoder's state, resident or not; soft=True: `frames` holds
+        mbe_soft_bit cells as in decode_soft.  stream_index (int32 tensor [n]): row i belongs to stream stream_index[i] (no stream
+        twice); without it n = streams.  A stream with count 0 keeps its state.  Returns the dict of decode plus "offsets" (int32
+        device tensor [n + 1])."""
+        torch = _torch()
+        counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+        n = self.streams if stream_index is None else int(stream_index.numel())
+        if counts.size != n or (n and counts.min() < 0):
+            raise ValueError("counts must hold one frame count >= 0 per batch row")
+        total = int(counts.sum())
+        if total > 0x7FFFFFFF:
+            raise ValueError("more than 2^31-1 frames in one launch")
+        if soft and isinstance(frames, np.ndarray):
+            frames = _soft_array(self.codec, frames, total)
+            if frames.reshape(-1, 2)[:, 0].max(initial=0) > 1:
+                raise ValueError("soft frames: a hard decision is not 0 or 1")
+        d_frames = self.to_device(frames)
+        if d_frames.dtype != torch.uint8 or not d_frames.is_contiguous():
+            raise ValueError("frames must be a contiguous uint8 tensor")
+        if d_frames.numel() != total * (SOFT_CELLS[self.codec] * 2 if soft else FRAME_BYTES[self.codec]):
+            raise ValueError("frames must hold sum(counts) frames")
+        if stream_index is not None:
+            if stream_index.dtype != torch.int32 or stream_index.device != self.device:
+                raise ValueError("stream_index must be an int32 tensor on the decoder's device")
+            if n and (int(torch.unique(stream_index).numel()) != n or int(stream_index.min()) < 0 or int(stream_index.max()) >= self.streams):
+                raise ValueError("stream_index: out of range, or a stream listed twice (two rows would race on one state)")
+        offsets = np.zeros(n + 1, dtype=np.int32)
+        np.cumsum(counts, out=offsets[1:])
+        d_offsets = torch.from_numpy(offsets).to(self.device)
+        if out is None:
+            out = self.make_outputs(0, want_pcm16, want_float, want_results, total=total)
+        out["offsets"] = d_offsets
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        L = _native.lib()
+        with torch.cuda.device(self.device):
+            rc = (L.mbx_process_batch_soft_ragged if soft else L.mbx_process_batch_ragged)(
+                self.codec, n, d_offsets.data_ptr(), total, ptr(stream_index), d_frames.data_ptr(), self.state.data_ptr(), ptr(self.resident),
+                self.rng.data_ptr(), ptr(out["pcm16"]), ptr(out["pcmf"]), ptr(out["results"]), out["records"].data_ptr(),
+                torch.cuda.current_stream().cuda_stream,
+            )
+        _native.check(rc, "mbx_process_batch_ragged")
         return out
 
     def decode(self, frames, T, want_pcm16=True, want_float=False, want_results=True, out=None, staged=False):
