@@ -249,6 +249,38 @@ int mbx_process_batch_ragged(int codec, int S, const int32_t* d_frame_offset, si
 int mbx_process_batch_soft_ragged(int codec, int S, const int32_t* d_frame_offset, size_t total_frames, const int32_t* d_stream_index,
                                   const mbe_soft_bit* d_soft, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool,
                                   int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream);
+/* Mixed ragged batches: every stream brings a frame count AND a codec of its own.  A mixed batch is a ragged batch as above plus
+ * d_stream_codec: S bytes ON THE DEVICE, d_stream_codec[i] = the MBX_CODEC_* value of stream row i.  Rows have ONE size for all codecs,
+ * so row r of every batch array is still frame r: d_frames holds total_frames rows of MBX_IMBE_FRAME_BYTES (18) bytes, an AMBE frame in
+ * the first MBX_AMBE_FRAME_BYTES (9) of its row and the rest ignored; d_soft holds total_frames rows of MBX_IMBE_SOFT_BITS (184)
+ * mbe_soft_bit, a codec's own cell array ([8][23], [7][24] or [4][24], as mbx_process_batch_soft takes it) at the front of its row and
+ * the rest ignored.  Everything else is the contract of the ragged pair: identity or d_stream_index, ABI triplets or d_resident, a
+ * linear chain on `stream`, S == 0 or total_frames == 0 returns 0 and launches nothing, offsets clamped on the device.
+ * One step = one launch that spreads the codecs over the rows, ONE front launch and ONE expand launch over total_frames (each row
+ * through its codec's own front end and expansion: a 7100x4400 row leaves the front as a 7200x4400 record, a D-STAR row takes the
+ * 3600x2450 front and the 3600x2400 expansion, exactly as the single-codec calls do), the order launch where the ragged calls have
+ * it, and ONE stream-stage launch (mixed_stream_kernel_ragged[_res], as mbx_last_kernel_name reports) -- whatever the mix.
+ * Workspace: the codec bytes of the rows travel with the rows, so a caller who captures the step reserves
+ * total_frames + (S + 63) / 64 + (total_frames + 255) / 256 frames with mbx_reserve_stream() first.
+ * The codec bytes are device memory the host never sees; like the hard decisions of soft input they are the caller's to check.  A
+ * byte that is no MBX_CODEC_* value makes its stream a stream without frames: state, RNG state and elision word of its slot and its
+ * PCM, result and record rows keep their bytes, the call still returns 0 (mbe_process_result has no field to carry an error) and
+ * every other stream is decoded as if that one were idle.  A pool slot's codec is the caller's to keep constant from one
+ * (re-)initialisation of the slot to the next, as it is across single-codec calls: state written by one codec's frames is not
+ * meaningful input to another's.
+ * Results (state, RNG state, elision words, PCM, results, records) are bit-identical to one mbx_process_batch[_soft]_ragged call per
+ * codec present on the same pool, those calls' rows being the mixed batch's rows of that codec, in order.
+ * ref: a caller's loop over channels of different vocoders around mbe_processImbe7200x4400Frame[f] / mbe_processAmbe3600x2450Frame[f] /
+ *      mbe_processImbe7100x4400Frame[f] / mbe_processAmbe3600x2400Frame[f]  include/mbelib-neo/mbelib.h:429, 505, 564, 352 (hard) and
+ *      mbe_process*SoftFrame[f]  include/mbelib-neo/mbelib.h:437-447, 513-523 (soft); the state: include/mbelib-neo/mbelib.h:88-139 */
+int mbx_process_batch_mixed(int S, const uint8_t* d_stream_codec, const int32_t* d_frame_offset, size_t total_frames,
+                            const int32_t* d_stream_index, const uint8_t* d_frames, mbe_parms* d_state_pool, uint32_t* d_resident,
+                            mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
+                            mbx_param_record* d_records, void* stream);
+int mbx_process_batch_soft_mixed(int S, const uint8_t* d_stream_codec, const int32_t* d_frame_offset, size_t total_frames,
+                                 const int32_t* d_stream_index, const mbe_soft_bit* d_soft, mbe_parms* d_state_pool, uint32_t* d_resident,
+                                 mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
+                                 mbx_param_record* d_records, void* stream);
 /* ref: mbe_golay2312Soft (kind 0, 23 soft bits per block) / mbe_hamming1511Soft (kind 1, 15 soft bits)
  *      include/mbelib-neo/mbelib.h:246, 260.  out[i] bit j = corrected cell j, errs[i] = the reference's return value */
 int mbx_ecc_soft_words(int kind, const mbe_soft_bit* d_in, size_t n, uint32_t* d_out, int32_t* d_errs, void* stream);

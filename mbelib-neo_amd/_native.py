@@ -86,6 +86,8 @@ _SIGNATURES = {
     "mbx_process_batch_soft_resident": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mbx_process_batch_ragged": (C.c_int, [C.c_int, C.c_int, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mbx_process_batch_soft_ragged": (C.c_int, [C.c_int, C.c_int, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mbx_process_batch_mixed": (C.c_int, [C.c_int, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mbx_process_batch_soft_mixed": (C.c_int, [C.c_int, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mbx_ecc_soft_words": (C.c_int, [C.c_int, _vp, _sz, _vp, _vp, _vp]),
     "mbx_validate_soft_bits": (C.c_int, [_vp, _sz]),
     "mbx_soft_bits_from_hard": (C.c_int, [_vp, _vp, _sz, C.c_uint8]),

@@ -22,6 +22,7 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <algorithm>
 #include <vector>
 
 #include "mbe_neo_amd.h"
@@ -590,7 +591,10 @@ int decode_soft_frame(int codec, const mbe_soft_bit* cells, char* bits_out, mbe_
 // ==================================================================================================================
 // Queue mode (include/mbe_neo_amd.h): the hard-decision mbe_process*Frame[f] calls of a thread -- and, with
 // MBE_BATCH_QUEUE_SOFT, its mbe_process*SoftFrame[f] calls -- are recorded and run by mbe_flush() as batched launches,
-// one per (codec, input form, frames-per-channel) group, over a pool of channel states that lives on the device.  Host
+// over a pool of channel states that lives on the device: all pending hard frames as ONE launch set and all pending soft frames as
+// one -- a (codec, frames-per-channel) group alone in its input form by the single-codec launcher it has always had (one frame per
+// channel: the one-launch forms), several groups together by mbx_process_batch_mixed / _soft_mixed, whatever their codecs and
+// counts are.  Host
 // work per queued frame: validation + packing (what the synchronous call does on the host as well) and a queue entry;
 // a soft frame's cells (up to 368 B) go into the thread's cell arena, the entry keeps their offset.
 // ==================================================================================================================
@@ -689,6 +693,10 @@ struct Batch {
     PinArr<float>              h_pcmf;
     PinArr<mbe_process_result> h_results;
     PinArr<int32_t>            h_index;
+    DevArr<int32_t>            d_offsets;                 // a mixed launch set: first batch row of every channel (+ 1 entry) ...
+    PinArr<int32_t>            h_offsets;
+    DevArr<uint8_t>            d_codecs;                  // ... and its codec
+    PinArr<uint8_t>            h_codecs;
     PinArr<mbe_parms>          h_state;
     PinArr<mbx_stream_rng>     h_rng;
 };
@@ -860,12 +868,13 @@ int flush_batch(Batch& b) {
         HIP_OK(hipMemsetAsync(b.d_elided.p + first_slot, 0, upload.size() * sizeof(uint32_t), s.stream));   // whole triplets came up
         b.resident = first_slot + upload.size();
     }
-    // ---- groups of channels with the same codec and the same number of pending frames ----
+    // ---- groups of channels with the same codec, input form and number of pending frames ----
     struct Group {
         int    codec, T;
         bool   soft;
         size_t nch = 0, row0 = 0, byte0 = 0;    // channels, first batch row, byte offset of its frames
         std::vector<int> members;
+        size_t stride = 0;                      // bytes from one frame to the next in h_frames (mixed: the largest codec's)
     };
     std::vector<Group> groups;
     std::unordered_map<uint64_t, size_t> group_of;
@@ -884,12 +893,26 @@ int flush_batch(Batch& b) {
         ch.first = (int)g.nch++;
         g.members.push_back((int)c);
     }
+    // The groups of an input form are neighbours, hard first: form f owns groups [form_g0[f], form_g0[f + 1]).  A form with several
+    // groups goes out as ONE mixed launch set: its rows are one ragged batch (the groups' channels in order, each with its T rows),
+    // its frames rows of one size.  A form with one group keeps the group's own launcher.
+    std::stable_sort(groups.begin(), groups.end(), [](const Group& x, const Group& y) { return !x.soft && y.soft; });
+    size_t form_g0[3] = {0, 0, groups.size()};
+    while (form_g0[1] < groups.size() && !groups[form_g0[1]].soft) {
+        form_g0[1]++;
+    }
+    const bool form_mixed[2] = {form_g0[1] - form_g0[0] > 1, form_g0[2] - form_g0[1] > 1};
     size_t rows = 0, bytes = 0;
     for (Group& g : groups) {
         g.row0 = rows;
         g.byte0 = bytes;
+        g.stride = !form_mixed[g.soft] ? input_bytes_of(g.codec, g.soft)
+                                       : (g.soft ? MBX_IMBE_SOFT_BITS * sizeof(mbe_soft_bit) : (size_t)MBX_IMBE_FRAME_BYTES);
         rows += g.nch * (size_t)g.T;
-        bytes += (g.nch * (size_t)g.T * input_bytes_of(g.codec, g.soft) + 15u) & ~(size_t)15u;   // frame arrays start 16-byte aligned
+        bytes += g.nch * (size_t)g.T * g.stride;
+        if (!form_mixed[g.soft] || &g == &groups[form_g0[g.soft + 1] - 1]) {   // (the rows of a mixed form are one array)
+            bytes = (bytes + 15u) & ~(size_t)15u;                              // frame arrays start 16-byte aligned
+        }
     }
     // row of every queue entry: group row0 + position of the channel * T + (how many of the channel's frames came before)
     std::vector<size_t> row_of(n);
@@ -908,8 +931,8 @@ int flush_batch(Batch& b) {
         const Group& g = groups[group_idx[(size_t)qe.channel]];
         const size_t local = (size_t)b.channels[(size_t)qe.channel].first * (size_t)g.T + (size_t)seen[(size_t)qe.channel]++;
         row_of[e] = g.row0 + local;
-        const size_t fb = input_bytes_of(g.codec, g.soft);
-        memcpy(b.h_frames.p + g.byte0 + local * fb, g.soft ? static_cast<const void*>(&b.soft_cells[qe.soft_at]) : static_cast<const void*>(qe.frame), fb);
+        memcpy(b.h_frames.p + g.byte0 + local * g.stride, g.soft ? static_cast<const void*>(&b.soft_cells[qe.soft_at]) : static_cast<const void*>(qe.frame),
+               input_bytes_of(g.codec, g.soft));
         any_short |= qe.want_short != 0;
         any_float |= qe.want_short == 0;
     }
@@ -919,6 +942,31 @@ int flush_batch(Batch& b) {
         index_off[gi] = idx0;
         for (int c : groups[gi].members) {
             b.h_index.p[idx0++] = b.channels[(size_t)c].slot;
+        }
+    }
+    // mixed forms: offsets (channels + 1 per form) and codecs of their channels, in the order of the index
+    size_t off_at[2] = {0, 0}, codec_at[2] = {0, 0};
+    if (form_mixed[0] || form_mixed[1]) {
+        b.h_offsets.need(total + 2);
+        b.h_codecs.need(total);
+        b.d_offsets.need(total + 2);
+        b.d_codecs.need(total);
+        size_t no = 0, nc = 0;
+        for (int f = 0; f < 2; ++f) {
+            if (!form_mixed[f]) {
+                continue;
+            }
+            off_at[f] = no;
+            codec_at[f] = nc;
+            int32_t row = 0;   // (relative to the form's first row)
+            for (size_t gi = form_g0[f]; gi < form_g0[f + 1]; ++gi) {
+                for (size_t k = 0; k < groups[gi].nch; ++k) {
+                    b.h_offsets.p[no++] = row;
+                    b.h_codecs.p[nc++] = (uint8_t)groups[gi].codec;
+                    row += groups[gi].T;
+                }
+            }
+            b.h_offsets.p[no++] = row;
         }
     }
     b.d_frames.need(bytes);
@@ -956,14 +1004,43 @@ int flush_batch(Batch& b) {
     float* const k_pcmf = !any_float ? nullptr : (zero_copy ? b.h_pcmf.p : b.d_pcmf.p);
     mbe_process_result* const k_results = zero_copy ? b.h_results.p : b.d_results.p;
     mbx_param_record* const k_records = zero_copy ? b.h_records.p : b.d_records.p;
+    const int32_t* const k_offsets = zero_copy ? b.h_offsets.p : b.d_offsets.p;
+    const uint8_t* const k_codecs = zero_copy ? b.h_codecs.p : b.d_codecs.p;
     if (!zero_copy) {
         s.up(b.d_frames.p, b.h_frames.p, bytes);
         s.up(b.d_index.p, b.h_index.p, idx0 * sizeof(int32_t));
+        if (form_mixed[0] || form_mixed[1]) {
+            s.up(b.d_offsets.p, b.h_offsets.p, (idx0 + 2) * sizeof(int32_t));
+            s.up(b.d_codecs.p, b.h_codecs.p, idx0);
+        }
     }
     const double tr1 = g_trace_flush ? trace_now() : 0.0;
     for (size_t gi = 0; gi < groups.size(); ++gi) {
         const Group& g = groups[gi];
-        if (g.soft) {   // soft cells in: the soft twin of both launchers (no elision words in write-back mode)
+        if (form_mixed[g.soft]) {   // the whole form at its first group: one mixed launch set on the pool
+            if (gi != form_g0[g.soft]) {
+                continue;
+            }
+            size_t nch = 0, nrows = 0;
+            for (size_t k = gi; k < form_g0[g.soft + 1]; ++k) {
+                nch += groups[k].nch;
+                nrows += groups[k].nch * (size_t)groups[k].T;
+            }
+            uint32_t* const elided = b.mode == MBE_BATCH_STATE_RESIDENT ? b.d_elided.p : nullptr;
+            int16_t* const pcm16 = k_pcm16 ? k_pcm16 + g.row0 * 160 : nullptr;
+            float* const pcmf = k_pcmf ? k_pcmf + g.row0 * 160 : nullptr;
+            if (g.soft) {
+                must(mbx_process_batch_soft_mixed((int)nch, k_codecs + codec_at[1], k_offsets + off_at[1], nrows, k_index + index_off[gi],
+                                                  reinterpret_cast<const mbe_soft_bit*>(k_frames + g.byte0), b.d_state.p, elided, b.d_rng.p, pcm16,
+                                                  pcmf, k_results + g.row0, k_records + g.row0, s.stream),
+                     "mbx_process_batch_soft_mixed");
+            } else {
+                must(mbx_process_batch_mixed((int)nch, k_codecs + codec_at[0], k_offsets + off_at[0], nrows, k_index + index_off[gi],
+                                             k_frames + g.byte0, b.d_state.p, elided, b.d_rng.p, pcm16, pcmf, k_results + g.row0,
+                                             k_records + g.row0, s.stream),
+                     "mbx_process_batch_mixed");
+            }
+        } else if (g.soft) {   // soft cells in: the soft twin of both launchers (no elision words in write-back mode)
             must(mbx_process_batch_soft_resident(g.codec, (int)g.nch, g.T, k_index + index_off[gi],
                                                  reinterpret_cast<const mbe_soft_bit*>(k_frames + g.byte0), b.d_state.p,
                                                  b.mode == MBE_BATCH_STATE_RESIDENT ? b.d_elided.p : nullptr, b.d_rng.p,

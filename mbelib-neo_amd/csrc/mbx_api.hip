@@ -827,6 +827,17 @@ static const RaggedKernel kRagged[2][3] = {
      {"ambe_stream_kernel_ragged_res", mbx::ambe_stream_kernel_ragged_res},
      {"ambe2400_stream_kernel_ragged_res", mbx::ambe2400_stream_kernel_ragged_res}},
 };
+// The mixed-codec stream-stage kernels (mbx_process_batch_mixed: a codec and a frame count per stream), a row of their own beside
+// kRagged: [0] ABI triplets, [1] resident state.  One workgroup holds the LDS and the registers of the largest body, an AMBE one.
+struct MixedKernel {
+    const char* name;
+    void (*kernel)(MBX_MIXED_PARAMS);
+};
+static const MixedKernel kMixed[2] = {
+    {"mixed_stream_kernel_ragged", mbx::mixed_stream_kernel_ragged},
+    {"mixed_stream_kernel_ragged_res", mbx::mixed_stream_kernel_ragged_res},
+};
+static const int kMixedLdsWaves = MBX_AMBE_LDS_WAVES_PER_SIMD;   // (the kernels' launch bounds: mbx_stream.hip)
 // What the launcher knows of a codec beyond its shape (mbx_codec.h), keyed the same way, every kernel named once.  A codec's frames
 // go through the FEC kernels of the row CodecShape::front names and the expand kernel and kInstances column of the row
 // CodecShape::stream names: a row that is nobody's front end has no FEC kernels, one that is nobody's stream stage no expand kernel.
@@ -946,6 +957,8 @@ struct BatchCall {
     // a RAGGED step (mbx_process_batch_ragged): stream row i owns batch rows frame_offset[i] .. frame_offset[i + 1] - 1; T is unused
     const int32_t*      frame_offset = nullptr;   // S + 1 offsets on the device, or nullptr: S x T, stream-major
     size_t              total = 0;                // the host's copy of frame_offset[S]: rows of every batch array
+    // a MIXED ragged step (mbx_process_batch_mixed): stream row i is of codec stream_codec[i]; `codec` is unused
+    const uint8_t*      stream_codec = nullptr;   // S bytes on the device, or nullptr: every stream is of `codec`
 };
 static bool call_args_ok(const BatchCall& b) { return b.records && b.state && b.rng && b.S >= 0 && b.T >= 0; }
 static size_t batch_rows(const BatchCall& b) { return b.frame_offset ? b.total : (size_t)b.S * (size_t)b.T; }
@@ -1136,9 +1149,9 @@ static bool ragged_order_enabled() {
     return on;
 }
 static int launch_ragged(Context* c, const BatchCall& b, const mbx::FrameParams* params, int32_t* order_ws) {
-    const CodecKernels& k = stream_kernels(b.codec);
+    const int lds_waves = b.stream_codec ? kMixedLdsWaves : stream_kernels(b.codec).lds_waves;
     const int32_t* order = nullptr;
-    if (ragged_order_enabled() && b.S > k.lds_waves * c->simds) {
+    if (ragged_order_enabled() && b.S > lds_waves * c->simds) {
         // (one workgroup of the 1,024 threads the kernel strides by: mbx_stream.hip, kOrderThreads)
         hipLaunchKernelGGL(mbx::ragged_order_kernel, dim3(1), dim3(1024), 0, (hipStream_t)b.stream, b.S, b.frame_offset, order_ws);
         const int rc = check_launch("ragged_order_kernel");
@@ -1147,7 +1160,14 @@ static int launch_ragged(Context* c, const BatchCall& b, const mbx::FrameParams*
         }
         order = order_ws;
     }
-    const RaggedKernel& e = kRagged[b.resident ? 1 : 0][k.column];
+    if (b.stream_codec) {   // a mixed step: the same launch with a codec per stream
+        const MixedKernel& e = kMixed[b.resident ? 1 : 0];
+        hipLaunchKernelGGL(e.kernel, dim3((unsigned)b.S), dim3(64), 0, (hipStream_t)b.stream, b.stream_codec, b.S, (int)b.total, b.frame_offset, order,
+                           b.records, params, b.state, b.rng, b.pcm16, b.pcmf, b.results, launch_tables(c, false, b));
+        record_launch(c, b.stream, e.name);
+        return check_launch(e.name);
+    }
+    const RaggedKernel& e = kRagged[b.resident ? 1 : 0][stream_kernels(b.codec).column];
     hipLaunchKernelGGL(e.kernel, dim3((unsigned)b.S), dim3(64), 0, (hipStream_t)b.stream, b.S, (int)b.total, b.frame_offset, order, b.records, params,
                        b.state, b.rng, b.pcm16, b.pcmf, b.results, launch_tables(c, false, b));
     record_launch(c, b.stream, e.name);
@@ -1401,6 +1421,30 @@ struct CallerWorkspace {
     void*  p;
     size_t bytes;
 };
+// The staged launches of a MIXED step (BatchCall::stream_codec): the codec of every batch row into `row_codec` (the step's own
+// workspace), then what a ragged step launches, by kernels that look the codec of a row or a stream up -- one front launch and one
+// expand launch over all rows, (the order,) one stream-stage launch, whatever the mix.
+static int run_mixed_stages(Context* c, const BatchCall& b, InputKind kind, const void* d_input, mbx::FrameParams* ws, int32_t* order_ws,
+                            uint8_t* row_codec) {
+    const size_t n = b.total;
+    const hipStream_t st = (hipStream_t)b.stream;
+    hipLaunchKernelGGL(mbx::mixed_row_codec_kernel, dim3((unsigned)((b.S + 3) / 4)), dim3(256), 0, st, b.S, (int)n, b.frame_offset, b.stream_codec, row_codec);
+    int rc = check_launch("mixed_row_codec_kernel");
+    if (rc >= 0 && kind == kFrames) {
+        hipLaunchKernelGGL(mbx::fec_mixed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const uint8_t*>(d_input), n, row_codec,
+                           b.records, c->tabs);
+        rc = check_launch("fec_mixed_kernel");
+    } else if (rc >= 0) {
+        hipLaunchKernelGGL(mbx::soft_front_mixed_kernel, dim3((unsigned)n), dim3(64), 0, st, static_cast<const mbe_soft_bit*>(d_input), n, row_codec,
+                           b.records, c->tabs);
+        rc = check_launch("soft_front_mixed_kernel");
+    }
+    if (rc >= 0) {
+        hipLaunchKernelGGL(mbx::expand_mixed_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, st, b.records, n, row_codec, ws, c->tabs);
+        rc = check_launch("expand_mixed_kernel");
+    }
+    return rc < 0 ? rc : launch_ragged(c, b, ws, order_ws);
+}
 // the staged launches of a step: the front launch (where the step has one), expand (where the stream stage reads rows: to `ws`) and the
 // stream kernel; `order` = the launch counter that decides the walking direction; `slot`: see launch_stream
 static int run_stages(Context* c, unsigned order, const BatchCall& b, InputKind kind, const void* d_input, mbx::FrameParams* ws, StreamSlot* slot) {
@@ -1425,15 +1469,17 @@ static int run_stages(Context* c, unsigned order, const BatchCall& b, InputKind 
     return launch_stream(c, (order & 1u) != 0u, b, ws, slot);
 }
 static int run_batch(Context* c, const char* who, const BatchCall& b, InputKind kind, const void* d_input, const CallerWorkspace* caller_ws) {
+    const bool mixed = b.stream_codec != nullptr;   // every stream brings its codec (wire frames or soft cells only): b.codec is not looked at
     const mbx::CodecShape* sh = mbx::codec_shape(b.codec);
-    if (!d_input || !call_args_ok(b) || (kind == kRecords && !mbx::codec_streams(b.codec)) || (kind == kSoft && !sh)) {
+    if (!d_input || !call_args_ok(b) || (kind == kRecords && (mixed || !mbx::codec_streams(b.codec))) || (kind == kSoft && !sh && !mixed) ||
+        (mixed && !b.frame_offset)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     const size_t n = batch_rows(b);
     if (b.S == 0 || n == 0) {
         return 0;
     }
-    if (!sh) {   // (a hard-frame step has always come to its codec only here, after the empty batch)
+    if (!sh && !mixed) {   // (a hard-frame step has always come to its codec only here, after the empty batch)
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     char text[128];
@@ -1446,12 +1492,18 @@ static int run_batch(Context* c, const char* who, const BatchCall& b, InputKind 
         // stream, no one-launch form, never sliced.  The slot's workspace holds the rows and, behind them, S order words.
         std::lock_guard<std::mutex> lock(c->mu);
         StreamSlot& slot = c->slots[b.stream];
-        const int wrc = ensure_workspace(c, slot, n + ((size_t)b.S + 63) / 64, b.stream);
+        // A mixed step keeps one codec byte per row behind the order words.
+        const size_t order_frames = ((size_t)b.S + 63) / 64, codec_frames = mixed ? (n + sizeof(mbx::FrameParams) - 1) / sizeof(mbx::FrameParams) : 0;
+        const int wrc = ensure_workspace(c, slot, n + order_frames + codec_frames, b.stream);
         if (wrc < 0) {
             return wrc;
         }
         slot.exp_codec = -1;   // the rows are about to be replaced
         slot.launches++;
+        if (mixed) {
+            return run_mixed_stages(c, b, kind, d_input, slot.workspace, reinterpret_cast<int32_t*>(slot.workspace + n),
+                                    reinterpret_cast<uint8_t*>(slot.workspace + n + order_frames));
+        }
         return run_stages(c, 0u, b, kind, d_input, slot.workspace, nullptr);
     }
     const uint8_t* const d_frames = kind == kFrames ? static_cast<const uint8_t*>(d_input) : nullptr;
@@ -1709,12 +1761,14 @@ int mbx_process_batch_soft_resident(int codec, int S, int T, const int32_t* d_st
 
 // ---- ragged batches: run_batch with BatchCall::frame_offset ---------------------------------------------------------------------------
 // (what can be refused without a device is refused before one is asked for, as mbx_process_batch does)
-static int process_batch_ragged(const char* who, InputKind kind, int codec, int S, const int32_t* d_frame_offset, size_t total_frames,
-                                const int32_t* d_stream_index, const void* d_input, mbe_parms* d_state_pool, uint32_t* d_resident,
-                                mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
-                                mbx_param_record* d_records, void* stream) {
+// (`mixed`: d_stream_codec is the codec of every stream row and `codec` is not looked at)
+static int process_batch_ragged(const char* who, InputKind kind, bool mixed, int codec, int S, const uint8_t* d_stream_codec,
+                                const int32_t* d_frame_offset, size_t total_frames, const int32_t* d_stream_index, const void* d_input,
+                                mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf,
+                                mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
     const bool empty = S == 0 || total_frames == 0;   // (a batch without frames has no frame and no record array to name)
-    if (!d_frame_offset || !d_state_pool || !d_rng_pool || S < 0 || !mbx::codec_shape(codec) || (!empty && (!d_input || !d_records))) {
+    if (!d_frame_offset || !d_state_pool || !d_rng_pool || S < 0 || (mixed ? !d_stream_codec : !mbx::codec_shape(codec)) ||
+        (!empty && (!d_input || !d_records))) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     REQUIRE_CTX(c);
@@ -1724,19 +1778,35 @@ static int process_batch_ragged(const char* who, InputKind kind, int codec, int 
     BatchCall b{codec, S, 0, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index, d_resident};
     b.frame_offset = d_frame_offset;
     b.total = total_frames;
+    b.stream_codec = mixed ? d_stream_codec : nullptr;
     return run_batch(c, who, b, kind, d_input, nullptr);
 }
 int mbx_process_batch_ragged(int codec, int S, const int32_t* d_frame_offset, size_t total_frames, const int32_t* d_stream_index,
                              const uint8_t* d_frames, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool,
                              int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
-    return process_batch_ragged("mbx_process_batch_ragged", kFrames, codec, S, d_frame_offset, total_frames, d_stream_index, d_frames, d_state_pool,
+    return process_batch_ragged("mbx_process_batch_ragged", kFrames, false, codec, S, nullptr, d_frame_offset, total_frames, d_stream_index, d_frames, d_state_pool,
                                 d_resident, d_rng_pool, d_pcm16, d_pcmf, d_results, d_records, stream);
 }
 int mbx_process_batch_soft_ragged(int codec, int S, const int32_t* d_frame_offset, size_t total_frames, const int32_t* d_stream_index,
                                   const mbe_soft_bit* d_soft, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool,
                                   int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
-    return process_batch_ragged("mbx_process_batch_soft_ragged", kSoft, codec, S, d_frame_offset, total_frames, d_stream_index, d_soft, d_state_pool,
+    return process_batch_ragged("mbx_process_batch_soft_ragged", kSoft, false, codec, S, nullptr, d_frame_offset, total_frames, d_stream_index, d_soft, d_state_pool,
                                 d_resident, d_rng_pool, d_pcm16, d_pcmf, d_results, d_records, stream);
+}
+
+// ---- mixed ragged batches: a ragged batch call with BatchCall::stream_codec ---------------------------------------------------------------
+int mbx_process_batch_mixed(int S, const uint8_t* d_stream_codec, const int32_t* d_frame_offset, size_t total_frames, const int32_t* d_stream_index,
+                            const uint8_t* d_frames, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16,
+                            float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
+    return process_batch_ragged("mbx_process_batch_mixed", kFrames, true, 0, S, d_stream_codec, d_frame_offset, total_frames, d_stream_index, d_frames,
+                                d_state_pool, d_resident, d_rng_pool, d_pcm16, d_pcmf, d_results, d_records, stream);
+}
+int mbx_process_batch_soft_mixed(int S, const uint8_t* d_stream_codec, const int32_t* d_frame_offset, size_t total_frames,
+                                 const int32_t* d_stream_index, const mbe_soft_bit* d_soft, mbe_parms* d_state_pool, uint32_t* d_resident,
+                                 mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
+                                 mbx_param_record* d_records, void* stream) {
+    return process_batch_ragged("mbx_process_batch_soft_mixed", kSoft, true, 0, S, d_stream_codec, d_frame_offset, total_frames, d_stream_index, d_soft,
+                                d_state_pool, d_resident, d_rng_pool, d_pcm16, d_pcmf, d_results, d_records, stream);
 }
 
 int mbx_synthesize_speech(int S, mbe_parms* d_cur, mbe_parms* d_prev, mbx_stream_rng* d_rng, float* d_pcmf,

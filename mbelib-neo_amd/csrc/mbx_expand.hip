@@ -90,4 +90,39 @@ expand_ambe2400_kernel(const mbx_param_record* __restrict__ recs, size_t n, Fram
     expand_ambe_body<true>(recs, n, out, tabs);
 }
 
+// The expansion of a MIXED step (mbx_process_batch_mixed): the codec of record i in row_codec[i], each record expanded as the stream
+// stage CodecShape::stream names for its codec wants it -- 7200x4400 and 7100x4400 records by expand_imbe_frame_rec, 3600x2450 by
+// expand_ambe_frame<false>, D-STAR by expand_ambe_frame<true>: the per-frame functions of the three kernels above.  The eight lanes
+// of a frame share its codec and exchange nothing with other frames, so a wave whose eight frames are of one codec (all but those
+// that straddle a stream boundary) takes one path.  A byte that names no codec: no row is written.
+__global__ void __launch_bounds__(64 * kWavesPerBlock)
+expand_mixed_kernel(const mbx_param_record* __restrict__ recs, size_t n, const uint8_t* __restrict__ row_codec, FrameParams* __restrict__ out,
+                    DeviceTables tabs) {
+    __shared__ float tile[kFramesPerBlock][kRow];
+    __shared__ uint32_t words[kFramesPerBlock][64];
+    __shared__ float gains[kFramesPerBlock][8];
+    const size_t first = (size_t)blockIdx.x * kFramesPerBlock;
+    const int fi = threadIdx.x >> 3, sub = threadIdx.x & 7;
+    const size_t i = first + fi;
+    const int codec = (i < n) ? (int)row_codec[i] : -1;
+    if (codec == MBX_CODEC_IMBE7200X4400 || codec == MBX_CODEC_IMBE7100X4400) {
+        xp::expand_imbe_frame_rec(true, *reinterpret_cast<const uint4*>(&recs[i]), tile[fi], words[fi], gains[fi], sub, tabs);
+    } else if (codec == MBX_CODEC_AMBE3600X2450) {
+        xp::expand_ambe_frame<false>(true, &recs[i], tile[fi], sub, tabs);
+    } else if (codec == MBX_CODEC_AMBE3600X2400) {
+        xp::expand_ambe_frame<true>(true, &recs[i], tile[fi], sub, tabs);
+    }
+    // write_out, for the rows that have been made (bit 8 q of the ballot: frame q of this wave)
+    const unsigned long long made = __ballot(codec >= 0 && codec <= MBX_CODEC_AMBE3600X2400);
+    wave_lds_sync();
+    const int lane = lane_id(), wave = (int)(threadIdx.x >> 6);
+#pragma unroll
+    for (int q = 0; q < kFramesPerWave; ++q) {
+        const int r = kFramesPerWave * wave + q;
+        if ((made >> (8 * q)) & 1ull) {
+            reinterpret_cast<float*>(&out[first + r])[lane] = tile[r][lane];
+        }
+    }
+}
+
 }  // namespace mbx

@@ -56,6 +56,35 @@ fec_imbe7100x4400_kernel(const uint8_t* __restrict__ frames, size_t n, mbx_param
     *reinterpret_cast<uint4*>(&out[i]) = fec_imbe7100x4400_frame(tabs.t, frames + i * MBX_IMBE7100_FRAME_BYTES);
 }
 
+// The front of a MIXED hard-decision step (mbx_process_batch_mixed): rows of MBX_IMBE_FRAME_BYTES whatever the codec (an AMBE frame
+// in the first nine bytes), the codec of row i in row_codec[i] (mixed_row_codec_kernel).  Each row takes the front end
+// CodecShape::front names for its codec -- the per-frame functions of the three kernels above, nothing of its own -- so a
+// 7100x4400 row leaves as a 7200x4400 record and a D-STAR row takes the 3600x2450 front.  Rows of one stream are neighbours:
+// lanes diverge only where a wave straddles a stream boundary.  A byte that names no codec: no record is written.
+__global__ void __launch_bounds__(256)
+fec_mixed_kernel(const uint8_t* __restrict__ frames, size_t n, const uint8_t* __restrict__ row_codec, mbx_param_record* __restrict__ out,
+                 DeviceTables tabs) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) {
+        return;
+    }
+    const uint8_t* const f = frames + i * MBX_IMBE_FRAME_BYTES;
+    switch (row_codec[i]) {
+    case MBX_CODEC_IMBE7200X4400:
+        *reinterpret_cast<uint4*>(&out[i]) = fec_imbe7200x4400_frame(tabs.t, f);
+        break;
+    case MBX_CODEC_IMBE7100X4400:
+        *reinterpret_cast<uint4*>(&out[i]) = fec_imbe7100x4400_frame(tabs.t, f);
+        break;
+    case MBX_CODEC_AMBE3600X2450:
+    case MBX_CODEC_AMBE3600X2400:
+        *reinterpret_cast<uint4*>(&out[i]) = fec_ambe3600x2450_frame(tabs.t, f);
+        break;
+    default:
+        break;
+    }
+}
+
 // float -> int16 (a21): ref src/core/mbelib.c:1148-1177.  One thread per sample.
 __device__ __forceinline__ int16_t float_to_pcm16(float x) {
     const float top = 32767.0f * 0.95f;

@@ -27,6 +27,8 @@
 #define MBX_RAGGED_PARAMS                                                                                                           \
     int S, int total, const int32_t* __restrict__ frame_offset, const int32_t* __restrict__ order, const mbx_param_record* __restrict__ records, \
         const FrameParams* __restrict__ params, MBX_OUT_PARAMS
+// mixed (beside the ragged family): a ragged launch whose stream row s is of codec stream_codec[s]
+#define MBX_MIXED_PARAMS const uint8_t* __restrict__ stream_codec, MBX_RAGGED_PARAMS
 
 namespace mbx {
 
@@ -68,6 +70,14 @@ __global__ void imbe_stream_kernel_ragged_res(MBX_RAGGED_PARAMS);
 __global__ void ambe_stream_kernel_ragged_res(MBX_RAGGED_PARAMS);
 __global__ void ambe2400_stream_kernel_ragged_res(MBX_RAGGED_PARAMS);
 __global__ void ragged_order_kernel(int, const int32_t*, int32_t*);
+// ---- the mixed-codec launch set (mbx_process_batch_mixed): row codecs (mbx_stream.hip), front (mbx_fec.hip / mbx_soft_front.hip),
+// expansion (mbx_expand.hip), stream stage (mbx_stream.hip; mbx_api.hip, kMixed) ----
+__global__ void mixed_row_codec_kernel(int, int, const int32_t*, const uint8_t*, uint8_t*);
+__global__ void fec_mixed_kernel(const uint8_t*, size_t, const uint8_t*, mbx_param_record*, DeviceTables);
+__global__ void soft_front_mixed_kernel(const mbe_soft_bit*, size_t, const uint8_t*, mbx_param_record*, DeviceTables);
+__global__ void expand_mixed_kernel(const mbx_param_record*, size_t, const uint8_t*, FrameParams*, DeviceTables);
+__global__ void mixed_stream_kernel_ragged(MBX_MIXED_PARAMS);
+__global__ void mixed_stream_kernel_ragged_res(MBX_MIXED_PARAMS);
 
 // ---- mbx_stream.hip: single-frame kernels, frame server, per-stage kernels -------------------------------------------------------
 __global__ void imbe_frame_kernel(int, const uint8_t*, mbx_param_record*, mbe_parms*, mbx_stream_rng*, int16_t*, float*, mbe_process_result*, uint32_t*,

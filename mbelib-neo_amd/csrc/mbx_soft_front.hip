@@ -63,4 +63,37 @@ soft_front_ambe_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, mbx_para
     }
 }
 
+// The front of a MIXED soft step (mbx_process_batch_soft_mixed): rows of MBX_IMBE_SOFT_BITS cells whatever the codec (a codec's own
+// cell array at the front of its row), the codec of row i in row_codec[i].  One wave per row, so the codec is wave-uniform: a scalar
+// branch into the search of the three kernels above, on one SoftScratch.  A byte that names no codec: no record is written.
+__global__ void __launch_bounds__(64, 8)
+soft_front_mixed_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, const uint8_t* __restrict__ row_codec,
+                        mbx_param_record* __restrict__ records, DeviceTables tabs) {
+    __shared__ SoftScratch S;
+    const size_t i = blockIdx.x;
+    if (i >= n) {
+        return;
+    }
+    const int lane = lane_id();
+    const mbe_soft_bit* const row = soft + i * MBX_IMBE_SOFT_BITS;
+    uint4 rec;
+    switch (__builtin_amdgcn_readfirstlane((int)row_codec[i])) {   // (one row per wave: uniform)
+    case MBX_CODEC_IMBE7200X4400:
+        rec = soft_record_imbe7200x4400(S, row, tabs, lane);
+        break;
+    case MBX_CODEC_IMBE7100X4400:
+        rec = soft_record_imbe7100x4400(S, row, tabs, lane);
+        break;
+    case MBX_CODEC_AMBE3600X2450:
+    case MBX_CODEC_AMBE3600X2400:
+        rec = soft_record_ambe3600(S, row, tabs, lane);
+        break;
+    default:
+        return;
+    }
+    if (lane == 0) {
+        *reinterpret_cast<uint4*>(&records[i]) = rec;
+    }
+}
+
 }  // namespace mbx

@@ -2147,10 +2147,21 @@ struct FrontLink {
     void*           lds = nullptr;    // the workgroup's LDS block (shared with the front blocks' arrays: one allocation for both kinds)
     uint32_t*       fallbacks = nullptr;   // counts the stream blocks that expanded their frame themselves (diagnostics: expected 0)
 };
+// The LDS of an LDS-parked body (kPark) as ONE block: what imbe_stream_body<kLds> declares for itself is the first two members, what
+// ambe_stream_body<.., kLds> declares all three.  A kernel whose waves enter one body OR another (the mixed-codec kernels) declares
+// this block once and hands it in through FrontLink::lds (kLdsIn), so the workgroup pays for the largest body, not for their sum.
+#ifndef MBX_AMBE_XROWS
+#define MBX_AMBE_XROWS 8   // rows of the AMBE bodies' in-wave expansion (ambe_stream_body)
+#endif
+struct ParkedLds {
+    WaveScratchT<0> scratch;
+    ParkedPrevOnly  park;
+    float           xrows[MBX_AMBE_XROWS][65];
+};
 #ifndef MBX_FRONT_SPIN
 #define MBX_FRONT_SPIN 160   // polls, ~0.25 us apart (s_sleep 8 = 512 cycles), before a stream block gives up on its front block and
 #endif                       // expands its frame itself: ~40 us, four times a front block's life
-template <bool kPark, bool kFrame = false, bool kRes = false, bool kOne = false, int kFuse = 0>
+template <bool kPark, bool kFrame = false, bool kRes = false, bool kOne = false, int kFuse = 0, bool kLdsIn = false>
 __device__ __forceinline__ void
 imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
                  mbe_parms* __restrict__ state,
@@ -2159,13 +2170,22 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
                  int fec_codec = 0, FrameShadow shadow = FrameShadow{}, FrontLink link = FrontLink{}, FrameSlice slice = FrameSlice{}) {
     using ScratchT = WaveScratchT<kPark ? 0 : MBX_PARK_N>;
     ScratchT* scratch_ptr;
-    if constexpr (kFuse == 3) {
-        scratch_ptr = reinterpret_cast<ScratchT*>(link.lds);
+    static_assert(!kLdsIn || (kPark && kFuse == 0), "a ParkedLds is the LDS of an LDS-parked body");
+    std::conditional_t<kPark, ParkedPrevOnly, ParkedState<false>>* park_ptr;
+    if constexpr (kLdsIn) {
+        scratch_ptr = &static_cast<ParkedLds*>(link.lds)->scratch;
+        park_ptr = &static_cast<ParkedLds*>(link.lds)->park;
     } else {
-        __shared__ ScratchT scratch_own;
-        scratch_ptr = &scratch_own;
+        if constexpr (kFuse == 3) {
+            scratch_ptr = reinterpret_cast<ScratchT*>(link.lds);
+        } else {
+            __shared__ ScratchT scratch_own;
+            scratch_ptr = &scratch_own;
+        }
+        __shared__ std::conditional_t<kPark, ParkedPrevOnly, ParkedState<false>> park_own;
+        park_ptr = &park_own;
     }
-    __shared__ std::conditional_t<kPark, ParkedPrevOnly, ParkedState<false>> park;
+    auto& park = *park_ptr;
     ScratchT& scratch = *scratch_ptr;
     uint4 rec_in = make_uint4(0u, 0u, 0u, 0u);
     const int bpos = (kFuse == 3) ? link.pos : (int)blockIdx.x;
@@ -2932,7 +2952,7 @@ __device__ void tone_dstar_frame(float out[3], int id1, Parms& cur, int lane, in
 // kFuse = 3 (with kOne): the stream blocks of ambe_one_launch_kernel -- see imbe_stream_body and FrontLink
 // kOne: see imbe_stream_body.  Its header stores are gathered here too (store_parms<kOne>): 78 VGPRs = six waves per SIMD, and still 1.7 %
 // faster than seven waves with fourteen one-lane stores per struct (with a 16 B spill at seven: 2.4 % slower).
-template <bool k2400, bool kPark, bool kFrame = false, bool kRes = false, bool kOne = false, int kFuse = 0>
+template <bool k2400, bool kPark, bool kFrame = false, bool kRes = false, bool kOne = false, int kFuse = 0, bool kLdsIn = false>
 __device__ __forceinline__ void
 ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
                  mbe_parms* __restrict__ state,
@@ -2942,23 +2962,32 @@ ambe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
     uint4 rec_in = make_uint4(0u, 0u, 0u, 0u);
     using ScratchT = WaveScratchT<kPark ? 0 : MBX_PARK_N>;
     ScratchT* scratch_ptr;
-    if constexpr (kFuse == 3) {
-        scratch_ptr = reinterpret_cast<ScratchT*>(link.lds);
-    } else {
-        __shared__ ScratchT scratch_own;
-        scratch_ptr = &scratch_own;
-    }
-    ScratchT& scratch = *scratch_ptr;
-    __shared__ std::conditional_t<kPark, ParkedPrevOnly, ParkedState<false>> park;   // T >= 4: prev_mp resident in LDS
+    std::conditional_t<kPark, ParkedPrevOnly, ParkedState<false>>* park_ptr;
     // kPark without a workspace (params == nullptr, the normal case): the wave expands the records of its next EIGHT frames
     // itself, eight lanes per frame exactly like the expand kernels (mbx_expand_ambe.h), into eight LDS rows -- no
     // expand launch, no 256-byte row per frame through HBM.  (One frame at a time fills 8 of 64 lanes: round 2 measured
     // that slower than the separate launch.)  Row stride 65 dwords: the eight frames write the same columns at once.
-#ifndef MBX_AMBE_XROWS
-#define MBX_AMBE_XROWS 8
-#endif
     constexpr int kXRows = MBX_AMBE_XROWS, kXStride = 65;
-    __shared__ float xrows[kPark ? kXRows : 1][kPark ? kXStride : 1];
+    float (*xrows)[kPark ? kXStride : 1];
+    static_assert(!kLdsIn || (kPark && kFuse == 0), "a ParkedLds is the LDS of an LDS-parked body");
+    if constexpr (kLdsIn) {
+        scratch_ptr = &static_cast<ParkedLds*>(link.lds)->scratch;
+        park_ptr = &static_cast<ParkedLds*>(link.lds)->park;
+        xrows = static_cast<ParkedLds*>(link.lds)->xrows;
+    } else {
+        if constexpr (kFuse == 3) {
+            scratch_ptr = reinterpret_cast<ScratchT*>(link.lds);
+        } else {
+            __shared__ ScratchT scratch_own;
+            scratch_ptr = &scratch_own;
+        }
+        __shared__ std::conditional_t<kPark, ParkedPrevOnly, ParkedState<false>> park_own;   // T >= 4: prev_mp resident in LDS
+        park_ptr = &park_own;
+        __shared__ float xrows_own[kPark ? kXRows : 1][kPark ? kXStride : 1];
+        xrows = xrows_own;
+    }
+    ScratchT& scratch = *scratch_ptr;
+    auto& park = *park_ptr;
     const int bpos = (kFuse == 3) ? link.pos : (int)blockIdx.x;
     if (bpos >= S) {
         return;
@@ -4017,6 +4046,67 @@ ragged_order_kernel(int S, const int32_t* __restrict__ frame_offset, int32_t* __
     __syncthreads();
     for (int i = tid; i < S; i += kOrderThreads) {
         order[atomicAdd(&bin[bin_of(i)], 1u)] = i;   // (< S: the bins hold S streams in all)
+    }
+}
+
+// ---- mixed family (mixed_stream_kernel_ragged, _ragged_res): a ragged launch whose stream rows each bring a codec of their own,
+// stream_codec[s] = MBX_CODEC_*.  A stream is one wave, so its codec is wave-uniform: one load next to the row range, a SCALAR branch
+// into the ragged body of that codec's stream stage (a 7100x4400 stream runs as 7200x4400, its records are in that order), never
+// lane divergence.  The three bodies share ONE block of LDS (ParkedLds): the workgroup costs what the AMBE ragged kernels cost.
+// A codec byte that names no codec makes the stream one without frames: the wave leaves before it has read or written anything
+// of the stream's slot or rows.  Written out beside the ragged family for the same reason: no answer of select_instance. ----
+template <bool kRes>
+__device__ __forceinline__ void mixed_stream_body(const uint8_t* __restrict__ stream_codec, MBX_RAGGED_PARAMS) {
+    __shared__ ParkedLds lds;
+    if ((int)blockIdx.x >= S) {
+        return;
+    }
+    const FrameSlice sl = MBX_RAGGED_SLICE;
+    const int s = stream_rows((int)blockIdx.x, S, 0, 0, sl).s;   // (in [0, S) whatever the order words hold)
+    const int codec = uni((int)stream_codec[s]);
+    FrontLink link;
+    link.lds = &lds;
+    switch (codec) {
+    case MBX_CODEC_IMBE7200X4400:
+    case MBX_CODEC_IMBE7100X4400:
+        imbe_stream_body<kLds, kBatch, kRes, false, 0, true>(S, 0, records, params, MBX_OUT_ARGS, nullptr, 0, FrameShadow{}, link, sl);
+        break;
+    case MBX_CODEC_AMBE3600X2450:
+        ambe_stream_body<kAmbe2450, kLds, kBatch, kRes, false, 0, true>(S, 0, records, params, MBX_OUT_ARGS, nullptr, FrameShadow{}, sl, link);
+        break;
+    case MBX_CODEC_AMBE3600X2400:
+        ambe_stream_body<kAmbe2400, kLds, kBatch, kRes, false, 0, true>(S, 0, records, params, MBX_OUT_ARGS, nullptr, FrameShadow{}, sl, link);
+        break;
+    default:
+        break;
+    }
+}
+__global__ void __launch_bounds__(64, MBX_AMBE_LDS_WAVES_PER_SIMD)
+mixed_stream_kernel_ragged(MBX_MIXED_PARAMS) {
+    mixed_stream_body<kPlain>(stream_codec, S, total, frame_offset, order, records, params, MBX_OUT_ARGS);
+}
+__global__ void __launch_bounds__(64, MBX_AMBE_LDS_WAVES_PER_SIMD)
+mixed_stream_kernel_ragged_res(MBX_MIXED_PARAMS) {
+    mixed_stream_body<kResident>(stream_codec, S, total, frame_offset, order, records, params, MBX_OUT_ARGS);
+}
+
+// row_codec[r] := stream_codec[s] for the rows r of stream row s, s = 0 .. S - 1: what the front and expand launches of a mixed step
+// read, one byte per batch row.  One wave per stream; the row range is clamped as stream_rows clamps it, so offsets that break the
+// contract write no byte outside row_codec[0 .. total).  (Rows that no stream owns keep what the workspace held: the front and
+// expand kernels bound every codec byte themselves, and no stream reads such a row.)
+__global__ void __launch_bounds__(256)
+mixed_row_codec_kernel(int S, int total, const int32_t* __restrict__ frame_offset, const uint8_t* __restrict__ stream_codec,
+                       uint8_t* __restrict__ row_codec) {
+    const int s = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (s >= S) {
+        return;
+    }
+    int lo = frame_offset[s], hi = frame_offset[s + 1];
+    lo = lo < 0 ? 0 : (lo > total ? total : lo);
+    hi = hi < lo ? lo : (hi > total ? total : hi);
+    const uint8_t codec = stream_codec[s];
+    for (int r = lo + lane_id(); r < hi; r += 64) {
+        row_codec[r] = codec;
     }
 }
 

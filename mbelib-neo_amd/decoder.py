@@ -157,14 +157,18 @@ class BatchDecoder:
         _native.check(rc, "mbx_process_batch_soft_resident")
         return out
 
-    def decode_ragged(self, frames, counts, soft=False, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None):
+    def decode_ragged(self, frames, counts, soft=False, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None,
+                      codec=None):
         """A frame count per stream: row i of the batch brings counts[i] >= 0 frames (host sequence or array), its rows of `frames`
         and of every output are offsets[i] .. offsets[i + 1] - 1 with offsets = [0, cumsum(counts)], in time order.  One
         mbx_process_batch_ragged / _soft_ragged call on this decoder's state, resident or not; soft=True: `frames` holds
         mbe_soft_bit cells as in decode_soft.  stream_index (int32 tensor [n]): row i belongs to stream stream_index[i] (no stream
         twice); without it n = streams.  A stream with count 0 keeps its state.  Returns the dict of decode plus "offsets" (int32
-        device tensor [n + 1])."""
-        torch = _torch()
+        device tensor [n + 1]).
+        codec (array of n MBX_CODEC_* values): a MIXED batch, row i of codec[i], decoded by one mbx_process_batch_mixed /
+        _soft_mixed call whatever the decoder's own codec is; `frames` then holds rows of ONE size, MIXED_ROW_BYTES bytes
+        (soft: MIXED_ROW_CELLS cells), as pack_mixed_rows makes them from each stream's own frames -- or is the list of per-stream
+        arrays itself.  The codec of a stream stays what it was in the stream's earlier calls: that is the caller's to keep."""
         counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
         n = self.streams if stream_index is None else int(stream_index.numel())
         if counts.size != n or (n and counts.min() < 0):
@@ -172,14 +176,26 @@ class BatchDecoder:
         total = int(counts.sum())
         if total > 0x7FFFFFFF:
             raise ValueError("more than 2^31-1 frames in one launch")
+        mixed = codec is not None
+        if mixed:   # (everything the host can check, before torch or the library is touched)
+            codec = mixed_codecs(codec, n)
+            if isinstance(frames, (list, tuple)):
+                frames = pack_mixed_rows(codec, counts, frames, soft)
+            row_bytes = MIXED_ROW_CELLS * 2 if soft else MIXED_ROW_BYTES
+            if isinstance(frames, np.ndarray) and (frames.dtype != np.uint8 or frames.size != total * row_bytes):
+                raise ValueError(f"frames must hold sum(counts) = {total} uint8 rows of {row_bytes} bytes")
+        else:
+            row_bytes = SOFT_CELLS[self.codec] * 2 if soft else FRAME_BYTES[self.codec]
+        torch = _torch()
         if soft and isinstance(frames, np.ndarray):
-            frames = _soft_array(self.codec, frames, total)
+            if not mixed:
+                frames = _soft_array(self.codec, frames, total)
             if frames.reshape(-1, 2)[:, 0].max(initial=0) > 1:
                 raise ValueError("soft frames: a hard decision is not 0 or 1")
         d_frames = self.to_device(frames)
         if d_frames.dtype != torch.uint8 or not d_frames.is_contiguous():
             raise ValueError("frames must be a contiguous uint8 tensor")
-        if d_frames.numel() != total * (SOFT_CELLS[self.codec] * 2 if soft else FRAME_BYTES[self.codec]):
+        if d_frames.numel() != total * row_bytes:
             raise ValueError("frames must hold sum(counts) frames")
         if stream_index is not None:
             if stream_index.dtype != torch.int32 or stream_index.device != self.device:
@@ -197,13 +213,17 @@ class BatchDecoder:
             return t.data_ptr() if t is not None else None
 
         L = _native.lib()
+        tail = (d_offsets.data_ptr(), total, ptr(stream_index), d_frames.data_ptr(), self.state.data_ptr(), ptr(self.resident),
+                self.rng.data_ptr(), ptr(out["pcm16"]), ptr(out["pcmf"]), ptr(out["results"]), out["records"].data_ptr())
         with torch.cuda.device(self.device):
-            rc = (L.mbx_process_batch_soft_ragged if soft else L.mbx_process_batch_ragged)(
-                self.codec, n, d_offsets.data_ptr(), total, ptr(stream_index), d_frames.data_ptr(), self.state.data_ptr(), ptr(self.resident),
-                self.rng.data_ptr(), ptr(out["pcm16"]), ptr(out["pcmf"]), ptr(out["results"]), out["records"].data_ptr(),
-                torch.cuda.current_stream().cuda_stream,
-            )
-        _native.check(rc, "mbx_process_batch_ragged")
+            if mixed:
+                d_codec = torch.from_numpy(codec).to(self.device)
+                rc = (L.mbx_process_batch_soft_mixed if soft else L.mbx_process_batch_mixed)(
+                    n, d_codec.data_ptr(), *tail, torch.cuda.current_stream().cuda_stream)
+            else:
+                rc = (L.mbx_process_batch_soft_ragged if soft else L.mbx_process_batch_ragged)(
+                    self.codec, n, *tail, torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_process_batch_mixed" if mixed else "mbx_process_batch_ragged")
         return out
 
     def decode(self, frames, T, want_pcm16=True, want_float=False, want_results=True, out=None, staged=False):
@@ -322,6 +342,42 @@ def process_batch_host(codec, S, T, frames, state, rng, device=0):
 
 # ---- soft-decision front end (mbe_soft_bit arrays: uint8 [..., 2] = (bit, reliability)) ------------
 SOFT_CELLS = {0: 184, 1: 96, 2: 168, 3: 96}
+
+
+# a mixed batch (decode_ragged(codec=array)): rows of one size for all codecs, the largest codec's
+MIXED_ROW_BYTES, MIXED_ROW_CELLS = 18, 184
+
+
+def mixed_codecs(codec, n):
+    """the per-row codec array of a mixed batch as the uint8 array the library takes; ValueError unless n values in 0..3"""
+    codec = np.asarray(codec)
+    if codec.ndim != 1 or codec.size != n:
+        raise ValueError(f"codec must hold one MBX_CODEC_* value per batch row ({n})")
+    if codec.dtype.kind not in "iu" or (n and (codec.min() < 0 or codec.max() > 3)):
+        raise ValueError("codec: every value must be one of 0 (IMBE 7200x4400), 1 (AMBE 3600x2450), 2 (IMBE 7100x4400), 3 (AMBE 3600x2400)")
+    return np.ascontiguousarray(codec, dtype=np.uint8)
+
+
+def pack_mixed_rows(codec, counts, frames, soft=False):
+    """The rows of a mixed batch from each stream's own frames: frames[i] holds counts[i] frames of codec[i] -- FRAME_BYTES[codec[i]]
+    bytes each, or soft: SOFT_CELLS[codec[i]] (bit, reliability) pairs -- and lands, frame by frame, at the FRONT of rows of
+    MIXED_ROW_BYTES bytes (soft: MIXED_ROW_CELLS pairs); the rest of a row is zero and ignored.  Returns uint8 [sum(counts), 18]
+    (soft: [sum(counts), 184, 2]).  Host only."""
+    counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
+    codec = mixed_codecs(codec, counts.size)
+    if len(frames) != counts.size:
+        raise ValueError("frames must hold one array per batch row")
+    width = MIXED_ROW_CELLS * 2 if soft else MIXED_ROW_BYTES
+    rows = np.zeros((int(counts.sum()), width), dtype=np.uint8)
+    at = 0
+    for i, (c, k) in enumerate(zip(codec.tolist(), counts.tolist())):
+        own = SOFT_CELLS[c] * 2 if soft else FRAME_BYTES[c]
+        f = np.ascontiguousarray(frames[i], dtype=np.uint8)
+        if f.size != k * own:
+            raise ValueError(f"frames[{i}] must hold counts[{i}] = {k} frames of {own} bytes (codec {c})")
+        rows[at:at + k, :own] = f.reshape(k, own)
+        at += k
+    return rows.reshape(-1, MIXED_ROW_CELLS, 2) if soft else rows
 
 
 def _soft_array(codec, soft, n):
