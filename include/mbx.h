@@ -36,6 +36,35 @@
 extern "C" {
 #endif
 
+/* Alignment.  What the address of each kind of pointer must be a multiple of, in bytes: the widest access the kernels make through
+ * it.  A launcher that is handed a pointer below the alignment of its kind returns MBE_STATUS_INVALID_ARGUMENT before anything is
+ * launched (mbx_last_error() names the call).  Sizes are exact: a launcher must not write outside the arrays its comment names.
+ * tests/test_gpu_memory_contract.py holds the launch forms that have a case in tests/instance_cases.py or tests/memory_cases.py to
+ * both, with every buffer at exactly this alignment and no better between guard bands.  One read outside an array is known and
+ * allowed: the one-frame IMBE instances fetch the five aligned dwords that cover an 18-byte frame, so behind the last frame of an
+ * ODD number of frames they read the 2 bytes that complete its last dword (never across a page; the same test runs every such
+ * launch twice with different bytes there and gets the same results).
+ *   kind        bytes  which pointers
+ *   frames      1      d_frames / d_frame of the AMBE codecs (9-byte frames, byte loads); d_packed; packed frames of mbx_fec_stage
+ *   frames2     2      d_frames / d_frame of the IMBE codecs and the 18-byte rows of a mixed batch: read in 16-bit pieces
+ *   frames4     4      IMBE d_frames for the one-launch and in-wave fused instances at T = 1: below it the staged launches serve
+ *   codec       1      d_stream_codec
+ *   cells       4      d_cells of mbx_pack_cells: read four cells at a time
+ *   soft        2      d_soft / d_in of the soft calls: one (bit, reliability) pair is one 16-bit load
+ *   pcm16       2      d_pcm16
+ *   pcmf        4      d_pcmf
+ *   results     4      d_results / d_result
+ *   state       4      d_state / d_state_pool / d_cur / d_prev / d_parms (mbe_parms is 2,604 bytes: a triplet array gives no more)
+ *   resident    4      d_resident
+ *   index       4      d_stream_index, d_frame_offset, d_status, d_errs, d_rc, d_dstar_ids, d_done, the words of mbx_ecc_words
+ *   rng         8      d_rng / d_rng_pool (mbx_stream_rng starts with a 64-bit word)
+ *   hist        8      d_hist: 64-bit atomic adds
+ *   records     16     d_records / d_record: one record is one 16-byte store
+ *   workspace   16     d_workspace
+ *   stage       16     both buffers of mbx_stage_in
+ *   f2s_in      8      d_in of mbx_floattoshort: two samples per lane, a float pair in ...
+ *   f2s_out     4      d_out of mbx_floattoshort: ... and one dword out
+ */
 #define MBX_ENODEVICE (-100) /* no HIP device / HIP call failed */
 #define MBX_ENOTINIT  (-101) /* mbx_init() has not been called on this device */
 #define MBX_EBADTABLE (-102) /* table blob has the wrong magic, size or checksum */

@@ -162,9 +162,11 @@ struct Slot {
         done = reinterpret_cast<uint32_t*>(block + o_done);
         shadow_ok = reinterpret_cast<uint32_t*>(block + o_sok);
         void* sh = nullptr;
-        HIP_OK(hipMalloc(&sh, 3 * sizeof(mbe_parms) + sizeof(mbx_stream_rng)));
+        // (mbx_stream_rng starts with a 64-bit word and needs 8-byte alignment -- include/mbx.h, Alignment --; three structs of 2,604 B end at 4 mod 8)
+        const size_t rng_at = (3 * sizeof(mbe_parms) + 7u) & ~(size_t)7u;
+        HIP_OK(hipMalloc(&sh, rng_at + sizeof(mbx_stream_rng)));
         d_shadow = static_cast<mbe_parms*>(sh);
-        d_shadow_rng = reinterpret_cast<mbx_stream_rng*>(d_shadow + 3);
+        d_shadow_rng = reinterpret_cast<mbx_stream_rng*>(static_cast<char*>(sh) + rng_at);
         mailbox = reinterpret_cast<mbx_frame_mailbox*>(block + o_mail);
         frame_out = block + o_fout;
         soft = reinterpret_cast<mbe_soft_bit*>(block + o_soft);

@@ -69,6 +69,24 @@ int fail(int code, const char* what, hipError_t e = hipSuccess) {
     return code;
 }
 
+// The alignment table of include/mbx.h, host side, before anything is launched (a null pointer is aligned: whether it may be null is
+// each caller's check): the kernels store records as 16-byte vectors, the RNG state as a 64-bit word, load IMBE wire frames in 16-bit
+// pieces and soft cells as 16-bit words, and a pointer below its alignment must never reach them.
+static bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
+static bool batch_pointers_aligned(const mbx_param_record* records, const mbe_parms* state, const mbx_stream_rng* rng, const int16_t* pcm16,
+                                   const float* pcmf, const mbe_process_result* results, const int32_t* stream_index, const uint32_t* resident,
+                                   const int32_t* frame_offset) {
+    return aligned_to(records, 16) && aligned_to(state, 4) && aligned_to(rng, 8) && aligned_to(pcm16, 2) && aligned_to(pcmf, 4) &&
+           aligned_to(results, 4) && aligned_to(stream_index, 4) && aligned_to(resident, 4) && aligned_to(frame_offset, 4);
+}
+// wire frames: 18-byte IMBE frames (and the 18-byte rows of a mixed batch) are read in 16-bit pieces, 9-byte AMBE frames byte by byte
+static bool frames_aligned(const void* d_frames, bool imbe_rows) { return aligned_to(d_frames, imbe_rows ? 2 : 1); }
+static int misaligned(const char* who) {
+    char text[160];
+    snprintf(text, sizeof(text), "%s: a pointer is below the alignment of its kind (include/mbx.h, Alignment)", who);
+    return fail(MBE_STATUS_INVALID_ARGUMENT, text);
+}
+
 #define HIP_TRY(expr)                                  \
     do {                                               \
         hipError_t e_ = (expr);                        \
@@ -705,6 +723,9 @@ int mbx_ecc_soft_words(int kind, const mbe_soft_bit* d_in, size_t n, uint32_t* d
     if (!d_in || !d_out || kind < 0 || kind > 2 || n > 0x7fffffffu) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_in, 2) || !aligned_to(d_out, 4) || !aligned_to(d_errs, 4)) {
+        return misaligned("mbx_ecc_soft_words");
+    }
     if (n == 0) {
         return 0;
     }
@@ -884,6 +905,9 @@ static int fec_export(int codec, const uint8_t* d_frames, size_t n, mbx_param_re
     if (!d_frames || !d_records) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_records, 16) || !frames_aligned(d_frames, imbe_codec(codec))) {
+        return misaligned("mbx_fec");
+    }
     return n == 0 ? 0 : launch_fec(c, codec, d_frames, n, d_records, stream);
 }
 int mbx_fec_imbe7200x4400(const uint8_t* d_frames, size_t n, mbx_param_record* d_records, void* stream) { return fec_export(MBX_CODEC_IMBE7200X4400, d_frames, n, d_records, stream); }
@@ -903,6 +927,9 @@ int mbx_fec_soft(int codec, const mbe_soft_bit* d_soft, size_t n, mbx_param_reco
     REQUIRE_CTX(c);
     if (!d_soft || !d_records || !mbx::codec_shape(codec)) {
         return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (!aligned_to(d_soft, 2) || !aligned_to(d_records, 16)) {
+        return misaligned("mbx_fec_soft");
     }
     if (n == 0) {
         return 0;
@@ -961,6 +988,9 @@ struct BatchCall {
     const uint8_t*      stream_codec = nullptr;   // S bytes on the device, or nullptr: every stream is of `codec`
 };
 static bool call_args_ok(const BatchCall& b) { return b.records && b.state && b.rng && b.S >= 0 && b.T >= 0; }
+static bool call_aligned(const BatchCall& b) {
+    return batch_pointers_aligned(b.records, b.state, b.rng, b.pcm16, b.pcmf, b.results, b.stream_index, b.resident, b.frame_offset);
+}
 static size_t batch_rows(const BatchCall& b) { return b.frame_offset ? b.total : (size_t)b.S * (size_t)b.T; }
 // the tables of a launch: the context's + what this launch walks (`reverse`: see launch_stream)
 static mbx::DeviceTables launch_tables(const Context* c, bool reverse, const BatchCall& b) {
@@ -1314,6 +1344,9 @@ int mbx_expand_records(int codec, const mbx_param_record* d_records, size_t n, v
     if (!d_records || !mbx::codec_streams(codec)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_records, 16)) {
+        return misaligned("mbx_expand_records");
+    }
     if (n == 0) {
         return 0;
     }
@@ -1341,6 +1374,9 @@ int mbx_expand_records_ws(int codec, const mbx_param_record* d_records, size_t n
     if (!d_records || !mbx::codec_streams(codec) || !d_workspace || workspace_bytes < mbx_workspace_bytes(n)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_records, 16) || !aligned_to(d_workspace, 16)) {
+        return misaligned("mbx_expand_records_ws");
+    }
     if (n == 0) {
         return 0;
     }
@@ -1355,6 +1391,9 @@ int mbx_stream_expanded_ws(int codec, int S, int T, const mbx_param_record* d_re
     const BatchCall b{codec, S, T, const_cast<mbx_param_record*>(d_records), d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, d_resident};
     if (!call_args_ok(b) || !mbx::codec_streams(codec) || !d_workspace || workspace_bytes < mbx_workspace_bytes((size_t)S * (size_t)T)) {
         return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (!call_aligned(b) || !aligned_to(d_workspace, 16)) {
+        return misaligned("mbx_stream_expanded_ws");
     }
     if (S == 0 || T == 0) {
         return 0;
@@ -1372,6 +1411,9 @@ static int stream_expanded(const BatchCall& b) {
     REQUIRE_CTX(c);
     if (!call_args_ok(b) || !mbx::codec_streams(b.codec)) {
         return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (!call_aligned(b)) {
+        return misaligned("mbx_stream_expanded");
     }
     if (b.S == 0 || b.T == 0) {
         return 0;
@@ -1475,6 +1517,10 @@ static int run_batch(Context* c, const char* who, const BatchCall& b, InputKind 
         (mixed && !b.frame_offset)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!call_aligned(b) || (kind == kSoft && !aligned_to(d_input, 2)) || (kind == kFrames && !frames_aligned(d_input, mixed || imbe_codec(b.codec))) ||
+        (caller_ws && !aligned_to(caller_ws->p, 16))) {
+        return misaligned(who);
+    }
     const size_t n = batch_rows(b);
     if (b.S == 0 || n == 0) {
         return 0;
@@ -1564,6 +1610,10 @@ int mbx_process_batch(int codec, int S, int T, const uint8_t* d_frames, mbe_parm
     if (!d_frames || !d_records || S < 0 || T < 0 || !mbx::codec_shape(codec)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!batch_pointers_aligned(d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, nullptr, nullptr, nullptr) ||
+        !frames_aligned(d_frames, imbe_codec(codec))) {
+        return misaligned("mbx_process_batch");
+    }
     REQUIRE_CTX(c);
     const BatchCall b{codec, S, T, d_records, d_state, d_rng, d_pcm16, d_pcmf, d_results, stream, nullptr, nullptr};
     return run_batch(c, "mbx_process_batch", b, kFrames, d_frames, nullptr);
@@ -1590,6 +1640,10 @@ static int launch_frame(const BatchCall& b, const uint8_t* d_frame, uint32_t* d_
     REQUIRE_CTX(c);
     if (!d_frame || !call_args_ok(b) || !mbx::codec_shape(b.codec)) {
         return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (!call_aligned(b) || !frames_aligned(d_frame, imbe_codec(b.codec)) || !aligned_to(d_done, 4) || !aligned_to(shadow.state, 4) ||
+        !aligned_to(shadow.rng, 8) || !aligned_to(shadow.ok, 4)) {
+        return misaligned("mbx_process_frame");
     }
     const mbx::DeviceTables tabs = launch_tables(c, false, b);
     const hipStream_t stream = (hipStream_t)b.stream;
@@ -1724,6 +1778,9 @@ int mbx_resident_materialize(int n, const int32_t* d_stream_index, mbe_parms* d_
     if (!d_state_pool || !d_resident || n < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_state_pool, 4) || !aligned_to(d_resident, 4) || !aligned_to(d_stream_index, 4)) {
+        return misaligned("mbx_resident_materialize");
+    }
     if (n == 0) {
         return 0;
     }
@@ -1771,6 +1828,10 @@ static int process_batch_ragged(const char* who, InputKind kind, bool mixed, int
         (!empty && (!d_input || !d_records))) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!batch_pointers_aligned(d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, d_stream_index, d_resident, d_frame_offset) ||
+        (kind == kSoft && !aligned_to(d_input, 2)) || (kind == kFrames && !frames_aligned(d_input, mixed || imbe_codec(codec)))) {
+        return misaligned(who);
+    }
     REQUIRE_CTX(c);
     if (empty) {
         return 0;
@@ -1815,6 +1876,9 @@ int mbx_synthesize_speech(int S, mbe_parms* d_cur, mbe_parms* d_prev, mbx_stream
     if (!d_cur || !d_prev || !d_rng || S < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_cur, 4) || !aligned_to(d_prev, 4) || !aligned_to(d_rng, 8) || !aligned_to(d_pcmf, 4) || !aligned_to(d_pcm16, 2)) {
+        return misaligned("mbx_synthesize_speech");
+    }
     if (S == 0) {
         return 0;
     }
@@ -1827,6 +1891,9 @@ int mbx_floattoshort(const float* d_in, int16_t* d_out, size_t nframes, void* st
     REQUIRE_CTX(c);
     if (!d_in || !d_out) {
         return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (!aligned_to(d_in, 8) || !aligned_to(d_out, 4)) {   // (the kernel moves two samples per lane: a float pair in, one dword out)
+        return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_floattoshort: d_in must be 8-byte aligned and d_out 4-byte aligned");
     }
     if (nframes == 0) {
         return 0;
@@ -1843,6 +1910,9 @@ int mbx_result_histogram(const mbe_process_result* d_results, size_t n, mbx_resu
     if (!d_results || !d_hist) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_results, 4) || !aligned_to(d_hist, 8)) {   // (64-bit atomic adds on the counters)
+        return misaligned("mbx_result_histogram");
+    }
     if (n == 0) {
         return 0;
     }
@@ -1857,6 +1927,9 @@ int mbx_spectral_amp_enhance(int S, mbe_parms* d_parms, void* stream) {
     if (!d_parms || S < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_parms, 4)) {
+        return misaligned("mbx_spectral_amp_enhance");
+    }
     if (S == 0) {
         return 0;
     }
@@ -1869,6 +1942,9 @@ int mbx_adaptive_smoothing(int S, mbe_parms* d_cur, const mbe_parms* d_prev, voi
     if (!d_cur || !d_prev || S < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_cur, 4) || !aligned_to(d_prev, 4)) {
+        return misaligned("mbx_adaptive_smoothing");
+    }
     if (S == 0) {
         return 0;
     }
@@ -1880,6 +1956,9 @@ int mbx_comfort_noise(int S, mbx_stream_rng* d_rng, float* d_pcmf, int16_t* d_pc
     REQUIRE_CTX(c);
     if (!d_rng || S < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (!aligned_to(d_rng, 8) || !aligned_to(d_pcmf, 4) || !aligned_to(d_pcm16, 2)) {
+        return misaligned("mbx_comfort_noise");
     }
     if (S == 0) {
         return 0;
@@ -1895,6 +1974,9 @@ int mbx_synthesize_tone(int S, const mbx_param_record* d_records, const int32_t*
     if (!d_cur || S < 0 || (!d_records && !d_dstar_ids)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_records, 16) || !aligned_to(d_dstar_ids, 4) || !aligned_to(d_cur, 4) || !aligned_to(d_pcmf, 4) || !aligned_to(d_pcm16, 2)) {
+        return misaligned("mbx_synthesize_tone");
+    }
     if (S == 0) {
         return 0;
     }
@@ -1908,6 +1990,9 @@ int mbx_state_copy(int S, mbe_parms* d_state, void* stream) {
     if (!d_state || S < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_state, 4)) {
+        return misaligned("mbx_state_copy");
+    }
     if (S == 0) {
         return 0;
     }
@@ -1919,6 +2004,9 @@ int mbx_ecc_words(int kind, const uint32_t* d_in, size_t n, uint32_t* d_out, int
     REQUIRE_CTX(c);
     if (!d_in || !d_out || kind < 0 || kind > 2) {
         return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (!aligned_to(d_in, 4) || !aligned_to(d_out, 4) || !aligned_to(d_errs, 4)) {
+        return misaligned("mbx_ecc_words");
     }
     if (n == 0) {
         return 0;
@@ -1943,6 +2031,9 @@ int mbx_pack_cells(int codec, const char* d_cells, size_t n, uint8_t* d_packed, 
     if (!d_cells || !d_packed || !mbx::codec_shape(codec)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_cells, 4) || !aligned_to(d_status, 4)) {   // (the cells are read four at a time)
+        return misaligned("mbx_pack_cells");
+    }
     if (n == 0) {
         return 0;
     }
@@ -1959,6 +2050,9 @@ int mbx_fec_stage(int codec, int stage, const void* d_in, size_t n, uint8_t* d_f
         || ((stage == MBX_STAGE_C0 || stage == MBX_STAGE_DEMODULATE) && !d_frames_out)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!aligned_to(d_out, 16) || (stage == MBX_STAGE_CONVERT7100 && !aligned_to(d_in, 16))) {   // (packed frames: byte loads and stores)
+        return misaligned("mbx_fec_stage");
+    }
     if (n == 0) {
         return 0;
     }
@@ -1972,6 +2066,9 @@ int mbx_decode_parms(int codec, const mbx_param_record* d_records, size_t n, mbe
     REQUIRE_CTX(c);
     if (!d_records || !d_cur || !d_prev || !d_rc || !mbx::codec_streams(codec) || n > 0x7fffffffu) {
         return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (!aligned_to(d_records, 16) || !aligned_to(d_cur, 4) || !aligned_to(d_prev, 4) || !aligned_to(d_rc, 4)) {
+        return misaligned("mbx_decode_parms");
     }
     if (n == 0) {
         return 0;

@@ -9,7 +9,8 @@ so both walking directions and the hand-over of the state are under the oracle.
 Importable without a GPU (tests/test_host_logic.py holds CASES to the table).  Cases without switches run inside the GPU suite's
 process when its environment holds no MBX_* switch; a case with environment switches -- the library reads them once per process --
 and every case of a suite that itself runs under switches runs as `python tests/instance_cases.py <id>` in a fresh child with
-exactly the case's switches: exit status 0 = passed, 1 = a mismatch (printed)."""
+exactly the case's switches: exit status 0 = passed, 1 = a mismatch (printed).  `python tests/instance_cases.py <id> --guarded`
+(tests/test_gpu_memory_contract.py): the same case twice with every buffer in a guarded arena (run_guarded)."""
 import os
 import sys
 from collections import namedtuple
@@ -83,9 +84,78 @@ def child_timeout(case):
     return 180 + case.S * case.T * case.launches // 2000
 
 
-def run_case(case):
+class PlainBuffers:
+    """the buffers of a case as torch allocates them (what the instance tests have always run on)"""
+
+    trace = None
+    OUTPUTS = ("records", "results", "pcm16", "pcmf")
+
+    def layout(self, specs):
+        import torch
+
+        self.bufs = {s.name: torch.empty(s.nbytes, dtype=torch.uint8, device="cuda") for s in specs}
+        return self.bufs
+
+    def load(self, name, bufs, data):
+        import torch
+
+        bufs[name].copy_(torch.from_numpy(np.ascontiguousarray(data).reshape(-1).view(np.uint8)))
+
+    def before_launch(self):
+        for n in self.OUTPUTS:   # (the outputs are reused from launch to launch: a row a launch leaves unwritten must not hold the last launch's)
+            self.bufs[n].fill_(0xA5)
+
+    def after_launch(self, what):
+        pass
+
+    def note(self, label, data):
+        pass
+
+
+class GuardedBuffers(PlainBuffers):
+    """the same buffers in ONE guarded arena (tests/guarded.py): each at exactly the alignment of its kind, exact size, guard bands on
+    both sides, outputs pre-filled with the arena's pattern before every launch, guards and read-only inputs checked after every
+    launch; `trace` keeps the bytes of every output of every launch and of the final state for the two-run comparison"""
+
+    def __init__(self, seed):
+        self.seed, self.trace, self.arena = seed, [], None
+
+    def layout(self, specs):
+        import guarded
+
+        self.arena = guarded.Arena(specs, where="cuda", seed=self.seed)
+        return {s.name: self.arena.view(s.name) for s in specs}
+
+    def load(self, name, bufs, data):
+        self.arena.load(name, data)
+
+    def before_launch(self):
+        self.arena.prefill(*[n for n in self.OUTPUTS if n in self.arena.by_name])
+
+    def after_launch(self, what):
+        self.arena.check(what)
+
+    def note(self, label, data):
+        self.trace.append((label, np.ascontiguousarray(data).reshape(-1).view(np.uint8).copy()))
+
+
+def compare_traces(first, second, what):
+    """two runs of one case from the same inputs, under different guard and pre-fill patterns: byte-identical outputs of every launch,
+    state, RNG state and elision words -- every output byte was written, and nothing outside the inputs was read into a result"""
+    assert [a for a, _ in first] == [a for a, _ in second], what
+    for (label, a), (_, b) in zip(first, second):
+        assert a.size == b.size, (what, label)
+        bad = np.flatnonzero(a != b)
+        assert bad.size == 0, (f"{what}: {label} differs between two runs that differ only in the pre-fill of the outputs and in the guard bytes: "
+                               f"{bad.size} byte(s), first at offset {int(bad[0])}, last at offset {int(bad[-1])} of {a.size}")
+
+
+def run_case(case, mem=None, oracle=True):
     """Runs the case on the current device and compares with the oracle; raises AssertionError on the first mismatch.  The process's
-    environment must already hold case.env (the library reads its switches once)."""
+    environment must already hold case.env (the library reads its switches once).
+    mem: where the buffers of the case live (PlainBuffers by default; GuardedBuffers: every buffer the launches are handed -- frames,
+    records, state pool, RNG pool, elision words, index, PCM, results, caller workspace -- in one guarded arena, checked after every
+    launch).  oracle=False: the launches and the checks of `mem` only (the second of two runs, compared with the first by trace)."""
     import torch
 
     import edge_mix
@@ -107,21 +177,47 @@ def run_case(case):
     assert len(slots) == S and len(set(slots.tolist())) == S
     pool_seeds = np.full(pool, 999, dtype=np.int64)
     pool_seeds[slots] = seeds
+    import guarded
+
+    mem = mem if mem is not None else PlainBuffers()
     L = _native.lib()
     dec = decoder.BatchDecoder(codec, pool, seeds=pool_seeds, resident=resident)
     untouched_state, untouched_rng = dec.state_numpy().copy(), dec.rng_numpy().copy()
     strm = torch.cuda.current_stream().cuda_stream
-    d_index = torch.from_numpy(slots.astype(np.int32)).cuda() if indexed else None
-    ws = torch.empty(int(L.mbx_workspace_bytes(S * T)), dtype=torch.uint8, device="cuda") if case.entry == "batch_ws" else None
+    n = S * T
+    # (IMBE frames are read in 16-bit pieces, and the one-launch and fused instances are selected only for frames on a 4-byte
+    # boundary: exactly that, no better; AMBE frames are read byte by byte and sit on an odd address)
+    specs = [guarded.buf("frames", n * fb, guarded.frames_kind(codec, one_frame=T == 1), readonly=True), guarded.buf("records", n * 16, "records"),
+             guarded.buf("state", dec.state.numel(), "state"), guarded.buf("rng", dec.rng.numel(), "rng"),
+             guarded.buf("pcm16", n * 320, "pcm16"), guarded.buf("pcmf", n * 640, "pcmf"), guarded.buf("results", n * 20, "results")]
+    if resident:
+        specs.append(guarded.buf("resident", pool * 4, "resident"))
+    if indexed:
+        specs.append(guarded.buf("index", S * 4, "index", readonly=True))
+    if case.entry == "batch_ws":
+        specs.append(guarded.buf("workspace", int(L.mbx_workspace_bytes(n)), "workspace"))   # EXACTLY the documented need
+    bufs = mem.layout(specs)
+    bufs["state"].copy_(dec.state)
+    bufs["rng"].copy_(dec.rng)
+    dec.state, dec.rng = bufs["state"], bufs["rng"]   # (plain tensor attributes: every launch and state_numpy() go through them)
+    if resident:
+        bufs["resident"].copy_(dec.resident.view(torch.uint8))
+        dec.resident = bufs["resident"].view(torch.int32)
+    if indexed:
+        mem.load("index", bufs, slots.astype(np.int32))
+    d_index = bufs["index"] if indexed else None
+    ws = bufs.get("workspace")
+    out = {"records": bufs["records"].view(torch.int32).view(n, 4), "results": bufs["results"].view(torch.int32).view(n, 5),
+           "pcm16": bufs["pcm16"].view(torch.int16).view(n, 160), "pcmf": bufs["pcmf"].view(torch.float32).view(n, 160)}
     got = {k: [] for k in ("records", "results", "pcm16", "pcmf")}
     for k in range(n_launch):
         part = np.ascontiguousarray(frames[:, k * T:(k + 1) * T])
+        mem.load("frames", bufs, part)
+        d_frames = bufs["frames"]
+        mem.before_launch()
         if case.entry in ("batch", "staged") or (case.entry == "resident"):
-            out = dec.decode(part.reshape(-1, fb), T, want_float=True, staged=case.entry == "staged")
+            dec.decode(d_frames, T, want_float=True, staged=case.entry == "staged", out=out)
         else:
-            d_frames = dec.to_device(part)
-            out = {"records": torch.empty((S * T, 4), dtype=torch.int32, device="cuda"), "results": torch.empty((S * T, 5), dtype=torch.int32, device="cuda"),
-                   "pcm16": torch.empty((S * T, 160), dtype=torch.int16, device="cuda"), "pcmf": torch.empty((S * T, 160), dtype=torch.float32, device="cuda")}
             o = [out[x].data_ptr() for x in ("pcm16", "pcmf", "results", "records")]
             if case.entry == "batch_ws":
                 rc = L.mbx_process_batch_ws(codec, S, T, d_frames.data_ptr(), dec.state.data_ptr(), dec.rng.data_ptr(), *o, ws.data_ptr(), ws.numel(), strm)
@@ -135,10 +231,22 @@ def run_case(case):
         ran = L.mbx_last_kernel_name(strm)
         assert ran is not None and ran.decode() == case.name, f"{case.id}: launch {k} ran {ran!r}, the case is for {case.name}"
         torch.cuda.synchronize()
+        mem.after_launch(f"{case.id}: launch {k}")
         for x in got:
             got[x].append(out[x].cpu().numpy().reshape(S, T, -1))
+            mem.note(f"launch {k}: {x}", got[x][-1])
+    if mem.trace is not None:   # the state as the launches left it, elision words and all, before anything materialises it
+        mem.note("state as left", dec.state.cpu().numpy())
+        if resident:
+            mem.note("elision words", dec.resident.cpu().numpy())
     got = {x: np.concatenate(v, axis=1) for x, v in got.items()}   # [S, Tt, ...]
-    state, rng = dec.state_numpy(), dec.rng_numpy()
+    state, rng = dec.state_numpy(), dec.rng_numpy()   # (resident: mbx_resident_materialize on the same buffers)
+    torch.cuda.synchronize()
+    mem.after_launch(f"{case.id}: materialize")
+    mem.note("state", state)
+    mem.note("rng", rng)
+    if not oracle:
+        return None
 
     o = oracle_lib.load()
     ref = o.process_batch(codec, S, Tt, frames.reshape(S * Tt, fb), o.init_state(S), o.rng_seeded(seeds))
@@ -156,14 +264,30 @@ def run_case(case):
     return m
 
 
+def run_guarded(case):
+    """the case twice from the same inputs, every buffer in a guarded arena (GuardedBuffers), under two patterns: the first run against
+    the oracle as run_case always does, the second against the first run's bytes"""
+    import torch
+
+    first = GuardedBuffers(seed=1)
+    m = run_case(case, mem=first)
+    first.arena = None
+    torch.cuda.empty_cache()
+    second = GuardedBuffers(seed=2)
+    run_case(case, mem=second, oracle=False)
+    compare_traces(first.trace, second.trace, case.id)
+    return m
+
+
 def main():
     case = BY_ID[sys.argv[1]]
+    guarded_run = len(sys.argv) > 2 and sys.argv[2] == "--guarded"
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     from mbelib_neo_amd import decoder
 
     decoder.ensure_init(0)
     try:
-        m = run_case(case)
+        m = run_guarded(case) if guarded_run else run_case(case)
     except AssertionError as e:
         print(f"MISMATCH {case.id}: {e}")
         return 1
