@@ -1,0 +1,138 @@
+/*
+ * mbx_burst.h -- burst input of the MI355X batch launcher (libmbx_hip.so): a caller's de-interleave schedule applied on the device.
+ *
+ * include/mbx.h starts at the packed wire frame.  A host receives air-interface BURSTS: a P25 phase 1 LDU carries 9 IMBE frames of
+ * one stream, a DMR voice burst 3 AMBE+2 frames, NXDN 4, D-STAR 1, their channel bits interleaved with each other and with sync
+ * words, status symbols and slow data.  The reference leaves that step to its callers (ref include/mbelib-neo/mbelib.h:352,429,505,564:
+ * mbe_process*Frame[f] take the filled imbe_fr / ambe_fr arrays), and so did this library: a per-bit loop on the host, per frame.
+ * Here the caller brings its schedule ONCE -- which received bit goes to which cell of which frame's array: the tables it already
+ * has -- and the library applies it on the device to every burst: "S bursts" is "S streams x T = F frames", stream-major.  No
+ * air-interface table of any standard is written down in this library.
+ *
+ * Conventions are those of mbx.h: d_ pointers are DEVICE pointers, `stream` is a hipStream_t passed as void*, launchers are
+ * asynchronous on `stream`, never synchronise, and return 0 or a negative MBE_STATUS_* / MBX_E* code with the reason in
+ * mbx_last_error().
+ *
+ * Burst formats.
+ *   hard   burst_stride bytes per burst, burst b at d_bursts + b * burst_stride; received bit j at byte j >> 3, mask 0x80 >> (j & 7)
+ *          (MSB first, as everywhere in this library); burst_stride >= ceil(burst_bits / 8), any value; bytes and bits of a burst
+ *          behind bit burst_bits - 1 are never read
+ *   soft   burst_bits mbe_soft_bit per burst in received order, burst b at d_soft + b * burst_bits cells
+ *
+ * Alignment, in the style of the table in mbx.h (kinds not named here keep their row of that table):
+ *   kind        bytes  which pointers
+ *   bursts      1      d_bursts: with d_bursts and burst_stride both multiples of 4 the bursts are fetched in dwords, otherwise byte by byte
+ *   softbursts  2      d_soft of the burst calls: one (bit, reliability) pair is one 16-bit piece; fetched in dwords from the first 4-aligned pair on
+ *   frames      1      d_frames of mbx_deinterleave, for every codec: dwords where they are whole and aligned, single bytes at the edges
+ *   soft        2      d_cells of mbx_deinterleave_soft
+ * Sizes are exact: nothing is read behind the last burst's burst_stride bytes (ceil(burst_bits / 8) of them are read) or outside
+ * the n * burst_bits cells of soft bursts, nothing is written outside the rows each call names.  A launcher that is handed a
+ * pointer below its alignment returns MBE_STATUS_INVALID_ARGUMENT before anything is launched, the call named in mbx_last_error().
+ */
+#ifndef MBX_BURST_H
+#define MBX_BURST_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "mbx_types.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define MBX_BURST_MAX_FRAMES 18   /* frames of one stream in one burst (a P25 LDU: 9) */
+#define MBX_BURST_MAX_BITS   4096 /* received bits of one burst (a P25 LDU: 1,728) */
+#define MBX_MIXED_ROW_BYTES  18   /* the row of mbx_process_batch_mixed ... */
+#define MBX_MIXED_ROW_CELLS  184  /* ... and of mbx_process_batch_soft_mixed */
+
+struct mbx_session; /* mbx.h */
+
+/* ---- the schedule ---------------------------------------------------------------------------------------------------------- */
+
+/* A de-interleave schedule, immutable once made: any number of host threads and streams may use one at the same time. */
+typedef struct mbx_burst_schedule mbx_burst_schedule;
+
+/* Replaces the caller-side loop in front of mbe_processImbe7200x4400Frame[f] / mbe_processAmbe3600x2450Frame[f] /
+ * mbe_processImbe7100x4400Frame[f] / mbe_processAmbe2400Dstar... (ref include/mbelib-neo/mbelib.h:429,505,564,352) that fills
+ * imbe_fr / ambe_fr from the received bits, for every frame of a burst at once.
+ * For frame k of the burst (k < frames_per_burst, in time order) and its i-th channel bit (i < n; n = 144, 72, 142, 72 for codecs
+ * 0..3): received bit src_bit[k*n + i] of the burst goes to cell [cell_row[k*n + i]][cell_col[k*n + i]] of that frame's array.
+ * The three arrays hold frames_per_burst * n ints each.  Burst bits no entry names (sync, status symbols, slow data) are ignored.
+ * Checked on the host before a device is asked for -- MBE_STATUS_INVALID_ARGUMENT, the reason in mbx_last_error():
+ *   codec is one of MBX_CODEC_*;  1 <= frames_per_burst <= MBX_BURST_MAX_FRAMES;  frames_per_burst * n <= burst_bits <= MBX_BURST_MAX_BITS;
+ *   the cells of each frame are a bijection onto the codec's wire cells (the rule of mbx_wire_permutation);
+ *   every src_bit is in [0, burst_bits) and no burst bit is named twice.
+ * Then the schedule is folded into the tables the kernels read and uploaded to the calling thread's CURRENT device (which must
+ * have been mbx_init()ed: MBX_ENODEVICE / MBX_ENOTINIT otherwise, as for every launcher); a schedule used while another device is
+ * current is refused.  Synchronous (one small upload). */
+int mbx_burst_schedule_create(mbx_burst_schedule** out, int codec, int frames_per_burst, int burst_bits, const int* src_bit,
+                              const int* cell_row, const int* cell_col);
+/* frees the device tables (the caller must have no launch in flight that uses the schedule); NULL is allowed */
+int mbx_burst_schedule_destroy(mbx_burst_schedule* sched);
+int mbx_burst_schedule_codec(const mbx_burst_schedule* sched);            /* MBX_CODEC_*, or MBE_STATUS_INVALID_ARGUMENT for NULL */
+int mbx_burst_schedule_frames(const mbx_burst_schedule* sched);           /* frames_per_burst */
+int mbx_burst_schedule_bits(const mbx_burst_schedule* sched);             /* burst_bits */
+size_t mbx_burst_schedule_bytes(const mbx_burst_schedule* sched);         /* ceil(burst_bits / 8): the smallest burst_stride; 0 for NULL */
+
+/* ---- the gather alone ------------------------------------------------------------------------------------------------------ */
+
+/* n hard bursts -> n * frames_per_burst packed wire frames, burst after burst: frame k of burst b is row b * frames_per_burst + k,
+ * at d_frames + row * frame_stride.  The same bytes as the caller-side scatter into imbe_fr / ambe_fr followed by
+ * mbx_pack_imbe7200x4400 / mbx_pack_ambe3600x2450 / mbx_pack_imbe7100x4400 (mbx.h): frame bits that pad the last byte (codec 2) are 0.
+ * frame_stride = the codec's frame size (18 | 9), or MBX_MIXED_ROW_BYTES for an AMBE codec: then bytes 0..8 of each row are
+ * written and bytes 9..17 keep what they hold -- the rows of mbx_process_batch_mixed.  A host with traffic of several air
+ * interfaces calls this once per schedule into disjoint row ranges of one array and then makes ONE mixed launch.
+ * One launch; n = 0 launches nothing. */
+int mbx_deinterleave(const mbx_burst_schedule* sched, const uint8_t* d_bursts, size_t burst_stride, size_t n, uint8_t* d_frames,
+                     size_t frame_stride, void* stream);
+/* n soft bursts -> n * frames_per_burst cell arrays in the reference's shapes (mbe_soft_bit [8][23] | [4][24] | [7][24]: what
+ * mbe_processImbe7200x4400FrameSoft and its kin take, ref include/mbelib-neo/mbelib.h), row b * frames_per_burst + k at
+ * d_cells + row * row_cells cells.  row_cells = the codec's cells (184 | 96 | 168 | 96) or MBX_MIXED_ROW_CELLS (the rows of
+ * mbx_process_batch_soft_mixed).  EVERY cell of a row is written: cells that are not on the wire, and the cells of a mixed row
+ * behind the codec's array, get {0, 0}. */
+int mbx_deinterleave_soft(const mbx_burst_schedule* sched, const mbe_soft_bit* d_soft, size_t n, mbe_soft_bit* d_cells,
+                          size_t row_cells, void* stream);
+
+/* ---- burst launches -------------------------------------------------------------------------------------------------------- */
+
+/* The gather, then the batch step of (codec, S streams, T = frames_per_burst) exactly as the frames calls of mbx.h run it: burst
+ * row s carries the next frames_per_burst frames of pool slot d_stream_index[s] (NULL: slot s).  With d_resident what
+ * mbx_process_batch_resident runs (mbx_process_bursts_soft: mbx_process_batch_soft_resident); with d_resident == NULL the ABI
+ * triplets are whole after the launch: what mbx_process_batch_indexed / mbx_process_batch (soft: mbx_process_batch_soft_resident
+ * without the words) run.  PCM, results, records, state, RNG state and elision words are byte-identical to those calls on the
+ * frames the host would have built, and mbx_last_kernel_name(stream) reports the same stream-stage instance.
+ * Replaces, for S streams at once, the caller's de-interleave loop AND the mbe_process*Frame[f] / mbe_process*FrameSoft calls behind
+ * it (ref include/mbelib-neo/mbelib.h:352,429,505,564).
+ * The gather is ONE launch on `stream` in front of that step and adds no internal stream, event or host synchronisation to it.  The
+ * gathered frames live in the stream's workspace behind the step's own rows: mbx_burst_workspace_frames(sched, S, soft) is what
+ * mbx_reserve_stream(stream, .) must have been given for the call to allocate nothing.
+ * d_pcm16, d_pcmf and d_results may each be NULL (outputs: S * frames_per_burst rows, stream-major); S = 0 returns 0 and launches nothing. */
+int mbx_process_bursts(const mbx_burst_schedule* sched, int S, const int32_t* d_stream_index, const uint8_t* d_bursts,
+                       size_t burst_stride, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16,
+                       float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream);
+int mbx_process_bursts_soft(const mbx_burst_schedule* sched, int S, const int32_t* d_stream_index, const mbe_soft_bit* d_soft,
+                            mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf,
+                            mbe_process_result* d_results, mbx_param_record* d_records, void* stream);
+/* workspace frames (the unit of mbx_reserve_stream / mbx_reserve) a burst launch of S bursts needs; 0 for a NULL schedule or S < 0 */
+size_t mbx_burst_workspace_frames(const mbx_burst_schedule* sched, int S, int soft);
+
+/* ---- sessions -------------------------------------------------------------------------------------------------------------- */
+
+/* mbx_session_submit[_indexed] / mbx_session_submit_soft[_indexed] (mbx.h) fed with bursts in HOST memory: n bursts, burst i for
+ * stream stream_index[i] (NULL: n must be the session's stream count, burst i for stream i), T = frames_per_burst,
+ * n * frames_per_burst <= max_frames_per_submit, the schedule's codec the session's (MBE_STATUS_INVALID_ARGUMENT otherwise).  The
+ * bursts take the road frames take -- pinned buffers are read in place, pageable ones staged, fetched on the compute stream --
+ * then the burst launch above.  Outputs: n * frames_per_burst rows each, as for the frames submits.  Soft bursts are validated
+ * like soft frames (a hard decision > 1: MBE_STATUS_INVALID_BITS, nothing queued).  The first burst submit of a session grows the
+ * compute stream's workspace once. */
+int mbx_session_submit_bursts(struct mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index,
+                              const uint8_t* bursts, size_t burst_stride, int16_t* pcm16, float* pcmf, mbe_process_result* results);
+int mbx_session_submit_bursts_soft(struct mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index,
+                                   const mbe_soft_bit* soft, int16_t* pcm16, float* pcmf, mbe_process_result* results);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* MBX_BURST_H */

@@ -31,5 +31,6 @@ from .layout import (  # noqa: F401
 from ._native import NativeLibraryError, lib, library_path  # noqa: F401
 from . import framegen  # noqa: F401
 from .decoder import BatchDecoder  # noqa: F401
+from .bursts import BurstSchedule, ScheduleArrays, apply_schedule, deinterleave  # noqa: F401
 
-__all__ = ["BatchDecoder", "framegen", "lib", "NativeLibraryError"]
+__all__ = ["BatchDecoder", "BurstSchedule", "ScheduleArrays", "apply_schedule", "deinterleave", "framegen", "lib", "NativeLibraryError"]

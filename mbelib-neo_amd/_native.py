@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI HIP launcher (include/mbx.h).  Fails loudly when the library
+"""ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -118,6 +118,23 @@ _SIGNATURES = {
     "mbx_launch_slices": (C.c_int, [C.c_int, C.c_int, C.c_int]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+# burst input (include/mbx_burst.h): a table of its own, so that EXPORTED_SYMBOLS stays what include/mbx.h declares
+_BURST_SIGNATURES = {
+    "mbx_burst_schedule_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "mbx_burst_schedule_destroy": (C.c_int, [_vp]),
+    "mbx_burst_schedule_codec": (C.c_int, [_vp]),
+    "mbx_burst_schedule_frames": (C.c_int, [_vp]),
+    "mbx_burst_schedule_bits": (C.c_int, [_vp]),
+    "mbx_burst_schedule_bytes": (_sz, [_vp]),
+    "mbx_burst_workspace_frames": (_sz, [_vp, C.c_int, C.c_int]),
+    "mbx_deinterleave": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _vp]),
+    "mbx_deinterleave_soft": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp]),
+    "mbx_process_bursts": (C.c_int, [_vp, C.c_int, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mbx_process_bursts_soft": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mbx_session_submit_bursts": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "mbx_session_submit_bursts_soft": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+}
+BURST_SYMBOLS = tuple(_BURST_SIGNATURES)
 
 
 def lib():
@@ -140,7 +157,7 @@ def lib():
             handle = C.CDLL(path)
         except OSError as e:  # e.g. libamdhip64 not found
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

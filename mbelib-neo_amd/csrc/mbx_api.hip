@@ -15,6 +15,7 @@
 #include "mbx.h"
 #include "mbx_codec.h"
 #include "mbx_device.h"
+#include "mbx_gather.h"
 #include "mbx_kernels.h"
 
 namespace {
@@ -1510,6 +1511,23 @@ static int run_stages(Context* c, unsigned order, const BatchCall& b, InputKind 
     }
     return launch_stream(c, (order & 1u) != 0u, b, ws, slot);
 }
+// An S x T step on the stream slot's own workspace (the last case of run_batch; a burst launch, behind its gather): the one-launch
+// form where the shape has one, the staged launches otherwise.  Caller holds c->mu and has made run_batch's checks.
+static int run_step_on_slot(Context* c, StreamSlot& slot, const BatchCall& b, InputKind kind, const void* d_input) {
+    const uint8_t* const d_frames = kind == kFrames ? static_cast<const uint8_t*>(d_input) : nullptr;
+    int rc = 0;
+    if (d_frames && try_fused_one(c, slot, b, d_frames, true, &rc)) {
+        return rc;
+    }
+    if (needs_workspace(b.codec, b.S, b.T)) {
+        rc = ensure_workspace(c, slot, batch_rows(b), b.stream);
+        if (rc < 0) {
+            return rc;
+        }
+        slot.exp_codec = -1;   // the rows are about to be replaced
+    }
+    return run_stages(c, slot.launches++, b, kind, d_input, slot.workspace, &slot);
+}
 static int run_batch(Context* c, const char* who, const BatchCall& b, InputKind kind, const void* d_input, const CallerWorkspace* caller_ws) {
     const bool mixed = b.stream_codec != nullptr;   // every stream brings its codec (wire frames or soft cells only): b.codec is not looked at
     const mbx::CodecShape* sh = mbx::codec_shape(b.codec);
@@ -1572,18 +1590,7 @@ static int run_batch(Context* c, const char* who, const BatchCall& b, InputKind 
         return run_stages(c, order, b, kind, d_input, static_cast<mbx::FrameParams*>(caller_ws->p), nullptr);
     }
     std::lock_guard<std::mutex> lock(c->mu);
-    StreamSlot& slot = c->slots[b.stream];
-    if (d_frames && try_fused_one(c, slot, b, d_frames, true, &rc)) {
-        return rc;
-    }
-    if (rows) {
-        rc = ensure_workspace(c, slot, n, b.stream);
-        if (rc < 0) {
-            return rc;
-        }
-        slot.exp_codec = -1;   // the rows are about to be replaced
-    }
-    return run_stages(c, slot.launches++, b, kind, d_input, slot.workspace, &slot);
+    return run_step_on_slot(c, c->slots[b.stream], b, kind, d_input);
 }
 
 int mbx_process_records(int codec, int S, int T, const mbx_param_record* d_records, mbe_parms* d_state,
@@ -1814,6 +1821,71 @@ int mbx_process_batch_soft_resident(int codec, int S, int T, const int32_t* d_st
     REQUIRE_CTX(c);
     const BatchCall b{codec, S, T, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index, d_resident};
     return run_batch(c, "mbx_process_batch_soft_resident", b, kSoft, d_soft, nullptr);
+}
+
+// ---- burst launches (include/mbx_burst.h): the gather of mbx_burst.hip, then run_step_on_slot ------------------------------------------
+// One launch in front of the step the frames calls run for (codec, S, T = frames per burst), on the caller's stream.  The gathered
+// frames live in the stream slot's workspace BEHIND the S * T rows of the step (256-byte aligned: a T = 1 step takes its one-launch
+// kernel), so c->mu is held from the growth of the workspace to the last launch, as run_batch holds it.
+static int process_bursts(const char* who, bool soft, const mbx_burst_schedule* sched, int S, const int32_t* d_stream_index, const void* d_bursts,
+                          size_t burst_stride, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf,
+                          mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
+    char text[160];
+    // (alignment first: it needs neither the schedule nor a device)
+    if (!batch_pointers_aligned(d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, d_stream_index, d_resident, nullptr) ||
+        !aligned_to(d_bursts, soft ? 2 : 1)) {
+        return misaligned(who);
+    }
+    if (!sched || !d_bursts || !d_records || !d_state_pool || !d_rng_pool || S < 0) {
+        snprintf(text, sizeof(text), "%s: schedule, bursts, state, RNG state and records are all needed", who);
+        return fail(MBE_STATUS_INVALID_ARGUMENT, text);
+    }
+    const mbx::BurstShape sh = mbx::burst_shape(sched);
+    if (!soft && burst_stride < sh.bytes) {
+        snprintf(text, sizeof(text), "%s: burst_stride is below ceil(burst_bits / 8)", who);
+        return fail(MBE_STATUS_INVALID_ARGUMENT, text);
+    }
+    REQUIRE_CTX(c);
+    if (sh.device != c->device) {
+        snprintf(text, sizeof(text), "%s: the schedule was made on device %d, the current device is %d", who, sh.device, c->device);
+        return fail(MBE_STATUS_INVALID_ARGUMENT, text);
+    }
+    if (S == 0) {
+        return 0;
+    }
+    const size_t n = (size_t)S * (size_t)sh.frames;
+    if (n > 0x7fffffffu) {
+        snprintf(text, sizeof(text), "%s: more than 2^31-1 frames in one launch", who);
+        return fail(MBE_STATUS_INVALID_ARGUMENT, text);
+    }
+    const BatchCall b{sh.codec, S, sh.frames, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index, d_resident};
+    std::lock_guard<std::mutex> lock(c->mu);
+    StreamSlot& slot = c->slots[stream];
+    int rc = ensure_workspace(c, slot, mbx_burst_workspace_frames(sched, S, soft ? 1 : 0), stream);
+    if (rc < 0) {
+        return rc;
+    }
+    slot.exp_codec = -1;   // rows an earlier mbx_expand_records() left behind the step's own are being replaced
+    void* const gathered = slot.workspace + n;
+    rc = mbx::burst_gather(sched, soft, d_bursts, burst_stride, (size_t)S, gathered, soft ? sh.cells : sh.frame_bytes, stream);
+    if (rc < 0) {
+        return rc;
+    }
+    return run_step_on_slot(c, slot, b, soft ? kSoft : kFrames, gathered);
+}
+
+int mbx_process_bursts(const mbx_burst_schedule* sched, int S, const int32_t* d_stream_index, const uint8_t* d_bursts, size_t burst_stride,
+                       mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf,
+                       mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
+    return process_bursts("mbx_process_bursts", false, sched, S, d_stream_index, d_bursts, burst_stride, d_state_pool, d_resident, d_rng_pool, d_pcm16,
+                          d_pcmf, d_results, d_records, stream);
+}
+
+int mbx_process_bursts_soft(const mbx_burst_schedule* sched, int S, const int32_t* d_stream_index, const mbe_soft_bit* d_soft, mbe_parms* d_state_pool,
+                            uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
+                            mbx_param_record* d_records, void* stream) {
+    return process_bursts("mbx_process_bursts_soft", true, sched, S, d_stream_index, d_soft, 0, d_state_pool, d_resident, d_rng_pool, d_pcm16, d_pcmf,
+                          d_results, d_records, stream);
 }
 
 // ---- ragged batches: run_batch with BatchCall::frame_offset ---------------------------------------------------------------------------

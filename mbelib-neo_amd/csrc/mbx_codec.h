@@ -1,6 +1,6 @@
 // mbx_codec.h -- what a codec IS on the host side, declared once: the shape of its frame in every form the launchers and the
 // mbe_* shim handle it in (the reference's cell array, the packed wire frame, the parameter bits), and which codec's FEC front end
-// and stream stage its frames go through.  Host-only and private: included by mbx_api.hip, mbx_session.hip and mbe_shim.cpp, each
+// and stream stage its frames go through.  Host-only and private: included by mbx_api.hip, mbx_session.hip, mbx_burst.hip and mbe_shim.cpp, each
 // of which compiles its own copy of these constants; nothing here is exported.  (The kernels of mbx_fec.hip unpack the same rows
 // with widths of their own: device code does not read this table.)
 // A new codec, or a change to a frame form: its row here, its row in kCodecKernels (mbx_api.hip), its case in the shim's

@@ -1,5 +1,5 @@
 // mbx_kernels.h -- every __global__ kernel of libmbx_hip.so, declared exactly once.
-// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_expand.hip, mbx_stream.hip, mbx_api.hip) and by the
+// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
 // one that launches it (mbx_api.hip), so a parameter list that drifts from its definition is a compile error (an unmatched
 // overload at the launch site or in the instance table), not an unresolved symbol when the library is loaded.
 // A new kernel: declare it here, define it, and -- a stream-stage instance -- give it its row in kInstances (mbx_api.hip).
@@ -120,6 +120,10 @@ __global__ void soft_front_ambe_kernel(const mbe_soft_bit*, size_t, mbx_param_re
 __global__ void expand_imbe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
 __global__ void expand_ambe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
 __global__ void expand_ambe2400_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
+
+// ---- mbx_burst.hip: burst input, in front of a batch step -- received bursts -> wire frames / cell arrays by a caller's schedule -----------
+__global__ void burst_gather_kernel(const uint8_t*, size_t, size_t, int, int, int, const uint16_t*, uint8_t*, int, int);
+__global__ void burst_gather_soft_kernel(const mbe_soft_bit*, size_t, int, int, int, const uint16_t*, mbe_soft_bit*, int, int);
 
 // ---- mbx_api.hip ---------------------------------------------------------------------------------------------------------------
 // (C linkage: defined inside the extern "C" block of the entry points, so the profiler prints the bare name)

@@ -25,7 +25,9 @@
 #include <vector>
 
 #include "mbx.h"
+#include "mbx_burst.h"
 #include "mbx_codec.h"
+#include "mbx_gather.h"
 
 void mbx_set_error_text(const char* text);   // mbx_api.hip: the per-thread text behind mbx_last_error()
 
@@ -73,9 +75,13 @@ struct Slot {
     mbe_process_result* d_results = nullptr;
     int32_t*            d_index = nullptr;
     void*               d_workspace = nullptr;
+    uint8_t*            d_bursts = nullptr;   // bursts (hard or soft), grown by the burst submits that need more
+    size_t              bursts_cap = 0;
     // pinned staging, allocated on first need
     uint8_t*            h_in = nullptr;
     uint8_t*            h_soft = nullptr;
+    uint8_t*            h_bursts = nullptr;   // ... and their pinned staging
+    size_t              h_bursts_cap = 0;
     int32_t*            h_index = nullptr;
     int16_t*            h_pcm16 = nullptr;
     float*              h_pcmf = nullptr;
@@ -164,12 +170,19 @@ bool range_ok(const mbx_session* s, int first, int count) {
     return s && first >= 0 && count >= 0 && (long long)first + count <= s->streams;
 }
 
+// a submit of BURSTS (include/mbx_burst.h): `frames` holds n bursts of `bytes` bytes each, T is the schedule's frames per burst
+struct BurstIn {
+    const mbx_burst_schedule* sched;
+    size_t                    stride;   // hard bursts: the caller's burst_stride
+    size_t                    bytes;    // one burst in the input: burst_stride, or burst_bits cells
+};
+
 // `soft`: frames are mbe_soft_bit cells (soft_bytes per frame) instead of wire frames (frame_bytes)
 int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-            mbe_process_result* results, mbx_param_record* records);
+            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst);
 
 int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-           mbe_process_result* results, mbx_param_record* records) {
+           mbe_process_result* results, mbx_param_record* records, const BurstIn* burst = nullptr) {
     if (!s || !frames || n < 0 || T < 0 || n > s->streams || (size_t)n * (size_t)T > s->max_frames) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
@@ -181,7 +194,8 @@ int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frame
         return 0;
     }
     if (soft) {   // a hard decision > 1 is refused before anything is queued (ref mbe_validate_soft_bits, src/internal/mbe_result.h:31-42)
-        const int rc = mbx_validate_soft_bits(static_cast<const mbe_soft_bit*>(frames), (size_t)n * (size_t)T * (s->soft_bytes / sizeof(mbe_soft_bit)));
+        const size_t cells = burst ? (size_t)n * (burst->bytes / sizeof(mbe_soft_bit)) : (size_t)n * (size_t)T * (s->soft_bytes / sizeof(mbe_soft_bit));
+        const int rc = mbx_validate_soft_bits(static_cast<const mbe_soft_bit*>(frames), cells);
         if (rc < 0) {
             return rc;
         }
@@ -204,7 +218,7 @@ int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frame
     }
     // From here on work is queued on the three streams against this slot's buffers.  If anything fails halfway the slot is
     // NOT marked busy, so before the error goes back the streams are drained: the next submit may reuse the slot at once.
-    rc = enqueue(s, sl, n, T, index, frames, soft, pcm16, pcmf, results, records);
+    rc = enqueue(s, sl, n, T, index, frames, soft, pcm16, pcmf, results, records, burst);
     if (rc < 0) {
         (void)hipStreamSynchronize(s->s_comp);
         (void)hipStreamSynchronize(s->s_out);
@@ -218,26 +232,45 @@ int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frame
 }
 
 int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-            mbe_process_result* results, mbx_param_record* records) {
+            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst) {
     int rc = 0;
     const size_t nf = (size_t)n * (size_t)T;
     // ---- in ----
     // Soft frames are 368 / 336 / 192 B each against 18 / 9: their device buffer and their pinned staging belong to the slot's
-    // first soft submit, so a session that never sees one pays for neither.
+    // first soft submit, so a session that never sees one pays for neither.  Bursts likewise: their buffers belong to the burst
+    // submits and grow with them (the slot's earlier batch is finished: nothing reads the old ones).
     const size_t in_bytes = soft ? s->soft_bytes : s->frame_bytes;
-    uint8_t*& stage = soft ? sl.h_soft : sl.h_in;
-    if (soft && !sl.d_soft) {
+    const size_t in_total = burst ? (size_t)n * burst->bytes : nf * in_bytes;
+    uint8_t*& stage = burst ? sl.h_bursts : (soft ? sl.h_soft : sl.h_in);
+    if (burst && sl.bursts_cap < in_total) {
+        (void)hipFree(sl.d_bursts);
+        sl.d_bursts = nullptr;
+        sl.bursts_cap = 0;
+        S_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_bursts), in_total));
+        sl.bursts_cap = in_total;
+    }
+    if (!burst && soft && !sl.d_soft) {
         S_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_soft), s->max_frames * s->soft_bytes));
     }
     const uint8_t* src = static_cast<const uint8_t*>(frames);
     // The frames (and the stream index) are fetched by a kernel on the COMPUTE stream, not by a DMA copy: see stage_in_kernel
     // (mbx_fec.hip).  A pinned buffer that is not 16-byte aligned goes through the slot's own pinned staging like a pageable one.
     if (!is_pinned(frames) || (reinterpret_cast<uintptr_t>(src) & 15u)) {
-        rc = pinned(stage, s->max_frames * in_bytes);
-        if (rc < 0) {
-            return rc;
+        if (burst) {
+            if (sl.h_bursts_cap < in_total) {
+                (void)hipHostFree(sl.h_bursts);
+                sl.h_bursts = nullptr;
+                sl.h_bursts_cap = 0;
+                S_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.h_bursts), in_total, hipHostMallocDefault));
+                sl.h_bursts_cap = in_total;
+            }
+        } else {
+            rc = pinned(stage, s->max_frames * in_bytes);
+            if (rc < 0) {
+                return rc;
+            }
         }
-        memcpy(stage, frames, nf * in_bytes);
+        memcpy(stage, frames, in_total);
         src = stage;
     }
     const void* dev_view = src;   // what the GPU dereferences: the same address for hipHostMalloc memory, possibly another one for
@@ -247,7 +280,8 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
     } else {
         (void)hipGetLastError();
     }
-    rc = mbx_stage_in(soft ? static_cast<void*>(sl.d_soft) : static_cast<void*>(sl.d_frames), dev_view, nf * in_bytes, s->s_comp);
+    void* const d_in = burst ? static_cast<void*>(sl.d_bursts) : (soft ? static_cast<void*>(sl.d_soft) : static_cast<void*>(sl.d_frames));
+    rc = mbx_stage_in(d_in, dev_view, in_total, s->s_comp);
     if (rc < 0) {
         return rc;
     }
@@ -266,7 +300,13 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
     int16_t* d16 = pcm16 ? sl.d_pcm16 : nullptr;
     float*   dfl = pcmf ? sl.d_pcmf : nullptr;
     mbe_process_result* dres = results ? sl.d_results : nullptr;
-    if (soft) {   // the soft twin of the resident launcher takes every form: index or none, resident words or plain triplets
+    if (burst && soft) {   // the gather in front of the step the frames submits run: resident words or plain triplets, index or none
+        rc = mbx_process_bursts_soft(burst->sched, n, index ? sl.d_index : nullptr, reinterpret_cast<const mbe_soft_bit*>(sl.d_bursts), s->d_state,
+                                     s->d_resident, s->d_rng, d16, dfl, dres, sl.d_records, s->s_comp);
+    } else if (burst) {
+        rc = mbx_process_bursts(burst->sched, n, index ? sl.d_index : nullptr, sl.d_bursts, burst->stride, s->d_state, s->d_resident, s->d_rng, d16,
+                                dfl, dres, sl.d_records, s->s_comp);
+    } else if (soft) {   // the soft twin of the resident launcher takes every form: index or none, resident words or plain triplets
         rc = mbx_process_batch_soft_resident(s->codec, n, T, index ? sl.d_index : nullptr, sl.d_soft, s->d_state, s->d_resident, s->d_rng,
                                              d16, dfl, dres, sl.d_records, s->s_comp);
     } else if (s->d_resident) {   // the session owns the state between submits: the resident form (no prev_mp_enhanced traffic, lazy prev_mp)
@@ -423,6 +463,8 @@ int mbx_session_destroy(mbx_session* s) {
         (void)hipFree(sl.d_results);
         (void)hipFree(sl.d_index);
         (void)hipFree(sl.d_workspace);
+        (void)hipFree(sl.d_bursts);
+        (void)hipHostFree(sl.h_bursts);
         (void)hipHostFree(sl.h_in);
         (void)hipHostFree(sl.h_soft);
         (void)hipHostFree(sl.h_index);
@@ -566,6 +608,43 @@ int mbx_session_submit_soft_indexed(mbx_session* s, int n, int T, const int32_t*
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     return submit(s, n, T, stream_index, soft, true, pcm16, pcmf, results, records);
+}
+
+// ---- burst submits (include/mbx_burst.h) ---------------------------------------------------------------------------------------------
+static int submit_bursts(const char* who, mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index, const void* bursts,
+                         size_t burst_stride, bool soft, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
+    char text[160];
+    if (!s || !sched || !bursts || n < 0) {
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    const mbx::BurstShape sh = mbx::burst_shape(sched);
+    if (sh.codec != s->codec || sh.device != s->device) {
+        snprintf(text, sizeof(text), "%s: the schedule is of another codec or device than the session", who);
+        mbx_set_error_text(text);
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (!soft && burst_stride < sh.bytes) {
+        snprintf(text, sizeof(text), "%s: burst_stride is below ceil(burst_bits / 8)", who);
+        mbx_set_error_text(text);
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if ((!stream_index && n != s->streams) || (size_t)n * (size_t)sh.frames > s->max_frames) {
+        snprintf(text, sizeof(text), "%s: without an index n is the session's stream count; n * frames_per_burst <= max_frames_per_submit", who);
+        mbx_set_error_text(text);
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    const BurstIn in{sched, burst_stride, soft ? (size_t)sh.bits * sizeof(mbe_soft_bit) : burst_stride};
+    return submit(s, n, sh.frames, stream_index, bursts, soft, pcm16, pcmf, results, nullptr, &in);
+}
+
+int mbx_session_submit_bursts(mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index, const uint8_t* bursts,
+                              size_t burst_stride, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
+    return submit_bursts("mbx_session_submit_bursts", s, sched, n, stream_index, bursts, burst_stride, false, pcm16, pcmf, results);
+}
+
+int mbx_session_submit_bursts_soft(mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index, const mbe_soft_bit* soft,
+                                   int16_t* pcm16, float* pcmf, mbe_process_result* results) {
+    return submit_bursts("mbx_session_submit_bursts_soft", s, sched, n, stream_index, soft, 0, true, pcm16, pcmf, results);
 }
 
 }  // extern "C"

@@ -157,6 +157,48 @@ class BatchDecoder:
         _native.check(rc, "mbx_process_batch_soft_resident")
         return out
 
+    def decode_bursts(self, schedule, bursts, soft=False, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None,
+                      burst_stride=None):
+        """Received bursts instead of frames: `schedule` (bursts.BurstSchedule, of this decoder's codec) says where the channel bits of
+        the F frames of a burst sit; burst row i carries the next F frames of stream i (stream_index[i]).  One mbx_process_bursts /
+        _soft call: the gather on the device, then the step decode(frames, T=F) / decode_soft run, on this decoder's state, resident
+        or not.  bursts: uint8 tensor or array -- hard: n bursts of burst_stride bytes (default ceil(burst_bits / 8)), MSB first;
+        soft=True: [n, burst_bits, 2] (bit, reliability).  Returns the dict of decode at T = F."""
+        torch = _torch()
+        if schedule.codec != self.codec:
+            raise ValueError("the schedule is of another codec than the decoder")
+        if soft and isinstance(bursts, np.ndarray) and np.ascontiguousarray(bursts, dtype=np.uint8).reshape(-1, 2)[:, 0].max(initial=0) > 1:
+            raise ValueError("soft bursts: a hard decision is not 0 or 1")
+        d_bursts = self.to_device(np.ascontiguousarray(bursts, dtype=np.uint8) if isinstance(bursts, np.ndarray) else bursts)
+        if d_bursts.dtype != torch.uint8 or not d_bursts.is_contiguous():
+            raise ValueError("bursts must be a contiguous uint8 tensor")
+        n = self.streams if stream_index is None else int(stream_index.numel())
+        stride = schedule.burst_bytes if burst_stride is None else int(burst_stride)
+        if d_bursts.numel() != n * (schedule.burst_bits * 2 if soft else stride):
+            raise ValueError("bursts must hold one burst per batch row")
+        if stream_index is not None:
+            if stream_index.dtype != torch.int32 or stream_index.device != self.device:
+                raise ValueError("stream_index must be an int32 tensor on the decoder's device")
+            if n and (int(torch.unique(stream_index).numel()) != n or int(stream_index.min()) < 0 or int(stream_index.max()) >= self.streams):
+                raise ValueError("stream_index: out of range, or a stream listed twice (two rows would race on one state)")
+        if out is None:
+            out = self.make_outputs(schedule.frames_per_burst, want_pcm16, want_float, want_results, streams=n)
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        L = _native.lib()
+        tail = (self.state.data_ptr(), ptr(self.resident), self.rng.data_ptr(), ptr(out["pcm16"]), ptr(out["pcmf"]), ptr(out["results"]),
+                out["records"].data_ptr(), None)
+        with torch.cuda.device(self.device):
+            tail = tail[:-1] + (torch.cuda.current_stream().cuda_stream,)
+            if soft:
+                rc = L.mbx_process_bursts_soft(schedule.handle, n, ptr(stream_index), d_bursts.data_ptr(), *tail)
+            else:
+                rc = L.mbx_process_bursts(schedule.handle, n, ptr(stream_index), d_bursts.data_ptr(), stride, *tail)
+        _native.check(rc, "mbx_process_bursts")
+        return out
+
     def decode_ragged(self, frames, counts, soft=False, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None,
                       codec=None):
         """A frame count per stream: row i of the batch brings counts[i] >= 0 frames (host sequence or array), its rows of `frames`
