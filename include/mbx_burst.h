@@ -13,21 +13,30 @@
  * asynchronous on `stream`, never synchronise, and return 0 or a negative MBE_STATUS_* / MBX_E* code with the reason in
  * mbx_last_error().
  *
- * Burst formats.
- *   hard   burst_stride bytes per burst, burst b at d_bursts + b * burst_stride; received bit j at byte j >> 3, mask 0x80 >> (j & 7)
- *          (MSB first, as everywhere in this library); burst_stride >= ceil(burst_bits / 8), any value; bytes and bits of a burst
- *          behind bit burst_bits - 1 are never read
- *   soft   burst_bits mbe_soft_bit per burst in received order, burst b at d_soft + b * burst_bits cells
+ * Burst formats.  The FORM of a schedule (MBX_BURST_FORM_*, below) says how a receiver holds its bursts; src_bit always counts
+ * received BITS, in every form.
+ *   hard   burst_stride bytes per burst, burst b at d_bursts + b * burst_stride; burst_stride >= mbx_burst_schedule_bytes(), any
+ *          value; of a burst exactly mbx_burst_schedule_bytes() bytes are read, never the bytes or bits behind bit burst_bits - 1
+ *            PACKED  received bit j at byte j >> 3, mask 0x80 >> (j & 7) (MSB first, as everywhere in this library)
+ *            BITS    received bit j is bit 0 of byte j
+ *            DIBITS  received bits 2d and 2d + 1 are bits 1 and 0 of byte d (the first bit of a symbol is the upper one)
+ *   soft   mbx_burst_schedule_soft_cells() mbe_soft_bit-sized cells per burst in received order, dense: burst b at
+ *          d_soft + b * soft_cells cells
+ *            PACKED, BITS  one mbe_soft_bit per received bit
+ *            DIBITS        one {dibit, reliability} pair per dibit: field `bit` carries the dibit, both bits take the reliability
+ * The device never validates: of a BITS byte `& 1` is used, of a DIBITS byte or dibit cell `& 3`, and a soft hard decision goes
+ * on as it came (as for soft frames, mbx.h).  Input on the device is the caller's to check; mbx_burst_validate is the host check,
+ * and the session submits call it.
  *
  * Alignment, in the style of the table in mbx.h (kinds not named here keep their row of that table):
  *   kind        bytes  which pointers
  *   bursts      1      d_bursts: with d_bursts and burst_stride both multiples of 4 the bursts are fetched in dwords, otherwise byte by byte
- *   softbursts  2      d_soft of the burst calls: one (bit, reliability) pair is one 16-bit piece; fetched in dwords from the first 4-aligned pair on
+ *   softbursts  2      d_soft of the burst calls: one (bit | dibit, reliability) pair is one 16-bit piece; fetched in dwords from the first 4-aligned pair on
  *   frames      1      d_frames of mbx_deinterleave, for every codec: dwords where they are whole and aligned, single bytes at the edges
  *   soft        2      d_cells of mbx_deinterleave_soft
- * Sizes are exact: nothing is read behind the last burst's burst_stride bytes (ceil(burst_bits / 8) of them are read) or outside
- * the n * burst_bits cells of soft bursts, nothing is written outside the rows each call names.  A launcher that is handed a
- * pointer below its alignment returns MBE_STATUS_INVALID_ARGUMENT before anything is launched, the call named in mbx_last_error().
+ * Sizes are exact: nothing is read behind the last burst's burst_stride bytes (mbx_burst_schedule_bytes() of them are read) or
+ * outside the n * soft_cells cells of soft bursts, nothing is written outside the rows each call names.  A launcher that is handed
+ * a pointer below its alignment returns MBE_STATUS_INVALID_ARGUMENT before anything is launched, the call named in mbx_last_error().
  */
 #ifndef MBX_BURST_H
 #define MBX_BURST_H
@@ -68,12 +77,37 @@ typedef struct mbx_burst_schedule mbx_burst_schedule;
  * current is refused.  Synchronous (one small upload). */
 int mbx_burst_schedule_create(mbx_burst_schedule** out, int codec, int frames_per_burst, int burst_bits, const int* src_bit,
                               const int* cell_row, const int* cell_col);
+
+/* How a receiver holds its bursts.  A 4-level FSK / C4FM demodulator emits one symbol per sample point, so the callers of the
+ * reference keep one byte per dibit (or per bit), and one reliability per symbol: those bursts are taken as they are. */
+#define MBX_BURST_FORM_PACKED 0 /* 8 received bits per byte, MSB first; soft: one mbe_soft_bit per bit */
+#define MBX_BURST_FORM_BITS   1 /* one byte per received bit, the bit in bit 0; soft: one mbe_soft_bit per bit (as PACKED) */
+#define MBX_BURST_FORM_DIBITS 2 /* one byte per dibit: received bit 2d = (byte >> 1) & 1, bit 2d + 1 = byte & 1; soft: one
+                                   {dibit, reliability} pair per dibit in an mbe_soft_bit-sized cell */
+/* mbx_burst_schedule_create with the form of the bursts and a fixed descrambling sequence: invert (HOST memory, burst_bits bytes of
+ * 0 / 1, or NULL for none) says which received bits arrive inverted.  A hard bit is flipped; of a soft bit the hard decision is
+ * flipped and the reliability kept.  Bits no entry names stay ignored, frame bits that pad the last byte (codec 2) stay 0 and
+ * cells that are not on the wire stay {0, 0} whatever the sequence says.  Only a sequence that is a property of the burst POSITION
+ * can be stated: one that depends on the data is the caller's.  mbx_burst_schedule_create(...) is this call with
+ * MBX_BURST_FORM_PACKED and NULL.  Refused like the rest, before a device is asked for: a form that is none of the three, the
+ * dibit form with an odd burst_bits, an invert byte above 1. */
+int mbx_burst_schedule_create_form(mbx_burst_schedule** out, int codec, int frames_per_burst, int burst_bits, const int* src_bit,
+                                   const int* cell_row, const int* cell_col, int form, const uint8_t* invert);
 /* frees the device tables (the caller must have no launch in flight that uses the schedule); NULL is allowed */
 int mbx_burst_schedule_destroy(mbx_burst_schedule* sched);
 int mbx_burst_schedule_codec(const mbx_burst_schedule* sched);            /* MBX_CODEC_*, or MBE_STATUS_INVALID_ARGUMENT for NULL */
 int mbx_burst_schedule_frames(const mbx_burst_schedule* sched);           /* frames_per_burst */
 int mbx_burst_schedule_bits(const mbx_burst_schedule* sched);             /* burst_bits */
-size_t mbx_burst_schedule_bytes(const mbx_burst_schedule* sched);         /* ceil(burst_bits / 8): the smallest burst_stride; 0 for NULL */
+int mbx_burst_schedule_form(const mbx_burst_schedule* sched);             /* MBX_BURST_FORM_*, or MBE_STATUS_INVALID_ARGUMENT for NULL */
+/* the smallest burst_stride of this schedule's hard bursts: ceil(burst_bits / 8) (PACKED), burst_bits (BITS), burst_bits / 2 (DIBITS); 0 for NULL */
+size_t mbx_burst_schedule_bytes(const mbx_burst_schedule* sched);
+/* mbe_soft_bit-sized cells of one soft burst: burst_bits, or burst_bits / 2 in the dibit form; 0 for NULL */
+size_t mbx_burst_schedule_soft_cells(const mbx_burst_schedule* sched);
+/* The host check of n bursts in HOST memory (soft != 0: soft bursts, burst_stride is not looked at): 0, MBE_STATUS_INVALID_ARGUMENT
+ * (NULL, a burst_stride below mbx_burst_schedule_bytes()), or MBE_STATUS_INVALID_BITS for a BITS byte above 1, a DIBITS byte or a
+ * dibit cell above 3, a hard decision of a per-bit soft cell above 1.  Only the bytes and cells a gather would read are looked at:
+ * not the padding of the stride.  No device is needed. */
+int mbx_burst_validate(const mbx_burst_schedule* sched, const void* bursts, size_t burst_stride, size_t n, int soft);
 
 /* ---- the gather alone ------------------------------------------------------------------------------------------------------ */
 
@@ -123,9 +157,9 @@ size_t mbx_burst_workspace_frames(const mbx_burst_schedule* sched, int S, int so
  * stream stream_index[i] (NULL: n must be the session's stream count, burst i for stream i), T = frames_per_burst,
  * n * frames_per_burst <= max_frames_per_submit, the schedule's codec the session's (MBE_STATUS_INVALID_ARGUMENT otherwise).  The
  * bursts take the road frames take -- pinned buffers are read in place, pageable ones staged, fetched on the compute stream --
- * then the burst launch above.  Outputs: n * frames_per_burst rows each, as for the frames submits.  Soft bursts are validated
- * like soft frames (a hard decision > 1: MBE_STATUS_INVALID_BITS, nothing queued).  The first burst submit of a session grows the
- * compute stream's workspace once. */
+ * then the burst launch above.  Outputs: n * frames_per_burst rows each, as for the frames submits.  Bursts of every form that
+ * can be invalid are checked with mbx_burst_validate first, as soft frames are (MBE_STATUS_INVALID_BITS, nothing queued: state, RNG
+ * state and outputs keep their bytes).  The first burst submit of a session grows the compute stream's workspace once. */
 int mbx_session_submit_bursts(struct mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index,
                               const uint8_t* bursts, size_t burst_stride, int16_t* pcm16, float* pcmf, mbe_process_result* results);
 int mbx_session_submit_bursts_soft(struct mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index,

@@ -121,11 +121,15 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 # burst input (include/mbx_burst.h): a table of its own, so that EXPORTED_SYMBOLS stays what include/mbx.h declares
 _BURST_SIGNATURES = {
     "mbx_burst_schedule_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "mbx_burst_schedule_create_form": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     "mbx_burst_schedule_destroy": (C.c_int, [_vp]),
     "mbx_burst_schedule_codec": (C.c_int, [_vp]),
     "mbx_burst_schedule_frames": (C.c_int, [_vp]),
     "mbx_burst_schedule_bits": (C.c_int, [_vp]),
+    "mbx_burst_schedule_form": (C.c_int, [_vp]),
     "mbx_burst_schedule_bytes": (_sz, [_vp]),
+    "mbx_burst_schedule_soft_cells": (_sz, [_vp]),
+    "mbx_burst_validate": (C.c_int, [_vp, _vp, _sz, _sz, C.c_int]),
     "mbx_burst_workspace_frames": (_sz, [_vp, C.c_int, C.c_int]),
     "mbx_deinterleave": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _vp]),
     "mbx_deinterleave_soft": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _vp]),

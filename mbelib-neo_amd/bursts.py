@@ -5,6 +5,11 @@ are not voice at all.  The caller states ONCE where every channel bit sits -- fo
 ``src_bit[k, i]`` of the burst goes to cell ``[cell_row[k, i]][cell_col[k, i]]`` of that frame's imbe_fr / ambe_fr array -- and the
 library applies that to every burst: ``deinterleave`` (the gather alone), ``BatchDecoder.decode_bursts`` (gather + decode).
 
+A schedule also says in which FORM the receiver holds its bursts (FORM_PACKED: 8 bits per byte, MSB first; FORM_BITS: one byte per
+bit; FORM_DIBITS: one byte per dibit, and for soft input one {dibit, reliability} pair per dibit) and, optionally, which received
+bits arrive inverted (``invert``: a fixed descrambling sequence, one 0 / 1 per received bit).  ``src_bit`` counts received BITS in
+every form.  ``to_form`` turns packed bursts into the form of a schedule.
+
 ``apply_schedule`` is the same thing in numpy, on the host: the definition, and what the tests expect of the kernels.  No
 air-interface table of any standard is written here; ``random_schedule`` and ``gap_schedule`` make schedules of a given SHAPE.
 """
@@ -17,6 +22,7 @@ from .layout import FRAME_BYTES, FRAME_CELLS, ROW_WIDTHS
 
 MAX_FRAMES, MAX_BITS = 18, 4096          # MBX_BURST_MAX_FRAMES, MBX_BURST_MAX_BITS
 MIXED_ROW_BYTES, MIXED_ROW_CELLS = 18, 184
+FORM_PACKED, FORM_BITS, FORM_DIBITS = 0, 1, 2   # MBX_BURST_FORM_*
 
 
 def channel_bits(codec):
@@ -34,32 +40,52 @@ def wire_bit_of_cell(codec, row, col):
 
 
 class ScheduleArrays:
-    """The three integer arrays of a schedule, [frames_per_burst, channel_bits(codec)] each, on the host.  Checks shapes only: whether
-    the schedule is a valid one is the library's to say (mbx_burst_schedule_create)."""
+    """The three integer arrays of a schedule, [frames_per_burst, channel_bits(codec)] each, on the host, the form of its bursts and
+    its inversion sequence (None, or burst_bits values of 0 / 1).  Checks shapes only: whether the schedule is a valid one is the
+    library's to say (mbx_burst_schedule_create_form)."""
 
-    def __init__(self, codec, frames_per_burst, burst_bits, src_bit, cell_row, cell_col):
+    def __init__(self, codec, frames_per_burst, burst_bits, src_bit, cell_row, cell_col, form=FORM_PACKED, invert=None):
         self.codec, self.frames_per_burst, self.burst_bits = int(codec), int(frames_per_burst), int(burst_bits)
         if self.codec not in FRAME_BYTES:
             raise ValueError("no such codec")
         shape = (self.frames_per_burst, channel_bits(self.codec))
         self.src_bit, self.cell_row, self.cell_col = (np.ascontiguousarray(a, dtype=np.int32).reshape(shape) for a in (src_bit, cell_row, cell_col))
+        self.form = int(form)
+        self.invert = None if invert is None else np.ascontiguousarray(invert, dtype=np.uint8).reshape(self.burst_bits)
+
+    @property
+    def packed_bytes(self):
+        """bytes of one hard burst in the packed form, whatever the schedule's own"""
+        return (self.burst_bits + 7) // 8
 
     @property
     def burst_bytes(self):
-        return (self.burst_bits + 7) // 8
+        """the smallest burst_stride of a hard burst in the schedule's form (mbx_burst_schedule_bytes)"""
+        return {FORM_BITS: self.burst_bits, FORM_DIBITS: self.burst_bits // 2}.get(self.form, self.packed_bytes)
+
+    @property
+    def soft_cells(self):
+        """mbe_soft_bit-sized cells of one soft burst (mbx_burst_schedule_soft_cells)"""
+        return self.burst_bits // 2 if self.form == FORM_DIBITS else self.burst_bits
+
+    def in_form(self, form=FORM_PACKED, invert=None, device=False):
+        """the same three arrays as a schedule of another form / inversion sequence"""
+        return (BurstSchedule if device else ScheduleArrays)(self.codec, self.frames_per_burst, self.burst_bits, self.src_bit, self.cell_row,
+                                                            self.cell_col, form, invert)
 
 
 class BurstSchedule(ScheduleArrays):
-    """A schedule on the device (mbx_burst_schedule_create on the current device, which must have been initialised:
+    """A schedule on the device (mbx_burst_schedule_create_form on the current device, which must have been initialised:
     decoder.ensure_init).  Owns the native handle; immutable."""
 
-    def __init__(self, codec, frames_per_burst, burst_bits, src_bit, cell_row, cell_col):
-        super().__init__(codec, frames_per_burst, burst_bits, src_bit, cell_row, cell_col)
+    def __init__(self, codec, frames_per_burst, burst_bits, src_bit, cell_row, cell_col, form=FORM_PACKED, invert=None):
+        super().__init__(codec, frames_per_burst, burst_bits, src_bit, cell_row, cell_col, form, invert)
         self.handle = None
         h = C.c_void_p()
-        rc = _native.lib().mbx_burst_schedule_create(C.byref(h), self.codec, self.frames_per_burst, self.burst_bits, self.src_bit.ctypes.data,
-                                                     self.cell_row.ctypes.data, self.cell_col.ctypes.data)
-        _native.check(rc, "mbx_burst_schedule_create")
+        rc = _native.lib().mbx_burst_schedule_create_form(C.byref(h), self.codec, self.frames_per_burst, self.burst_bits, self.src_bit.ctypes.data,
+                                                          self.cell_row.ctypes.data, self.cell_col.ctypes.data, self.form,
+                                                          None if self.invert is None else self.invert.ctypes.data)
+        _native.check(rc, "mbx_burst_schedule_create_form")
         self.handle = h
 
     def close(self):
@@ -74,29 +100,91 @@ class BurstSchedule(ScheduleArrays):
             pass
 
 
+def _received_bits(s, raw):
+    """[n, burst_bits] 0 / 1 of hard bursts [n, >= burst_bytes] in the schedule's form, as the device reads them"""
+    if s.form == FORM_BITS:
+        return raw[:, :s.burst_bits] & 1
+    if s.form == FORM_DIBITS:
+        d = raw[:, :s.burst_bits // 2]
+        return np.stack([(d >> 1) & 1, d & 1], axis=-1).reshape(raw.shape[0], -1)
+    return np.unpackbits(raw[:, :s.packed_bytes], axis=1)[:, :s.burst_bits]
+
+
 def apply_schedule(schedule, bursts, soft=False, burst_stride=None):
     """What the gather kernels do, in numpy.  schedule: ScheduleArrays (or BurstSchedule).
-    hard: bursts = uint8, n bursts of burst_stride bytes (default ceil(burst_bits / 8)), bit j at byte j >> 3, mask 0x80 >> (j & 7)
+    hard: bursts = uint8, n bursts of burst_stride bytes (default schedule.burst_bytes) in the schedule's form -- PACKED: bit j at
+          byte j >> 3, mask 0x80 >> (j & 7); BITS: bit j = byte j & 1; DIBITS: bits 2d, 2d + 1 = bits 1, 0 of byte d
           -> uint8 [n * F, FRAME_BYTES[codec]] packed wire frames, frame k of burst b at row b * F + k
-    soft: bursts = uint8 [n, burst_bits, 2] (bit, reliability) -> uint8 [n * F, cells, 2] cell arrays in the reference's shape,
-          cells that are not on the wire {0, 0}"""
+    soft: bursts = uint8 [n, soft_cells, 2] -- (bit, reliability) per bit, DIBITS: (dibit, reliability) per dibit, both bits of the
+          dibit with its reliability -> uint8 [n * F, cells, 2] cell arrays in the reference's shape, cells that are not on the wire {0, 0}
+    schedule.invert: the received bits with a 1 are flipped (soft: the hard decision; the reliability stays)"""
     s = schedule
     F, B, nbits = s.frames_per_burst, s.burst_bits, channel_bits(s.codec)
     rows, stride = FRAME_CELLS[s.codec]
     if soft:
-        cells = np.ascontiguousarray(bursts, dtype=np.uint8).reshape(-1, B, 2)
+        cells = np.ascontiguousarray(bursts, dtype=np.uint8).reshape(-1, s.soft_cells, 2)
+        if s.form == FORM_DIBITS:
+            d, rel = cells[:, :, 0], cells[:, :, 1]
+            cells = np.stack([np.stack([(d >> 1) & 1, d & 1], axis=-1).reshape(-1, B), np.repeat(rel, 2, axis=1)], axis=-1)
+        if s.invert is not None:
+            cells = cells.copy()
+            cells[:, :, 0] ^= s.invert
         out = np.zeros((cells.shape[0], F, rows * stride, 2), dtype=np.uint8)
         for k in range(F):
             out[:, k, s.cell_row[k] * stride + s.cell_col[k]] = cells[:, s.src_bit[k]]
         return out.reshape(-1, rows * stride, 2)
     burst_stride = s.burst_bytes if burst_stride is None else int(burst_stride)
     raw = np.ascontiguousarray(bursts, dtype=np.uint8).reshape(-1, burst_stride)[:, :s.burst_bytes]
-    bits = np.unpackbits(raw, axis=1)[:, :B]
+    bits = _received_bits(s, raw)
+    if s.invert is not None:
+        bits = bits ^ s.invert
     out = np.zeros((raw.shape[0], F, FRAME_BYTES[s.codec] * 8), dtype=np.uint8)
     for k in range(F):
         out[:, k, wire_bit_of_cell(s.codec, s.cell_row[k], s.cell_col[k])] = bits[:, s.src_bit[k]]
     assert nbits <= out.shape[2]
     return np.packbits(out, axis=2).reshape(-1, FRAME_BYTES[s.codec])
+
+
+def to_form(schedule, packed_bursts, soft=False, junk=None):
+    """Bursts in the packed form -> the same received bits in the schedule's form, at the tight stride.
+    hard: packed_bursts = uint8 [n, >= ceil(burst_bits / 8)], MSB first -> uint8 [n, schedule.burst_bytes]
+    soft: packed_bursts = uint8 [n, burst_bits, 2] (bit, reliability) per bit -> uint8 [n, schedule.soft_cells, 2]; for the dibit form
+          the two bits of a dibit must come with ONE reliability (ValueError otherwise)
+    junk: an rng (numpy Generator) that fills the bits of every byte which the DEVICE does not read -- bits 1..7 of a bit byte, bits
+          2..7 of a dibit byte or dibit cell, the bits of the last packed byte behind burst_bits.  Such bursts are what the device
+          calls mask; mbx_burst_validate and the session submits refuse them.
+    The inversion sequence plays no part: it says how the bits ARRIVE."""
+    s = schedule
+    B = s.burst_bits
+    if soft:
+        cells = np.ascontiguousarray(packed_bursts, dtype=np.uint8).reshape(-1, B, 2)
+        if s.form != FORM_DIBITS:
+            return cells.copy()
+        pairs = cells.reshape(-1, B // 2, 2, 2)
+        if not np.array_equal(pairs[:, :, 0, 1], pairs[:, :, 1, 1]):
+            raise ValueError("soft dibits: the two bits of a dibit must have one reliability")
+        d = ((pairs[:, :, 0, 0] & 1) << 1) | (pairs[:, :, 1, 0] & 1)
+        if junk is not None:
+            d = d | (junk.integers(0, 64, size=d.shape, dtype=np.uint8) << 2)
+        return np.stack([d, pairs[:, :, 0, 1]], axis=-1)
+    raw = np.ascontiguousarray(packed_bursts, dtype=np.uint8)
+    raw = raw.reshape(-1, s.packed_bytes) if raw.ndim != 2 else raw[:, :s.packed_bytes]
+    bits = np.unpackbits(raw, axis=1)
+    if s.form == FORM_BITS:
+        out = bits[:, :B].copy()
+        if junk is not None:
+            out |= junk.integers(0, 128, size=out.shape, dtype=np.uint8) << 1
+        return out
+    if s.form == FORM_DIBITS:
+        out = (bits[:, 0:B:2] << 1) | bits[:, 1:B:2]
+        if junk is not None:
+            out |= junk.integers(0, 64, size=out.shape, dtype=np.uint8) << 2
+        return out
+    if junk is not None:
+        bits[:, B:] = junk.integers(0, 2, size=bits[:, B:].shape, dtype=np.uint8)
+    else:
+        bits[:, B:] = 0
+    return np.packbits(bits, axis=1)
 
 
 def _wire_cells(codec):
@@ -106,14 +194,14 @@ def _wire_cells(codec):
     return rows, cols
 
 
-def random_schedule(codec, frames_per_burst, burst_bits, rng, device=False):
+def random_schedule(codec, frames_per_burst, burst_bits, rng, device=False, form=FORM_PACKED, invert=None):
     """A random valid schedule of the given shape: the channel bits of the F frames at random distinct places of the burst, the
     cells of each frame in random order.  device=True: a BurstSchedule."""
     nbits = channel_bits(codec)
     src = rng.permutation(burst_bits)[:frames_per_burst * nbits].reshape(frames_per_burst, nbits)
     rows, cols = _wire_cells(codec)
     order = np.stack([rng.permutation(nbits) for _ in range(frames_per_burst)])
-    return (BurstSchedule if device else ScheduleArrays)(codec, frames_per_burst, burst_bits, src, rows[order], cols[order])
+    return (BurstSchedule if device else ScheduleArrays)(codec, frames_per_burst, burst_bits, src, rows[order], cols[order], form, invert)
 
 
 def gap_schedule(codec, frames_per_burst, gap=48, device=False):
@@ -129,8 +217,8 @@ def gap_schedule(codec, frames_per_burst, gap=48, device=False):
 
 def deinterleave(schedule, bursts, soft=False, mixed_rows=False, burst_stride=None, out=None):
     """The gather alone, on the device (mbx_deinterleave / mbx_deinterleave_soft on the current torch stream).  bursts: uint8 device
-    tensor (or host array, uploaded) of n bursts -- hard: burst_stride bytes each (default ceil(burst_bits / 8)); soft:
-    [n, burst_bits, 2].  Returns uint8 [n * F, row] wire frames (soft: [n * F, row, 2] cells); mixed_rows=True: rows of
+    tensor (or host array, uploaded) of n bursts in the schedule's form -- hard: burst_stride bytes each (default
+    schedule.burst_bytes); soft: [n, schedule.soft_cells, 2].  Returns uint8 [n * F, row] wire frames (soft: [n * F, row, 2] cells); mixed_rows=True: rows of
     MIXED_ROW_BYTES bytes / MIXED_ROW_CELLS cells, as mbx_process_batch_mixed takes them (bytes 9..17 of an AMBE wire row are not
     written: zero in a tensor made here, kept in `out`)."""
     import torch
@@ -140,7 +228,7 @@ def deinterleave(schedule, bursts, soft=False, mixed_rows=False, burst_stride=No
         bursts = torch.from_numpy(np.ascontiguousarray(bursts, dtype=np.uint8).reshape(-1)).cuda()
     if bursts.dtype != torch.uint8 or not bursts.is_contiguous():
         raise ValueError("bursts must be a contiguous uint8 tensor")
-    per = s.burst_bits * 2 if soft else (s.burst_bytes if burst_stride is None else int(burst_stride))
+    per = s.soft_cells * 2 if soft else (s.burst_bytes if burst_stride is None else int(burst_stride))
     if per < 1 or bursts.numel() % per:
         raise ValueError("bursts must hold whole bursts")
     n = bursts.numel() // per

@@ -1842,7 +1842,7 @@ static int process_bursts(const char* who, bool soft, const mbx_burst_schedule* 
     }
     const mbx::BurstShape sh = mbx::burst_shape(sched);
     if (!soft && burst_stride < sh.bytes) {
-        snprintf(text, sizeof(text), "%s: burst_stride is below ceil(burst_bits / 8)", who);
+        snprintf(text, sizeof(text), "%s: burst_stride is below mbx_burst_schedule_bytes()", who);
         return fail(MBE_STATUS_INVALID_ARGUMENT, text);
     }
     REQUIRE_CTX(c);

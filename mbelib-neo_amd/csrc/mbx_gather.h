@@ -12,9 +12,11 @@ namespace mbx {
 // what a schedule is, as far as its users look: the folded tables stay inside mbx_burst.hip
 struct BurstShape {
     int    codec, frames, bits, device;
-    size_t bytes;          // ceil(bits / 8)
+    size_t bytes;          // the smallest burst_stride of a hard burst in the schedule's form (mbx_burst_schedule_bytes)
     size_t frame_bytes;    // one gathered wire frame
     size_t cells;          // one gathered cell array (mbe_soft_bit cells)
+    int    form;           // MBX_BURST_FORM_*
+    size_t soft_cells;     // cells of one soft burst in the schedule's form (mbx_burst_schedule_soft_cells)
 };
 BurstShape burst_shape(const mbx_burst_schedule* sched);   // sched != nullptr
 

@@ -174,7 +174,7 @@ bool range_ok(const mbx_session* s, int first, int count) {
 struct BurstIn {
     const mbx_burst_schedule* sched;
     size_t                    stride;   // hard bursts: the caller's burst_stride
-    size_t                    bytes;    // one burst in the input: burst_stride, or burst_bits cells
+    size_t                    bytes;    // one burst in the input: burst_stride, or the soft cells of the schedule's form
 };
 
 // `soft`: frames are mbe_soft_bit cells (soft_bytes per frame) instead of wire frames (frame_bytes)
@@ -193,9 +193,13 @@ int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frame
     if (n == 0 || T == 0) {
         return 0;
     }
-    if (soft) {   // a hard decision > 1 is refused before anything is queued (ref mbe_validate_soft_bits, src/internal/mbe_result.h:31-42)
-        const size_t cells = burst ? (size_t)n * (burst->bytes / sizeof(mbe_soft_bit)) : (size_t)n * (size_t)T * (s->soft_bytes / sizeof(mbe_soft_bit));
-        const int rc = mbx_validate_soft_bits(static_cast<const mbe_soft_bit*>(frames), cells);
+    if (burst) {   // bursts of a form that can be invalid: a bit byte > 1, a dibit > 3, a soft hard decision > 1 (mbx_burst_validate)
+        const int rc = mbx_burst_validate(burst->sched, frames, burst->stride, (size_t)n, soft ? 1 : 0);
+        if (rc < 0) {
+            return rc;
+        }
+    } else if (soft) {   // a hard decision > 1 is refused before anything is queued (ref mbe_validate_soft_bits, src/internal/mbe_result.h:31-42)
+        const int rc = mbx_validate_soft_bits(static_cast<const mbe_soft_bit*>(frames), (size_t)n * (size_t)T * (s->soft_bytes / sizeof(mbe_soft_bit)));
         if (rc < 0) {
             return rc;
         }
@@ -624,7 +628,7 @@ static int submit_bursts(const char* who, mbx_session* s, const mbx_burst_schedu
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     if (!soft && burst_stride < sh.bytes) {
-        snprintf(text, sizeof(text), "%s: burst_stride is below ceil(burst_bits / 8)", who);
+        snprintf(text, sizeof(text), "%s: burst_stride is below mbx_burst_schedule_bytes()", who);
         mbx_set_error_text(text);
         return MBE_STATUS_INVALID_ARGUMENT;
     }
@@ -633,7 +637,7 @@ static int submit_bursts(const char* who, mbx_session* s, const mbx_burst_schedu
         mbx_set_error_text(text);
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    const BurstIn in{sched, burst_stride, soft ? (size_t)sh.bits * sizeof(mbe_soft_bit) : burst_stride};
+    const BurstIn in{sched, burst_stride, soft ? sh.soft_cells * sizeof(mbe_soft_bit) : burst_stride};
     return submit(s, n, sh.frames, stream_index, bursts, soft, pcm16, pcmf, results, nullptr, &in);
 }
 

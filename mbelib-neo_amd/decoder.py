@@ -162,19 +162,23 @@ class BatchDecoder:
         """Received bursts instead of frames: `schedule` (bursts.BurstSchedule, of this decoder's codec) says where the channel bits of
         the F frames of a burst sit; burst row i carries the next F frames of stream i (stream_index[i]).  One mbx_process_bursts /
         _soft call: the gather on the device, then the step decode(frames, T=F) / decode_soft run, on this decoder's state, resident
-        or not.  bursts: uint8 tensor or array -- hard: n bursts of burst_stride bytes (default ceil(burst_bits / 8)), MSB first;
-        soft=True: [n, burst_bits, 2] (bit, reliability).  Returns the dict of decode at T = F."""
+        or not.  bursts: uint8 tensor or array in the schedule's form -- hard: n bursts of burst_stride bytes (default
+        schedule.burst_bytes); soft=True: [n, schedule.soft_cells, 2] (bit or dibit, reliability).  A host array is checked with
+        mbx_burst_validate; a device tensor is the caller's to check.  Returns the dict of decode at T = F."""
         torch = _torch()
         if schedule.codec != self.codec:
             raise ValueError("the schedule is of another codec than the decoder")
-        if soft and isinstance(bursts, np.ndarray) and np.ascontiguousarray(bursts, dtype=np.uint8).reshape(-1, 2)[:, 0].max(initial=0) > 1:
-            raise ValueError("soft bursts: a hard decision is not 0 or 1")
+        stride = schedule.burst_bytes if burst_stride is None else int(burst_stride)
+        if isinstance(bursts, np.ndarray):
+            bursts = np.ascontiguousarray(bursts, dtype=np.uint8)
+            per = schedule.soft_cells * 2 if soft else stride
+            if per > 0 and bursts.size % per == 0 and _native.lib().mbx_burst_validate(schedule.handle, bursts.ctypes.data, stride, bursts.size // per, int(soft)) == -2:
+                raise ValueError("soft bursts: a hard decision is not 0 or 1 (a dibit not 0 .. 3)" if soft else "bursts: a bit byte is not 0 or 1, or a dibit byte not 0 .. 3")
         d_bursts = self.to_device(np.ascontiguousarray(bursts, dtype=np.uint8) if isinstance(bursts, np.ndarray) else bursts)
         if d_bursts.dtype != torch.uint8 or not d_bursts.is_contiguous():
             raise ValueError("bursts must be a contiguous uint8 tensor")
         n = self.streams if stream_index is None else int(stream_index.numel())
-        stride = schedule.burst_bytes if burst_stride is None else int(burst_stride)
-        if d_bursts.numel() != n * (schedule.burst_bits * 2 if soft else stride):
+        if d_bursts.numel() != n * (schedule.soft_cells * 2 if soft else stride):
             raise ValueError("bursts must hold one burst per batch row")
         if stream_index is not None:
             if stream_index.dtype != torch.int32 or stream_index.device != self.device:

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""burst_bench.py [--kernels | --sessions] [--streams S] [--steps N] -- what burst input (include/mbx_burst.h) costs and saves.
+"""burst_bench.py [--kernels | --sessions] [--form FORM] [--streams S] [--steps N] -- what burst input (include/mbx_burst.h) costs and saves.
 
 Two SHAPES, random bijections with the right frame count and burst length (no air-interface table is written down anywhere):
 "dmr" = AMBE+2, 3 frames in 264 bits; "ldu" = IMBE, 9 frames in 1,728 bits.  Hard and soft, S streams (default 65,536), resident state.
@@ -10,6 +10,9 @@ Two SHAPES, random bijections with the right frame count and burst length (no ai
 --sessions  frames/s of sessions fed with bursts (mbx_session_submit_bursts[_soft]) against the same sessions fed with frames the
             host scatters first (numpy apply_schedule, vectorised over the batch -- kinder to the host than the per-bit C loop of
             INTEGRATION.md), 1 and 8 host threads, each thread with its own session of S / threads streams; pinned input, int16 PCM out.
+--form      packed (default) | bits | dibits: the form of the bursts (mbx_burst_schedule_create_form).  With another form than packed
+            every measurement is made for the packed form AND for that form in the same process, their windows alternating:
+            --kernels adds the form's step and both gathers alone, --sessions replaces the scatter route by the packed bursts.
 Needs a GPU; prints one JSON line per measurement.  Development aid."""
 import argparse
 import ctypes as C
@@ -25,20 +28,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SHAPES = {"dmr": (1, 3, 264), "ldu": (0, 9, 1728)}
+FORMS = {"packed": 0, "bits": 1, "dibits": 2}
 
 
-def make(shape, n, soft, seed=1):
+def make(shape, n, soft, seed=1, form="packed"):
+    """(schedule, bursts): the same random schedule and the same received bits for every form"""
     from mbelib_neo_amd import bursts as B
 
     codec, F, bits = SHAPES[shape]
     rng = np.random.default_rng(seed)
-    s = B.random_schedule(codec, F, bits, rng, device=True)
+    s = B.random_schedule(codec, F, bits, rng, device=True, form=FORMS[form])
     if soft:
         bursts = rng.integers(0, 256, size=(n, bits, 2), dtype=np.uint8)
         bursts[:, :, 0] &= 1
+        bursts[:, 1::2, 1] = bursts[:, 0::2, 1]   # one reliability per symbol
     else:
-        bursts = rng.integers(0, 256, size=(n, s.burst_bytes), dtype=np.uint8)
-    return s, bursts
+        bursts = rng.integers(0, 256, size=(n, (bits + 7) // 8), dtype=np.uint8)
+    return s, B.to_form(s, bursts, soft=soft)
 
 
 def timed(step, steps):
@@ -56,35 +62,44 @@ def timed(step, steps):
     return a.elapsed_time(b) / steps
 
 
-def kernels(S, steps):
+def kernels(S, steps, form="packed"):
     import torch
     from mbelib_neo_amd import _native, bursts as B, decoder
 
     decoder.ensure_init(0)
     L = _native.lib()
+    forms = ["packed"] + ([form] if form != "packed" else [])
     for shape in SHAPES:
         for soft in (False, True):
-            s, bursts = make(shape, S, soft)
             codec, F, _ = SHAPES[shape]
             dec = decoder.BatchDecoder(codec, S, seeds=np.arange(S) + 1, resident=True)
-            d_bursts = dec.to_device(bursts)
-            d_frames = B.deinterleave(s, d_bursts, soft=soft).reshape(-1)
             out = dec.make_outputs(F)
-            _native.check(L.mbx_reserve_stream(torch.cuda.current_stream().cuda_stream, L.mbx_burst_workspace_frames(s.handle, S, int(soft))), "reserve")
-            from_bursts = lambda: dec.decode_bursts(s, d_bursts, soft=soft, out=out)   # noqa: E731
+            made = {f: make(shape, S, soft, form=f) for f in forms}
+            d_bursts = {f: dec.to_device(made[f][1]) for f in forms}
+            d_frames = B.deinterleave(made["packed"][0], d_bursts["packed"], soft=soft).reshape(-1)
+            for f in forms:
+                assert torch.equal(B.deinterleave(made[f][0], d_bursts[f], soft=soft).reshape(-1), d_frames), f
+                _native.check(L.mbx_reserve_stream(torch.cuda.current_stream().cuda_stream, L.mbx_burst_workspace_frames(made[f][0].handle, S, int(soft))), "reserve")
+            from_bursts = {f: (lambda f=f: dec.decode_bursts(made[f][0], d_bursts[f], soft=soft, out=out)) for f in forms}
+            gather = {f: (lambda f=f: B.deinterleave(made[f][0], d_bursts[f], soft=soft, out=d_frames)) for f in forms}
             from_frames = (lambda: dec.decode_soft(d_frames, F, out=out)) if soft else (lambda: dec.decode(d_frames, F, out=out))
-            t_bursts, t_frames = 1e9, 1e9
+            t_frames, t_bursts, t_gather = 1e9, dict.fromkeys(forms, 1e9), dict.fromkeys(forms, 1e9)
             for _ in range(3):   # interleaved, the better of three each: the first measurement of a process runs on a cold clock
                 t_frames = min(t_frames, timed(from_frames, steps))
-                t_bursts = min(t_bursts, timed(from_bursts, steps))
-            t_gather = timed(lambda: B.deinterleave(s, d_bursts, soft=soft, out=d_frames), steps)
-            print(json.dumps({"mode": "kernels", "shape": shape, "soft": soft, "streams": S, "frames_per_burst": F, "step_from_bursts_ms": round(t_bursts, 4),
-                              "step_from_frames_ms": round(t_frames, 4), "gather_alone_ms": round(t_gather, 4),
-                              "gather_share_of_step": round((t_bursts - t_frames) / t_frames, 4)}), flush=True)
-            s.close()
+                for f in forms:
+                    t_bursts[f] = min(t_bursts[f], timed(from_bursts[f], steps))
+            for _ in range(3):
+                for f in forms:
+                    t_gather[f] = min(t_gather[f], timed(gather[f], steps))
+            for f in forms:
+                print(json.dumps({"mode": "kernels", "shape": shape, "soft": soft, "form": f, "streams": S, "frames_per_burst": F,
+                                  "input_bytes_per_burst": int(made[f][1].size // S), "step_from_bursts_ms": round(t_bursts[f], 4),
+                                  "step_from_frames_ms": round(t_frames, 4), "gather_alone_ms": round(t_gather[f], 4),
+                                  "gather_share_of_step": round((t_bursts[f] - t_frames) / t_frames, 4)}), flush=True)
+                made[f][0].close()
 
 
-def sessions(S, steps):
+def sessions(S, steps, form="packed"):
     from mbelib_neo_amd import _native, bursts as B, decoder
 
     decoder.ensure_init(0)
@@ -95,14 +110,16 @@ def sessions(S, steps):
             for threads in (1, 8):
                 per = S // threads
                 s, bursts = make(shape, per, soft)
+                formed = make(shape, per, soft, form=form) if form != "packed" else None
                 rates = {}
-                for route in ("bursts", "scatter"):
+                for route in ("bursts", "scatter") if formed is None else ("bursts", "form", "bursts", "form"):   # (twice: the better of two windows)
+                    sched, data = (s, bursts) if route != "form" else formed
                     work = []
                     for _ in range(threads):
                         h = C.c_void_p()
                         _native.check(L.mbx_session_create(C.byref(h), codec, per, per * F, 1), "create")
-                        pin = L.mbx_host_alloc(bursts.size)
-                        np.ctypeslib.as_array((C.c_uint8 * bursts.size).from_address(pin))[:] = bursts.reshape(-1)
+                        pin = L.mbx_host_alloc(data.size)
+                        np.ctypeslib.as_array((C.c_uint8 * data.size).from_address(pin))[:] = data.reshape(-1)
                         pcm = L.mbx_host_alloc(per * F * 320)
                         work.append((h, pin, pcm))
 
@@ -110,11 +127,11 @@ def sessions(S, steps):
                         import torch
 
                         torch.cuda.set_device(0)
-                        src = np.ctypeslib.as_array((C.c_uint8 * bursts.size).from_address(pin)).reshape(bursts.shape)
+                        src = np.ctypeslib.as_array((C.c_uint8 * data.size).from_address(pin)).reshape(data.shape)
                         for _ in range(count):
-                            if route == "bursts":
-                                rc = (L.mbx_session_submit_bursts_soft(h, s.handle, per, None, pin, pcm, None, None) if soft else
-                                      L.mbx_session_submit_bursts(h, s.handle, per, None, pin, s.burst_bytes, pcm, None, None))
+                            if route != "scatter":
+                                rc = (L.mbx_session_submit_bursts_soft(h, sched.handle, per, None, pin, pcm, None, None) if soft else
+                                      L.mbx_session_submit_bursts(h, sched.handle, per, None, pin, sched.burst_bytes, pcm, None, None))
                             else:
                                 frames = B.apply_schedule(s, src, soft=soft)
                                 rc = (L.mbx_session_submit_soft if soft else L.mbx_session_submit)(h, F, frames.ctypes.data, pcm, None, None)
@@ -129,14 +146,19 @@ def sessions(S, steps):
                         t.start()
                     for t in ts:
                         t.join()
-                    rates[route] = threads * per * F * steps / (time.perf_counter() - t0)
+                    rates[route] = max(rates.get(route, 0.0), threads * per * F * steps / (time.perf_counter() - t0))
                     for h, pin, pcm in work:
                         L.mbx_session_destroy(h)
                         L.mbx_host_free(pin)
                         L.mbx_host_free(pcm)
-                print(json.dumps({"mode": "sessions", "shape": shape, "soft": soft, "streams": per * threads, "host_threads": threads,
-                                  "bursts_in_Mframes_per_s": round(rates["bursts"] / 1e6, 2), "scatter_then_frames_Mframes_per_s": round(rates["scatter"] / 1e6, 2)}),
-                      flush=True)
+                line = {"mode": "sessions", "shape": shape, "soft": soft, "streams": per * threads, "host_threads": threads,
+                        "bursts_in_Mframes_per_s": round(rates["bursts"] / 1e6, 2)}
+                if formed is None:
+                    line["scatter_then_frames_Mframes_per_s"] = round(rates["scatter"] / 1e6, 2)
+                else:
+                    line[form + "_in_Mframes_per_s"] = round(rates["form"] / 1e6, 2)
+                    formed[0].close()
+                print(json.dumps(line), flush=True)
                 s.close()
 
 
@@ -144,10 +166,11 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--sessions", action="store_true")
+    ap.add_argument("--form", choices=sorted(FORMS), default="packed")
     ap.add_argument("--streams", type=int, default=65536)
     ap.add_argument("--steps", type=int, default=20)
     a = ap.parse_args()
     if a.kernels or not a.sessions:
-        kernels(a.streams, a.steps)
+        kernels(a.streams, a.steps, a.form)
     if a.sessions:
-        sessions(a.streams, a.steps)
+        sessions(a.streams, a.steps, a.form)
