@@ -1,8 +1,9 @@
 // mbx_burst.hip -- burst input (include/mbx_burst.h): the caller's de-interleave schedule, folded once on the host into two tables,
 // and the gather kernels that apply them to every burst on the device: received bursts -> packed wire frames (hard) or the
-// reference's cell arrays (soft), i.e. what the batch launchers of mbx_api.hip start from.  burst_gather_kernel and
-// burst_gather_soft_kernel serve packed (soft: per-bit) bursts; their _form twins serve the other forms a receiver holds its bursts
-// in -- one byte per bit, one byte per dibit, soft {dibit, reliability} pairs -- and a fixed inversion sequence.  The launchers that chain a gather in
+// reference's cell arrays (soft), i.e. what the batch launchers of mbx_api.hip start from.  One kernel template per kind,
+// burst_gather_kernel<form, invert> and burst_gather_soft_kernel<dibits, flip>, serves every form a receiver holds its bursts in --
+// packed bits, one byte per bit, one byte per dibit; soft per-bit cells, soft {dibit, reliability} pairs -- with or without a fixed
+// inversion sequence.  The launchers that chain a gather in
 // front of a batch step are in mbx_api.hip (they need the stream's workspace), the session submits in mbx_session.hip.
 //
 // No air-interface table is written here: F, B, the strides and the tables are kernel arguments, one code object serves every
@@ -28,7 +29,7 @@ constexpr int      kGatherBursts = 64;     // hard gather: bursts per workgroup,
 constexpr int      kSoftStageBytes = 32768;   // soft gather: a workgroup stages at most this much of soft bursts (and at most 16 bursts)
 constexpr uint32_t kNoBit = 0xffffu;       // table entry of a frame bit / cell no received bit goes to
 constexpr int      kSoftDibitBursts = 32;  // soft gather of dibit pairs: half the bytes per burst, twice the bursts of a workgroup at most
-constexpr uint32_t kFlip = 0x8000u;        // cell table: the received bit arrives inverted (entries are below MBX_BURST_MAX_BITS = 0x1000) ...
+constexpr uint32_t kInverted = 0x8000u;    // cell table: the received bit arrives inverted (entries are below MBX_BURST_MAX_BITS = 0x1000) ...
 constexpr uint32_t kBitOf = 0x0fffu;       // ... and the received bit of an entry
 
 // ---- hard bursts -> packed wire frames ---------------------------------------------------------------------------------------------
@@ -39,12 +40,26 @@ constexpr uint32_t kBitOf = 0x0fffu;       // ... and the received bit of an ent
 // each a scalar, so per bit a lane does one address add, one LDS byte read and a shift-and-merge.  The output bytes of the 64 bursts
 // are collected in LDS as the image of the rows and leave as whole aligned dwords across the workgroup (single bytes only where a
 // dword is not wholly inside a frame: the edges of the row range, the upper halves of 18-byte AMBE rows).
+//   kForm      the form the bursts come in (MBX_BURST_FORM_*).  The working set is the PACKED image of the 64 bursts whatever the
+//              form, so table, lstride and dynamic LDS do not depend on it: BITS and DIBITS bursts are converted WHILE they are
+//              staged.  Four dibit bytes, one aligned dword, are exactly one packed byte, eight bit bytes are one: a lane makes a
+//              whole LDS dword from 16 B (DIBITS) or 32 B (BITS) of its burst, neighbouring lanes from neighbouring pieces; the
+//              four (two) bit fields of a dword are brought together by one multiplication.  Input dwords are read up to the one
+//              that holds the burst's last byte (inside the stride: pointer and stride are multiples of 4 on this path); with any
+//              other pointer or stride a lane builds one packed byte from its 4 / 8 input bytes, and reads none behind the burst's
+//              last.  Of a BITS byte `& 1` counts, of a DIBITS byte `& 3`.
+//   kInvert    the inversion sequence is applied, folded per OUTPUT byte: one XOR with xor_tab[item] per eight bits.  Without it
+//              xor_tab is not read.  (Only a PACKED schedule is launched without: BITS and DIBITS read their table, zero or not.)
 //   wire_tab   [F][fbytes * 8] burst bit of each wire bit, kNoBit for the bits that pad the last byte
+//   xor_tab    [F * fbytes] a 1 where the wire bit's received bit arrives inverted (0 for the bits that pad the last byte)
 //   lstride    bytes between two bursts in LDS
 // dynamic LDS: table | 64 * lstride | 64 * F * fbytes
+template <int kForm, bool kInvert>
 __global__ void __launch_bounds__(256)
 burst_gather_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride, size_t n, int F, int B, int fbytes,
-                    const uint16_t* __restrict__ wire_tab, uint8_t* __restrict__ frames, int frame_stride, int lstride) {
+                    const uint16_t* __restrict__ wire_tab, const uint8_t* __restrict__ xor_tab, uint8_t* __restrict__ frames,
+                    int frame_stride, int lstride) {
+    static_assert(kInvert || kForm == MBX_BURST_FORM_PACKED, "not an instance that mbx::burst_gather launches");
     extern __shared__ uint32_t lds[];
     const int items = F * fbytes;   // output bytes of one burst; eight table entries each
     const int tab_dwords = items * 4;
@@ -57,181 +72,7 @@ burst_gather_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride, siz
     for (int i = tid; i < tab_dwords; i += 256) {
         lds[i] = reinterpret_cast<const uint32_t*>(wire_tab)[i];
     }
-    const int bbytes = (B + 7) >> 3;
-    const uint8_t* src = bursts + first * burst_stride;
-    if (((reinterpret_cast<uintptr_t>(bursts) | burst_stride) & 3u) == 0) {
-        const int dw = (bbytes + 3) >> 2;   // (burst_stride is a multiple of 4 and >= bbytes: the last dword is inside the burst's stride)
-        for (int j = wave; j < here; j += 4) {
-            const uint32_t* s = reinterpret_cast<const uint32_t*>(src + (size_t)j * burst_stride);
-            uint32_t* d = reinterpret_cast<uint32_t*>(in + j * lstride);
-            for (int i = lane; i < dw; i += 64) {
-                d[i] = s[i];
-            }
-        }
-    } else {
-        for (int j = wave; j < here; j += 4) {
-            for (int i = lane; i < bbytes; i += 64) {
-                in[j * lstride + i] = src[(size_t)j * burst_stride + i];
-            }
-        }
-    }
-    __syncthreads();
-    // lane = burst (lanes behind `here` work on stale LDS bytes; their rows are not written out)
-    const uint8_t* mine = in + lane * lstride;
-    for (int item = wave; item < items; item += 4) {
-        const uint32_t e = tab[item * 8 + (lane & 7)];
-        uint32_t byte = 0;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const uint32_t j = (uint32_t)__builtin_amdgcn_readlane((int)e, k);
-            uint32_t bit = 0;
-            if (j != kNoBit) {
-                bit = ((uint32_t)mine[j >> 3] >> (7u - (j & 7u))) & 1u;
-            }
-            byte = (byte << 1) | bit;
-        }
-        out[lane * items + item] = (uint8_t)byte;
-    }
-    __syncthreads();
-    // rows first * F .. (first + here) * F - 1; out[row * fbytes + b] is byte b of the row
-    uint8_t* dst = frames + first * (size_t)F * (size_t)frame_stride;
-    const int region = (here * F - 1) * frame_stride + fbytes;   // from dst to behind the last byte written
-    const int a = (int)(reinterpret_cast<uintptr_t>(dst) & 3u);
-    const int ndw = (a + region + 3) >> 2;
-    for (int m = tid; m < ndw; m += 256) {
-        uint32_t word = 0, valid = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int q = 4 * m + k - a;
-            if (q >= 0 && q < region) {
-                // (frame_stride is the codec's frame size or the mixed row: 9 or 18, divisions by constants)
-                const uint32_t row = frame_stride == MBX_AMBE_FRAME_BYTES ? (uint32_t)q / (uint32_t)MBX_AMBE_FRAME_BYTES : (uint32_t)q / (uint32_t)MBX_IMBE_FRAME_BYTES;
-                const uint32_t off = (uint32_t)q - row * (uint32_t)frame_stride;
-                if (off < (uint32_t)fbytes) {
-                    word |= (uint32_t)out[row * (uint32_t)fbytes + off] << (8 * k);
-                    valid |= 1u << k;
-                }
-            }
-        }
-        uint8_t* p = dst + (4 * m - a);
-        if (valid == 15u) {
-            *reinterpret_cast<uint32_t*>(p) = word;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (valid & (1u << k)) {
-                    p[k] = (uint8_t)(word >> (8 * k));
-                }
-            }
-        }
-    }
-}
-
-// ---- soft bursts -> cell arrays ----------------------------------------------------------------------------------------------------
-// A workgroup takes nb consecutive bursts (a contiguous range of cells) into LDS with dword loads from the first aligned pair on,
-// then every wave takes rows of the output: a lane owns the two cells of one aligned output dword, looks each up in the schedule's
-// table (cell -> burst bit, in LDS), fetches it with one 16-bit LDS read and stores the pair; cells without a received bit, and
-// the cells of a mixed row behind the codec's array, are {0, 0}.
-//   cell_tab   [F][cells] burst bit of each cell of the reference's array, kNoBit for a cell that is not on the wire
-// dynamic LDS: table | nb * B cells (+ one pair of slack for the alignment phase)
-__global__ void __launch_bounds__(256)
-burst_gather_soft_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, int F, int B, int cells, const uint16_t* __restrict__ cell_tab,
-                         mbe_soft_bit* __restrict__ rows_out, int row_cells, int nb) {
-    extern __shared__ uint32_t lds[];
-    const int tab_dwords = (F * cells) >> 1;   // (every codec has an even number of cells)
-    const uint16_t* tab = reinterpret_cast<const uint16_t*>(lds);
-    uint16_t* in16 = reinterpret_cast<uint16_t*>(lds + tab_dwords);
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const size_t first = (size_t)blockIdx.x * (size_t)nb;
-    const int here = (int)((n - first) < (size_t)nb ? (n - first) : (size_t)nb);
-    for (int i = tid; i < tab_dwords; i += 256) {
-        lds[i] = reinterpret_cast<const uint32_t*>(cell_tab)[i];
-    }
-    // cell i of the range sits at in16[i + head]: an aligned dword of the source is an aligned dword of LDS
-    const uint16_t* src = reinterpret_cast<const uint16_t*>(soft) + first * (size_t)B;
-    const int ncells = here * B;
-    const int head = (int)((reinterpret_cast<uintptr_t>(src) >> 1) & 1u);
-    const int ndw = (ncells - head) >> 1;
-    {
-        const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src + head);
-        uint32_t* d32 = reinterpret_cast<uint32_t*>(in16) + head;
-        for (int m = tid; m < ndw; m += 256) {
-            d32[m] = s32[m];
-        }
-        if (tid == 0) {
-            if (head) {
-                in16[head] = src[0];
-            }
-            if ((ncells - head) & 1) {
-                in16[ncells - 1 + head] = src[ncells - 1];
-            }
-        }
-    }
-    __syncthreads();
-    const int nrows = here * F;
-    uint16_t* dst = reinterpret_cast<uint16_t*>(rows_out) + first * (size_t)F * (size_t)row_cells;
-    const int a = (int)((reinterpret_cast<uintptr_t>(dst) >> 1) & 1u);   // (row_cells is even: every row has the phase of the first)
-    const int pairs = (row_cells + 1 + a) >> 1;
-    for (int r = wave; r < nrows; r += 4) {
-        const int j = r / F, k = r - j * F;
-        const uint16_t* t = tab + k * cells;
-        const uint16_t* b = in16 + head + j * B;
-        uint16_t* o = dst + (size_t)r * (size_t)row_cells;
-        for (int p = lane; p < pairs; p += 64) {
-            const int c0 = 2 * p - a, c1 = c0 + 1;
-            uint32_t v0 = 0, v1 = 0;
-            if (c0 >= 0 && c0 < cells) {
-                const uint32_t e = t[c0];
-                if (e != kNoBit) {
-                    v0 = b[e];
-                }
-            }
-            if (c1 < cells) {
-                const uint32_t e = t[c1];
-                if (e != kNoBit) {
-                    v1 = b[e];
-                }
-            }
-            if (c0 >= 0 && c1 < row_cells) {
-                *reinterpret_cast<uint32_t*>(o + c0) = v0 | (v1 << 16);
-            } else if (c0 >= 0) {
-                o[c0] = (uint16_t)v0;
-            } else {
-                o[c1] = (uint16_t)v1;
-            }
-        }
-    }
-}
-
-// ---- hard bursts in the receiver's forms, descrambled ------------------------------------------------------------------------------
-// burst_gather_kernel for a schedule of another form than PACKED, or with an inversion sequence (mbx_burst_schedule_create_form).
-// The working set is the one of burst_gather_kernel -- the PACKED image of 64 bursts at the odd-dword lstride, lane = burst, table
-// entries as scalars -- so table, lstride and dynamic LDS do not depend on the form: the bursts are converted WHILE they are staged.
-// Four dibit bytes, one aligned dword, are exactly one packed byte, eight bit bytes are one: a lane makes a whole LDS dword from
-// 16 B (DIBITS) or 32 B (BITS) of its burst, neighbouring lanes from neighbouring pieces; the four (two) bit fields of a dword are
-// brought together by one multiplication.  Input dwords are read up to the one that holds the burst's last byte (inside the stride:
-// pointer and stride are multiples of 4 on this path); with any other pointer or stride a lane builds one packed byte from its 4 / 8
-// input bytes, and reads none behind the burst's last.  Of a BITS byte `& 1` counts, of a DIBITS byte `& 3`.
-// The inversion sequence is folded per OUTPUT byte: xor_tab[item] has a 1 where the wire bit's received bit arrives inverted (0 for
-// the bits that pad the last byte), one XOR per eight bits.
-//   xor_tab    [F * fbytes]
-template <int kForm>
-__global__ void __launch_bounds__(256)
-burst_gather_form_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride, size_t n, int F, int B, int fbytes,
-                         const uint16_t* __restrict__ wire_tab, const uint8_t* __restrict__ xor_tab, uint8_t* __restrict__ frames,
-                         int frame_stride, int lstride) {
-    extern __shared__ uint32_t lds[];
-    const int items = F * fbytes;   // output bytes of one burst; eight table entries each
-    const int tab_dwords = items * 4;
-    const uint16_t* tab = reinterpret_cast<const uint16_t*>(lds);
-    uint8_t* in = reinterpret_cast<uint8_t*>(lds + tab_dwords);
-    uint8_t* out = in + kGatherBursts * lstride;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const size_t first = (size_t)blockIdx.x * kGatherBursts;
-    const int here = (int)((n - first) < (size_t)kGatherBursts ? (n - first) : (size_t)kGatherBursts);
-    for (int i = tid; i < tab_dwords; i += 256) {
-        lds[i] = reinterpret_cast<const uint32_t*>(wire_tab)[i];
-    }
+    // stage the packed image of the bursts
     const int bbytes = (B + 7) >> 3;   // of the packed image
     const int nin = kForm == MBX_BURST_FORM_BITS ? B : (kForm == MBX_BURST_FORM_DIBITS ? B >> 1 : bbytes);   // bytes of a burst as it comes
     const uint8_t* src = bursts + first * burst_stride;
@@ -281,11 +122,14 @@ burst_gather_form_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride
         }
     }
     __syncthreads();
-    // lane = burst (lanes behind `here` work on stale LDS bytes; their rows are not written out)
+    // gather the bytes of the rows: lane = burst (lanes behind `here` work on stale LDS bytes; their rows are not written out)
     const uint8_t* mine = in + lane * lstride;
     for (int item = wave; item < items; item += 4) {
         const uint32_t e = tab[item * 8 + (lane & 7)];
-        const uint32_t flips = xor_tab[item];
+        uint32_t flips = 0;
+        if constexpr (kInvert) {
+            flips = xor_tab[item];
+        }
         uint32_t byte = 0;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -299,9 +143,9 @@ burst_gather_form_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride
         out[lane * items + item] = (uint8_t)(byte ^ flips);
     }
     __syncthreads();
-    // rows first * F .. (first + here) * F - 1, as burst_gather_kernel stores them
+    // store rows first * F .. (first + here) * F - 1; out[row * fbytes + b] is byte b of the row
     uint8_t* dst = frames + first * (size_t)F * (size_t)frame_stride;
-    const int region = (here * F - 1) * frame_stride + fbytes;
+    const int region = (here * F - 1) * frame_stride + fbytes;   // from dst to behind the last byte written
     const int a = (int)(reinterpret_cast<uintptr_t>(dst) & 3u);
     const int ndw = (a + region + 3) >> 2;
     for (int m = tid; m < ndw; m += 256) {
@@ -310,6 +154,7 @@ burst_gather_form_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride
         for (int k = 0; k < 4; ++k) {
             const int q = 4 * m + k - a;
             if (q >= 0 && q < region) {
+                // (frame_stride is the codec's frame size or the mixed row: 9 or 18, divisions by constants)
                 const uint32_t row = frame_stride == MBX_AMBE_FRAME_BYTES ? (uint32_t)q / (uint32_t)MBX_AMBE_FRAME_BYTES : (uint32_t)q / (uint32_t)MBX_IMBE_FRAME_BYTES;
                 const uint32_t off = (uint32_t)q - row * (uint32_t)frame_stride;
                 if (off < (uint32_t)fbytes) {
@@ -332,16 +177,24 @@ burst_gather_form_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride
     }
 }
 
-// ---- soft bursts of dibit pairs, or descrambled ------------------------------------------------------------------------------------
-// burst_gather_soft_kernel with the look-up of the new forms.  The cells are staged as they come, C per burst: B per-bit cells, or
-// B / 2 {dibit, reliability} pairs -- half the bytes, so up to kSoftDibitBursts bursts per workgroup.  A table entry is the received
-// bit j, with kFlip where it arrives inverted: per-bit cells give cell j with its hard decision flipped; pairs give pair j >> 1 as
-// ((dibit >> (1 - (j & 1))) & 1) ^ flip | reliability << 8, i.e. of a dibit `& 3` counts.
+// ---- soft bursts -> cell arrays ----------------------------------------------------------------------------------------------------
+// A workgroup takes nb consecutive bursts (a contiguous range of cells, C per burst) into LDS as they come, with dword loads from
+// the first aligned pair on, then every wave takes rows of the output: a lane owns the two cells of one aligned output dword, looks
+// each up in the schedule's table (cell -> burst bit, in LDS), fetches it with one 16-bit LDS read and stores the pair; cells
+// without a received bit, and the cells of a mixed row behind the codec's array, are {0, 0}.
+//   kDibits    a staged cell is a {dibit, reliability} pair, C = B / 2 of them per burst -- half the bytes, so up to
+//              kSoftDibitBursts bursts per workgroup -- and not one of C = B per-bit cells.  Entry j gives pair j >> 1 as
+//              ((dibit >> (1 - (j & 1))) & 1) ^ flip | reliability << 8, i.e. of a dibit `& 3` counts.
+//   kFlip      the table's entries carry kInverted where the received bit arrives inverted: per-bit cells give cell j with its
+//              hard decision flipped.  Without it an entry is the received bit alone (a schedule without a sequence has no such
+//              entry) and the fetch is the plain read of cell j: no mask, no shift.  (Only per-bit cells are launched without.)
+//   cell_tab   [F][cells] burst bit of each cell of the reference's array, kNoBit for a cell that is not on the wire
 // dynamic LDS: table | nb * C cells (+ one pair of slack for the alignment phase)
-template <bool kDibits>
+template <bool kDibits, bool kFlip>
 __global__ void __launch_bounds__(256)
-burst_gather_soft_form_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, int F, int C, int cells, const uint16_t* __restrict__ cell_tab,
-                              mbe_soft_bit* __restrict__ rows_out, int row_cells, int nb) {
+burst_gather_soft_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, int F, int C, int cells, const uint16_t* __restrict__ cell_tab,
+                         mbe_soft_bit* __restrict__ rows_out, int row_cells, int nb) {
+    static_assert(kFlip || !kDibits, "not an instance that mbx::burst_gather launches");
     extern __shared__ uint32_t lds[];
     const int tab_dwords = (F * cells) >> 1;   // (every codec has an even number of cells)
     const uint16_t* tab = reinterpret_cast<const uint16_t*>(lds);
@@ -374,12 +227,16 @@ burst_gather_soft_form_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, i
     }
     __syncthreads();
     const auto fetch = [](const uint16_t* b, uint32_t e) -> uint32_t {
-        const uint32_t j = e & kBitOf, flip = e >> 15;
-        if constexpr (kDibits) {
-            const uint32_t c = b[j >> 1];
-            return ((((c & 0xffu) >> (1u - (j & 1u))) & 1u) ^ flip) | (c & 0xff00u);
+        if constexpr (!kFlip) {
+            return b[e];
         } else {
-            return (uint32_t)b[j] ^ flip;
+            const uint32_t j = e & kBitOf, flip = e >> 15;
+            if constexpr (kDibits) {
+                const uint32_t c = b[j >> 1];
+                return ((((c & 0xffu) >> (1u - (j & 1u))) & 1u) ^ flip) | (c & 0xff00u);
+            } else {
+                return (uint32_t)b[j] ^ flip;
+            }
         }
     };
     const int nrows = here * F;
@@ -427,7 +284,7 @@ struct mbx_burst_schedule {
     int       soft_bursts = 0;  // soft gather: bursts per workgroup
     unsigned  soft_lds = 0;
     uint16_t* d_wire_tab = nullptr;   // [frames][frame_bytes * 8]
-    uint16_t* d_cell_tab = nullptr;   // [frames][cells], kFlip on the inverted bits; the same allocation, behind the wire table
+    uint16_t* d_cell_tab = nullptr;   // [frames][cells], kInverted on the inverted bits; the same allocation, behind the wire table
     uint8_t*  d_xor_tab = nullptr;    // [frames * frame_bytes] the inversion sequence per output byte; the same allocation, behind the cell table
     bool      inverts = false;        // the inversion sequence has a 1 on a bit that an entry names
 };
@@ -448,6 +305,36 @@ int hip_fail(const char* what, hipError_t e) {
     return MBX_ENODEVICE;
 }
 
+// the current device, after mbx_init() for it
+int ready_device(int* dev) {
+    const hipError_t e = hipGetDevice(dev);
+    if (e != hipSuccess) {
+        return hip_fail("hipGetDevice", e);
+    }
+    if (!mbx_device_ready(*dev)) {
+        mbx_set_error_text("mbx_init() has not been called for the current device");
+        return MBX_ENOTINIT;
+    }
+    return 0;
+}
+
+// the argument list of each kind, once
+template <int kForm, bool kInvert>
+void launch_hard(const mbx_burst_schedule* s, const uint8_t* in, size_t burst_stride, size_t n, uint8_t* out, int frame_stride, hipStream_t strm) {
+    const mbx::BurstShape& sh = s->shape;
+    const unsigned grid = (unsigned)((n + mbx::kGatherBursts - 1) / mbx::kGatherBursts);
+    hipLaunchKernelGGL((mbx::burst_gather_kernel<kForm, kInvert>), dim3(grid), dim3(256), s->hard_lds, strm, in, burst_stride, n, sh.frames, sh.bits,
+                       (int)sh.frame_bytes, s->d_wire_tab, s->d_xor_tab, out, frame_stride, s->lstride);
+}
+
+template <bool kDibits, bool kFlip>
+void launch_soft(const mbx_burst_schedule* s, const mbe_soft_bit* in, size_t n, mbe_soft_bit* out, int row_cells, hipStream_t strm) {
+    const mbx::BurstShape& sh = s->shape;
+    const unsigned grid = (unsigned)((n + (size_t)s->soft_bursts - 1) / (size_t)s->soft_bursts);
+    hipLaunchKernelGGL((mbx::burst_gather_soft_kernel<kDibits, kFlip>), dim3(grid), dim3(256), s->soft_lds, strm, in, n, sh.frames, (int)sh.soft_cells,
+                       (int)sh.cells, s->d_cell_tab, out, row_cells, s->soft_bursts);
+}
+
 }  // namespace
 
 namespace mbx {
@@ -456,41 +343,19 @@ BurstShape burst_shape(const mbx_burst_schedule* sched) { return sched->shape; }
 
 int burst_gather(const mbx_burst_schedule* sched, bool soft, const void* d_in, size_t burst_stride, size_t n, void* d_out, size_t row,
                  void* stream) {
-    const BurstShape& sh = sched->shape;
-    // a packed schedule without inversion (soft: a per-bit one) keeps the two kernels it has always had
-    const hipStream_t strm = (hipStream_t)stream;
+    // the seven instances, by (soft, form, inverts): BITS and DIBITS bursts always read their inversion table, dibit pairs always
+    // look for kInverted; a packed schedule (soft: a per-bit one) does so only where its sequence inverts a bit
+    const int form = sched->shape.form;
+    const bool inverts = sched->inverts;
     if (soft) {
-        const unsigned grid = (unsigned)((n + (size_t)sched->soft_bursts - 1) / (size_t)sched->soft_bursts);
-        const mbe_soft_bit* in = static_cast<const mbe_soft_bit*>(d_in);
-        mbe_soft_bit* out = static_cast<mbe_soft_bit*>(d_out);
-        if (sh.form == MBX_BURST_FORM_DIBITS) {
-            hipLaunchKernelGGL(burst_gather_soft_form_kernel<true>, dim3(grid), dim3(256), sched->soft_lds, strm, in, n, sh.frames, (int)sh.soft_cells,
-                               (int)sh.cells, sched->d_cell_tab, out, (int)row, sched->soft_bursts);
-        } else if (sched->inverts) {
-            hipLaunchKernelGGL(burst_gather_soft_form_kernel<false>, dim3(grid), dim3(256), sched->soft_lds, strm, in, n, sh.frames, (int)sh.soft_cells,
-                               (int)sh.cells, sched->d_cell_tab, out, (int)row, sched->soft_bursts);
-        } else {
-            hipLaunchKernelGGL(burst_gather_soft_kernel, dim3(grid), dim3(256), sched->soft_lds, strm, in, n, sh.frames, sh.bits, (int)sh.cells,
-                               sched->d_cell_tab, out, (int)row, sched->soft_bursts);
-        }
+        const auto launch = form == MBX_BURST_FORM_DIBITS ? launch_soft<true, true> : inverts ? launch_soft<false, true> : launch_soft<false, false>;
+        launch(sched, static_cast<const mbe_soft_bit*>(d_in), n, static_cast<mbe_soft_bit*>(d_out), (int)row, (hipStream_t)stream);
     } else {
-        const unsigned grid = (unsigned)((n + kGatherBursts - 1) / kGatherBursts);
-        const uint8_t* in = static_cast<const uint8_t*>(d_in);
-        uint8_t* out = static_cast<uint8_t*>(d_out);
-#define MBX_LAUNCH_FORM(form)                                                                                                                   \
-    hipLaunchKernelGGL(burst_gather_form_kernel<form>, dim3(grid), dim3(256), sched->hard_lds, strm, in, burst_stride, n, sh.frames, sh.bits, \
-                       (int)sh.frame_bytes, sched->d_wire_tab, sched->d_xor_tab, out, (int)row, sched->lstride)
-        if (sh.form == MBX_BURST_FORM_DIBITS) {
-            MBX_LAUNCH_FORM(MBX_BURST_FORM_DIBITS);
-        } else if (sh.form == MBX_BURST_FORM_BITS) {
-            MBX_LAUNCH_FORM(MBX_BURST_FORM_BITS);
-        } else if (sched->inverts) {
-            MBX_LAUNCH_FORM(MBX_BURST_FORM_PACKED);
-        } else {
-            hipLaunchKernelGGL(burst_gather_kernel, dim3(grid), dim3(256), sched->hard_lds, strm, in, burst_stride, n, sh.frames, sh.bits,
-                               (int)sh.frame_bytes, sched->d_wire_tab, out, (int)row, sched->lstride);
-        }
-#undef MBX_LAUNCH_FORM
+        const auto launch = form == MBX_BURST_FORM_DIBITS ? launch_hard<MBX_BURST_FORM_DIBITS, true>
+                            : form == MBX_BURST_FORM_BITS ? launch_hard<MBX_BURST_FORM_BITS, true>
+                            : inverts                     ? launch_hard<MBX_BURST_FORM_PACKED, true>
+                                                          : launch_hard<MBX_BURST_FORM_PACKED, false>;
+        launch(sched, static_cast<const uint8_t*>(d_in), burst_stride, n, static_cast<uint8_t*>(d_out), (int)row, (hipStream_t)stream);
     }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : hip_fail(soft ? "the soft burst gather" : "the burst gather", e);
@@ -504,13 +369,9 @@ namespace {
 int gather_ready(const char* who, const mbx_burst_schedule* sched, size_t n) {
     char text[200];
     int dev = -1;
-    const hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) {
-        return hip_fail("hipGetDevice", e);
-    }
-    if (!mbx_device_ready(dev)) {
-        mbx_set_error_text("mbx_init() has not been called for the current device");
-        return MBX_ENOTINIT;
+    const int rc = ready_device(&dev);
+    if (rc < 0) {
+        return rc;
     }
     if (dev != sched->shape.device) {
         snprintf(text, sizeof(text), "%s: the schedule was made on device %d, the current device is %d", who, sched->shape.device, dev);
@@ -532,6 +393,108 @@ int misaligned(const char* who) {
     return MBE_STATUS_INVALID_ARGUMENT;
 }
 
+int channel_bits(const mbx::CodecShape* sh) {   // of one frame
+    int nbits = 0;
+    for (int r = 0; r < sh->rows; ++r) {
+        nbits += sh->width[r];
+    }
+    return nbits;
+}
+
+// what of mbx_burst_schedule_create_form's arguments can be refused before their tables are read: the text, or nullptr
+const char* schedule_args_refused(const mbx::CodecShape* sh, int frames_per_burst, int burst_bits, const int* src_bit, const int* cell_row,
+                                  const int* cell_col, int form, const uint8_t* invert) {
+    if (!sh) {
+        return "no such codec";
+    }
+    if (!src_bit || !cell_row || !cell_col) {
+        return "src_bit, cell_row and cell_col are all needed";
+    }
+    if (frames_per_burst < 1 || frames_per_burst > MBX_BURST_MAX_FRAMES) {
+        return "frames_per_burst must be 1 .. MBX_BURST_MAX_FRAMES";
+    }
+    if (burst_bits < 1 || burst_bits > MBX_BURST_MAX_BITS) {
+        return "burst_bits must be 1 .. MBX_BURST_MAX_BITS";
+    }
+    if (form != MBX_BURST_FORM_PACKED && form != MBX_BURST_FORM_BITS && form != MBX_BURST_FORM_DIBITS) {
+        return "form must be one of MBX_BURST_FORM_*";
+    }
+    if (form == MBX_BURST_FORM_DIBITS && (burst_bits & 1)) {
+        return "the dibit form needs an even burst_bits";
+    }
+    for (int j = 0; invert && j < burst_bits; ++j) {
+        if (invert[j] > 1) {
+            return "an invert byte is not 0 or 1";
+        }
+    }
+    if ((long long)frames_per_burst * channel_bits(sh) > burst_bits) {
+        return "the burst has fewer bits than its frames have channel bits";
+    }
+    return nullptr;
+}
+
+// the caller's schedule folded into what the kernels read, in one array as it is uploaded:
+// wire table | cell table | one XOR byte per output byte (zero where no bit is inverted)
+struct FoldedSchedule {
+    std::vector<uint16_t> tabs;
+    size_t wire_entries = 0;   // F * frame_bytes * 8: the cell table starts here ...
+    size_t tab_entries = 0;    // ... and the XOR bytes here
+    bool   inverts = false;
+};
+
+// Host only, no device is asked for.  Returns the text of a refusal that only reading the tables can find, or nullptr.
+const char* fold_schedule(FoldedSchedule* f, int codec, const mbx::CodecShape* sh, int F, int burst_bits, const int* src_bit, const int* cell_row,
+                          const int* cell_col, const uint8_t* invert) {
+    const int nbits = channel_bits(sh), fbits = sh->frame_bytes * 8;
+    const size_t items = (size_t)F * (size_t)sh->frame_bytes;
+    f->wire_entries = (size_t)F * (size_t)fbits;
+    f->tab_entries = f->wire_entries + (size_t)F * (size_t)sh->cells;
+    f->tabs.assign(f->tab_entries + (items + 1) / 2, (uint16_t)mbx::kNoBit);
+    uint16_t* wire = f->tabs.data();
+    uint16_t* cell = f->tabs.data() + f->wire_entries;
+    uint8_t* flips = reinterpret_cast<uint8_t*>(f->tabs.data() + f->tab_entries);
+    memset(flips, 0, ((items + 1) / 2) * sizeof(uint16_t));
+    std::vector<uint8_t> named((size_t)burst_bits, 0);
+    for (int k = 0; k < F; ++k) {
+        for (int i = 0; i < nbits; ++i) {
+            const size_t at = (size_t)k * (size_t)nbits + (size_t)i;
+            const int w = mbx_wire_bit_of_cell(codec, cell_row[at], cell_col[at]);   // (the one table of mbx_codec.h, behind it)
+            if (w < 0) {
+                return "a cell that is not on the codec's wire";
+            }
+            if (wire[(size_t)k * fbits + w] != mbx::kNoBit) {
+                return "a cell of a frame is named twice";
+            }
+            const int j = src_bit[at];
+            if (j < 0 || j >= burst_bits) {
+                return "a src_bit outside [0, burst_bits)";
+            }
+            if (named[(size_t)j]) {
+                return "a burst bit is named twice";
+            }
+            named[(size_t)j] = 1;
+            wire[(size_t)k * fbits + w] = (uint16_t)j;
+            const bool flip = invert && invert[j];
+            cell[(size_t)k * sh->cells + (size_t)cell_row[at] * sh->stride + cell_col[at]] = (uint16_t)(flip ? (uint32_t)j | mbx::kInverted : (uint32_t)j);
+            if (flip) {
+                flips[((size_t)k * fbits + w) >> 3] |= (uint8_t)(0x80u >> (w & 7));
+                f->inverts = true;
+            }
+        }
+    }
+    // (nbits distinct wire bits per frame, all on the wire: every wire cell of every frame has its bit)
+    return nullptr;
+}
+
+// largest of `count` bytes, `step` apart, is above `most`
+bool any_byte_above(const uint8_t* bytes, size_t count, size_t step, uint32_t most) {
+    uint32_t seen = 0;
+    for (size_t i = 0; i < count; ++i) {
+        seen |= bytes[i * step];
+    }
+    return seen > most;
+}
+
 }  // namespace
 
 extern "C" {
@@ -548,93 +511,31 @@ int mbx_burst_schedule_create_form(mbx_burst_schedule** out, int codec, int fram
     }
     *out = nullptr;
     const mbx::CodecShape* sh = mbx::codec_shape(codec);
-    if (!sh) {
-        return refuse("no such codec");
+    const int F = frames_per_burst;
+    FoldedSchedule folded;
+    const char* why = schedule_args_refused(sh, F, burst_bits, src_bit, cell_row, cell_col, form, invert);
+    if (!why) {
+        why = fold_schedule(&folded, codec, sh, F, burst_bits, src_bit, cell_row, cell_col, invert);
     }
-    if (!src_bit || !cell_row || !cell_col) {
-        return refuse("src_bit, cell_row and cell_col are all needed");
+    if (why) {
+        return refuse(why);
     }
-    if (frames_per_burst < 1 || frames_per_burst > MBX_BURST_MAX_FRAMES) {
-        return refuse("frames_per_burst must be 1 .. MBX_BURST_MAX_FRAMES");
-    }
-    if (burst_bits < 1 || burst_bits > MBX_BURST_MAX_BITS) {
-        return refuse("burst_bits must be 1 .. MBX_BURST_MAX_BITS");
-    }
-    if (form != MBX_BURST_FORM_PACKED && form != MBX_BURST_FORM_BITS && form != MBX_BURST_FORM_DIBITS) {
-        return refuse("form must be one of MBX_BURST_FORM_*");
-    }
-    if (form == MBX_BURST_FORM_DIBITS && (burst_bits & 1)) {
-        return refuse("the dibit form needs an even burst_bits");
-    }
-    for (int j = 0; invert && j < burst_bits; ++j) {
-        if (invert[j] > 1) {
-            return refuse("an invert byte is not 0 or 1");
-        }
-    }
-    int nbits = 0;   // channel bits of one frame
-    for (int r = 0; r < sh->rows; ++r) {
-        nbits += sh->width[r];
-    }
-    const int F = frames_per_burst, fbits = sh->frame_bytes * 8;
-    if ((long long)F * nbits > burst_bits) {
-        return refuse("the burst has fewer bits than its frames have channel bits");
-    }
-    // wire table | cell table | one XOR byte per output byte (zero where no bit is inverted: after the fill with kNoBit)
-    const size_t items = (size_t)F * (size_t)sh->frame_bytes;
-    const size_t tab_entries = (size_t)F * (size_t)fbits + (size_t)F * (size_t)sh->cells;
-    std::vector<uint16_t> tabs(tab_entries + (items + 1) / 2, (uint16_t)mbx::kNoBit);
-    uint16_t* wire = tabs.data();
-    uint16_t* cell = tabs.data() + (size_t)F * (size_t)fbits;
-    uint8_t* flips = reinterpret_cast<uint8_t*>(tabs.data() + tab_entries);
-    memset(flips, 0, ((items + 1) / 2) * sizeof(uint16_t));
-    bool inverts = false;
-    std::vector<uint8_t> named((size_t)burst_bits, 0);
-    for (int k = 0; k < F; ++k) {
-        for (int i = 0; i < nbits; ++i) {
-            const size_t at = (size_t)k * (size_t)nbits + (size_t)i;
-            const int w = mbx_wire_bit_of_cell(codec, cell_row[at], cell_col[at]);   // (the one table of mbx_codec.h, behind it)
-            if (w < 0) {
-                return refuse("a cell that is not on the codec's wire");
-            }
-            if (wire[(size_t)k * fbits + w] != mbx::kNoBit) {
-                return refuse("a cell of a frame is named twice");
-            }
-            const int j = src_bit[at];
-            if (j < 0 || j >= burst_bits) {
-                return refuse("a src_bit outside [0, burst_bits)");
-            }
-            if (named[(size_t)j]) {
-                return refuse("a burst bit is named twice");
-            }
-            named[(size_t)j] = 1;
-            wire[(size_t)k * fbits + w] = (uint16_t)j;
-            const bool flip = invert && invert[j];
-            cell[(size_t)k * sh->cells + (size_t)cell_row[at] * sh->stride + cell_col[at]] = (uint16_t)(flip ? (uint32_t)j | mbx::kFlip : (uint32_t)j);
-            if (flip) {
-                flips[((size_t)k * fbits + w) >> 3] |= (uint8_t)(0x80u >> (w & 7));
-                inverts = true;
-            }
-        }
-    }
-    // (nbits distinct wire bits per frame, all on the wire: every wire cell of every frame has its bit)
+    // every refusal is behind us: now the device
     int dev = -1;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) {
-        return hip_fail("hipGetDevice", e);
-    }
-    if (!mbx_device_ready(dev)) {
-        mbx_set_error_text("mbx_init() has not been called for the current device");
-        return MBX_ENOTINIT;
+    const int rc = ready_device(&dev);
+    if (rc < 0) {
+        return rc;
     }
     mbx_burst_schedule* s = new (std::nothrow) mbx_burst_schedule();
     if (!s) {
         return refuse("out of memory");
     }
+    const size_t items = (size_t)F * (size_t)sh->frame_bytes;
     const size_t packed_bytes = ((size_t)burst_bits + 7) / 8;
     const size_t bytes = form == MBX_BURST_FORM_BITS ? (size_t)burst_bits : (form == MBX_BURST_FORM_DIBITS ? (size_t)burst_bits / 2 : packed_bytes);
     const size_t soft_cells = form == MBX_BURST_FORM_DIBITS ? (size_t)burst_bits / 2 : (size_t)burst_bits;
     s->shape = mbx::BurstShape{codec, F, burst_bits, dev, bytes, (size_t)sh->frame_bytes, (size_t)sh->cells, form, soft_cells};
-    s->inverts = inverts;
+    s->inverts = folded.inverts;
     // the hard gather works on the PACKED image of the bursts whatever their form: lstride and the dynamic LDS do not depend on it
     const int bdw = (int)((packed_bytes + 3) / 4);
     s->lstride = 4 * (bdw | 1);
@@ -643,7 +544,8 @@ int mbx_burst_schedule_create_form(mbx_burst_schedule** out, int codec, int fram
     const int most = form == MBX_BURST_FORM_DIBITS ? mbx::kSoftDibitBursts : 16;
     s->soft_bursts = nb < 1 ? 1 : (nb > most ? most : nb);
     s->soft_lds = (unsigned)((size_t)F * (size_t)sh->cells * 2 + ((size_t)s->soft_bursts * soft_cells + 2) * 2 + 3) & ~3u;
-    e = hipMalloc(reinterpret_cast<void**>(&s->d_wire_tab), tabs.size() * sizeof(uint16_t));
+    const std::vector<uint16_t>& tabs = folded.tabs;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->d_wire_tab), tabs.size() * sizeof(uint16_t));
     if (e == hipSuccess) {
         e = hipMemcpy(s->d_wire_tab, tabs.data(), tabs.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
     }
@@ -652,8 +554,8 @@ int mbx_burst_schedule_create_form(mbx_burst_schedule** out, int codec, int fram
         delete s;
         return hip_fail("mbx_burst_schedule_create: upload of the tables", e);
     }
-    s->d_cell_tab = s->d_wire_tab + (size_t)F * (size_t)fbits;
-    s->d_xor_tab = reinterpret_cast<uint8_t*>(s->d_wire_tab + tab_entries);
+    s->d_cell_tab = s->d_wire_tab + folded.wire_entries;
+    s->d_xor_tab = reinterpret_cast<uint8_t*>(s->d_wire_tab + folded.tab_entries);
     *out = s;
     return 0;
 }
@@ -684,11 +586,7 @@ int mbx_burst_validate(const mbx_burst_schedule* sched, const void* bursts, size
             return mbx_validate_soft_bits(static_cast<const mbe_soft_bit*>(bursts), n * sh.soft_cells);
         }
         const mbe_soft_bit* c = static_cast<const mbe_soft_bit*>(bursts);
-        uint32_t seen = 0;
-        for (size_t i = 0; i < n * sh.soft_cells; ++i) {
-            seen |= c[i].bit;
-        }
-        return seen > 3u ? MBE_STATUS_INVALID_BITS : 0;
+        return any_byte_above(&c->bit, n * sh.soft_cells, sizeof(mbe_soft_bit), 3u) ? MBE_STATUS_INVALID_BITS : 0;
     }
     if (burst_stride < sh.bytes) {
         mbx_set_error_text("mbx_burst_validate: burst_stride is below mbx_burst_schedule_bytes()");
@@ -700,11 +598,7 @@ int mbx_burst_validate(const mbx_burst_schedule* sched, const void* bursts, size
     const uint32_t most = sh.form == MBX_BURST_FORM_BITS ? 1u : 3u;
     const uint8_t* b = static_cast<const uint8_t*>(bursts);
     for (size_t i = 0; i < n; ++i, b += burst_stride) {
-        uint32_t seen = 0;
-        for (size_t k = 0; k < sh.bytes; ++k) {
-            seen |= b[k];
-        }
-        if (seen > most) {
+        if (any_byte_above(b, sh.bytes, 1, most)) {
             return MBE_STATUS_INVALID_BITS;
         }
     }

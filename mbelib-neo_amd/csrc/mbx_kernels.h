@@ -122,13 +122,12 @@ __global__ void expand_ambe_kernel(const mbx_param_record*, size_t, FrameParams*
 __global__ void expand_ambe2400_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
 
 // ---- mbx_burst.hip: burst input, in front of a batch step -- received bursts -> wire frames / cell arrays by a caller's schedule -----------
-__global__ void burst_gather_kernel(const uint8_t*, size_t, size_t, int, int, int, const uint16_t*, uint8_t*, int, int);
+// (one template per kind over the forms of mbx_burst_schedule_create_form: packed bits, bit bytes, dibit bytes; per-bit cells, dibit
+// pairs; with or without an inversion sequence)
+template <int kForm, bool kInvert>
+__global__ void burst_gather_kernel(const uint8_t*, size_t, size_t, int, int, int, const uint16_t*, const uint8_t*, uint8_t*, int, int);
+template <bool kDibits, bool kFlip>
 __global__ void burst_gather_soft_kernel(const mbe_soft_bit*, size_t, int, int, int, const uint16_t*, mbe_soft_bit*, int, int);
-// (the forms of mbx_burst_schedule_create_form: bursts of bit bytes, dibit bytes, dibit pairs, and an inversion sequence)
-template <int kForm>
-__global__ void burst_gather_form_kernel(const uint8_t*, size_t, size_t, int, int, int, const uint16_t*, const uint8_t*, uint8_t*, int, int);
-template <bool kDibits>
-__global__ void burst_gather_soft_form_kernel(const mbe_soft_bit*, size_t, int, int, int, const uint16_t*, mbe_soft_bit*, int, int);
 
 // ---- mbx_api.hip ---------------------------------------------------------------------------------------------------------------
 // (C linkage: defined inside the extern "C" block of the entry points, so the profiler prints the bare name)
