@@ -15,16 +15,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <condition_variable>
-#include <deque>
-#include <functional>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <algorithm>
 #include <vector>
 
+#include "mbe_flush_plan.h"
 #include "mbe_neo_amd.h"
 #include "mbx.h"
 #include "mbx_codec.h"
@@ -121,7 +118,6 @@ struct Slot {
     mbx_frame_mailbox* mailbox = nullptr;
     hipStream_t       server_stream = nullptr;
     uint32_t          seq = 0;
-    hipEvent_t        batch_done = nullptr;
     hipEvent_t        chunk_done[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // mbe_flush: small outputs, then four PCM chunks
     uint8_t*          frame_out = nullptr; // 18 bytes: a frame after one of the in-place sub-stages
     mbe_soft_bit*     soft = nullptr;     // one soft frame (184 cells)
@@ -269,20 +265,6 @@ struct Slot {
             __atomic_store_n(&mailbox->alive, 0u, __ATOMIC_RELEASE);
         }
     }
-    // the end of a queued batch (mbe_flush): the thread SLEEPS until the stream is done instead of spinning -- a flush takes
-    // a millisecond, a wake-up tens of microseconds, and a host with one decoder thread per core must not have all of
-    // them burning their cores (and the container's CPU quota) in wait loops
-    void sync_blocking() {
-        if (!batch_done) {
-            HIP_OK(hipEventCreateWithFlags(&batch_done, hipEventDisableTiming | hipEventBlockingSync));
-        }
-        HIP_OK(hipEventRecord(batch_done, stream));
-        HIP_OK(hipEventSynchronize(batch_done));
-        for (int i = 0; i < npending; ++i) {
-            memcpy(pending[i].dst, pending[i].src, pending[i].n);
-        }
-        npending = 0;
-    }
     void sync() {
         HIP_OK(hipStreamSynchronize(stream));
         for (int i = 0; i < npending; ++i) {
@@ -309,9 +291,6 @@ struct SlotHolder {
             }
             (void)hipStreamSynchronize(p->stream);
             (void)mbx_release_stream(p->stream);
-            if (p->batch_done) {
-                (void)hipEventDestroy(p->batch_done);
-            }
             for (hipEvent_t e : p->chunk_done) {
                 if (e) {
                     (void)hipEventDestroy(e);
@@ -616,7 +595,6 @@ struct QChannel {
     int  codec = -1;       // codec of the frames pending for this channel (one codec per channel and flush)
     bool soft = false;     // ... and their input form (one per channel and flush as well)
     int  pending = 0;
-    int  first = -1;       // per-flush scratch: position of the channel inside its group
     int  slot = -1;        // where its state lives in the device pool (resident mode: = channel index; write-back: per flush)
     bool on_device = false;
     mbx_stream_rng rng;    // the thread's RNG state at the channel's first queued frame; in write-back mode the channel's
@@ -701,6 +679,8 @@ struct Batch {
     PinArr<uint8_t>            h_codecs;
     PinArr<mbe_parms>          h_state;
     PinArr<mbx_stream_rng>     h_rng;
+    mbx::FlushPlan             plan;                      // the flush under way: groups, rows, bytes (mbe_flush_plan.h); reused from flush to flush
+    std::vector<int>           upload;                    // ... and the channels whose state went up for it, in slot order
 };
 
 struct BatchHolder {   // freed with the thread (the arrays' destructors return the device and pinned memory)
@@ -714,11 +694,6 @@ Batch& batch() {
         holder.p = new Batch();
     }
     return *holder.p;
-}
-
-// one frame as the batch launchers take it: packed wire bytes, or the reference's array of soft cells
-size_t input_bytes_of(int codec, bool soft) {
-    return soft ? (size_t)mbx::kCodecs[codec].cells * sizeof(mbe_soft_bit) : (size_t)mbx::kCodecs[codec].frame_bytes;
 }
 
 // grow the device pool to `n` channels, keeping what is resident
@@ -827,17 +802,34 @@ static const bool g_trace_flush = [] {
 }();
 thread_local FlushTrace t_flush_trace;
 
-int flush_batch(Batch& b) {
-    const size_t n = b.q.size();
-    if (n == 0) {
-        return 0;
-    }
-    Slot& s = slot();
-    const double tr0 = g_trace_flush ? trace_now() : 0.0;
-    // ---- state upload.  Resident mode: the channels first seen since the last flush, appended at slots [resident, total).
-    //      Write-back mode: every channel that has frames this time, at slots [0, k); nothing stays afterwards. ----
+// How one flush runs, decided once its inputs are staged: where the kernels read and write -- the thread's PINNED arrays themselves
+// (zero-copy) or their device twins -- and how the PCM comes back.
+struct FlushRun {
+    bool   zero_copy;
+    int    chunks;        // PCM chunks of the copy-out: 4 from 8,192 rows on
+    size_t per_chunk;     // rows of a chunk (the last may be shorter)
+    const uint8_t* frames;
+    const int32_t* index;
+    const int32_t* offsets;
+    const uint8_t* codecs;
+    int16_t*            pcm16;     // nullptr: no queued call wants it
+    float*              pcmf;
+    mbe_process_result* results;
+    mbx_param_record*   records;
+};
+constexpr int kMaxChunks = 4;
+
+template <class U>
+U* flush_view(bool zero_copy, const PinArr<U>& h, const DevArr<U>& d) {
+    return zero_copy ? h.p : d.p;
+}
+
+// ---- state upload.  Resident mode: the channels first seen since the last flush, appended at slots [resident, total).
+//      Write-back mode: every channel that has frames this time, at slots [0, k); nothing stays afterwards. ----
+void flush_upload_state(Batch& b, Slot& s) {
     const size_t total = b.channels.size();
-    std::vector<int> upload;
+    std::vector<int>& upload = b.upload;
+    upload.clear();
     size_t first_slot = 0;
     if (b.mode == MBE_BATCH_STATE_RESIDENT) {
         first_slot = b.resident;
@@ -854,124 +846,68 @@ int flush_batch(Batch& b) {
         }
     }
     pool_reserve(b, s, first_slot + upload.size());
-    if (!upload.empty()) {
-        b.h_state.need(upload.size() * 3);
-        b.h_rng.need(upload.size());
-        for (size_t i = 0; i < upload.size(); ++i) {
-            QChannel& ch = b.channels[(size_t)upload[i]];
-            b.h_state.p[3 * i + 0] = *ch.cur;
-            b.h_state.p[3 * i + 1] = *ch.prev;
-            b.h_state.p[3 * i + 2] = *ch.enh;
-            b.h_rng.p[i] = ch.rng;
-            ch.on_device = true;
-        }
-        s.up(b.d_state.p + 3 * first_slot, b.h_state.p, upload.size() * 3 * sizeof(mbe_parms));
-        s.up(b.d_rng.p + first_slot, b.h_rng.p, upload.size() * sizeof(mbx_stream_rng));
-        HIP_OK(hipMemsetAsync(b.d_elided.p + first_slot, 0, upload.size() * sizeof(uint32_t), s.stream));   // whole triplets came up
-        b.resident = first_slot + upload.size();
+    if (upload.empty()) {
+        return;
     }
-    // ---- groups of channels with the same codec, input form and number of pending frames ----
-    struct Group {
-        int    codec, T;
-        bool   soft;
-        size_t nch = 0, row0 = 0, byte0 = 0;    // channels, first batch row, byte offset of its frames
-        std::vector<int> members;
-        size_t stride = 0;                      // bytes from one frame to the next in h_frames (mixed: the largest codec's)
-    };
-    std::vector<Group> groups;
-    std::unordered_map<uint64_t, size_t> group_of;
-    for (size_t c = 0; c < total; ++c) {
-        QChannel& ch = b.channels[c];
-        if (ch.pending == 0) {
-            continue;
-        }
-        const uint64_t key = ((uint64_t)ch.codec << 33) | ((uint64_t)ch.soft << 32) | (uint32_t)ch.pending;
-        auto it = group_of.find(key);
-        if (it == group_of.end()) {
-            it = group_of.emplace(key, groups.size()).first;
-            groups.push_back(Group{ch.codec, ch.pending, ch.soft});
-        }
-        Group& g = groups[it->second];
-        ch.first = (int)g.nch++;
-        g.members.push_back((int)c);
+    b.h_state.need(upload.size() * 3);
+    b.h_rng.need(upload.size());
+    for (size_t i = 0; i < upload.size(); ++i) {
+        QChannel& ch = b.channels[(size_t)upload[i]];
+        b.h_state.p[3 * i + 0] = *ch.cur;
+        b.h_state.p[3 * i + 1] = *ch.prev;
+        b.h_state.p[3 * i + 2] = *ch.enh;
+        b.h_rng.p[i] = ch.rng;
+        ch.on_device = true;
     }
-    // The groups of an input form are neighbours, hard first: form f owns groups [form_g0[f], form_g0[f + 1]).  A form with several
-    // groups goes out as ONE mixed launch set: its rows are one ragged batch (the groups' channels in order, each with its T rows),
-    // its frames rows of one size.  A form with one group keeps the group's own launcher.
-    std::stable_sort(groups.begin(), groups.end(), [](const Group& x, const Group& y) { return !x.soft && y.soft; });
-    size_t form_g0[3] = {0, 0, groups.size()};
-    while (form_g0[1] < groups.size() && !groups[form_g0[1]].soft) {
-        form_g0[1]++;
-    }
-    const bool form_mixed[2] = {form_g0[1] - form_g0[0] > 1, form_g0[2] - form_g0[1] > 1};
-    size_t rows = 0, bytes = 0;
-    for (Group& g : groups) {
-        g.row0 = rows;
-        g.byte0 = bytes;
-        g.stride = !form_mixed[g.soft] ? input_bytes_of(g.codec, g.soft)
-                                       : (g.soft ? MBX_IMBE_SOFT_BITS * sizeof(mbe_soft_bit) : (size_t)MBX_IMBE_FRAME_BYTES);
-        rows += g.nch * (size_t)g.T;
-        bytes += g.nch * (size_t)g.T * g.stride;
-        if (!form_mixed[g.soft] || &g == &groups[form_g0[g.soft + 1] - 1]) {   // (the rows of a mixed form are one array)
-            bytes = (bytes + 15u) & ~(size_t)15u;                              // frame arrays start 16-byte aligned
-        }
-    }
-    // row of every queue entry: group row0 + position of the channel * T + (how many of the channel's frames came before)
-    std::vector<size_t> row_of(n);
-    std::vector<int> seen(total, 0);
-    std::vector<size_t> group_idx(total);
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        for (int c : groups[gi].members) {
-            group_idx[(size_t)c] = gi;
-        }
-    }
-    b.h_frames.need(bytes);
+    s.up(b.d_state.p + 3 * first_slot, b.h_state.p, upload.size() * 3 * sizeof(mbe_parms));
+    s.up(b.d_rng.p + first_slot, b.h_rng.p, upload.size() * sizeof(mbx_stream_rng));
+    HIP_OK(hipMemsetAsync(b.d_elided.p + first_slot, 0, upload.size() * sizeof(uint32_t), s.stream));   // whole triplets came up
+    b.resident = first_slot + upload.size();
+}
+
+// SMALL flushes (many host threads, each with a share of the channels) move nothing with copy calls: the kernels read the frames
+// and the index from, and write PCM / results / records to, the thread's PINNED host buffers directly (device-visible addresses),
+// and the flush is then two or three trips into the HIP runtime -- launch, event, wait -- instead of a dozen.  What bounds the
+// rate from many threads is the number of such trips, not the bytes (tools/fanin_evidence.py: no CPU throttling at sixteen
+// threads, profiles/r05/fanin.json).  Large flushes keep the chunked copies: PCIe runs at its best with a DMA engine, and the
+// host scatters one chunk while the next one crosses.  MBE_NEO_ZERO_COPY_FLUSH=0 switches it off (A/B timing).
+// Every thread launches its own flush (a "pump" thread that launched for all of them was slower: EXPERIMENTS.md 6.4).
+bool flush_zero_copy(size_t rows) {
+    static const bool zero_copy_on = [] {
+        const char* e = getenv("MBE_NEO_ZERO_COPY_FLUSH");
+        return !(e && e[0] == '0');
+    }();
+    return zero_copy_on && rows < 8192;
+}
+
+// ---- inputs: the queued frames gathered into h_frames where the plan puts them, the plan's channels as pool slots, the offsets and
+//      codecs of the mixed forms; every array sized; the views chosen; the inputs uploaded unless the kernels read them in place ----
+FlushRun flush_stage_inputs(Batch& b, Slot& s) {
+    const mbx::FlushPlan& p = b.plan;
+    const size_t total = b.channels.size(), rows = p.rows;
+    b.h_frames.need(p.bytes);
     b.h_index.need(total);
     bool any_short = false, any_float = false;
-    for (size_t e = 0; e < n; ++e) {
+    for (size_t e = 0; e < b.q.size(); ++e) {
         const QEntry& qe = b.q[e];
-        const Group& g = groups[group_idx[(size_t)qe.channel]];
-        const size_t local = (size_t)b.channels[(size_t)qe.channel].first * (size_t)g.T + (size_t)seen[(size_t)qe.channel]++;
-        row_of[e] = g.row0 + local;
-        memcpy(b.h_frames.p + g.byte0 + local * g.stride, g.soft ? static_cast<const void*>(&b.soft_cells[qe.soft_at]) : static_cast<const void*>(qe.frame),
-               input_bytes_of(g.codec, g.soft));
+        const QChannel& ch = b.channels[(size_t)qe.channel];
+        memcpy(b.h_frames.p + p.byte_of(e, qe.channel), ch.soft ? static_cast<const void*>(&b.soft_cells[qe.soft_at]) : static_cast<const void*>(qe.frame),
+               mbx::flush_input_bytes(ch.codec, ch.soft));
         any_short |= qe.want_short != 0;
         any_float |= qe.want_short == 0;
     }
-    size_t idx0 = 0;
-    std::vector<size_t> index_off(groups.size());
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        index_off[gi] = idx0;
-        for (int c : groups[gi].members) {
-            b.h_index.p[idx0++] = b.channels[(size_t)c].slot;
-        }
+    for (size_t i = 0; i < p.channels.size(); ++i) {
+        b.h_index.p[i] = b.channels[(size_t)p.channels[i]].slot;
     }
-    // mixed forms: offsets (channels + 1 per form) and codecs of their channels, in the order of the index
-    size_t off_at[2] = {0, 0}, codec_at[2] = {0, 0};
-    if (form_mixed[0] || form_mixed[1]) {
+    if (p.any_mixed()) {
         b.h_offsets.need(total + 2);
         b.h_codecs.need(total);
         b.d_offsets.need(total + 2);
         b.d_codecs.need(total);
-        size_t no = 0, nc = 0;
-        for (int f = 0; f < 2; ++f) {
-            if (!form_mixed[f]) {
-                continue;
-            }
-            off_at[f] = no;
-            codec_at[f] = nc;
-            int32_t row = 0;   // (relative to the form's first row)
-            for (size_t gi = form_g0[f]; gi < form_g0[f + 1]; ++gi) {
-                for (size_t k = 0; k < groups[gi].nch; ++k) {
-                    b.h_offsets.p[no++] = row;
-                    b.h_codecs.p[nc++] = (uint8_t)groups[gi].codec;
-                    row += groups[gi].T;
-                }
-            }
-            b.h_offsets.p[no++] = row;
-        }
+        memcpy(b.h_offsets.p, p.offsets.data(), p.offsets.size() * sizeof(int32_t));
+        memcpy(b.h_codecs.p, p.codecs.data(), p.codecs.size());
     }
-    b.d_frames.need(bytes);
+    b.d_frames.need(p.bytes);
     b.d_index.need(total);
     b.d_records.need(rows);
     b.d_results.need(rows);
@@ -985,145 +921,164 @@ int flush_batch(Batch& b) {
         b.d_pcmf.need(rows * 160);
         b.h_pcmf.need(rows * 160);
     }
-    // SMALL flushes (many host threads, each with a share of the channels) move nothing with copy calls: the kernels read the frames
-    // and the index from, and write PCM / results / records to, the thread's PINNED host buffers directly (device-visible addresses),
-    // and the flush is then two or three trips into the HIP runtime -- launch, event, wait -- instead of a dozen.  What bounds the
-    // rate from many threads is the number of such trips, not the bytes (tools/fanin_evidence.py: no CPU throttling at sixteen
-    // threads, profiles/r05/fanin.json).  Large flushes keep the chunked copies: PCIe runs at its best with a DMA engine, and the
-    // host scatters one chunk while the next one crosses.  MBE_NEO_ZERO_COPY_FLUSH=0 switches it off (A/B timing).
-    // (Round 5 also handed the launches of such flushes to ONE "pump" thread.  Timed over a region long enough to mean something --
-    // the same number of frames per thread at every thread count, tools/src/host_bench.c -- every thread launching for itself is as
-    // fast or faster: 4 / 8 / 16 threads 43 / 72 / 50 M frames/s against 36 / 63 / 37-59 M through the pump, reworked or not
-    // (profiles/r06/fanin_pump_ab.log).  The pump is gone, and with it the stack-lifetime hazard ADVICE r5 found in its wake-up.)
-    static const bool zero_copy_on = [] {
-        const char* e = getenv("MBE_NEO_ZERO_COPY_FLUSH");
-        return !(e && e[0] == '0');
-    }();
-    const bool zero_copy = zero_copy_on && rows < 8192;
-    const uint8_t* const k_frames = zero_copy ? b.h_frames.p : b.d_frames.p;
-    const int32_t* const k_index = zero_copy ? b.h_index.p : b.d_index.p;
-    int16_t* const k_pcm16 = !any_short ? nullptr : (zero_copy ? b.h_pcm16.p : b.d_pcm16.p);
-    float* const k_pcmf = !any_float ? nullptr : (zero_copy ? b.h_pcmf.p : b.d_pcmf.p);
-    mbe_process_result* const k_results = zero_copy ? b.h_results.p : b.d_results.p;
-    mbx_param_record* const k_records = zero_copy ? b.h_records.p : b.d_records.p;
-    const int32_t* const k_offsets = zero_copy ? b.h_offsets.p : b.d_offsets.p;
-    const uint8_t* const k_codecs = zero_copy ? b.h_codecs.p : b.d_codecs.p;
-    if (!zero_copy) {
-        s.up(b.d_frames.p, b.h_frames.p, bytes);
-        s.up(b.d_index.p, b.h_index.p, idx0 * sizeof(int32_t));
-        if (form_mixed[0] || form_mixed[1]) {
-            s.up(b.d_offsets.p, b.h_offsets.p, (idx0 + 2) * sizeof(int32_t));
-            s.up(b.d_codecs.p, b.h_codecs.p, idx0);
+    const bool zc = flush_zero_copy(rows);
+    const int chunks = rows >= 8192 ? kMaxChunks : 1;
+    const FlushRun r = {zc, chunks, (rows + chunks - 1) / chunks,
+                        flush_view(zc, b.h_frames, b.d_frames), flush_view(zc, b.h_index, b.d_index), flush_view(zc, b.h_offsets, b.d_offsets),
+                        flush_view(zc, b.h_codecs, b.d_codecs), any_short ? flush_view(zc, b.h_pcm16, b.d_pcm16) : nullptr,
+                        any_float ? flush_view(zc, b.h_pcmf, b.d_pcmf) : nullptr, flush_view(zc, b.h_results, b.d_results),
+                        flush_view(zc, b.h_records, b.d_records)};
+    if (!zc) {
+        s.up(b.d_frames.p, b.h_frames.p, p.bytes);
+        s.up(b.d_index.p, b.h_index.p, p.channels.size() * sizeof(int32_t));
+        if (p.any_mixed()) {
+            s.up(b.d_offsets.p, b.h_offsets.p, p.offsets.size() * sizeof(int32_t));
+            s.up(b.d_codecs.p, b.h_codecs.p, p.codecs.size());
         }
     }
-    const double tr1 = g_trace_flush ? trace_now() : 0.0;
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const Group& g = groups[gi];
-        if (form_mixed[g.soft]) {   // the whole form at its first group: one mixed launch set on the pool
-            if (gi != form_g0[g.soft]) {
-                continue;
-            }
-            size_t nch = 0, nrows = 0;
-            for (size_t k = gi; k < form_g0[g.soft + 1]; ++k) {
-                nch += groups[k].nch;
-                nrows += groups[k].nch * (size_t)groups[k].T;
-            }
-            uint32_t* const elided = b.mode == MBE_BATCH_STATE_RESIDENT ? b.d_elided.p : nullptr;
-            int16_t* const pcm16 = k_pcm16 ? k_pcm16 + g.row0 * 160 : nullptr;
-            float* const pcmf = k_pcmf ? k_pcmf + g.row0 * 160 : nullptr;
+    return r;
+}
+
+// ---- launches: a mixed form as ONE launch set at its first group; a group alone in its form by the single-codec launcher of its
+//      input form and state mode ----
+void flush_launch(Batch& b, Slot& s, const FlushRun& r) {
+    const mbx::FlushPlan& p = b.plan;
+    const bool resident = b.mode == MBE_BATCH_STATE_RESIDENT;
+    uint32_t* const elided = resident ? b.d_elided.p : nullptr;   // (no elision words in write-back mode)
+    for (size_t gi = 0; gi < p.groups.size(); ++gi) {
+        const mbx::FlushGroup& g = p.groups[gi];
+        const int f = g.soft ? 1 : 0;
+        if (p.form_mixed[f] && gi != p.form_g0[f]) {
+            continue;   // (went out with the first group of its form)
+        }
+        const int32_t* const index = r.index + g.index0;
+        const uint8_t* const frames = r.frames + g.byte0;
+        const mbe_soft_bit* const cells = reinterpret_cast<const mbe_soft_bit*>(frames);
+        // every launcher ends in the same arguments: the RNG pool, the group's rows of the four output arrays, the stream
+        auto launch = [&](const char* name, auto fn, auto... head) {
+            must(fn(head..., b.d_rng.p, r.pcm16 ? r.pcm16 + g.row0 * 160 : nullptr, r.pcmf ? r.pcmf + g.row0 * 160 : nullptr, r.results + g.row0,
+                    r.records + g.row0, s.stream),
+                 name);
+        };
+        if (p.form_mixed[f]) {
+            const int nch = (int)p.form_channels(f);
+            const uint8_t* const codecs = r.codecs + p.codec_at[f];
+            const int32_t* const offsets = r.offsets + p.off_at[f];
             if (g.soft) {
-                must(mbx_process_batch_soft_mixed((int)nch, k_codecs + codec_at[1], k_offsets + off_at[1], nrows, k_index + index_off[gi],
-                                                  reinterpret_cast<const mbe_soft_bit*>(k_frames + g.byte0), b.d_state.p, elided, b.d_rng.p, pcm16,
-                                                  pcmf, k_results + g.row0, k_records + g.row0, s.stream),
-                     "mbx_process_batch_soft_mixed");
+                launch("mbx_process_batch_soft_mixed", mbx_process_batch_soft_mixed, nch, codecs, offsets, p.form_rows(f), index, cells, b.d_state.p, elided);
             } else {
-                must(mbx_process_batch_mixed((int)nch, k_codecs + codec_at[0], k_offsets + off_at[0], nrows, k_index + index_off[gi],
-                                             k_frames + g.byte0, b.d_state.p, elided, b.d_rng.p, pcm16, pcmf, k_results + g.row0,
-                                             k_records + g.row0, s.stream),
-                     "mbx_process_batch_mixed");
+                launch("mbx_process_batch_mixed", mbx_process_batch_mixed, nch, codecs, offsets, p.form_rows(f), index, frames, b.d_state.p, elided);
             }
-        } else if (g.soft) {   // soft cells in: the soft twin of both launchers (no elision words in write-back mode)
-            must(mbx_process_batch_soft_resident(g.codec, (int)g.nch, g.T, k_index + index_off[gi],
-                                                 reinterpret_cast<const mbe_soft_bit*>(k_frames + g.byte0), b.d_state.p,
-                                                 b.mode == MBE_BATCH_STATE_RESIDENT ? b.d_elided.p : nullptr, b.d_rng.p,
-                                                 k_pcm16 ? k_pcm16 + g.row0 * 160 : nullptr, k_pcmf ? k_pcmf + g.row0 * 160 : nullptr,
-                                                 k_results + g.row0, k_records + g.row0, s.stream),
-                 "mbx_process_batch_soft_resident");
-        } else if (b.mode == MBE_BATCH_STATE_RESIDENT) {   // the pool owns the state between flushes: no prev_mp_enhanced traffic, lazy prev_mp
-            must(mbx_process_batch_resident(g.codec, (int)g.nch, g.T, k_index + index_off[gi], k_frames + g.byte0, b.d_state.p,
-                                            b.d_elided.p, b.d_rng.p, k_pcm16 ? k_pcm16 + g.row0 * 160 : nullptr,
-                                            k_pcmf ? k_pcmf + g.row0 * 160 : nullptr, k_results + g.row0, k_records + g.row0, s.stream),
-                 "mbx_process_batch_resident");
+        } else if (g.soft) {   // soft cells in: the soft twin of both launchers
+            launch("mbx_process_batch_soft_resident", mbx_process_batch_soft_resident, g.codec, (int)g.nch, g.T, index, cells, b.d_state.p, elided);
+        } else if (resident) {   // the pool owns the state between flushes: no prev_mp_enhanced traffic, lazy prev_mp
+            launch("mbx_process_batch_resident", mbx_process_batch_resident, g.codec, (int)g.nch, g.T, index, frames, b.d_state.p, elided);
         } else {
-            must(mbx_process_batch_indexed(g.codec, (int)g.nch, g.T, k_index + index_off[gi], k_frames + g.byte0, b.d_state.p,
-                                           b.d_rng.p, k_pcm16 ? k_pcm16 + g.row0 * 160 : nullptr,
-                                           k_pcmf ? k_pcmf + g.row0 * 160 : nullptr, k_results + g.row0, k_records + g.row0, s.stream),
-                 "mbx_process_batch_indexed");
+            launch("mbx_process_batch_indexed", mbx_process_batch_indexed, g.codec, (int)g.nch, g.T, index, frames, b.d_state.p);
         }
     }
-    // ---- outputs: the small arrays first, then the PCM in chunks -- the host hands chunk k to the callers' buffers while
-    //      chunk k + 1 is still crossing PCIe (the scatter is as long as the copy: 5 MB per 16,384 frames each) ----
-    constexpr int kMaxChunks = 4;
-    const int kChunks = rows >= 8192 ? kMaxChunks : 1;
+}
+
+// ---- outputs: the small arrays first, then the PCM in chunks -- the host hands chunk k to the callers' buffers while
+//      chunk k + 1 is still crossing PCIe (the scatter is as long as the copy: 5 MB per 16,384 frames each) ----
+void flush_copy_out(Batch& b, Slot& s, const FlushRun& r) {
+    const size_t rows = b.plan.rows;
     if (!s.chunk_done[0]) {
         HIP_OK(hipEventCreateWithFlags(&s.chunk_done[0], hipEventDisableTiming | hipEventBlockingSync));   // the long wait sleeps
         for (int k = 1; k <= kMaxChunks; ++k) {
             HIP_OK(hipEventCreateWithFlags(&s.chunk_done[k], hipEventDisableTiming));
         }
     }
-    const size_t per_chunk = (rows + kChunks - 1) / kChunks;
-    if (zero_copy) {   // everything is already where the host reads it once the kernels have retired: ONE event for all of it
+    if (r.zero_copy) {   // everything is already where the host reads it once the kernels have retired: ONE event for all of it
         HIP_OK(hipEventRecord(s.chunk_done[0], s.stream));
-    } else {
-        HIP_OK(hipMemcpyAsync(b.h_results.p, b.d_results.p, rows * sizeof(mbe_process_result), hipMemcpyDeviceToHost, s.stream));
-        HIP_OK(hipMemcpyAsync(b.h_records.p, b.d_records.p, rows * sizeof(mbx_param_record), hipMemcpyDeviceToHost, s.stream));
-        HIP_OK(hipEventRecord(s.chunk_done[0], s.stream));
-        for (int k = 0; k < kChunks; ++k) {
-            const size_t r0 = (size_t)k * per_chunk, r1 = r0 + per_chunk < rows ? r0 + per_chunk : rows;
-            if (r0 < r1) {
-                if (any_short) {
-                    HIP_OK(hipMemcpyAsync(b.h_pcm16.p + r0 * 160, b.d_pcm16.p + r0 * 160, (r1 - r0) * 160 * sizeof(int16_t), hipMemcpyDeviceToHost, s.stream));
-                }
-                if (any_float) {
-                    HIP_OK(hipMemcpyAsync(b.h_pcmf.p + r0 * 160, b.d_pcmf.p + r0 * 160, (r1 - r0) * 160 * sizeof(float), hipMemcpyDeviceToHost, s.stream));
-                }
+        return;
+    }
+    HIP_OK(hipMemcpyAsync(b.h_results.p, b.d_results.p, rows * sizeof(mbe_process_result), hipMemcpyDeviceToHost, s.stream));
+    HIP_OK(hipMemcpyAsync(b.h_records.p, b.d_records.p, rows * sizeof(mbx_param_record), hipMemcpyDeviceToHost, s.stream));
+    HIP_OK(hipEventRecord(s.chunk_done[0], s.stream));
+    for (int k = 0; k < r.chunks; ++k) {
+        const size_t r0 = (size_t)k * r.per_chunk, r1 = r0 + r.per_chunk < rows ? r0 + r.per_chunk : rows;
+        if (r0 < r1) {
+            if (r.pcm16) {
+                HIP_OK(hipMemcpyAsync(b.h_pcm16.p + r0 * 160, b.d_pcm16.p + r0 * 160, (r1 - r0) * 160 * sizeof(int16_t), hipMemcpyDeviceToHost, s.stream));
             }
-            HIP_OK(hipEventRecord(s.chunk_done[k + 1], s.stream));
+            if (r.pcmf) {
+                HIP_OK(hipMemcpyAsync(b.h_pcmf.p + r0 * 160, b.d_pcmf.p + r0 * 160, (r1 - r0) * 160 * sizeof(float), hipMemcpyDeviceToHost, s.stream));
+            }
+        }
+        HIP_OK(hipEventRecord(s.chunk_done[k + 1], s.stream));
+    }
+}
+
+// ---- scatter into the callers' buffers: results and parameter bits, then the PCM chunk by chunk as it arrives ----
+void flush_scatter(Batch& b, Slot& s, const FlushRun& r) {
+    const mbx::FlushPlan& p = b.plan;
+    for (size_t e = 0; e < b.q.size(); ++e) {
+        const QEntry& qe = b.q[e];
+        const size_t row = p.row_of[e];
+        if (qe.result) {
+            *qe.result = b.h_results.p[row];
+        }
+        unpack_bits_fast(b.h_records.p[row], mbx::kCodecs[qe.codec].data_bits, qe.bits_out);
+    }
+    for (int k = 0; k < r.chunks; ++k) {
+        const size_t r0 = (size_t)k * r.per_chunk, r1 = r0 + r.per_chunk < p.rows ? r0 + r.per_chunk : p.rows;
+        if (!r.zero_copy) {
+            HIP_OK(hipEventSynchronize(s.chunk_done[k + 1]));
+        }
+        for (size_t row = r0; row < r1; ++row) {
+            const QEntry& qe = b.q[p.by_row[row]];
+            if (qe.want_short) {
+                memcpy(qe.aout, b.h_pcm16.p + row * 160, 160 * sizeof(int16_t));
+            } else {
+                memcpy(qe.aout, b.h_pcmf.p + row * 160, 160 * sizeof(float));
+            }
         }
     }
-    std::vector<uint32_t> by_row(rows);
-    for (size_t e = 0; e < n; ++e) {
-        by_row[row_of[e]] = (uint32_t)e;
+}
+
+// ---- the queue is empty again; write-back mode: the host structs are current again, nothing stays on the device ----
+void flush_finish(Batch& b, Slot& s) {
+    s.npending = 0;
+    b.q.clear();
+    b.soft_cells.clear();
+    for (QChannel& ch : b.channels) {
+        ch.pending = 0;
+        ch.codec = -1;
     }
+    if (b.mode == MBE_BATCH_STATE_WRITEBACK) {
+        pool_download(b, s, 0, b.upload, true);
+        for (int c : b.upload) {
+            b.channels[(size_t)c].on_device = false;
+            b.channels[(size_t)c].slot = -1;
+        }
+        b.resident = 0;
+    }
+}
+
+// One flush: where everything goes is planned on the host alone (mbe_flush_plan.h); the steps above carry the plan out.
+int flush_batch(Batch& b) {
+    const size_t n = b.q.size();
+    if (n == 0) {
+        return 0;
+    }
+    Slot& s = slot();
+    const double tr0 = g_trace_flush ? trace_now() : 0.0;
+    flush_upload_state(b, s);
+    b.plan.build(b.channels.data(), b.channels.size(), b.q.data(), n);
+    const FlushRun r = flush_stage_inputs(b, s);
+    const double tr1 = g_trace_flush ? trace_now() : 0.0;
+    flush_launch(b, s, r);
+    flush_copy_out(b, s, r);
+    b.plan.invert_rows();   // (host work behind the launches: the device is busy)
     const double tr2 = g_trace_flush ? trace_now() : 0.0;
-    if (rows < 256) {
+    if (b.plan.rows < 256) {
         HIP_OK(hipStreamSynchronize(s.stream));   // a small flush: spin, the sleeping wait's wake-up would be most of it
     } else {
         HIP_OK(hipEventSynchronize(s.chunk_done[0]));
     }
     const double tr3 = g_trace_flush ? trace_now() : 0.0;
-    for (size_t e = 0; e < n; ++e) {   // results and parameter bits
-        const QEntry& qe = b.q[e];
-        const size_t r = row_of[e];
-        if (qe.result) {
-            *qe.result = b.h_results.p[r];
-        }
-        unpack_bits_fast(b.h_records.p[r], mbx::kCodecs[qe.codec].data_bits, qe.bits_out);
-    }
-    for (int k = 0; k < kChunks; ++k) {   // PCM, chunk by chunk
-        const size_t r0 = (size_t)k * per_chunk, r1 = r0 + per_chunk < rows ? r0 + per_chunk : rows;
-        if (!zero_copy) {
-            HIP_OK(hipEventSynchronize(s.chunk_done[k + 1]));
-        }
-        for (size_t r = r0; r < r1; ++r) {
-            const QEntry& qe = b.q[by_row[r]];
-            if (qe.want_short) {
-                memcpy(qe.aout, b.h_pcm16.p + r * 160, 160 * sizeof(int16_t));
-            } else {
-                memcpy(qe.aout, b.h_pcmf.p + r * 160, 160 * sizeof(float));
-            }
-        }
-    }
+    flush_scatter(b, s, r);
     if (g_trace_flush) {
         FlushTrace& t = t_flush_trace;
         const double tr4 = trace_now();
@@ -1133,25 +1088,10 @@ int flush_batch(Batch& b) {
             t.wait += tr3 - tr2;
             t.scatter += tr4 - tr3;
             t.flushes += 1;
-            t.rows += (long)rows;
+            t.rows += (long)b.plan.rows;
         }
     }
-    s.npending = 0;
-    b.q.clear();
-    b.soft_cells.clear();
-    for (QChannel& ch : b.channels) {
-        ch.pending = 0;
-        ch.codec = -1;
-        ch.first = -1;
-    }
-    if (b.mode == MBE_BATCH_STATE_WRITEBACK) {   // the host structs are current again; nothing stays on the device
-        pool_download(b, s, 0, upload, true);
-        for (int c : upload) {
-            b.channels[(size_t)c].on_device = false;
-            b.channels[(size_t)c].slot = -1;
-        }
-        b.resident = 0;
-    }
+    flush_finish(b, s);
     return (int)n;
 }
 
@@ -1732,8 +1672,8 @@ int mbe_batchEnd(void) {
     }
     if (g_trace_flush && t_flush_trace.flushes) {
         const FlushTrace& t = t_flush_trace;
-        fprintf(stderr, "[flush trace] %ld flushes, %.0f rows each: prep %.1f us, issue%s %.1f us, wait %.1f us, scatter %.1f us per flush\n", t.flushes,
-                (double)t.rows / (double)t.flushes, 1e6 * t.prep / t.flushes, "", 1e6 * t.issue / t.flushes, 1e6 * t.wait / t.flushes,
+        fprintf(stderr, "[flush trace] %ld flushes, %.0f rows each: prep %.1f us, issue %.1f us, wait %.1f us, scatter %.1f us per flush\n", t.flushes,
+                (double)t.rows / (double)t.flushes, 1e6 * t.prep / t.flushes, 1e6 * t.issue / t.flushes, 1e6 * t.wait / t.flushes,
                 1e6 * t.scatter / t.flushes);
         t_flush_trace = FlushTrace{};
     }

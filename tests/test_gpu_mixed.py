@@ -1,7 +1,7 @@
 """GPU suite (-m gpu) for mixed-codec ragged batches: mbx_process_batch_mixed / _soft_mixed, BatchDecoder.decode_ragged(codec=array) and
 the queue mode of the per-frame library on top of them.  Every stream is compared with the CPU oracle at its OWN codec and frame
 count, and every byte with one single-codec ragged call per codec present on a second copy of the pool.  One test starts a child
-process (a fresh one, under a time limit)."""
+process (a fresh one, under a time limit), and the two queue-mode flush fixtures one each (tests/queue_flush_case.py)."""
 import os
 import subprocess
 import sys
@@ -12,8 +12,8 @@ import pytest
 import mixed_case
 import parity
 import ragged_case
-import soft_mix
 from mixed_case import mixed_frames, rows_of
+from queue_channels import MBE_BATCH_QUEUE_SOFT, Channel as _Channel
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -268,43 +268,30 @@ def test_empty_mixed_batches_launch_nothing_and_a_captured_step_replays_like_dir
 
 
 # ---- queue mode of the per-frame library ---------------------------------------------------------------------------------------
-HARD_CALLS = {0: "mbe_processImbe7200x4400Frame", 1: "mbe_processAmbe3600x2450Frame", 2: "mbe_processImbe7100x4400Frame",
-              3: "mbe_processAmbe3600x2400Frame"}
-SOFT_CALLS = {c: n.replace("Frame", "SoftFrame") for c, n in HARD_CALLS.items()}
-NBITS = {0: 88, 1: 49, 2: 88, 3: 49}
-MBE_BATCH_QUEUE_SOFT = 0x10
+def _flush_case(scenario, env_extra):
+    """tests/queue_flush_case.py in a fresh process under a time limit: {mode: its line}"""
+    env = dict(os.environ, **env_extra)
+    try:
+        r = subprocess.run([sys.executable, os.path.join(HERE, "queue_flush_case.py"), scenario], capture_output=True, text=True, timeout=300, env=env)
+    except subprocess.TimeoutExpired as e:
+        pytest.exit(f"queue_flush_case {scenario}: the child process did not finish in {e.timeout} s -- nothing more is started on the card", returncode=3)
+    tail = (r.stdout or "")[-3000:] + (r.stderr or "")[-3000:]
+    if r.returncode < 0 or r.returncode in (124, 134, 137, 139):
+        pytest.exit(f"queue_flush_case {scenario}: the child process ended with status {r.returncode} -- nothing more is started on the card\n{tail}", returncode=3)
+    assert r.returncode in (0, 1), tail
+    lines = dict(line.split(" ", 1) for line in r.stdout.strip().splitlines())
+    assert sorted(lines) == ["0", "1"], tail
+    return lines
 
 
-class _Channel:
-    """channel c: codec c % 4, soft input where (c // 4) % 2, the short call where (c // 8) % 2; 9 frames"""
+@pytest.fixture(scope="module")
+def dma_flush(mbx):
+    return _flush_case("mixed48", {"MBE_NEO_ZERO_COPY_FLUSH": "0"})
 
-    def __init__(self, mbe, c):
-        import ctypes as C
 
-        from mbelib_neo_amd.layout import PARMS_DTYPE, RESULT_DTYPE
-
-        self.c, self.codec, self.soft, self.T, self.t = c, c % 4, (c // 4) % 2 == 1, 9, 0
-        short = (c // 8) % 2 == 1
-        cells = soft_mix.frames(self.codec, 1, self.T, tag=300 + c)
-        self.frames = cells if self.soft else np.ascontiguousarray(cells[..., 0]).astype(np.int8)
-        self.fn = getattr(mbe, (SOFT_CALLS if self.soft else HARD_CALLS)[self.codec] + ("" if short else "f"))
-        self.pcm = np.zeros((self.T, 160), dtype=np.int16 if short else np.float32)
-        self.res = np.zeros(self.T, dtype=RESULT_DTYPE)
-        self.bits = np.zeros((self.T, NBITS[self.codec]), dtype=np.int8)
-        self.st = [np.zeros(1, dtype=PARMS_DTYPE) for _ in range(3)]
-        self.p = lambda a: a.ctypes.data_as(C.c_void_p)
-        mbe.mbe_initMbeParms(self.p(self.st[0]), self.p(self.st[1]), self.p(self.st[2]))
-        self.rets = []
-
-    def call(self, mbe):
-        t, p = self.t, self.p
-        if t == 0:
-            mbe.mbe_setThreadRngSeed(9000 + self.c)
-        self.rets.append(self.fn(p(self.pcm[t]), p(self.res[t:t + 1]), p(self.frames[t]), p(self.bits[t]), p(self.st[0]), p(self.st[1]), p(self.st[2])))
-        self.t += 1
-
-    def outputs(self):
-        return self.pcm.tobytes(), self.res.tobytes(), self.bits.tobytes(), np.concatenate(self.st).tobytes()
+@pytest.fixture(scope="module")
+def chunked_flush(mbx):
+    return _flush_case("chunks", {})
 
 
 @pytest.mark.parametrize("mode", [0, 1], ids=["writeback", "resident"])
@@ -334,3 +321,17 @@ def test_queue_mode_flushes_all_codecs_and_counts_of_an_input_form_as_one_mixed_
         assert all(r == 0 for r in b.rets)
         for what, x, y in zip(("pcm", "result", "bits", "state"), a.outputs(), b.outputs()):
             assert x == y, f"channel {a.c} (codec {a.codec}, soft {a.soft}): {what} differs from the synchronous calls"
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["writeback", "resident"])
+def test_queue_mode_flush_by_dma_copies_equals_the_synchronous_calls(dma_flush, mode):
+    """the 48-channel scenario above in a process with MBE_NEO_ZERO_COPY_FLUSH=0: frames, index, offsets and codecs are uploaded, the
+    kernels work on device arrays, results, records and ONE PCM chunk are copied back"""
+    assert dma_flush[str(mode)] == "ok", dma_flush[str(mode)]
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["writeback", "resident"])
+def test_queue_mode_flush_of_8195_rows_in_four_pcm_chunks_equals_the_synchronous_calls(chunked_flush, mode):
+    """8,195 hard rows of 65 channels in three groups (tests/queue_flush_case.py, chunks): four PCM chunks of 2,049, 2,049, 2,049 and
+    2,048 rows, int16 and float calls alternating by channel, chunk edges inside channels"""
+    assert chunked_flush[str(mode)] == "ok", chunked_flush[str(mode)]
