@@ -24,6 +24,7 @@
 #include "mbe_flush_plan.h"
 #include "mbe_neo_amd.h"
 #include "mbx.h"
+#include "mbx_cells.h"
 #include "mbx_codec.h"
 
 namespace {
@@ -337,22 +338,7 @@ void must(int rc, const char* what) {
 constexpr unsigned kContext = MBE_PROCESS_FLAG_SOFT_INPUT | MBE_PROCESS_FLAG_C0_VALID | MBE_PROCESS_FLAG_C4_VALID;
 constexpr unsigned kStatus = MBE_PROCESS_FLAG_TONE | MBE_PROCESS_FLAG_ERASURE | MBE_PROCESS_FLAG_REPEAT | MBE_PROCESS_FLAG_MUTE;
 
-int validate_bits(const char* bits, size_t count) {   // ref src/internal/mbe_result.h:18-29; eight cells at a time
-    if (!bits) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    uint64_t acc = 0;
-    size_t i = 0;
-    for (; i + 8 <= count; i += 8) {
-        uint64_t v;
-        memcpy(&v, bits + i, 8);
-        acc |= v;
-    }
-    for (; i < count; ++i) {
-        acc |= (uint8_t)bits[i];
-    }
-    return (acc & 0xfefefefefefefefeULL) ? MBE_STATUS_INVALID_BITS : 0;
-}
+using mbx::validate_bits;   // (mbx_cells.h; ref src/internal/mbe_result.h:18-29)
 
 bool count_ok(int c) { return c >= 0 && c <= 184; }
 

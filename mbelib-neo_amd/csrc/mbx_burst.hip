@@ -19,9 +19,8 @@
 #include "mbx_burst.h"
 #include "mbx_codec.h"
 #include "mbx_gather.h"
+#include "mbx_host.h"
 #include "mbx_kernels.h"
-
-void mbx_set_error_text(const char* text);   // mbx_api.hip: the per-thread text behind mbx_last_error()
 
 namespace mbx {
 
@@ -298,18 +297,11 @@ int refuse(const char* why) {
     return MBE_STATUS_INVALID_ARGUMENT;
 }
 
-int hip_fail(const char* what, hipError_t e) {
-    char text[200];
-    snprintf(text, sizeof(text), "%s: %s", what, hipGetErrorString(e));
-    mbx_set_error_text(text);
-    return MBX_ENODEVICE;
-}
-
 // the current device, after mbx_init() for it
 int ready_device(int* dev) {
     const hipError_t e = hipGetDevice(dev);
     if (e != hipSuccess) {
-        return hip_fail("hipGetDevice", e);
+        return mbx::hip_failed("", "hipGetDevice", e);
     }
     if (!mbx_device_ready(*dev)) {
         mbx_set_error_text("mbx_init() has not been called for the current device");
@@ -358,7 +350,7 @@ int burst_gather(const mbx_burst_schedule* sched, bool soft, const void* d_in, s
         launch(sched, static_cast<const uint8_t*>(d_in), burst_stride, n, static_cast<uint8_t*>(d_out), (int)row, (hipStream_t)stream);
     }
     const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : hip_fail(soft ? "the soft burst gather" : "the burst gather", e);
+    return e == hipSuccess ? 0 : hip_failed("", soft ? "the soft burst gather" : "the burst gather", e);
 }
 
 }  // namespace mbx
@@ -384,13 +376,6 @@ int gather_ready(const char* who, const mbx_burst_schedule* sched, size_t n) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     return 0;
-}
-
-int misaligned(const char* who) {
-    char text[200];
-    snprintf(text, sizeof(text), "%s: a pointer is below the alignment of its kind (include/mbx_burst.h, Alignment)", who);
-    mbx_set_error_text(text);
-    return MBE_STATUS_INVALID_ARGUMENT;
 }
 
 int channel_bits(const mbx::CodecShape* sh) {   // of one frame
@@ -552,7 +537,7 @@ int mbx_burst_schedule_create_form(mbx_burst_schedule** out, int codec, int fram
     if (e != hipSuccess) {
         (void)hipFree(s->d_wire_tab);
         delete s;
-        return hip_fail("mbx_burst_schedule_create: upload of the tables", e);
+        return mbx::hip_failed("", "mbx_burst_schedule_create: upload of the tables", e);
     }
     s->d_cell_tab = s->d_wire_tab + folded.wire_entries;
     s->d_xor_tab = reinterpret_cast<uint8_t*>(s->d_wire_tab + folded.tab_entries);
@@ -636,8 +621,8 @@ int mbx_deinterleave(const mbx_burst_schedule* sched, const uint8_t* d_bursts, s
 
 int mbx_deinterleave_soft(const mbx_burst_schedule* sched, const mbe_soft_bit* d_soft, size_t n, mbe_soft_bit* d_cells, size_t row_cells,
                           void* stream) {
-    if ((reinterpret_cast<uintptr_t>(d_soft) | reinterpret_cast<uintptr_t>(d_cells)) & 1u) {   // (first: it needs neither the schedule nor a device)
-        return misaligned("mbx_deinterleave_soft");
+    if (!mbx::aligned_to(d_soft, 2) || !mbx::aligned_to(d_cells, 2)) {   // (first: it needs neither the schedule nor a device)
+        return mbx::misaligned("mbx_deinterleave_soft", "mbx_burst.h");
     }
     if (!sched || !d_soft || !d_cells) {
         mbx_set_error_text("mbx_deinterleave_soft: schedule, d_soft and d_cells are all needed");

@@ -30,8 +30,7 @@
 #include <mutex>
 
 #include "mbx.h"
-
-void mbx_set_error_text(const char* text);   // mbx_api.hip
+#include "mbx_host.h"
 
 namespace {
 

@@ -1,0 +1,35 @@
+// mbx_host.h -- what the host units of libmbx_hip.so (mbx_api.hip, mbx_session.hip, mbx_burst.hip, mbx_collective.hip) share to
+// refuse a call: the per-thread text behind mbx_last_error(), the failed-HIP-call text, the alignment refusal.  Host-only and
+// private; the inlines have internal linkage, nothing here is exported.  Only what at least two units use belongs here.
+#pragma once
+
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+#include <cstdio>
+
+#include "mbx.h"
+
+void mbx_set_error_text(const char* text);   // mbx_api.hip: sets the calling thread's mbx_last_error()
+
+namespace mbx {
+
+static inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
+
+// a HIP call failed: "<prefix><what>: <HIP's text>", MBX_ENODEVICE
+static inline int hip_failed(const char* prefix, const char* what, hipError_t e) {
+    char text[256];
+    snprintf(text, sizeof(text), "%s%s: %s", prefix, what, hipGetErrorString(e));
+    mbx_set_error_text(text);
+    return MBX_ENODEVICE;
+}
+
+// a pointer below the alignment its kind has in `header`'s Alignment table: refused before anything is launched
+static inline int misaligned(const char* who, const char* header) {
+    char text[200];
+    snprintf(text, sizeof(text), "%s: a pointer is below the alignment of its kind (include/%s, Alignment)", who, header);
+    mbx_set_error_text(text);
+    return MBE_STATUS_INVALID_ARGUMENT;
+}
+
+}  // namespace mbx

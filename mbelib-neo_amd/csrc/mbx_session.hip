@@ -28,25 +28,17 @@
 #include "mbx_burst.h"
 #include "mbx_codec.h"
 #include "mbx_gather.h"
-
-void mbx_set_error_text(const char* text);   // mbx_api.hip: the per-thread text behind mbx_last_error()
+#include "mbx_host.h"
 
 namespace {
 
 constexpr int kDepth = 3;
 
-int sfail(const char* what, hipError_t e) {
-    char buf[256];
-    snprintf(buf, sizeof(buf), "session: %s: %s", what, hipGetErrorString(e));
-    mbx_set_error_text(buf);
-    return MBX_ENODEVICE;
-}
-
 #define S_TRY(expr)                        \
     do {                                   \
         hipError_t e_ = (expr);            \
         if (e_ != hipSuccess) {            \
-            return sfail(#expr, e_);       \
+            return mbx::hip_failed("session: ", #expr, e_);       \
         }                                  \
     } while (0)
 
@@ -345,7 +337,7 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
             sl.out[sl.nout++] = CopyOut{user, stage, bytes};
         }
         hipError_t e = hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, s->s_out);
-        return e == hipSuccess ? 0 : sfail("hipMemcpyAsync (device to host)", e);
+        return e == hipSuccess ? 0 : mbx::hip_failed("session: ", "hipMemcpyAsync (device to host)", e);
     };
     if ((rc = out(pcm16, sl.d_pcm16, sl.h_pcm16, 160)) < 0 || (rc = out(pcmf, sl.d_pcmf, sl.h_pcmf, 160)) < 0
         || (rc = out(results, sl.d_results, sl.h_results, 1)) < 0 || (rc = out(records, sl.d_records, sl.h_records, 1)) < 0) {
@@ -403,7 +395,7 @@ int mbx_session_create(mbx_session** out, int codec, int streams, size_t max_fra
     do {                                     \
         hipError_t e_ = (expr);              \
         if (e_ != hipSuccess) {              \
-            return bail(sfail(#expr, e_));   \
+            return bail(mbx::hip_failed("session: ", #expr, e_));   \
         }                                    \
     } while (0)
     C_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_state), (size_t)streams * 3 * sizeof(mbe_parms)));
