@@ -20,6 +20,7 @@
 #include "mbx_gather.h"
 #include "mbx_host.h"
 #include "mbx_kernels.h"
+#include "mbx_launch_plan.h"
 
 namespace {
 
@@ -154,23 +155,9 @@ void free_context(Context& c) {   // caller holds g_init_mu and c.mu
     c.device = -1;
 }
 
-int lds_min_frames() {   // frames per stream from which the LDS-resident instances are used (MBX_LDS_MIN_FRAMES: A/B timing)
-    static const int v = [] {
-        const char* e = getenv("MBX_LDS_MIN_FRAMES");
-        const int n = e ? atoi(e) : 4;
-        return (n >= 1 && n <= 1 << 20) ? n : 4;   // anything else (0, negative, not a number) is ignored
-    }();
-    return v;
-}
-#define kLdsResidentMinFrames lds_min_frames()
-bool res1_enabled() {   // MBX_NO_RES1 (A/B timing): resident one-frame launches through the LDS-resident instance; read once
-    static const bool on = getenv("MBX_NO_RES1") == nullptr;
-    return on;
-}
-
-bool lds_resident_enabled() {
-    static const bool on = getenv("MBX_NO_LDS_RESIDENT") == nullptr;   // development switch for A/B timing; read once
-    return on;
+const mbx::LaunchSwitches& launch_switches() {   // the MBX_* launch switches (mbx_launch_plan.h): read once per process
+    static const mbx::LaunchSwitches s = mbx::read_launch_switches();   // thread-safe static initialisation
+    return s;
 }
 
 // Walking order of successive stream-kernel launches (see launch_stream): alternating by default; MBX_NO_REVERSE=1 in the
@@ -528,9 +515,10 @@ int mbx_soft_bits_from_llr(const int16_t* llr, mbe_soft_bit* soft, size_t count)
 }
 
 // ---- the stream-stage kernel instances (mbx_stream.hip) ------------------------------------------------------------------------------
-// ONE table of what can run and ONE function that says what does (select_instance, below the switches it reads): the launchers
-// launch the entry it returns and report entry.name, mbx_batch_kernel_name / mbx_stream_kernel_name return the same entry's name.
-// A new instance: its declaration in mbx_kernels.h, its row here, its case in select_instance.
+// ONE table of what can run and ONE function that says what does (plan_step, mbx_launch_plan.h, with the switches it reads): the
+// launchers launch the entry its plan names and report entry.name, mbx_batch_kernel_name / mbx_stream_kernel_name return the same
+// entry's name.  A new instance: its declaration in mbx_kernels.h, its row here (rows by their first entry: Row, mbx_launch_plan.h),
+// its case in plan_step.
 using mbx::DeviceTables;
 using mbx::FrameParams;
 enum Family { kStreamArgs, kSliceArgs, kFusedArgs, kOneLaunchArgs, kOneLaunchLeadArgs };   // (one-launch: without / with the front blocks' lead)
@@ -551,9 +539,6 @@ struct Instance {
     constexpr Instance(const char* n, void (*k)(int S, MBX_ONE_LAUNCH_PARAMS)) : name(n), family(kOneLaunchArgs), one_launch(k) {}
     constexpr Instance(const char* n, void (*k)(int S, int lead, MBX_ONE_LAUNCH_PARAMS)) : name(n), family(kOneLaunchLeadArgs), one_launch_lead(k) {}
 };
-// rows of kInstances by their first entry; a row's columns: IMBE 7200x4400 | AMBE 3600x2450 | AMBE 3600x2400 (the two fused rows: IMBE
-// 7200x4400 | IMBE 7100x4400, the only codecs with a front end of their own inside the stream's wave)
-enum Row { kPlain = 0, kOne = 3, kLds = 6, kRes = 9, kRes1 = 12, kSlice = 15, kOneLaunch = 18, kOneLaunchRes = 21, kOneFused = 24, kRes1Fused = 26 };
 static const Instance kInstances[] = {
     {"imbe_stream_kernel", mbx::imbe_stream_kernel},
     {"ambe_stream_kernel", mbx::ambe_stream_kernel},
@@ -584,9 +569,10 @@ static const Instance kInstances[] = {
     {"imbe_stream_kernel_res1_fused", mbx::imbe_stream_kernel_res1_fused},
     {"imbe7100_stream_kernel_res1_fused", mbx::imbe7100_stream_kernel_res1_fused},
 };
-static_assert(sizeof(kInstances) / sizeof(kInstances[0]) == kRes1Fused + 2, "kInstances: Row names the first entry of every row");
+static_assert(sizeof(kInstances) / sizeof(kInstances[0]) == mbx::kInstanceCount, "kInstances: Row names the first entry of every row");
 // The ragged stream-stage kernels (mbx_process_batch_ragged: a frame count per stream).  A table of their own: a ragged call has no
-// shape to select by -- one kernel per codec column (as in kInstances) and state form, whatever the counts are.
+// shape to select by -- one kernel per codec column (as in kInstances) and state form, whatever the counts are: a ragged plan's
+// instance is state form * 3 + column.
 struct RaggedKernel {
     const char* name;
     void (*kernel)(MBX_RAGGED_PARAMS);
@@ -611,11 +597,10 @@ static const MixedKernel kMixed[2] = {
     {"mixed_stream_kernel_ragged", mbx::mixed_stream_kernel_ragged},
     {"mixed_stream_kernel_ragged_res", mbx::mixed_stream_kernel_ragged_res},
 };
-static const int kMixedLdsWaves = MBX_AMBE_LDS_WAVES_PER_SIMD;   // (the kernels' launch bounds: mbx_stream.hip)
-// What the launcher knows of a codec beyond its shape (mbx_codec.h), keyed the same way, every kernel named once.  A codec's frames
-// go through the FEC kernels of the row CodecShape::front names and the expand kernel and kInstances column of the row
-// CodecShape::stream names: a row that is nobody's front end has no FEC kernels, one that is nobody's stream stage no expand kernel.
-// A new codec: its shape in mbx_codec.h, its row here.
+// The kernels of a codec's own stages, keyed as its shape is (mbx_codec.h), every kernel named once.  A codec's frames go through the
+// FEC kernels of the row CodecShape::front names and the expand kernel of the row CodecShape::stream names: a row that is nobody's
+// front end has no FEC kernels, one that is nobody's stream stage no expand kernel.  (Its columns in kInstances: kCodecLaunch,
+// mbx_launch_plan.h.)  A new codec: its shape in mbx_codec.h, its row here and in kCodecLaunch.
 using FecKernel = void (*)(const uint8_t*, size_t, mbx_param_record*, DeviceTables);
 using SoftFecKernel = void (*)(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
 using ExpandKernel = void (*)(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
@@ -625,27 +610,17 @@ struct CodecKernels {
     SoftFecKernel fec_soft;       // soft FEC alone (mbx_fec_soft) ...
     SoftFecKernel soft_front;     // ... and as the front of a soft batch step (mbx_soft_front.hip); both one wavefront per frame
     ExpandKernel  expand;         // records -> FrameParams rows
-    int           column;         // of the stream stage in the three-column rows of kInstances
-    int           lds_waves;      // resident waves per SIMD of the kernel a long launch takes (the kernels' own launch bounds: mbx_device.h)
-    int           fused_column;   // the IMBE codecs -- a front end inside the stream's wave, a stream kernel that expands a record itself --:
-                                  // their column in the two fused rows; -1: an AMBE codec
 };
 static const CodecKernels kCodecKernels[4] = {
     {mbx::fec_imbe7200x4400_kernel, "fec_imbe7200x4400_kernel", mbx::fec_imbe7200x4400_soft_kernel, mbx::soft_front_imbe_kernel,
-     mbx::expand_imbe_kernel, 0, MBX_IMBE_LDS_WAVES_PER_SIMD, 0},
+     mbx::expand_imbe_kernel},
     {mbx::fec_ambe3600x2450_kernel, "fec_ambe3600x2450_kernel", mbx::fec_ambe3600x2450_soft_kernel, mbx::soft_front_ambe_kernel,
-     mbx::expand_ambe_kernel, 1, MBX_AMBE_LDS_WAVES_PER_SIMD, -1},
+     mbx::expand_ambe_kernel},
     {mbx::fec_imbe7100x4400_kernel, "fec_imbe7100x4400_kernel", mbx::fec_imbe7100x4400_soft_kernel, mbx::soft_front_imbe7100_kernel,
-     nullptr, -1, 0, 1},
-    {nullptr, nullptr, nullptr, nullptr, mbx::expand_ambe2400_kernel, 2, MBX_AMBE_LDS_WAVES_PER_SIMD, -1},
+     nullptr},
+    {nullptr, nullptr, nullptr, nullptr, mbx::expand_ambe2400_kernel},
 };
-// the row of the stream stage a codec's frames end in (a codec that is none of the four is rejected before any launch; the names'
-// functions answer for it as for AMBE 3600x2450, as they always have)
-static const CodecKernels& stream_kernels(int codec) {
-    const mbx::CodecShape* sh = mbx::codec_shape(codec);
-    return kCodecKernels[sh ? sh->stream : MBX_CODEC_AMBE3600X2450];
-}
-static bool imbe_codec(int codec) { return mbx::codec_shape(codec) && kCodecKernels[codec].fused_column >= 0; }
+using mbx::imbe_codec;
 
 // FEC stage of hard-decision frames of `codec` (one of the four): n frames -> records
 static int launch_fec(Context* c, int codec, const uint8_t* d_frames, size_t n, mbx_param_record* d_records, void* stream) {
@@ -699,17 +674,6 @@ static int launch_expand(Context* c, int codec, const mbx_param_record* d_record
     hipLaunchKernelGGL(kCodecKernels[codec].expand, dim3(egrid), dim3(256), 0, (hipStream_t)stream, d_records, n, out, c->tabs);
     return check_launch("expand_kernel");
 }
-// what select_instance decides on
-struct Shape {
-    int  codec, S, T;
-    bool resident = false;    // the launch carries DeviceTables::resident
-    bool rows = false;        // ... and FrameParams rows written by an expand launch
-    bool sliced = false;      // try_sliced_launch issues it slice by slice
-    bool frames = false;      // the call has the wire frames (mbx_process_batch*): a T = 1 step may be ONE launch, and they are ...
-    bool aligned = false;     // ... 4-byte aligned (the IMBE front ends load dwords)
-    bool workspace = false;   // ... and the rows may go through the stream slot's own workspace and flag words (the one-launch forms)
-};
-static const Instance& select_instance(const Shape& q);
 // every stream-stage launch ends here: what ran on `stream` (the caller's, also for the slices of a sliced launch) is written down
 // for mbx_last_kernel_name -- the table's own pointer, one store per launch, nothing on the device -- and the launch is checked
 static void record_launch(Context* c, void* stream, const char* name) {
@@ -754,67 +718,55 @@ static mbx::DeviceTables launch_tables(const Context* c, bool reverse, const Bat
     return tabs;
 }
 
-// ---- sliced launches (mbx_stream.hip, *_stream_kernel_lds_slice) ------------------------------------------------------------------
-// A launch of S streams x T frames is S workgroups of equal length; when S does not fill the device's resident wave slots evenly
-// the last round runs part-empty -- BASELINE configs[4]'s shard, 8,192 AMBE+2 streams on 5,120 slots, is 1.6 rounds: the second
-// holds 3,072 waves.  Frames of a stream are sequential, but nothing says they must be ONE launch's: the streams are split into
-// THREE groups and the frames into slices of 16, and the slices of each group are issued in order on an internal HIP stream of its
-// own (forked from and joined to the caller's stream with events).  Measured, 8,192 x 128 AMBE+2, interleaved A/B on one box: plain
-// 2.609 ms; two groups 2.518; three 2.481 (-4.7 %); FOUR 3.185 (+22 %: with the caller's stream that is five streams on HIP's four
-// hardware queues, and two groups then share one); slices of 8 / 16 / 32 frames with two groups: 2.512 / 2.524 / 2.585.  A slice IS a launch of 16 frames per stream (state in from HBM,
-// state out: results bit-identical by construction); the streams' kernels share the device, so the slots one group's slice
-// leaves empty are taken by another group's next one (ideal: work / slots = 2.29 ms for that shape instead of ceil(S / slots) rounds).
-// Kernel boundaries do the ordering: no in-kernel waiting, no assumption about dispatch.  (Built first as ONE grid of K x S
-// workgroups that waited for their stream's previous slice on a progress word: the agent-scope release / acquire pair every slice
-// then needs -- an L2 write-back with the PCM of 5,120 waves dirty in it -- made 8,192 x 128 in eight slices 34 % SLOWER.)
-// MBX_SLICE=0 switches it off, MBX_SLICE=n sets the slice length in frames (A/B timing; read once).
-static int slice_override() {
-    static const int v = [] {
-        const char* e = getenv("MBX_SLICE");
-        return e ? atoi(e) : -1;
-    }();
-    return v;
+// ---- planning (mbx_launch_plan.h) ---------------------------------------------------------------------------------------------------
+// Every launcher below: its own argument and alignment checks, a StepShape, ONE plan, the workspace grown to the plan's size, the plan
+// issued.  Nothing below this section asks the environment, a codec's facts or a frame count what to launch.
+using mbx::InputKind;
+using mbx::kFrames;
+using mbx::kRecords;
+using mbx::kSoft;
+using mbx::StepPlan;
+using mbx::StepShape;
+// (`c` may be nullptr: a prediction without a device context knows no wave slots)
+static StepPlan plan_of(const Context* c, const StepShape& q) {
+    return mbx::plan_step(q, launch_switches(), {c ? c->simds : 0, MBX_IMBE_LDS_WAVES_PER_SIMD, MBX_AMBE_LDS_WAVES_PER_SIMD, sizeof(mbx::FrameParams)});
 }
-// frames per slice for a launch of S streams x T frames on `slots` resident waves, or 0: the plain launch
-static int choose_slice_frames(int S, int T, int slots) {
-    const int forced = slice_override();
-    if (forced == 0 || slots <= 0 || S < 2) {
-        return 0;
-    }
-    const int Tc = forced > 0 ? ((forced + 7) & ~7) : 16;   // multiples of eight: the AMBE bodies expand eight frames at a time
-    if (T < 2 * Tc) {
-        return 0;
-    }
-    if (forced > 0) {
-        return Tc;
-    }
-    if (S <= slots) {   // every stream has a slot of its own: nothing to balance
-        return 0;
-    }
-    const double ideal = (double)S / (double)slots;
-    const double plain = (double)((S + slots - 1) / slots);
-    return (plain >= 1.06 * ideal) ? Tc : 0;   // what the part-empty last round costs must be worth the extra launches
+// what a batch call knows of its step; `own_workspace`: the rows go through the stream slot's own workspace (then the launch may be sliced)
+static StepShape step_shape(const BatchCall& b, InputKind kind, const void* d_input, bool own_workspace) {
+    StepShape q;
+    q.codec = b.codec, q.S = b.S, q.T = b.T, q.total = b.total;
+    q.kind = kind;
+    q.resident = b.resident != nullptr;
+    q.ragged = b.frame_offset != nullptr;
+    q.mixed = b.stream_codec != nullptr;
+    q.aligned = (reinterpret_cast<uintptr_t>(d_input) & 3u) == 0;
+    q.own_workspace = q.slices_allowed = own_workspace;
+    return q;
 }
-// caller holds c->mu.  0: issued (*rc); 1: not applicable (take the plain launch)
-static int try_sliced_launch(Context* c, StreamSlot& slot, const mbx::DeviceTables& tabs, const BatchCall& b, const mbx::FrameParams* params,
-                             int* rc) {
-    const int S = b.S, T = b.T;
+// THE plan of a step on `stream`.  A plan that needs the slot's flag words (a captured launch would be replayed with the same epoch,
+// and a replay would find the flags of the replay before it) or side streams holds outside stream capture only: then, and only then,
+// the stream is asked, and a step that is being captured is planned again as such (it takes the staged kernels, unsliced).
+static StepPlan plan_on_stream(const Context* c, StepShape& q, void* stream) {
+    StepPlan plan = plan_of(c, q);
+    if (plan.outside_capture_only) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        q.capturing = stream && hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+        (void)hipGetLastError();
+        if (q.capturing) {
+            plan = plan_of(c, q);
+        }
+    }
+    return plan;
+}
+
+// A sliced launch (why, and what was measured: mbx_launch_plan.h): the streams in plan.slice_groups groups, the frames in slices of
+// plan.slice_frames, the slices of each group issued in order on an internal HIP stream of its own, forked from and joined to the
+// caller's stream with events.  Caller holds c->mu.  0: issued (*rc); 1: its streams, events or waits could not be had and nothing
+// has been launched (take the plain launch)
+static int issue_slices(Context* c, StreamSlot& slot, const mbx::DeviceTables& tabs, const BatchCall& b, const mbx::FrameParams* params,
+                        const StepPlan& plan, int* rc) {
+    const int S = b.S, T = b.T, Tc = plan.slice_frames, groups = plan.slice_groups;
     void* const stream = b.stream;
-    const int Tc = choose_slice_frames(S, T, stream_kernels(b.codec).lds_waves * c->simds);
-    if (Tc <= 0) {
-        return 1;
-    }
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = stream && hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    (void)hipGetLastError();
-    if (capturing) {
-        return 1;
-    }
-    static const int groups = [] {
-        const char* e = getenv("MBX_SLICE_GROUPS");
-        const int v = e ? atoi(e) : 3;
-        return v < 2 ? 2 : (v > 4 ? 4 : v);
-    }();
     if (!slot.fork) {   // first sliced launch on this stream: the internal streams of the groups (at most four, MBX_SLICE_GROUPS) and their events
         bool ok = hipEventCreateWithFlags(&slot.fork, hipEventDisableTiming) == hipSuccess;
         for (int g = 0; g < groups && ok; ++g) {
@@ -831,21 +783,13 @@ static int try_sliced_launch(Context* c, StreamSlot& slot, const mbx::DeviceTabl
         (void)hipGetLastError();
         return 1;
     }
-    Shape q{b.codec, S, T};
-    q.sliced = true;
-    const Instance& e = select_instance(q);
+    const Instance& e = kInstances[plan.instance];
     int result = 0;
     record_launch(c, stream, e);   // one record for the whole sliced launch, under the caller's stream
-    // Group 0 runs on the caller's stream itself -- its kernels are queued before the stream waits for the other groups --, so g
-    // groups occupy g hardware queues, not g + 1, and one group needs no hand-over at all: 2.51 -> 2.42 ms on 8,192 x 128 AMBE+2
-    // (interleaved A/B; four groups are +26 % either way).  MBX_SLICE_OWN=0 puts every group on an internal stream (A/B timing; read once).
-    static const bool own = [] {
-        const char* e = getenv("MBX_SLICE_OWN");
-        return !(e && e[0] == '0');
-    }();
+    // Group 0 runs on the caller's stream itself (plan.slice_own) -- its kernels are queued before the stream waits for the other groups.
     // Every fork-side wait is queued BEFORE any group's kernels: should one fail, nothing has been launched yet and the state is
     // untouched (the caller then gets the plain launch).  A wait queued on an internal stream and never followed by work is harmless.
-    for (int g = (own ? 1 : 0); g < groups; ++g) {
+    for (int g = (plan.slice_own ? 1 : 0); g < groups; ++g) {
         if (hipStreamWaitEvent(slot.side[g], slot.fork, 0) != hipSuccess) {
             (void)hipGetLastError();
             return 1;
@@ -853,7 +797,7 @@ static int try_sliced_launch(Context* c, StreamSlot& slot, const mbx::DeviceTabl
     }
     for (int g = 0; g < groups; ++g) {
         const int s0 = (int)((long long)S * g / groups), Sg = (int)((long long)S * (g + 1) / groups) - s0;
-        const bool on_caller = own && g == 0;
+        const bool on_caller = plan.slice_own && g == 0;
         hipStream_t st = on_caller ? (hipStream_t)stream : slot.side[g];
         mbx::DeviceTables tg = tabs;
         if (tg.stream_map) {
@@ -888,7 +832,7 @@ static int try_sliced_launch(Context* c, StreamSlot& slot, const mbx::DeviceTabl
     return 0;
 }
 
-// Stream-stage launch.  `params` = FrameParams rows written by the expand stage, or nullptr: the IMBE stream kernel
+// Stream-stage launch of an S x T step.  `params` = FrameParams rows written by the expand stage, or nullptr: the IMBE stream kernel
 // then expands each record itself (one launch less, no workspace traffic).
 //
 // `reverse`: successive launches over the same streams walk them in opposite directions.  A decoder is called for the
@@ -896,45 +840,31 @@ static int try_sliced_launch(Context* c, StreamSlot& slot, const mbx::DeviceTabl
 // order every launch finds none of it there, while a launch that starts where the previous one ended finds its last
 // quarter-gigabyte.  The results do not depend on the order.  The alternation is kept per (device, hipStream_t) slot
 // and per session -- whoever re-walks the same state -- not process-wide.
-// `slot` (the caller holds c->mu) or nullptr: with it the launch may be issued slice by slice.
-static int launch_stream(Context* c, bool reverse, const BatchCall& b, const mbx::FrameParams* params, StreamSlot* slot) {
+// `slot` (the caller holds c->mu): what a sliced plan is issued on; nullptr where the shape allows no slices.
+static int launch_stream(Context* c, bool reverse, const BatchCall& b, const mbx::FrameParams* params, StreamSlot* slot, const StepShape& q, StepPlan plan) {
     const mbx::DeviceTables tabs = launch_tables(c, reverse, b);
-    // With several frames per stream prev_mp / prev_mp_enhanced stay in LDS for the whole launch (the *_lds instances,
-    // four waves per SIMD) instead of being parked in their HBM slots every frame: mbx_stream.hip, ParkedState.
-    // Resident state (d_resident) is understood by those instances only, whatever T is.
-    const bool lds_resident = b.T >= kLdsResidentMinFrames && lds_resident_enabled();
-    if (slot && lds_resident && !b.resident) {
+    if (plan.slice_frames > 0) {
         int rc = 0;
-        if (try_sliced_launch(c, *slot, tabs, b, params, &rc) == 0) {
+        if (issue_slices(c, *slot, tabs, b, params, plan, &rc) == 0) {
             return rc;
         }
+        StepShape plain = q;   // the same step without leave to slice
+        plain.slices_allowed = false;
+        plan = plan_of(c, plain);
     }
-    Shape q{b.codec, b.S, b.T};
-    q.resident = b.resident != nullptr;
-    q.rows = params != nullptr;
-    const Instance& e = select_instance(q);
+    const Instance& e = kInstances[plan.instance];
     hipLaunchKernelGGL(e.stream, dim3((unsigned)b.S), dim3(64), 0, (hipStream_t)b.stream, b.S, b.T, b.records, params, b.state, b.rng, b.pcm16,
                        b.pcmf, b.results, tabs);
     return launched(c, b.stream, e);
 }
 
-// The stream stage of a ragged step: ONE launch of S one-wave workgroups whose frame loops run frame_offset[s + 1] - frame_offset[s]
-// times, on the rows of the expand launch.  `order_ws`: S words behind the rows (the step's own workspace).
-// Workgroups are dispatched in grid order; with more streams than resident wave slots the launch ends when the last-dispatched long
-// stream does, so the streams are taken longest first: ragged_order_kernel, in front of the stream kernel on the same stream, writes
-// the order.  With S within the slots every stream starts at once and no order is made.  MBX_RAGGED_ORDER=0: no order kernel, grid
-// order (A/B timing and the byte test; read once).
-static bool ragged_order_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("MBX_RAGGED_ORDER");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-static int launch_ragged(Context* c, const BatchCall& b, const mbx::FrameParams* params, int32_t* order_ws) {
-    const int lds_waves = b.stream_codec ? kMixedLdsWaves : stream_kernels(b.codec).lds_waves;
+// The stream stage of a ragged or mixed step: ONE launch of S one-wave workgroups whose frame loops run frame_offset[s + 1] -
+// frame_offset[s] times, on the rows of the expand launch at `ws`, behind the order kernel where the plan has one (its S words:
+// behind the rows, at plan.order_offset).
+static int launch_ragged(Context* c, const BatchCall& b, mbx::FrameParams* ws, const StepPlan& plan) {
     const int32_t* order = nullptr;
-    if (ragged_order_enabled() && b.S > lds_waves * c->simds) {
+    if (plan.order) {
+        int32_t* const order_ws = reinterpret_cast<int32_t*>(ws + plan.order_offset);
         // (one workgroup of the 1,024 threads the kernel strides by: mbx_stream.hip, kOrderThreads)
         hipLaunchKernelGGL(mbx::ragged_order_kernel, dim3(1), dim3(1024), 0, (hipStream_t)b.stream, b.S, b.frame_offset, order_ws);
         const int rc = check_launch("ragged_order_kernel");
@@ -943,114 +873,40 @@ static int launch_ragged(Context* c, const BatchCall& b, const mbx::FrameParams*
         }
         order = order_ws;
     }
-    if (b.stream_codec) {   // a mixed step: the same launch with a codec per stream
-        const MixedKernel& e = kMixed[b.resident ? 1 : 0];
+    if (plan.form == mbx::kMixedStep) {   // the same launch with a codec per stream
+        const MixedKernel& e = kMixed[plan.instance];
         hipLaunchKernelGGL(e.kernel, dim3((unsigned)b.S), dim3(64), 0, (hipStream_t)b.stream, b.stream_codec, b.S, (int)b.total, b.frame_offset, order,
-                           b.records, params, b.state, b.rng, b.pcm16, b.pcmf, b.results, launch_tables(c, false, b));
+                           b.records, ws, b.state, b.rng, b.pcm16, b.pcmf, b.results, launch_tables(c, false, b));
         record_launch(c, b.stream, e.name);
         return check_launch(e.name);
     }
-    const RaggedKernel& e = kRagged[b.resident ? 1 : 0][stream_kernels(b.codec).column];
-    hipLaunchKernelGGL(e.kernel, dim3((unsigned)b.S), dim3(64), 0, (hipStream_t)b.stream, b.S, (int)b.total, b.frame_offset, order, b.records, params,
+    const RaggedKernel& e = kRagged[plan.instance / 3][plan.instance % 3];
+    hipLaunchKernelGGL(e.kernel, dim3((unsigned)b.S), dim3(64), 0, (hipStream_t)b.stream, b.S, (int)b.total, b.frame_offset, order, b.records, ws,
                        b.state, b.rng, b.pcm16, b.pcmf, b.results, launch_tables(c, false, b));
     record_launch(c, b.stream, e.name);
     return check_launch(e.name);
 }
 
-// IMBE with several frames per stream: the stream kernel expands the records itself, which saves the workspace round
-// trip and a launch (+4 % at T = 16).  With ONE frame per stream the whole-job rate is the same either way (measured
-// 0.296 vs 0.292 ms per 65,536 frames): the table look-ups of the expansion are a latency chain a one-frame wave cannot
-// hide, and the 8-lanes-per-frame expand kernel costs as much as it saves -- there the expansion stays a separate
-// launch, which keeps the dominant kernel to the stream stage proper.  The AMBE HBM-slot instances always read rows.
-// ... except for small batches (the synchronous per-frame API is S = T = 1): there a launch less is worth more than the
-// last few per cent of kernel efficiency, and the IMBE stream kernel expands the record itself.
-constexpr int kSmallBatchFrames = 256;
-static bool needs_workspace(int codec, int S, int T) {
-    if (imbe_codec(codec)) {
-        return T == 1 && S > kSmallBatchFrames;
-    }
-    // AMBE codecs: the LDS-resident instances (T >= 4) expand eight frames of their stream at a time into LDS rows;
-    // the HBM-slot instances read rows from the workspace
-    return !(T >= kLdsResidentMinFrames && lds_resident_enabled());
-}
-
-// The whole T = 1 step of the IMBE codecs as ONE launch (mbx_stream.hip).  Taken by the mbx_process_batch* entry points (which have
-// the frames); the records-based entry points keep the expand + stream pair.  Two forms:
-//   2 (default, 7200x4400): imbe_one_launch_kernel -- front blocks (FEC + expansion of eight frames per wave) and stream blocks in one
-//     grid, rows handed over through the stream's workspace (mbx_front_imbe.h);
-//   1 (7100x4400; 7200x4400 with MBX_FUSE_ONE=1): imbe_stream_kernel_one_fused -- the front end in the stream's own wave.
-// MBX_FUSE_ONE=0 switches both off (A/B timing; read once).  MBX_FRONT_LEAD: by how many chunks of eight streams a front block
-// runs ahead of its stream blocks in the grid.  Default: all front blocks first.  Measured (65,536 x 1, interleaved A/B, one box):
-// lead 0 / 128 / 512: 0.37 / 0.36 / 0.35 ms (stream blocks start before their rows exist and wait); 1024 / 2048 / 4096: 0.2245 /
-// 0.2245 / 0.2230; all first: 0.2229 -- and with the front blocks at a raised wave priority 0.2259 / 0.2253 against 0.2194: what a
-// front block costs is the wave SLOT it holds for the ~10 us of its table-read chain, not its instructions, and slots are what an
-// interleaved front block takes away from stream blocks that could use them.
-static int fused_one_mode() {
-    static const int mode = [] {
-        const char* e = getenv("MBX_FUSE_ONE");
-        return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 2;
-    }();
-    return mode;
-}
-static int front_lead_chunks() {
-    static const int lead = [] {
-        const char* e = getenv("MBX_FRONT_LEAD");
-        const int v = e ? atoi(e) : 0x7fffffff;
-        return v < 0 ? 0 : v;
-    }();
-    return lead;
-}
-// THE selection: which instance runs for a launch of this shape under the switches above.  (A codec that is none of the four:
-// see stream_kernels.)
-static const Instance& select_instance(const Shape& q) {
-    const mbx::CodecShape* sh = mbx::codec_shape(q.codec);
-    const bool imbe7100 = sh && sh->stream != q.codec;   // own front end, then the 7200x4400 column
-    const bool imbe = imbe_codec(q.codec);
-    const int col = stream_kernels(q.codec).column;
-    const int mode = fused_one_mode();
-    if (q.frames && q.T == 1 && q.S > kSmallBatchFrames && mode != 0) {   // the T = 1 step as one launch
-        if (sh && !imbe) {   // AMBE, 9-byte frames: byte loads, any alignment; no in-wave form: without a workspace the staged kernels
-            if (mode == 2 && q.workspace) {
-                return kInstances[(q.resident ? kOneLaunchRes : kOneLaunch) + col];
-            }
-        } else if (imbe && q.aligned) {
-            if (mode == 2 && !imbe7100 && q.workspace) {
-                return kInstances[(q.resident ? kOneLaunchRes : kOneLaunch) + col];
-            }
-            return kInstances[(q.resident ? kRes1Fused : kOneFused) + kCodecKernels[q.codec].fused_column];
-        }
-    }
-    if (q.sliced) {
-        return kInstances[kSlice + col];
-    }
-    if (q.resident) {   // understood by the *_res / *_res1 instances only, whatever T is and whatever MBX_NO_LDS_RESIDENT says
-        // (IMBE's one-frame instance expands a record itself; the AMBE ones read rows, and without rows the looped instance serves T = 1)
-        const bool one = q.T == 1 && res1_enabled() && (imbe || q.rows);
-        return kInstances[(one ? kRes1 : kRes) + col];
-    }
-    const bool lds = q.T >= kLdsResidentMinFrames && lds_resident_enabled();
-    // (Long AMBE+2 launches used to need a second, register-padded instance to even out their rounds of waves -- config 5's
-    // shard is 8 waves per SIMD on 6 slots: 6 + 2.  The LDS-resident instance runs 16 waves per CU: 2 x 16, and
-    // 8,192 streams x T = 128 went from 3.51 ms to 3.15 ms.)
-    return kInstances[(lds ? kLds : (q.T == 1 ? kOne : kPlain)) + col];
-}
-static int launch_fused_one(Context* c, const Instance& e, bool reverse, const BatchCall& b, const uint8_t* d_frames) {
+// The whole T = 1 step as ONE launch (which shapes take which form: plan_step): the front end in the stream's own wave ...
+static int launch_fused_one(Context* c, bool reverse, const BatchCall& b, const uint8_t* d_frames, const StepPlan& plan) {
+    const Instance& e = kInstances[plan.instance];
     const mbx::DeviceTables tabs = launch_tables(c, reverse, b);
     hipLaunchKernelGGL(e.fused, dim3((unsigned)b.S), dim3(64), 0, (hipStream_t)b.stream, b.S, b.codec, d_frames, b.records, b.state, b.rng, b.pcm16,
                        b.pcmf, b.results, tabs);
     return launched(c, b.stream, e);
 }
-// caller holds c->mu; the slot's workspace holds S rows and its flags
-static int launch_one_launch(Context* c, const Instance& e, StreamSlot& slot, bool reverse, const BatchCall& b, const uint8_t* d_frames) {
+// ... or front blocks and stream blocks in one grid, rows handed over through the slot's workspace and flag words.  Caller holds
+// c->mu; the slot's workspace holds S rows and its flags
+static int launch_one_launch(Context* c, StreamSlot& slot, bool reverse, const BatchCall& b, const uint8_t* d_frames, const StepPlan& plan) {
+    const Instance& e = kInstances[plan.instance];
     const mbx::DeviceTables tabs = launch_tables(c, reverse, b);
     if (++slot.epoch == 0u) {
         slot.epoch = 1u;
     }
-    slot.exp_codec = -1;   // the rows of an earlier mbx_expand_records() are being replaced
     const unsigned chunks = (unsigned)((b.S + 7) / 8);
     uint32_t* const fallbacks = slot.flags + (slot.frames + 7) / 8;
     if (e.family == kOneLaunchLeadArgs) {
-        hipLaunchKernelGGL(e.one_launch_lead, dim3(9u * chunks), dim3(64), 0, (hipStream_t)b.stream, b.S, front_lead_chunks(), d_frames, b.records,
+        hipLaunchKernelGGL(e.one_launch_lead, dim3(9u * chunks), dim3(64), 0, (hipStream_t)b.stream, b.S, plan.front_lead, d_frames, b.records,
                            slot.workspace, slot.flags, fallbacks, slot.epoch, b.state, b.rng, b.pcm16, b.pcmf, b.results, tabs);
     } else {
         hipLaunchKernelGGL(e.one_launch, dim3(9u * chunks), dim3(64), 0, (hipStream_t)b.stream, b.S, d_frames, b.records, slot.workspace, slot.flags,
@@ -1058,39 +914,15 @@ static int launch_one_launch(Context* c, const Instance& e, StreamSlot& slot, bo
     }
     return launched(c, b.stream, e);
 }
-// The one-launch forms of a hard-frame step.  Caller holds c->mu; `own_workspace`: the rows may go through the slot's workspace and
-// flag words.  Returns 1 when a launch was issued (*rc = its status; the slot's launch counter has been bumped), 0 when the
-// caller goes on with the stages.
-static int try_fused_one(Context* c, StreamSlot& slot, const BatchCall& b, const uint8_t* d_frames, bool own_workspace, int* rc) {
-    Shape q{b.codec, b.S, b.T};
-    q.resident = b.resident != nullptr;
-    q.frames = true;
-    q.aligned = (reinterpret_cast<uintptr_t>(d_frames) & 3u) == 0;
-    q.workspace = own_workspace;
-    const Instance& e = select_instance(q);
-    if (e.family == kStreamArgs) {   // no instance takes the frames of this shape: the staged kernels
-        return 0;
-    }
-    if (e.family != kFusedArgs) {   // rows handed over through the slot's workspace
-        // A launch that is being CAPTURED into a graph would be replayed with the same epoch, and a replay would find the flags of
-        // the replay before it: captured launches take the staged kernels.
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        const bool capturing = b.stream && hipStreamIsCapturing((hipStream_t)b.stream, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-        (void)hipGetLastError();
-        if (capturing) {
-            return 0;
-        }
-        *rc = ensure_workspace(c, slot, (size_t)b.S, b.stream);
-        if (*rc >= 0) {
-            *rc = launch_one_launch(c, e, slot, (slot.launches++ & 1u) != 0u, b, d_frames);
-        }
-        return 1;
-    }
-    *rc = launch_fused_one(c, e, (slot.launches++ & 1u) != 0u, b, d_frames);
-    return 1;
-}
 
-extern "C" int mbx_uses_expand_launch(int codec, int S, int T) { return needs_workspace(codec, S, T) ? 1 : 0; }
+// (records-based: what mbx_process_records launches for the shape, on the stream slot's own workspace, not being captured)
+static StepShape predicted_step(int codec, int S, int T) {
+    StepShape q;
+    q.codec = codec, q.S = S, q.T = T;
+    q.own_workspace = q.slices_allowed = true;
+    return q;
+}
+extern "C" int mbx_uses_expand_launch(int codec, int S, int T) { return plan_of(nullptr, predicted_step(codec, S, T)).expand ? 1 : 0; }
 
 int mbx_expand_records(int codec, const mbx_param_record* d_records, size_t n, void* stream) {
     REQUIRE_CTX(c);
@@ -1136,6 +968,14 @@ int mbx_expand_records_ws(int codec, const mbx_param_record* d_records, size_t n
     return launch_expand(c, codec, d_records, n, static_cast<mbx::FrameParams*>(d_workspace), stream);
 }
 
+// the stream stage alone, on rows that are there: never sliced, nothing of the slot but its launch counter
+static StepShape rows_shape(const BatchCall& b) {
+    StepShape q;
+    q.codec = b.codec, q.S = b.S, q.T = b.T;
+    q.rows_given = true;
+    q.resident = b.resident != nullptr;
+    return q;
+}
 // (the records of these calls are read, never written: a BatchCall holds the pointer a front launch would write through)
 int mbx_stream_expanded_ws(int codec, int S, int T, const mbx_param_record* d_records, mbe_parms* d_state, uint32_t* d_resident,
                            mbx_stream_rng* d_rng, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
@@ -1151,12 +991,14 @@ int mbx_stream_expanded_ws(int codec, int S, int T, const mbx_param_record* d_re
     if (S == 0 || T == 0) {
         return 0;
     }
+    const StepShape q = rows_shape(b);
+    const StepPlan plan = plan_of(c, q);
     unsigned order;
     {
         std::lock_guard<std::mutex> lock(c->mu);
         order = c->slots[stream].launches++;
     }
-    return launch_stream(c, (order & 1u) != 0u, b, static_cast<const mbx::FrameParams*>(d_workspace), nullptr);
+    return launch_stream(c, (order & 1u) != 0u, b, static_cast<const mbx::FrameParams*>(d_workspace), nullptr, q, plan);
 }
 
 // the stream stage on the rows the last mbx_expand_records() left in the stream's own workspace
@@ -1171,13 +1013,15 @@ static int stream_expanded(const BatchCall& b) {
     if (b.S == 0 || b.T == 0) {
         return 0;
     }
+    const StepShape q = rows_shape(b);
+    const StepPlan plan = plan_of(c, q);
     std::lock_guard<std::mutex> lock(c->mu);
     StreamSlot& slot = c->slots[b.stream];
     if (slot.exp_codec != b.codec || slot.exp_n != (size_t)b.S * (size_t)b.T || slot.exp_records != b.records) {
         return fail(MBE_STATUS_INVALID_ARGUMENT,
                     "mbx_stream_expanded: the last mbx_expand_records() on this stream was not for this codec / batch / record array");
     }
-    return launch_stream(c, (slot.launches++ & 1u) != 0u, b, slot.workspace, nullptr);
+    return launch_stream(c, (slot.launches++ & 1u) != 0u, b, slot.workspace, nullptr, q, plan);
 }
 
 int mbx_stream_expanded(int codec, int S, int T, const mbx_param_record* d_records, mbe_parms* d_state,
@@ -1198,34 +1042,28 @@ int mbx_stream_expanded_resident(int codec, int S, int T, const mbx_param_record
 
 // ---- the batch step ------------------------------------------------------------------------------------------------------------
 // Every batch entry point ends here: it makes the checks that are its own, fills the record and says what the step starts from
-// and whose workspace the FrameParams rows go to.
-//   kRecords: the records are there;  kFrames: packed hard frames, a FEC launch in front -- or the whole T = 1 step as ONE launch
-//   (try_fused_one);  kSoft: soft cells, a soft front launch (one wave per frame) in front.  Codec 2 records come out in 7200x4400
-//   order; codec 3 frames take the AMBE front end and are expanded by the 3600x2400 rules.
+// (InputKind, mbx_launch_plan.h) and whose workspace the FrameParams rows go to.
 //   caller_ws == nullptr: the stream slot's own workspace, grown here under c->mu, which is then held to the last launch -- the
 //   workspace cannot be grown (freed) by another thread between the launches of this call, and two threads that share one
 //   hipStream_t cannot interleave their steps.  The front launch is issued inside the lock as well.
 //   caller_ws: the caller's rows.  Nothing of the slot is touched but its launch counter, c->mu is held only to read and bump it
 //   (and across the in-wave fused launch of a T = 1 IMBE step, which needs no rows), the launch is never sliced and never one
 //   that needs the slot's flag words: the step can be captured into a graph.
-// The slot goes to launch_stream (sliced launches allowed) whenever the workspace is the slot's own, with resident state too:
-// launch_stream slices only without b.resident, so a resident step is never sliced either way.
-// The launch counter is bumped once per step: by the one-launch form when it issues, otherwise here.
-enum InputKind { kRecords, kFrames, kSoft };
+// The launch counter is bumped once per step, whatever its form.
 struct CallerWorkspace {
     void*  p;
     size_t bytes;
 };
-// The staged launches of a MIXED step (BatchCall::stream_codec): the codec of every batch row into `row_codec` (the step's own
-// workspace), then what a ragged step launches, by kernels that look the codec of a row or a stream up -- one front launch and one
-// expand launch over all rows, (the order,) one stream-stage launch, whatever the mix.
-static int run_mixed_stages(Context* c, const BatchCall& b, InputKind kind, const void* d_input, mbx::FrameParams* ws, int32_t* order_ws,
-                            uint8_t* row_codec) {
+// The staged launches of a MIXED step (BatchCall::stream_codec): the codec of every batch row into the step's own workspace (behind
+// the rows and the order words, at plan.codec_offset), then what a ragged step launches, by kernels that look the codec of a row or a
+// stream up -- one front launch and one expand launch over all rows, (the order,) one stream-stage launch, whatever the mix.
+static int run_mixed_stages(Context* c, const BatchCall& b, const StepPlan& plan, const void* d_input, mbx::FrameParams* ws) {
     const size_t n = b.total;
     const hipStream_t st = (hipStream_t)b.stream;
+    uint8_t* const row_codec = reinterpret_cast<uint8_t*>(ws + plan.codec_offset);
     hipLaunchKernelGGL(mbx::mixed_row_codec_kernel, dim3((unsigned)((b.S + 3) / 4)), dim3(256), 0, st, b.S, (int)n, b.frame_offset, b.stream_codec, row_codec);
     int rc = check_launch("mixed_row_codec_kernel");
-    if (rc >= 0 && kind == kFrames) {
+    if (rc >= 0 && plan.front == mbx::kFecFront) {
         hipLaunchKernelGGL(mbx::fec_mixed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const uint8_t*>(d_input), n, row_codec,
                            b.records, c->tabs);
         rc = check_launch("fec_mixed_kernel");
@@ -1238,47 +1076,51 @@ static int run_mixed_stages(Context* c, const BatchCall& b, InputKind kind, cons
         hipLaunchKernelGGL(mbx::expand_mixed_kernel, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, st, b.records, n, row_codec, ws, c->tabs);
         rc = check_launch("expand_mixed_kernel");
     }
-    return rc < 0 ? rc : launch_ragged(c, b, ws, order_ws);
+    return rc < 0 ? rc : launch_ragged(c, b, ws, plan);
 }
-// the staged launches of a step: the front launch (where the step has one), expand (where the stream stage reads rows: to `ws`) and the
+// the staged launches of a step: the front launch (where the plan has one), expand (where the stream stage reads rows: to `ws`) and the
 // stream kernel; `order` = the launch counter that decides the walking direction; `slot`: see launch_stream
-static int run_stages(Context* c, unsigned order, const BatchCall& b, InputKind kind, const void* d_input, mbx::FrameParams* ws, StreamSlot* slot) {
+static int run_stages(Context* c, unsigned order, const BatchCall& b, const StepShape& q, const StepPlan& plan, const void* d_input, mbx::FrameParams* ws,
+                      StreamSlot* slot) {
     const size_t n = batch_rows(b);
     int rc = 0;
-    if (kind == kFrames) {
+    if (plan.front == mbx::kFecFront) {
         rc = launch_fec(c, b.codec, static_cast<const uint8_t*>(d_input), n, b.records, b.stream);
-    } else if (kind == kSoft) {
+    } else if (plan.front == mbx::kSoftFront) {
         rc = launch_soft_fec(c, b.codec, true, static_cast<const mbe_soft_bit*>(d_input), n, b.records, b.stream);
     }
-    if (rc >= 0 && (b.frame_offset || needs_workspace(b.codec, b.S, b.T))) {
+    if (rc >= 0 && plan.expand) {
         rc = launch_expand(c, mbx::kCodecs[b.codec].stream, b.records, n, ws, b.stream);
-    } else {
-        ws = nullptr;
     }
     if (rc < 0) {
         return rc;
     }
-    if (b.frame_offset) {   // (the order words: behind the rows, see run_batch)
-        return launch_ragged(c, b, ws, reinterpret_cast<int32_t*>(ws + n));
+    if (plan.form == mbx::kRaggedStep) {
+        return launch_ragged(c, b, ws, plan);
     }
-    return launch_stream(c, (order & 1u) != 0u, b, ws, slot);
+    return launch_stream(c, (order & 1u) != 0u, b, plan.rows ? ws : nullptr, slot, q, plan);
 }
-// An S x T step on the stream slot's own workspace (the last case of run_batch; a burst launch, behind its gather): the one-launch
-// form where the shape has one, the staged launches otherwise.  Caller holds c->mu and has made run_batch's checks.
-static int run_step_on_slot(Context* c, StreamSlot& slot, const BatchCall& b, InputKind kind, const void* d_input) {
-    const uint8_t* const d_frames = kind == kFrames ? static_cast<const uint8_t*>(d_input) : nullptr;
-    int rc = 0;
-    if (d_frames && try_fused_one(c, slot, b, d_frames, true, &rc)) {
+// A planned step on the stream slot's own workspace (run_batch without a caller's; a burst launch, behind its gather): the workspace
+// grown to the plan's size, the launch counter bumped, the plan's form issued.  Caller holds c->mu and has made run_batch's checks.
+static int issue_on_slot(Context* c, StreamSlot& slot, const BatchCall& b, const StepShape& q, const StepPlan& plan, const void* d_input) {
+    const int rc = ensure_workspace(c, slot, plan.workspace_frames, b.stream);
+    if (rc < 0) {
         return rc;
     }
-    if (needs_workspace(b.codec, b.S, b.T)) {
-        rc = ensure_workspace(c, slot, batch_rows(b), b.stream);
-        if (rc < 0) {
-            return rc;
-        }
-        slot.exp_codec = -1;   // the rows are about to be replaced
+    if (plan.workspace_frames) {
+        slot.exp_codec = -1;   // the rows of an earlier mbx_expand_records() are about to be replaced
     }
-    return run_stages(c, slot.launches++, b, kind, d_input, slot.workspace, &slot);
+    const unsigned order = slot.launches++;
+    switch (plan.form) {
+    case mbx::kOneLaunchStep:
+        return launch_one_launch(c, slot, (order & 1u) != 0u, b, static_cast<const uint8_t*>(d_input), plan);
+    case mbx::kFusedOneStep:
+        return launch_fused_one(c, (order & 1u) != 0u, b, static_cast<const uint8_t*>(d_input), plan);
+    case mbx::kMixedStep:
+        return run_mixed_stages(c, b, plan, d_input, slot.workspace);
+    default:   // (a ragged step walks its streams in the order kernel's order or the grid's: no direction)
+        return run_stages(c, plan.form == mbx::kRaggedStep ? 0u : order, b, q, plan, d_input, slot.workspace, &slot);
+    }
 }
 static int run_batch(Context* c, const char* who, const BatchCall& b, InputKind kind, const void* d_input, const CallerWorkspace* caller_ws) {
     const bool mixed = b.stream_codec != nullptr;   // every stream brings its codec (wire frames or soft cells only): b.codec is not looked at
@@ -1303,46 +1145,26 @@ static int run_batch(Context* c, const char* who, const BatchCall& b, InputKind 
         snprintf(text, sizeof(text), "%s: more than 2^31-1 frames in one launch", who);
         return fail(MBE_STATUS_INVALID_ARGUMENT, text);
     }
-    if (b.frame_offset) {
-        // A ragged step: front launch over all rows, expansion, (order,) one ragged stream kernel -- a linear chain on the caller's
-        // stream, no one-launch form, never sliced.  The slot's workspace holds the rows and, behind them, S order words.
-        std::lock_guard<std::mutex> lock(c->mu);
-        StreamSlot& slot = c->slots[b.stream];
-        // A mixed step keeps one codec byte per row behind the order words.
-        const size_t order_frames = ((size_t)b.S + 63) / 64, codec_frames = mixed ? (n + sizeof(mbx::FrameParams) - 1) / sizeof(mbx::FrameParams) : 0;
-        const int wrc = ensure_workspace(c, slot, n + order_frames + codec_frames, b.stream);
-        if (wrc < 0) {
-            return wrc;
-        }
-        slot.exp_codec = -1;   // the rows are about to be replaced
-        slot.launches++;
-        if (mixed) {
-            return run_mixed_stages(c, b, kind, d_input, slot.workspace, reinterpret_cast<int32_t*>(slot.workspace + n),
-                                    reinterpret_cast<uint8_t*>(slot.workspace + n + order_frames));
-        }
-        return run_stages(c, 0u, b, kind, d_input, slot.workspace, nullptr);
-    }
-    const uint8_t* const d_frames = kind == kFrames ? static_cast<const uint8_t*>(d_input) : nullptr;
-    const bool rows = needs_workspace(b.codec, b.S, b.T);
-    int rc = 0;
+    StepShape q = step_shape(b, kind, d_input, caller_ws == nullptr);
+    const StepPlan plan = plan_on_stream(c, q, b.stream);
     if (caller_ws) {
         unsigned order;
         {
             std::lock_guard<std::mutex> lock(c->mu);
             StreamSlot& slot = c->slots[b.stream];
-            if (d_frames && try_fused_one(c, slot, b, d_frames, false, &rc)) {
-                return rc;
+            if (plan.form == mbx::kFusedOneStep) {
+                return launch_fused_one(c, (slot.launches++ & 1u) != 0u, b, static_cast<const uint8_t*>(d_input), plan);
             }
-            if (rows && (!caller_ws->p || caller_ws->bytes < mbx_workspace_bytes(n))) {
+            if (plan.expand && (!caller_ws->p || caller_ws->bytes < mbx_workspace_bytes(plan.workspace_frames))) {
                 snprintf(text, sizeof(text), "%s: workspace missing or smaller than mbx_workspace_bytes(S*T)", who);
                 return fail(MBE_STATUS_INVALID_ARGUMENT, text);
             }
             order = slot.launches++;
         }
-        return run_stages(c, order, b, kind, d_input, static_cast<mbx::FrameParams*>(caller_ws->p), nullptr);
+        return run_stages(c, order, b, q, plan, d_input, static_cast<mbx::FrameParams*>(caller_ws->p), nullptr);
     }
     std::lock_guard<std::mutex> lock(c->mu);
-    return run_step_on_slot(c, c->slots[b.stream], b, kind, d_input);
+    return issue_on_slot(c, c->slots[b.stream], b, q, plan, d_input);
 }
 
 int mbx_process_records(int codec, int S, int T, const mbx_param_record* d_records, mbe_parms* d_state,
@@ -1575,10 +1397,11 @@ int mbx_process_batch_soft_resident(int codec, int S, int T, const int32_t* d_st
     return run_batch(c, "mbx_process_batch_soft_resident", b, kSoft, d_soft, nullptr);
 }
 
-// ---- burst launches (include/mbx_burst.h): the gather of mbx_burst.hip, then run_step_on_slot ------------------------------------------
+// ---- burst launches (include/mbx_burst.h): the gather of mbx_burst.hip, then issue_on_slot ------------------------------------------
 // One launch in front of the step the frames calls run for (codec, S, T = frames per burst), on the caller's stream.  The gathered
 // frames live in the stream slot's workspace BEHIND the S * T rows of the step (256-byte aligned: a T = 1 step takes its one-launch
-// kernel), so c->mu is held from the growth of the workspace to the last launch, as run_batch holds it.
+// kernel), so c->mu is held from the growth of the workspace to the last launch, as run_batch holds it.  (The workspace is grown ONCE,
+// to mbx_burst_workspace_frames, which covers the rows of whatever the step's plan is: nothing grows -- frees -- it behind the gather.)
 static int process_bursts(const char* who, bool soft, const mbx_burst_schedule* sched, int S, const int32_t* d_stream_index, const void* d_bursts,
                           size_t burst_stride, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf,
                           mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
@@ -1611,6 +1434,8 @@ static int process_bursts(const char* who, bool soft, const mbx_burst_schedule* 
         return fail(MBE_STATUS_INVALID_ARGUMENT, text);
     }
     const BatchCall b{sh.codec, S, sh.frames, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index, d_resident};
+    StepShape q = step_shape(b, soft ? kSoft : kFrames, nullptr, true);   // (the gathered frames: 256-byte aligned)
+    const StepPlan plan = plan_on_stream(c, q, stream);
     std::lock_guard<std::mutex> lock(c->mu);
     StreamSlot& slot = c->slots[stream];
     int rc = ensure_workspace(c, slot, mbx_burst_workspace_frames(sched, S, soft ? 1 : 0), stream);
@@ -1623,7 +1448,7 @@ static int process_bursts(const char* who, bool soft, const mbx_burst_schedule* 
     if (rc < 0) {
         return rc;
     }
-    return run_step_on_slot(c, slot, b, soft ? kSoft : kFrames, gathered);
+    return issue_on_slot(c, slot, b, q, plan, gathered);
 }
 
 int mbx_process_bursts(const mbx_burst_schedule* sched, int S, const int32_t* d_stream_index, const uint8_t* d_bursts, size_t burst_stride,
@@ -1966,29 +1791,27 @@ const char* mbx_last_kernel_name(void* stream) {
 // 0, or the slice length in frames a launch of this shape is cut into (mbx_process_records and the batch calls on top of it)
 int mbx_launch_slices(int codec, int S, int T) {
     int crc;
-    Context* c = current_ctx(&crc);
-    if (!c || !(T >= kLdsResidentMinFrames && lds_resident_enabled())) {
-        return 0;
-    }
-    return choose_slice_frames(S, T, stream_kernels(codec).lds_waves * c->simds);
+    return plan_of(current_ctx(&crc), predicted_step(codec, S, T)).slice_frames;   // (no context: no wave slots, 0)
 }
 
 // the dominant kernel of mbx_process_batch / _resident for a batch shape (frames 4-byte aligned, as device allocations are; a launch
 // on the stream slot's own workspace that is not being captured into a graph)
 const char* mbx_batch_kernel_name(int codec, int S, int T, int resident) {
-    Shape q{codec, S, T};
+    StepShape q = predicted_step(codec, S, T);
+    q.kind = kFrames;
+    q.aligned = true;
+    q.rows_given = true;   // (a resident one-frame AMBE launch is named as on rows, also where MBX_LDS_MIN_FRAMES=1 leaves it none)
     q.resident = resident != 0;
-    q.rows = true;
-    q.sliced = !resident && mbx_launch_slices(codec, S, T) > 0;
-    q.frames = q.aligned = q.workspace = true;
-    return select_instance(q).name;
+    int crc;
+    return kInstances[plan_of(resident ? nullptr : current_ctx(&crc), q).instance].name;   // (resident state is never sliced: no wave slots asked for)
 }
 
 const char* mbx_stream_kernel_name(int codec, int T) {
-    Shape q{codec, 0, T < 0 ? -T : T};
-    q.resident = T < 0;   // the instances of the resident launches (mbx_process_batch_resident) with -T frames per stream ...
-    q.rows = true;        // ... on rows from the expand launch wherever the shape has one
-    return select_instance(q).name;
+    StepShape q;
+    q.codec = codec, q.T = T < 0 ? -T : T;
+    q.resident = T < 0;    // the instances of the resident launches (mbx_process_batch_resident) with -T frames per stream ...
+    q.rows_given = true;   // ... on rows from the expand launch wherever the shape has one
+    return kInstances[plan_of(nullptr, q).instance].name;
 }
 
 // ---- host-buffer conveniences ------------------------------------------------------------

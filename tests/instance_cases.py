@@ -230,6 +230,9 @@ def run_case(case, mem=None, oracle=True):
             _native.check(rc, case.entry)
         ran = L.mbx_last_kernel_name(strm)
         assert ran is not None and ran.decode() == case.name, f"{case.id}: launch {k} ran {ran!r}, the case is for {case.name}"
+        if case.entry in ("batch", "batch_indexed", "resident", "resident_indexed"):   # (the calls the prediction is made for: same plan, same name)
+            predicted = L.mbx_batch_kernel_name(codec, S, T, 1 if resident else 0)
+            assert predicted == ran, f"{case.id}: launch {k} ran {ran!r}, mbx_batch_kernel_name predicts {predicted!r}"
         torch.cuda.synchronize()
         mem.after_launch(f"{case.id}: launch {k}")
         for x in got:

@@ -76,9 +76,10 @@ def test_every_table_row_has_an_oracle_case_and_every_case_switch_is_one_the_lib
     covered = {c.name for c in instance_cases.CASES}
     assert not rows - covered, f"kInstances rows without an oracle case in tests/instance_cases.py: {sorted(rows - covered)}"
     assert not covered - rows, f"cases for instances that are not in kInstances: {sorted(covered - rows)}"
-    read = set(re.findall(r'getenv\("(MBX_\w+)"\)', api))
+    plan = open(os.path.join(ROOT, "mbelib-neo_amd", "csrc", "mbx_launch_plan.h")).read()   # (the launch switches are read there)
+    read = set(re.findall(r'getenv\("(MBX_\w+)"\)', api + plan))
     for c in instance_cases.CASES:
-        assert set(c.env) <= read, f"{c.id}: {sorted(set(c.env) - read)} is not read by mbx_api.hip"
+        assert set(c.env) <= read, f"{c.id}: {sorted(set(c.env) - read)} is not read by mbx_api.hip or mbx_launch_plan.h"
         assert c.launches >= 2 and c.S >= 2 and c.T >= 1 and c.S * c.T * c.launches <= 330_000, c.id
         assert c.entry in ("batch", "batch_ws", "batch_indexed", "resident", "resident_indexed", "staged"), c.id
         assert c.id == c.name or c.id.startswith(c.name + "-"), c.id
