@@ -266,8 +266,17 @@ __device__ __forceinline__ void st_state(T* p, T v) {
         *p = v;
     }
 }
-template <bool kGather = false, bool kNt = kGather>
-__device__ __forceinline__ void store_parms(const Parms& r, mbe_parms* __restrict__ p, int lane) {
+// Silent stores (IMBE one-frame instances, EXPERIMENTS.md "Silent stores"): a span of previousUw is not stored when every dword the wave
+// LOADED from that span of that slot was 0x00000000 and every dword it is about to store there is 0x00000000 -- a frame without an
+// unvoiced band after another one, 1,024 of a struct's 2,604 bytes.  Both halves of the condition are compared as BITS (-0.0f is
+// overwritten, a NaN is "not zero") and are wave-uniform: the decision sits in an SGPR, the stores are skipped by a scalar branch.
+enum UwSkip : int { kUwStoreAll = 0, kUwSkipUpper = 1, kUwSkipAll = 2 };   // kUwSkipUpper: uw[2], uw[3] -- all a wave loads of prev_mp_enhanced
+__device__ __forceinline__ bool uw_all_zero_bits(float a, float b, float c = 0.0f, float d = 0.0f) {
+    const uint32_t bits = (__float_as_uint(a) | __float_as_uint(b)) | (__float_as_uint(c) | __float_as_uint(d));
+    return __ballot(bits != 0u) == 0ULL;
+}
+template <bool kGather = false, bool kNt = kGather, bool kSilent = false>   // kSilent: uw_skip honoured (every other caller: as before)
+__device__ __forceinline__ void store_parms(const Parms& r, mbe_parms* __restrict__ p, int lane, UwSkip uw_skip = kUwStoreAll) {
     float* f = reinterpret_cast<float*>(p);
     int* i = reinterpret_cast<int*>(p);
     if constexpr (kGather) {
@@ -313,9 +322,20 @@ __device__ __forceinline__ void store_parms(const Parms& r, mbe_parms* __restric
         st_state<kNt>(&f[O_PHI + lane], (float)(r.PHIl));
         st_state<kNt>(&f[O_PSI + lane], (float)(r.PSIl));
     }
+    if constexpr (kSilent) {
+        if (uw_skip != kUwSkipAll) {
+            st_state<kNt>(&f[O_UW + lane], (float)(r.uw[0]));
+            st_state<kNt>(&f[O_UW + lane + 64], (float)(r.uw[1]));
+        }
+        if (uw_skip == kUwStoreAll) {
+            st_state<kNt>(&f[O_UW + lane + 128], (float)(r.uw[2]));
+            st_state<kNt>(&f[O_UW + lane + 192], (float)(r.uw[3]));
+        }
+    } else {
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        st_state<kNt>(&f[O_UW + lane + 64 * j], (float)(r.uw[j]));
+        for (int j = 0; j < 4; ++j) {
+            st_state<kNt>(&f[O_UW + lane + 64 * j], (float)(r.uw[j]));
+        }
     }
     st_state<kNt>(&f[O_OVERLAP + lane], (float)(r.ov[0]));
     if (lane < 32) {
@@ -2402,6 +2422,7 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
     }
 
     const int frames = (kOne && Tn > 1) ? 1 : Tn;
+    UwSkip skip_cur = kUwStoreAll;   // kOne: whether the final store of cur_mp leaves previousUw alone (store_parms)
     for (int t = 0; t < frames; ++t) {
         const size_t f = fbase + (size_t)t;
         // Keep per-frame table values out of the loop-carried register set: without this the compiler
@@ -2470,6 +2491,7 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         unsigned flags = (errw >> 24) & 0xffu;   // C0_VALID | C4_VALID from the FEC stage
         const int total = c0 + prot;
         bool muted;
+        bool cur_uw_was_zero = false, enh_uw_was_zero = false;   // kOne, wave-uniform (SGPRs across the synthesiser)
         {
 
             // prepare (imbe4400_prepare_process)
@@ -2479,6 +2501,10 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
             cur.errorRate = uni((0.95f * prev.errorRate) + (0.000365f * (float)total));
 
             const int bad = MBX_ABL(tabs, 1) ? 0 : decode_imbe(fp, cur, prev, tabs.d, lane, scratch.x.C);
+            if constexpr (kOne) {   // silent stores (store_parms): what the two slots HOLD, from the registers as loaded -- a repeat
+                cur_uw_was_zero = uw_all_zero_bits(cur.uw[0], cur.uw[1], cur.uw[2], cur.uw[3]);   // replaces cur below
+                enh_uw_was_zero = !kRes && uw_all_zero_bits(enh.uw[2], enh.uw[3]);
+            }
             const float repeat_threshold = 10.0f + (40.0f * cur.errorRate);
             const bool c0_valid = (flags & MBE_PROCESS_FLAG_C0_VALID) != 0u;
             const bool repeat =
@@ -2548,6 +2574,12 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         if (muted) {
             flags |= MBE_PROCESS_FLAG_MUTE;
         }
+        UwSkip skip_enh = kUwStoreAll;
+        if constexpr (kOne) {   // one ballot for every way the frame can end: all voiced, read back, headroom reset, repeat
+            const bool uw_is_zero = uw_all_zero_bits(cur.uw[0], cur.uw[1], cur.uw[2], cur.uw[3]);
+            skip_cur = (uw_is_zero && cur_uw_was_zero) ? kUwSkipAll : kUwStoreAll;
+            skip_enh = (uw_is_zero && enh_uw_was_zero) ? kUwSkipUpper : kUwStoreAll;
+        }
         if constexpr (kPark) {   // prev_mp_enhanced := cur_mp, as far as the next frame's synthesis reads it
             enh_keep = Parms{};
             enh_keep.w0 = cur.w0;
@@ -2565,7 +2597,7 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
                 res1[slot] = 1u;   // prev_mp_enhanced := cur_mp, elided
             }
         } else {
-            if (!MBX_ABL(tabs, 512)) store_parms<kOne>(cur, slot_enh, lane);    // prev_mp_enhanced := cur_mp
+            if (!MBX_ABL(tabs, 512)) store_parms<kOne, kOne, kOne>(cur, slot_enh, lane, skip_enh);    // prev_mp_enhanced := cur_mp
         }
         if (t + 1 < Tn) {
             slot_fence<kPark>();             // the next frame of this wave reloads both slots
@@ -2583,7 +2615,7 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         }
     }
 
-    if (!MBX_ABL(tabs_in, 1024)) store_parms<kOne>(cur, slot_cur, lane_in);
+    if (!MBX_ABL(tabs_in, 1024)) store_parms<kOne, kOne, kOne>(cur, slot_cur, lane_in, skip_cur);
     store_rng(rng, &rngs[slot], lane_in);
     if constexpr (kPark) {   // prev_mp goes home from LDS; prev_mp_enhanced IS cur_mp after the last frame
         if (res) {

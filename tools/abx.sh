@@ -1,6 +1,6 @@
 #!/bin/bash
 # abx.sh <rounds> <workload,...> <variant names...> -- GPU box: interleaved A/B of variant libraries (mbelib-neo_amd/variants/
-# libmbx_hip_<name>.so; "product" = the library in the tree) on one box, `rounds` alternations, median kernel time per variant.
+# libmbx_hip_<name>.so; "product" = the library in the tree) on one box, `rounds` alternations, median kernel time and median step time per variant.
 # Boxes differ by +-4 %: only numbers from one call compare.  (Development aid.)
 cd "$(dirname "$0")/.."
 R=$1; WL=$2; shift 2
@@ -20,6 +20,7 @@ for r in range(rounds):
             try:
                 d = json.loads(out.stdout.strip().splitlines()[-1])
                 res.setdefault((w, n), []).append(d["roofline"]["kernel_ms"])
+                res.setdefault((w, n, "step"), []).append(d["ms_per_step"])
             except Exception as e:
                 print(w, n, "FAILED", out.stderr[-400:])
                 sys.exit(1)
@@ -28,4 +29,7 @@ for w in wls:
     for n in names:
         v = res[(w, n)]
         print(f"{w:12s} {n:10s} median {statistics.median(v):.4f} ms  min {min(v):.4f}  ({statistics.median(v) / base - 1:+.2%} vs {names[0]})  {[round(x, 4) for x in v]}")
+        st = res[(w, n, "step")]
+        print(f"{w:12s} {n:10s} step   {statistics.median(st):.4f} ms  min {min(st):.4f}  max {max(st):.4f}  "
+              f"({statistics.median(st) / statistics.median(res[(w, names[0], 'step')]) - 1:+.2%} vs {names[0]})  {[round(x, 4) for x in st]}")
 PY

@@ -13,13 +13,15 @@ WL=${2:-imbe_voiced}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
+# every step that uses the GPU runs under a time limit of its own, and nothing more is started once one of them fails, faults or hangs
+step() { local limit=$1; shift; timeout -k 10 "$limit" "$@" || { echo "profile_round: '$1 ...' ended with status $? -- stopping" >&2; exit 1; }; }
 ROUND=${TAG%%_*}
-python3 $R/bench.py --warmup 3 --no-cpu-baseline --no-extras --workload $WL > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err   # kernel name for the summary
+step 180 python3 $R/bench.py --warmup 3 --no-cpu-baseline --no-extras --workload $WL > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err   # kernel name for the summary
 rm -rf /tmp/p_stats /tmp/p_fetch /tmp/p_write /tmp/c_fetch /tmp/c_write
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/p_fetch -- python3 $R/bench.py --steps 5 --warmup 1 --min-time-ms 0 --no-cpu-baseline --no-extras --workload $WL > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/p_write -- python3 $R/bench.py --steps 5 --warmup 1 --min-time-ms 0 --no-cpu-baseline --no-extras --workload $WL > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/c_fetch -- python3 $R/tools/calibrate_fetch.py > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/c_write -- python3 $R/tools/calibrate_fetch.py > /dev/null 2>&1
+step 180 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/p_fetch -- python3 $R/bench.py --steps 5 --warmup 1 --min-time-ms 0 --no-cpu-baseline --no-extras --workload $WL > /dev/null 2>&1
+step 180 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/p_write -- python3 $R/bench.py --steps 5 --warmup 1 --min-time-ms 0 --no-cpu-baseline --no-extras --workload $WL > /dev/null 2>&1
+step 120 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d /tmp/c_fetch -- python3 $R/tools/calibrate_fetch.py > /dev/null 2>&1
+step 120 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d /tmp/c_write -- python3 $R/tools/calibrate_fetch.py > /dev/null 2>&1
 python3 - "$OUT/${TAG}_pmc.json" "$OUT/${TAG}_bench.json" "$WL" <<'PY'
 import csv, glob, collections, hashlib, json, os, sys
 
@@ -71,15 +73,15 @@ if fk:
 json.dump(out, open(sys.argv[1], "w"), indent=1)
 print(json.dumps(out.get("dominant_kernel")), json.dumps(out["calibration"]))
 PY
-python3 $R/tools/sq_profile.py bench $WL $OUT/${TAG}_sq.json > $OUT/${TAG}_sq.log 2>&1
+step 600 python3 $R/tools/sq_profile.py bench $WL $OUT/${TAG}_sq.json > $OUT/${TAG}_sq.log 2>&1
 mkdir -p $R/profiles/$ROUND
 cp $OUT/${TAG}_pmc.json $R/profiles/$ROUND/${WL}_pmc.json
 cp $OUT/${TAG}_sq.json $R/profiles/$ROUND/${WL}_sq.json
 # the --stats pass directly in front of the un-profiled line: the two are compared (profiles/README.md), and a box that has been under load for
 # minutes runs the same kernel up to 9 % slower than a fresh one
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -- python3 $R/bench.py --warmup 5 --no-cpu-baseline --no-extras --workload $WL > /dev/null 2>&1
+step 180 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -- python3 $R/bench.py --warmup 5 --no-cpu-baseline --no-extras --workload $WL > /dev/null 2>&1
 cp /tmp/p_stats/*/*_kernel_stats.csv $OUT/${TAG}_kernel_stats.csv
-python3 $R/bench.py --warmup 5 --workload $WL > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+step 300 python3 $R/bench.py --warmup 5 --workload $WL > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 cp $R/bench_detail.json $OUT/${TAG}_bench_detail.json   # the full measurement behind the compact line
 cut -c1-60,150-230 $OUT/${TAG}_kernel_stats.csv
 python3 -c "
