@@ -150,16 +150,50 @@ def compare_traces(first, second, what):
                                f"{bad.size} byte(s), first at offset {int(bad[0])}, last at offset {int(bad[-1])} of {a.size}")
 
 
-def run_case(case, mem=None, oracle=True):
+class EdgeMixWorkload:
+    """the workload of every case of CASES: the edge mix of the case's codec (tests/edge_mix.py), decoded by the oracle for the case.
+    Another workload (tests/pitch_lattice.py) brings the same five things: the frames [S, T x launches, bytes], the oracle's decode of
+    them from the initial state under the case's seeds, the assertion of what the decode must hold, a context manager that may
+    say more about the streams a failed comparison names, and a report of figures that asserts nothing."""
+
+    def frames(self, case):
+        import edge_mix
+
+        return edge_mix.frames(case.codec, case.S, case.T * case.launches, tag=sum(case.id.encode()) & 0xFFF)
+
+    def reference(self, case, frames, seeds):
+        import oracle_lib
+
+        o = oracle_lib.load()
+        Tt = case.T * case.launches
+        return o.process_batch(case.codec, case.S, Tt, frames.reshape(case.S * Tt, -1), o.init_state(case.S), o.rng_seeded(seeds))
+
+    def assert_classes(self, codec, ref):
+        import edge_mix
+
+        edge_mix.assert_classes(codec, ref)
+
+    state_block = None   # streams per block of parity.check_state_blocks; None: parity.check_state over all streams at once
+
+    def naming(self, case):
+        import contextlib
+
+        return contextlib.nullcontext()
+
+    def report(self, case, ref, got):
+        """figures a workload wants of the run (got: records, results, pcm16, pcmf as [S, T x launches, ...]), taken before anything is asserted"""
+
+
+def run_case(case, mem=None, oracle=True, workload=None):
     """Runs the case on the current device and compares with the oracle; raises AssertionError on the first mismatch.  The process's
     environment must already hold case.env (the library reads its switches once).
+    workload: the frames of the case and what the oracle's decode of them must hold (EdgeMixWorkload by default); the launches, the
+    buffers, the name assertions and every comparison are the same for any workload.
     mem: where the buffers of the case live (PlainBuffers by default; GuardedBuffers: every buffer the launches are handed -- frames,
     records, state pool, RNG pool, elision words, index, PCM, results, caller workspace -- in one guarded arena, checked after every
     launch).  oracle=False: the launches and the checks of `mem` only (the second of two runs, compared with the first by trace)."""
     import torch
 
-    import edge_mix
-    import oracle_lib
     import parity
     from mbelib_neo_amd import _native, decoder
     from mbelib_neo_amd.layout import FRAME_BYTES, RECORD_DTYPE, RESULT_DTYPE
@@ -168,7 +202,9 @@ def run_case(case, mem=None, oracle=True):
         assert os.environ.get(k) == v, f"{case.id}: needs {k}={v} in the environment of a fresh process"
     codec, S, T, n_launch = case.codec, case.S, case.T, case.launches
     fb, Tt = FRAME_BYTES[codec], case.T * case.launches
-    frames = edge_mix.frames(codec, S, Tt, tag=sum(case.id.encode()) & 0xFFF)
+    workload = workload if workload is not None else EdgeMixWorkload()
+    frames = workload.frames(case)
+    assert frames.shape == (S, Tt, fb) and frames.dtype == np.uint8, (case.id, frames.shape)
     seeds = np.arange(S) * 3 + 11
     indexed = case.entry.endswith("_indexed")
     resident = case.entry.startswith("resident")
@@ -251,16 +287,20 @@ def run_case(case, mem=None, oracle=True):
     if not oracle:
         return None
 
-    o = oracle_lib.load()
-    ref = o.process_batch(codec, S, Tt, frames.reshape(S * Tt, fb), o.init_state(S), o.rng_seeded(seeds))
-    edge_mix.assert_classes(codec, ref)
+    ref = workload.reference(case, frames, seeds)
+    workload.assert_classes(codec, ref)
     what = case.id
-    parity.check_exact(ref["records"], np.ascontiguousarray(got["records"]).view(RECORD_DTYPE).reshape(-1), what + ": records", Tt)
-    with parity.located(Tt):
-        parity.check_results(ref["results"], np.ascontiguousarray(got["results"]).view(RESULT_DTYPE).reshape(-1), what + ": results")
-        m = parity.check_pcm(ref["pcmf"], got["pcmf"].reshape(-1, 160), ref["pcm16"], got["pcm16"].reshape(-1, 160), what=what + ": pcm", peak=ref["peak"])
-    parity.check_state(ref["state"], state[slots], what=what + ": state (rows are streams)")
-    parity.check_exact(ref["rng"], rng[slots], what + ": rng")
+    with workload.naming(case):
+        workload.report(case, ref, got)
+        parity.check_exact(ref["records"], np.ascontiguousarray(got["records"]).view(RECORD_DTYPE).reshape(-1), what + ": records", Tt)
+        with parity.located(Tt):
+            parity.check_results(ref["results"], np.ascontiguousarray(got["results"]).view(RESULT_DTYPE).reshape(-1), what + ": results")
+            m = parity.check_pcm(ref["pcmf"], got["pcmf"].reshape(-1, 160), ref["pcm16"], got["pcm16"].reshape(-1, 160), what=what + ": pcm", peak=ref["peak"])
+        if workload.state_block:   # (the same fields under the same bound, block by block)
+            parity.check_state_blocks(ref["state"], state[slots], block=workload.state_block, what=what + ": state (rows are streams)")
+        else:
+            parity.check_state(ref["state"], state[slots], what=what + ": state (rows are streams)")
+        parity.check_exact(ref["rng"], rng[slots], what + ": rng")
     if indexed:   # the slots of the pool the index does not name are as they were
         rest = np.setdiff1d(np.arange(pool), slots)
         assert state[rest].tobytes() == untouched_state[rest].tobytes() and rng[rest].tobytes() == untouched_rng[rest].tobytes(), what + ": a slot outside the index changed"

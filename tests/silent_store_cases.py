@@ -7,15 +7,15 @@ frame with the most errors the codes still correct (three data cells in every Go
 7200x4400, 14 of 7100x4400: a REPEAT with errors), 'E' the same with ONE error in C0 (13 / 12: decoded, c0 < 2 never repeats).
 A run of four X reaches the mute through the repeat counter.  A mute directly behind a decoded frame can only come from the error
 rate, and only on a frame that is not repeated (a repeat takes prev_mp's error rate): an E on an error rate planted just below
-the muting threshold (PLANTED_ERROR_RATE in the INITIAL state, the same for every launch form compared) crosses it.  IMBE 7100x4400 has no encoder in framegen: `encode_imbe7100x4400` here is the
-inverse of the oracle's front end, checked against it frame by frame (`check_encoder`).
+the muting threshold (PLANTED_ERROR_RATE in the INITIAL state, the same for every launch form compared) crosses it.  IMBE 7100x4400 has no encoder in framegen: `encode_imbe7100x4400`
+(tests/imbe7100_frames.py) is the inverse of the oracle's front end, checked against it frame by frame here (`check_encoder`).
 Test infrastructure: imported without a GPU; nothing in the package uses it."""
-import math
-
 import numpy as np
 
 from mbelib_neo_amd import framegen
 from mbelib_neo_amd.layout import FRAME_BYTES, PARMS_DTYPE, ROW_WIDTHS, init_state
+
+from imbe7100_frames import encode_imbe7100x4400
 
 FLAG_REPEAT, FLAG_MUTE = 0x40, 0x80
 S = 67          # nine chunks of eight streams, the last one short
@@ -49,69 +49,6 @@ def param_bits(kind, n, rng):
     elif kind == "X":
         _set_b0(bits, rng.integers(208, 256, size=n, dtype=np.int64))
     return bits
-
-
-def _k_of_b0(b0):   # K(b0) as the 7100 -> 7200 conversion computes it (float fundamental, double quotient)
-    w0 = float(np.float32(np.float32(4.0 * math.pi) / np.float32(b0 + 39.5)))
-    L = int(0.9254 * int((math.pi / w0) + 0.25))
-    return int(np.float32(L + 2) / np.float32(3)) if L < 37 else 12
-
-
-def _source_index_7100(K):
-    """src[j]: the 7100-order position of 7200-order bit j (the conversion is d7200[j] = d7100[src[j]])"""
-    src = np.zeros(88, dtype=np.int64)
-    src[87] = 0
-    src[48 + K] = 42
-    src[49 + K] = 43
-    for i in range(K):
-        src[48 + i] = 44 + i
-    j, k = 0, 1
-    while j < 87:
-        src[j] = k
-        j += 1
-        if j == 48:
-            j += K + 2
-        k += 1
-        if k == 42:
-            k += K + 2
-    return src
-
-
-_hamming7100_words = None
-
-
-def _hamming7100_encode(data11, oracle):
-    """the 15-bit word of the 7100x4400 Hamming code that carries data11 in bits 14..4 without an error (table from the oracle)"""
-    global _hamming7100_words
-    if _hamming7100_words is None:
-        table = np.zeros(2048, dtype=np.uint32)
-        for cw in range(1 << 15):
-            fixed, errs = oracle.hamming7100(cw)
-            if errs == 0:
-                table[(fixed >> 4) & 0x7FF] = fixed
-        _hamming7100_words = table
-    return _hamming7100_words[np.asarray(data11, dtype=np.int64)]
-
-
-def encode_imbe7100x4400(bits7200, oracle):
-    """[n, 88] parameter bits in the 7200x4400 order -> clean IMBE 7100x4400 wire frames [n, 18]"""
-    b = np.asarray(bits7200, dtype=np.uint8)
-    n = b.shape[0]
-    d = np.zeros_like(b)
-    for i in range(n):
-        b0 = int(framegen._bits_to_int(b[i:i + 1, :6], 0, 6)[0]) << 2 | int(b[i, 85]) << 1 | int(b[i, 86])
-        d[i, _source_index_7100(_k_of_b0(b0))] = b[i]
-    toi = framegen._bits_to_int
-    u0 = toi(d, 0, 7)
-    masks = framegen.pr_masks(u0, (24, 23, 23, 15, 15))
-    rows = [(framegen.golay2312_encode(u0) & 0x3FFFF) << 1,
-            (framegen.golay2312_encode(toi(d, 7, 19)) << 1) ^ masks[0],
-            framegen.golay2312_encode(toi(d, 19, 31)) ^ masks[1],
-            framegen.golay2312_encode(toi(d, 31, 43)) ^ masks[2],
-            _hamming7100_encode(toi(d, 43, 54), oracle) ^ masks[3],
-            _hamming7100_encode(toi(d, 54, 65), oracle) ^ masks[4],
-            toi(d, 65, 88)]
-    return framegen._pack_rows(rows, ROW_WIDTHS[2])
 
 
 def _damage(codec, frames, rng, c0=3):
