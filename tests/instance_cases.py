@@ -183,12 +183,33 @@ class EdgeMixWorkload:
     def report(self, case, ref, got):
         """figures a workload wants of the run (got: records, results, pcm16, pcmf as [S, T x launches, ...]), taken before anything is asserted"""
 
+    # optional: checkpoint(case, launch, state) -- called behind every launch with the state [S, 3] of the case's slots as that launch
+    # left it (slot_state); the workloads here do not define it (tests/error_lattice.py does)
+
+
+def slot_state(dec, slots):
+    """the state [S, 3] of the given slots as the last launch left it, taken from a COPY of the pool: for a resident decoder the copy is
+    materialised (mbx_resident_materialize on the copied structs and elision words), the decoder's own buffers stay as the launch left
+    them, elided structs and all"""
+    import torch
+
+    from mbelib_neo_amd import _native
+    from mbelib_neo_amd.layout import PARMS_DTYPE
+
+    state = dec.state.clone()
+    if dec.resident is not None:
+        words = dec.resident.clone()
+        _native.check(_native.lib().mbx_resident_materialize(dec.streams, None, state.data_ptr(), words.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                      "mbx_resident_materialize")
+    return state.cpu().numpy().view(PARMS_DTYPE).reshape(dec.streams, 3)[slots]
+
 
 def run_case(case, mem=None, oracle=True, workload=None):
     """Runs the case on the current device and compares with the oracle; raises AssertionError on the first mismatch.  The process's
     environment must already hold case.env (the library reads its switches once).
     workload: the frames of the case and what the oracle's decode of them must hold (EdgeMixWorkload by default); the launches, the
-    buffers, the name assertions and every comparison are the same for any workload.
+    buffers, the name assertions and every comparison are the same for any workload.  A workload with a `checkpoint` method is also
+    called behind every launch, with the launch index and the state of the case's slots (slot_state).
     mem: where the buffers of the case live (PlainBuffers by default; GuardedBuffers: every buffer the launches are handed -- frames,
     records, state pool, RNG pool, elision words, index, PCM, results, caller workspace -- in one guarded arena, checked after every
     launch).  oracle=False: the launches and the checks of `mem` only (the second of two runs, compared with the first by trace)."""
@@ -274,6 +295,8 @@ def run_case(case, mem=None, oracle=True, workload=None):
         for x in got:
             got[x].append(out[x].cpu().numpy().reshape(S, T, -1))
             mem.note(f"launch {k}: {x}", got[x][-1])
+        if oracle and hasattr(workload, "checkpoint"):
+            workload.checkpoint(case, k, slot_state(dec, slots))
     if mem.trace is not None:   # the state as the launches left it, elision words and all, before anything materialises it
         mem.note("state as left", dec.state.cpu().numpy())
         if resident:

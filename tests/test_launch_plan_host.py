@@ -49,7 +49,7 @@ def test_the_plan_gives_the_parents_decisions_and_holds_its_properties_under_asa
 
 
 def test_the_plan_names_every_instance_case_and_the_prediction_agrees(check_exe):
-    """every case of tests/instance_cases.py, and every form of the pitch-pair lattices (tests/pitch_lattice.py), planned for a whole MI355X (1,024 SIMDs) under the case's switches: the plan's index,
+    """every case of tests/instance_cases.py, and every form of the pitch-pair and the bit-error history lattices (tests/pitch_lattice.py, tests/error_lattice.py), planned for a whole MI355X (1,024 SIMDs) under the case's switches: the plan's index,
     through the order of the kInstances rows, is the case's instance -- and for the entries the prediction is made for, the plan behind
     mbx_batch_kernel_name names the same one (what tests/instance_cases.py then asserts on the card after every launch)"""
     api = open(os.path.join(ROOT, "mbelib-neo_amd", "csrc", "mbx_api.hip")).read()
@@ -58,7 +58,10 @@ def test_the_plan_names_every_instance_case_and_the_prediction_agrees(check_exe)
     assert len(names) == 28
     import pitch_lattice
 
-    for c in instance_cases.CASES + [case for case, _ in pitch_lattice.cases()]:   # (the lattices: the same entries at 17,344 ... 65,536 streams)
+    import error_lattice
+
+    lattices = [case for case, _ in pitch_lattice.cases() + error_lattice.cases()]   # (the same entries at 17,344 ... 65,536 streams, and at 274 ... 690)
+    for c in instance_cases.CASES + lattices:
         run = subprocess.run([check_exe, "case", str(c.codec), str(c.S), str(c.T), c.entry], capture_output=True, text=True, timeout=60, env=clean_env(c.env))
         assert run.returncode == 0, (c.id, (run.stdout + run.stderr)[-4000:])
         real, predicted = (names[int(x)] for x in run.stdout.split())
