@@ -414,7 +414,9 @@ int mbx_process_batch_ws(int codec, int S, int T, const uint8_t* d_frames, mbe_p
 
 /* ref: mbe_decodeImbe4400Parms / mbe_decodeAmbe2450Parms / mbe_decodeAmbe2400Parms  include/mbelib-neo/mbelib.h:461, 385, 301
  * (src/imbe/imbe7200x4400.c:589-630, src/ambe/ambe3600x2450.c:555-634, src/ambe/ambe3600x2400.c:427-561): the parameter
- * decode alone -- no frame policy, no synthesis -- for n (cur_mp, prev_mp) pairs.  d_rc[i] = the reference's return value. */
+ * decode alone -- no frame policy, no synthesis -- for n (cur_mp, prev_mp) pairs.  d_rc[i] = the reference's return value.
+ * cur_mp is what the reference's decode leaves, the silence model of an AMBE 3600x2400 tone-class frame whose id is no tone included
+ * (the frame policy of the batch calls overwrites that model; this call has no policy). */
 int mbx_decode_parms(int codec, const mbx_param_record* d_records, size_t n, mbe_parms* d_cur, mbe_parms* d_prev, int32_t* d_rc,
                      void* stream);
 
@@ -459,7 +461,17 @@ int mbx_stream_expanded_resident(int codec, int S, int T, const mbx_param_record
 int mbx_resident_materialize(int n, const int32_t* d_stream_index, mbe_parms* d_state_pool, uint32_t* d_resident, void* stream);
 
 /* ref: mbe_synthesizeSpeechf  include/mbelib-neo/mbelib.h:652, src/core/mbelib.c:1112-1115.
- * One frame for each of S (cur, prev) pairs; both structs are updated like the reference does. */
+ * One frame for each of S (cur, prev) pairs; both structs are updated like the reference does.
+ * DOMAIN -- the models a caller may write and get the reference's frame within the project's bounds (integers, decisions, the
+ * noise state, the RNG struct and the wrapped prev.PSIl exact; floats to 1e-4 relative RMS): any L and prev.L -- outside 1..56 on
+ * either side the frame is silence and no byte of cur, prev or the RNG state changes, as in the reference; w0 and prev.w0 anywhere
+ * between the smallest and the largest fundamental of the codec tables (0.0510 .. 0.3181), on or off their grids, whatever L is;
+ * PHIl and PSIl finite (tested: +-4000, and prev.PSIl negative and up to 1e9); Ml finite, of either sign, with a voiced sum
+ * 2 sum Ml inside the output range (beyond it the int16 bound is relative to the pre-clip peak, which only the batch path
+ * reports); Vl 1 (voiced), 0 (unvoiced) or another value (neither, the reference's reading; tested: 2); noiseSeed negative (a cold
+ * start) or in [0, 2^31), integral or not; noiseOverlap, previousUw, localEnergy finite; repeatCount, the error counts,
+ * errorRate, mutingThreshold and amplitudeThreshold finite.  Non-finite floats and fundamentals outside the tables' span are
+ * outside it.  tests/model_lattice.py holds the call to exactly this domain. */
 int mbx_synthesize_speech(int S, mbe_parms* d_cur, mbe_parms* d_prev, mbx_stream_rng* d_rng, float* d_pcmf,
                           int16_t* d_pcm16, void* stream);
 
@@ -483,9 +495,17 @@ int mbx_result_histogram(const mbe_process_result* d_results, size_t n, mbx_resu
 
 /* ---- single stages of the public API, batched (one wavefront per struct) ------------------- */
 
-/* ref: mbe_spectralAmpEnhance  include/mbelib-neo/mbelib.h:623, src/core/mbelib.c:641-666 */
+/* ref: mbe_spectralAmpEnhance  include/mbelib-neo/mbelib.h:623, src/core/mbelib.c:641-666
+ * DOMAIN: L 1..56 (any other L: the struct is left as it is); w0 >= 0 and finite -- not only the fundamentals of the codec tables:
+ * tested from 0.005 to 3, and w0 = 0, where the reference divides zero by zero and every amplitude becomes NaN, gives the same
+ * NaNs; Ml finite, of either sign (a negative amplitude above the L / 8 lowest harmonics makes the model NaN in the reference, and
+ * here, in the same places); an all-zero model is left alone.  Every other field is ignored and kept. */
 int mbx_spectral_amp_enhance(int S, mbe_parms* d_parms, void* stream);
-/* ref: mbe_applyAdaptiveSmoothing  include/mbelib-neo/mbelib.h:725, src/core/mbe_adaptive.c:268-276 */
+/* ref: mbe_applyAdaptiveSmoothing  include/mbelib-neo/mbelib.h:725, src/core/mbe_adaptive.c:268-276
+ * DOMAIN: L and prev.L 1..56 (otherwise nothing is written); Ml finite, of either sign; errorRate, errorCountTotal, errorCount4,
+ * prev.localEnergy and prev.amplitudeThreshold any finite value (a negative amplitude threshold Tm scales the amplitudes negative, as
+ * the reference does).  Vl, amplitudeThreshold and every decision are the reference's exactly, an amplitude AT the voicing threshold
+ * included; localEnergy and the scaled Ml to 1e-4 relative RMS.  w0 inside the span named at mbx_synthesize_speech. */
 int mbx_adaptive_smoothing(int S, mbe_parms* d_cur, const mbe_parms* d_prev, void* stream);
 /* ref: mbe_synthesizeComfortNoisef / mbe_synthesizeComfortNoise  include/mbelib-neo/mbelib.h:706-712 */
 int mbx_comfort_noise(int S, mbx_stream_rng* d_rng, float* d_pcmf, int16_t* d_pcm16, void* stream);

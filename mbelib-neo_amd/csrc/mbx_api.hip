@@ -1733,7 +1733,7 @@ int mbx_decode_parms(int codec, const mbx_param_record* d_records, size_t n, mbe
     if (rc < 0) {
         return rc;
     }
-    hipLaunchKernelGGL(mbx::decode_parms_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, codec, (int)n, slot.workspace,
+    hipLaunchKernelGGL(mbx::decode_parms_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, codec, (int)n, d_records, slot.workspace,
                        d_cur, d_prev, d_rc, c->tabs);
     return check_launch("decode_parms_kernel");
 }

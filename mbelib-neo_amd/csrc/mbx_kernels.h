@@ -93,7 +93,7 @@ __global__ void tone_kernel(int, const mbx_param_record*, const int32_t*, mbe_pa
 __global__ void enhance_kernel(int, mbe_parms*);
 __global__ void smoothing_kernel(int, mbe_parms*, const mbe_parms*);
 __global__ void comfort_noise_kernel(int, mbx_stream_rng*, float*, int16_t*);
-__global__ void decode_parms_kernel(int, int, const FrameParams*, mbe_parms*, mbe_parms*, int32_t*, DeviceTables);
+__global__ void decode_parms_kernel(int, int, const mbx_param_record*, const FrameParams*, mbe_parms*, mbe_parms*, int32_t*, DeviceTables);
 __global__ void state_copy_kernel(int, mbe_parms*);
 
 // ---- mbx_fec.hip ---------------------------------------------------------------------------------------------------------------

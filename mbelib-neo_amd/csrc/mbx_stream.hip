@@ -3829,7 +3829,15 @@ enhance_kernel(int S, mbe_parms* __restrict__ parms) {
     __shared__ alignas(16) float tmp[64];
     Parms cur;
     load_parms(cur, &parms[s], lane);
-    (void)enhance(cur, lane, tmp);
+    if (cur.w0 == 0.0f && cur.L >= 1 && cur.L <= 56) {
+        // A caller-made model with w0 = 0 (no codec table holds it): the reference divides zero by zero -- Rm1 equals Rm0 to the bit,
+        // numerator and divisor are both 0 -- and every amplitude of a model with a non-zero one becomes NaN.  enhance() forms Rm1 in
+        // another order than Rm0 and would give infinities in their place: such a struct goes through the reference's own sequence.
+        float rm0;
+        cur.Ml = enhance_exact(cur.Ml, cur.w0, cur.L, tmp, lane, rm0);
+    } else {
+        (void)enhance(cur, lane, tmp);
+    }
     store_parms(cur, &parms[s], lane);
 }
 
@@ -3874,8 +3882,8 @@ comfort_noise_kernel(int S, mbx_stream_rng* __restrict__ rngs, float* __restrict
 // fundamental, 2 erasure, 7 / tone index for tone frames).
 //   ref src/imbe/imbe7200x4400.c:589-630, src/ambe/ambe3600x2450.c:555-634, src/ambe/ambe3600x2400.c:427-561
 __global__ void __launch_bounds__(64)
-decode_parms_kernel(int codec, int n, const FrameParams* __restrict__ params, mbe_parms* __restrict__ curs,
-                    mbe_parms* __restrict__ prevs, int32_t* __restrict__ rc, DeviceTables tabs) {
+decode_parms_kernel(int codec, int n, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
+                    mbe_parms* __restrict__ curs, mbe_parms* __restrict__ prevs, int32_t* __restrict__ rc, DeviceTables tabs) {
     __shared__ float fp[64];
     __shared__ alignas(16) float tmp[64];
     const int i = blockIdx.x;
@@ -3889,6 +3897,23 @@ decode_parms_kernel(int codec, int n, const FrameParams* __restrict__ params, mb
     fp[lane] = params[i].v[lane];
     wave_lds_sync();
     const int bad = (codec == MBX_CODEC_IMBE7200X4400) ? decode_imbe(fp, cur, prev, tabs.d, lane, tmp) : decode_ambe(fp, cur, prev, tabs, lane, tmp);
+    if (codec == MBX_CODEC_AMBE3600X2400 && bad == 3) {
+        // A tone-class frame whose id is neither a tone (5..122, returned as the id) nor a dual tone (128..163): the reference's decode
+        // leaves the silence model in cur_mp (ref src/ambe/ambe3600x2400.c:202-210).  The frame policy of the stream stage overwrites
+        // it, so the expansion carries the class alone; this entry point is the decode without the policy and sets it here.
+        const uint4 rec = *reinterpret_cast<const uint4*>(&records[i]);
+        const uint32_t w[3] = {rec.x, rec.y, rec.z};
+        const uint32_t t7 = 0xE1u, t6 = 0x78u, t5 = 0xB4u;   // (the three 8-entry tables of mbx_expand_ambe.h)
+        const int def = pick_bits(w, 6, 7, 8);
+        const int tone = (int)(((t7 >> def) & 1u) << 7 | ((t6 >> def) & 1u) << 6 | ((t5 >> def) & 1u) << 5) | pick_bits(w, 9, 42, 43, 10, 11);
+        if (!(tone >= 128 && tone <= 163)) {
+            cur.w0 = (float)(((float)2 * M_PI) / (float)32);
+            cur.L = 14;
+            if (lane >= 1 && lane <= 14) {
+                cur.Vl = 0;
+            }
+        }
+    }
     store_parms(cur, &curs[i], lane);
     store_parms(prev, &prevs[i], lane);
     if (lane == 0) {
