@@ -318,6 +318,7 @@ int mbx_ecc_soft_words(int kind, const mbe_soft_bit* d_in, size_t n, uint32_t* d
 int mbx_validate_soft_bits(const mbe_soft_bit* soft, size_t count); /* 0, -1 (NULL), -2 (a hard decision > 1) */
 int mbx_soft_bits_from_hard(const char* bits, mbe_soft_bit* soft, size_t count, uint8_t reliability);
 int mbx_soft_bits_from_llr(const int16_t* llr, mbe_soft_bit* soft, size_t count);
+/* (on the device: mbx_soft_from_llr, mbx_llr.h; bursts of LLRs are converted inside their gather: mbx_burst_schedule_create_llr) */
 
 /* ---- stream stage: parameter records + per-stream state -> PCM (one wavefront per stream) */
 

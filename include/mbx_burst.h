@@ -20,10 +20,16 @@
  *            PACKED  received bit j at byte j >> 3, mask 0x80 >> (j & 7) (MSB first, as everywhere in this library)
  *            BITS    received bit j is bit 0 of byte j
  *            DIBITS  received bits 2d and 2d + 1 are bits 1 and 0 of byte d (the first bit of a symbol is the upper one)
- *   soft   mbx_burst_schedule_soft_cells() mbe_soft_bit-sized cells per burst in received order, dense: burst b at
- *          d_soft + b * soft_cells cells
+ *   soft   mbx_burst_schedule_soft_bytes() bytes per burst in received order, dense: burst b at byte b * soft_bytes of d_soft
  *            PACKED, BITS  one mbe_soft_bit per received bit
  *            DIBITS        one {dibit, reliability} pair per dibit: field `bit` carries the dibit, both bits take the reliability
+ *            LLR16         one signed 16-bit log-likelihood ratio per received bit, what a soft demodulator emits
+ *            LLR8          one signed 8-bit LLR per received bit: a reliability of its own for every bit in ONE byte per bit
+ *          An LLR v becomes the cell {bit = v > 0, reliability = min(|v|, 255)} inside the gather (|v| taken in int: -32768 gives
+ *          255, 0 gives {0, 0}; an int8 LLR is the int16 LLR of the same value) -- the conversion of mbx_soft_bits_from_llr (mbx.h),
+ *          ref mbe_softBitFromLlr src/core/mbelib.c:125-158 -- then an inverted bit has its hard decision flipped like any other.
+ *          LLR schedules (mbx_burst_schedule_create_llr) are soft-only: the soft calls take their bursts through the d_soft / soft
+ *          pointer, as a cast; the hard calls refuse them.  (LLRs that are not bursts: mbx_soft_from_llr, mbx_llr.h.)
  * The device never validates: of a BITS byte `& 1` is used, of a DIBITS byte or dibit cell `& 3`, and a soft hard decision goes
  * on as it came (as for soft frames, mbx.h).  Input on the device is the caller's to check; mbx_burst_validate is the host check,
  * and the session submits call it.
@@ -32,10 +38,12 @@
  *   kind        bytes  which pointers
  *   bursts      1      d_bursts: with d_bursts and burst_stride both multiples of 4 the bursts are fetched in dwords, otherwise byte by byte
  *   softbursts  2      d_soft of the burst calls: one (bit | dibit, reliability) pair is one 16-bit piece; fetched in dwords from the first 4-aligned pair on
+ *   llr16       2      d_soft of the burst calls with an LLR16 schedule: one LLR is one 16-bit piece; fetched like softbursts
+ *   llr8        1      d_soft of the burst calls with an LLR8 schedule: fetched in dwords from the first 4-aligned byte on, single bytes at the edges
  *   frames      1      d_frames of mbx_deinterleave, for every codec: dwords where they are whole and aligned, single bytes at the edges
  *   soft        2      d_cells of mbx_deinterleave_soft
  * Sizes are exact: nothing is read behind the last burst's burst_stride bytes (mbx_burst_schedule_bytes() of them are read) or
- * outside the n * soft_cells cells of soft bursts, nothing is written outside the rows each call names.  A launcher that is handed
+ * outside the n * soft_bytes bytes of soft bursts, nothing is written outside the rows each call names.  A launcher that is handed
  * a pointer below its alignment returns MBE_STATUS_INVALID_ARGUMENT before anything is launched, the call named in mbx_last_error().
  */
 #ifndef MBX_BURST_H
@@ -93,20 +101,37 @@ int mbx_burst_schedule_create(mbx_burst_schedule** out, int codec, int frames_pe
  * dibit form with an odd burst_bits, an invert byte above 1. */
 int mbx_burst_schedule_create_form(mbx_burst_schedule** out, int codec, int frames_per_burst, int burst_bits, const int* src_bit,
                                    const int* cell_row, const int* cell_col, int form, const uint8_t* invert);
+/* Soft bursts as LLRs, one per received bit (the format table at the top). */
+#define MBX_BURST_FORM_LLR16 16 /* int16_t per received bit */
+#define MBX_BURST_FORM_LLR8  8  /* int8_t per received bit */
+/* mbx_burst_schedule_create_form for a schedule whose soft bursts are LLRs of llr_bytes bytes each (2: int16, MBX_BURST_FORM_LLR16;
+ * 1: int8, MBX_BURST_FORM_LLR8).  The same checks in the same order with the same texts, every one before a device is asked for;
+ * in the place of the form check: llr_bytes is neither 1 nor 2.  Any burst_bits will do (nothing is shared between two bits).
+ * The schedule is SOFT-ONLY: mbx_deinterleave, mbx_process_bursts and mbx_session_submit_bursts refuse it
+ * (MBE_STATUS_INVALID_ARGUMENT, the call named in mbx_last_error(), nothing launched or staged), as does the hard form of
+ * mbx_burst_validate.  (mbx_burst_schedule_create_form goes on refusing every form but its three.) */
+int mbx_burst_schedule_create_llr(mbx_burst_schedule** out, int codec, int frames_per_burst, int burst_bits, const int* src_bit,
+                                  const int* cell_row, const int* cell_col, int llr_bytes /* 2: int16, 1: int8 */, const uint8_t* invert);
 /* frees the device tables (the caller must have no launch in flight that uses the schedule); NULL is allowed */
 int mbx_burst_schedule_destroy(mbx_burst_schedule* sched);
 int mbx_burst_schedule_codec(const mbx_burst_schedule* sched);            /* MBX_CODEC_*, or MBE_STATUS_INVALID_ARGUMENT for NULL */
 int mbx_burst_schedule_frames(const mbx_burst_schedule* sched);           /* frames_per_burst */
 int mbx_burst_schedule_bits(const mbx_burst_schedule* sched);             /* burst_bits */
 int mbx_burst_schedule_form(const mbx_burst_schedule* sched);             /* MBX_BURST_FORM_*, or MBE_STATUS_INVALID_ARGUMENT for NULL */
-/* the smallest burst_stride of this schedule's hard bursts: ceil(burst_bits / 8) (PACKED), burst_bits (BITS), burst_bits / 2 (DIBITS); 0 for NULL */
+/* the smallest burst_stride of this schedule's hard bursts: ceil(burst_bits / 8) (PACKED), burst_bits (BITS), burst_bits / 2 (DIBITS);
+ * 0 for an LLR schedule (it has no hard bursts) and for NULL */
 size_t mbx_burst_schedule_bytes(const mbx_burst_schedule* sched);
-/* mbe_soft_bit-sized cells of one soft burst: burst_bits, or burst_bits / 2 in the dibit form; 0 for NULL */
+/* mbe_soft_bit-sized cells of one soft burst: burst_bits, or burst_bits / 2 in the dibit form; 0 for NULL.  LLR16: burst_bits (an
+ * int16 is the size of a cell).  LLR8: 0 -- an int8 burst need not be a whole number of cells; size buffers with
+ * mbx_burst_schedule_soft_bytes(), in every form. */
 size_t mbx_burst_schedule_soft_cells(const mbx_burst_schedule* sched);
+/* bytes of one soft burst: 2 * soft_cells (PACKED, BITS, DIBITS), burst_bits * llr_bytes (LLR16, LLR8); 0 for NULL */
+size_t mbx_burst_schedule_soft_bytes(const mbx_burst_schedule* sched);
 /* The host check of n bursts in HOST memory (soft != 0: soft bursts, burst_stride is not looked at): 0, MBE_STATUS_INVALID_ARGUMENT
  * (NULL, a burst_stride below mbx_burst_schedule_bytes()), or MBE_STATUS_INVALID_BITS for a BITS byte above 1, a DIBITS byte or a
  * dibit cell above 3, a hard decision of a per-bit soft cell above 1.  Only the bytes and cells a gather would read are looked at:
- * not the padding of the stride.  No device is needed. */
+ * not the padding of the stride.  Every LLR is valid: soft bursts of an LLR schedule give 0 (bursts != NULL), hard validation of one
+ * MBE_STATUS_INVALID_ARGUMENT.  No device is needed. */
 int mbx_burst_validate(const mbx_burst_schedule* sched, const void* bursts, size_t burst_stride, size_t n, int soft);
 
 /* ---- the gather alone ------------------------------------------------------------------------------------------------------ */
@@ -125,6 +150,7 @@ int mbx_deinterleave(const mbx_burst_schedule* sched, const uint8_t* d_bursts, s
  * d_cells + row * row_cells cells.  row_cells = the codec's cells (184 | 96 | 168 | 96) or MBX_MIXED_ROW_CELLS (the rows of
  * mbx_process_batch_soft_mixed).  EVERY cell of a row is written: cells that are not on the wire, and the cells of a mixed row
  * behind the codec's array, get {0, 0}. */
+/* (an LLR schedule: d_soft is the int16_t / int8_t array, cast) */
 int mbx_deinterleave_soft(const mbx_burst_schedule* sched, const mbe_soft_bit* d_soft, size_t n, mbe_soft_bit* d_cells,
                           size_t row_cells, void* stream);
 
@@ -158,7 +184,7 @@ size_t mbx_burst_workspace_frames(const mbx_burst_schedule* sched, int S, int so
  * n * frames_per_burst <= max_frames_per_submit, the schedule's codec the session's (MBE_STATUS_INVALID_ARGUMENT otherwise).  The
  * bursts take the road frames take -- pinned buffers are read in place, pageable ones staged, fetched on the compute stream --
  * then the burst launch above.  Outputs: n * frames_per_burst rows each, as for the frames submits.  Bursts of every form that
- * can be invalid are checked with mbx_burst_validate first, as soft frames are (MBE_STATUS_INVALID_BITS, nothing queued: state, RNG
+ * can be invalid (LLR bursts cannot) are checked with mbx_burst_validate first, as soft frames are (MBE_STATUS_INVALID_BITS, nothing queued: state, RNG
  * state and outputs keep their bytes).  The first burst submit of a session grows the compute stream's workspace once. */
 int mbx_session_submit_bursts(struct mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index,
                               const uint8_t* bursts, size_t burst_stride, int16_t* pcm16, float* pcmf, mbe_process_result* results);

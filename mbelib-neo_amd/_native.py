@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h).  Fails loudly when the library
+"""ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -122,6 +122,7 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _BURST_SIGNATURES = {
     "mbx_burst_schedule_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     "mbx_burst_schedule_create_form": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
+    "mbx_burst_schedule_create_llr": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_int, _vp]),
     "mbx_burst_schedule_destroy": (C.c_int, [_vp]),
     "mbx_burst_schedule_codec": (C.c_int, [_vp]),
     "mbx_burst_schedule_frames": (C.c_int, [_vp]),
@@ -129,6 +130,7 @@ _BURST_SIGNATURES = {
     "mbx_burst_schedule_form": (C.c_int, [_vp]),
     "mbx_burst_schedule_bytes": (_sz, [_vp]),
     "mbx_burst_schedule_soft_cells": (_sz, [_vp]),
+    "mbx_burst_schedule_soft_bytes": (_sz, [_vp]),
     "mbx_burst_validate": (C.c_int, [_vp, _vp, _sz, _sz, C.c_int]),
     "mbx_burst_workspace_frames": (_sz, [_vp, C.c_int, C.c_int]),
     "mbx_deinterleave": (C.c_int, [_vp, _vp, _sz, _sz, _vp, _sz, _vp]),
@@ -139,6 +141,11 @@ _BURST_SIGNATURES = {
     "mbx_session_submit_bursts_soft": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
 }
 BURST_SYMBOLS = tuple(_BURST_SIGNATURES)
+# LLR input that is not a burst (include/mbx_llr.h)
+_LLR_SIGNATURES = {
+    "mbx_soft_from_llr": (C.c_int, [_vp, C.c_int, _sz, _vp, _vp]),
+}
+LLR_SYMBOLS = tuple(_LLR_SIGNATURES)
 
 
 def lib():
@@ -161,7 +168,7 @@ def lib():
             handle = C.CDLL(path)
         except OSError as e:  # e.g. libamdhip64 not found
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
-        for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

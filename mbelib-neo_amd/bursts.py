@@ -10,6 +10,9 @@ bit; FORM_DIBITS: one byte per dibit, and for soft input one {dibit, reliability
 bits arrive inverted (``invert``: a fixed descrambling sequence, one 0 / 1 per received bit).  ``src_bit`` counts received BITS in
 every form.  ``to_form`` turns packed bursts into the form of a schedule.
 
+FORM_LLR16 / FORM_LLR8 are SOFT-ONLY forms: one signed log-likelihood ratio per received bit, int16 or int8, as a soft demodulator
+emits them; the gather converts them (``cells_from_llr`` is the conversion in numpy) and the hard calls refuse such a schedule.
+
 ``apply_schedule`` is the same thing in numpy, on the host: the definition, and what the tests expect of the kernels.  No
 air-interface table of any standard is written here; ``random_schedule`` and ``gap_schedule`` make schedules of a given SHAPE.
 """
@@ -23,6 +26,8 @@ from .layout import FRAME_BYTES, FRAME_CELLS, ROW_WIDTHS
 MAX_FRAMES, MAX_BITS = 18, 4096          # MBX_BURST_MAX_FRAMES, MBX_BURST_MAX_BITS
 MIXED_ROW_BYTES, MIXED_ROW_CELLS = 18, 184
 FORM_PACKED, FORM_BITS, FORM_DIBITS = 0, 1, 2   # MBX_BURST_FORM_*
+FORM_LLR16, FORM_LLR8 = 16, 8                   # MBX_BURST_FORM_LLR*: soft bursts of one int16 / int8 LLR per received bit
+LLR_DTYPE = {FORM_LLR16: np.int16, FORM_LLR8: np.int8}
 
 
 def channel_bits(codec):
@@ -37,6 +42,40 @@ def wire_bit_of_cell(codec, row, col):
     start = np.concatenate(([0], np.cumsum(widths)[:-1]))
     row, col = np.asarray(row), np.asarray(col)
     return start[row] + widths[row] - 1 - col
+
+
+def cells_from_llr(llr):
+    """numpy form of the conversion (mbx_soft_bits_from_llr, and what the LLR gathers and mbx_soft_from_llr do on the device):
+    integer LLRs [...] -> uint8 [..., 2] cells, bit = v > 0, reliability = min(|v|, 255) with |v| taken in a wider type"""
+    v = np.asarray(llr).astype(np.int32)
+    return np.stack([v > 0, np.minimum(np.abs(v), 255)], axis=-1).astype(np.uint8)
+
+
+def llr_from_cells(cells, form=FORM_LLR16):
+    """per-bit cells uint8 [..., 2] -> the LLRs of the form's type that convert to exactly them: +-reliability.  ValueError for a
+    cell no LLR gives: {1, 0}, and for int8 a reliability above 127 ({1, .}) / 128 ({0, .})"""
+    c = np.asarray(cells, dtype=np.uint8)
+    bit, rel = c[..., 0].astype(np.int32), c[..., 1].astype(np.int32)
+    v = np.where(bit & 1, rel, -rel)
+    info = np.iinfo(LLR_DTYPE[form])
+    if ((bit > 1) | ((bit == 1) & (rel == 0)) | (v < info.min) | (v > info.max)).any():
+        raise ValueError("a cell that no LLR of this width converts to")
+    return v.astype(LLR_DTYPE[form])
+
+
+def as_bytes(schedule, bursts, soft=False):
+    """bursts (host array or device tensor) as the uint8 bytes the library reads: soft bursts of an LLR schedule may come as int16 /
+    int8 (any integer array is cast to the form's type; a uint8 one is taken as the bytes themselves), everything else is uint8"""
+    dtype = LLR_DTYPE.get(schedule.form) if soft else None
+    if isinstance(bursts, np.ndarray):
+        if dtype is not None and bursts.dtype != np.uint8:
+            return np.ascontiguousarray(bursts, dtype=dtype).reshape(-1).view(np.uint8)
+        return np.ascontiguousarray(bursts, dtype=np.uint8)
+    import torch
+
+    if dtype is not None and bursts.dtype == {np.int16: torch.int16, np.int8: torch.int8}[dtype] and bursts.is_contiguous():
+        return bursts.reshape(-1).view(torch.uint8)
+    return bursts
 
 
 class ScheduleArrays:
@@ -61,12 +100,17 @@ class ScheduleArrays:
     @property
     def burst_bytes(self):
         """the smallest burst_stride of a hard burst in the schedule's form (mbx_burst_schedule_bytes)"""
-        return {FORM_BITS: self.burst_bits, FORM_DIBITS: self.burst_bits // 2}.get(self.form, self.packed_bytes)
+        return {FORM_BITS: self.burst_bits, FORM_DIBITS: self.burst_bits // 2, FORM_LLR16: 0, FORM_LLR8: 0}.get(self.form, self.packed_bytes)
 
     @property
     def soft_cells(self):
-        """mbe_soft_bit-sized cells of one soft burst (mbx_burst_schedule_soft_cells)"""
-        return self.burst_bits // 2 if self.form == FORM_DIBITS else self.burst_bits
+        """mbe_soft_bit-sized cells of one soft burst (mbx_burst_schedule_soft_cells); LLR8: 0, its bursts need not be whole cells"""
+        return {FORM_DIBITS: self.burst_bits // 2, FORM_LLR8: 0}.get(self.form, self.burst_bits)
+
+    @property
+    def soft_bytes(self):
+        """bytes of one soft burst (mbx_burst_schedule_soft_bytes)"""
+        return self.burst_bits if self.form == FORM_LLR8 else 2 * self.soft_cells
 
     def in_form(self, form=FORM_PACKED, invert=None, device=False):
         """the same three arrays as a schedule of another form / inversion sequence"""
@@ -75,17 +119,18 @@ class ScheduleArrays:
 
 
 class BurstSchedule(ScheduleArrays):
-    """A schedule on the device (mbx_burst_schedule_create_form on the current device, which must have been initialised:
-    decoder.ensure_init).  Owns the native handle; immutable."""
+    """A schedule on the device (mbx_burst_schedule_create_form, for an LLR form mbx_burst_schedule_create_llr, on the current
+    device, which must have been initialised: decoder.ensure_init).  Owns the native handle; immutable."""
 
     def __init__(self, codec, frames_per_burst, burst_bits, src_bit, cell_row, cell_col, form=FORM_PACKED, invert=None):
         super().__init__(codec, frames_per_burst, burst_bits, src_bit, cell_row, cell_col, form, invert)
         self.handle = None
         h = C.c_void_p()
-        rc = _native.lib().mbx_burst_schedule_create_form(C.byref(h), self.codec, self.frames_per_burst, self.burst_bits, self.src_bit.ctypes.data,
-                                                          self.cell_row.ctypes.data, self.cell_col.ctypes.data, self.form,
-                                                          None if self.invert is None else self.invert.ctypes.data)
-        _native.check(rc, "mbx_burst_schedule_create_form")
+        L = _native.lib()
+        create, form = (L.mbx_burst_schedule_create_llr, self.form // 8) if self.form in LLR_DTYPE else (L.mbx_burst_schedule_create_form, self.form)
+        rc = create(C.byref(h), self.codec, self.frames_per_burst, self.burst_bits, self.src_bit.ctypes.data, self.cell_row.ctypes.data,
+                    self.cell_col.ctypes.data, form, None if self.invert is None else self.invert.ctypes.data)
+        _native.check(rc, "mbx_burst_schedule_create_llr" if self.form in LLR_DTYPE else "mbx_burst_schedule_create_form")
         self.handle = h
 
     def close(self):
@@ -116,13 +161,19 @@ def apply_schedule(schedule, bursts, soft=False, burst_stride=None):
           byte j >> 3, mask 0x80 >> (j & 7); BITS: bit j = byte j & 1; DIBITS: bits 2d, 2d + 1 = bits 1, 0 of byte d
           -> uint8 [n * F, FRAME_BYTES[codec]] packed wire frames, frame k of burst b at row b * F + k
     soft: bursts = uint8 [n, soft_cells, 2] -- (bit, reliability) per bit, DIBITS: (dibit, reliability) per dibit, both bits of the
-          dibit with its reliability -> uint8 [n * F, cells, 2] cell arrays in the reference's shape, cells that are not on the wire {0, 0}
+          dibit with its reliability; LLR16 / LLR8: [n, burst_bits] int16 / int8 (or their bytes as uint8), converted by
+          cells_from_llr first -> uint8 [n * F, cells, 2] cell arrays in the reference's shape, cells that are not on the wire {0, 0}
     schedule.invert: the received bits with a 1 are flipped (soft: the hard decision; the reliability stays)"""
     s = schedule
     F, B, nbits = s.frames_per_burst, s.burst_bits, channel_bits(s.codec)
     rows, stride = FRAME_CELLS[s.codec]
+    if s.form in LLR_DTYPE and not soft:
+        raise ValueError("an LLR schedule has soft bursts only")
     if soft:
-        cells = np.ascontiguousarray(bursts, dtype=np.uint8).reshape(-1, s.soft_cells, 2)
+        if s.form in LLR_DTYPE:
+            cells = cells_from_llr(as_bytes(s, np.asarray(bursts), True).view(LLR_DTYPE[s.form]).reshape(-1, B))
+        else:
+            cells = np.ascontiguousarray(bursts, dtype=np.uint8).reshape(-1, s.soft_cells, 2)
         if s.form == FORM_DIBITS:
             d, rel = cells[:, :, 0], cells[:, :, 1]
             cells = np.stack([np.stack([(d >> 1) & 1, d & 1], axis=-1).reshape(-1, B), np.repeat(rel, 2, axis=1)], axis=-1)
@@ -149,7 +200,8 @@ def to_form(schedule, packed_bursts, soft=False, junk=None):
     """Bursts in the packed form -> the same received bits in the schedule's form, at the tight stride.
     hard: packed_bursts = uint8 [n, >= ceil(burst_bits / 8)], MSB first -> uint8 [n, schedule.burst_bytes]
     soft: packed_bursts = uint8 [n, burst_bits, 2] (bit, reliability) per bit -> uint8 [n, schedule.soft_cells, 2]; for the dibit form
-          the two bits of a dibit must come with ONE reliability (ValueError otherwise)
+          the two bits of a dibit must come with ONE reliability (ValueError otherwise); LLR16 / LLR8: int16 / int8 [n, burst_bits],
+          the LLRs +-reliability that convert to exactly these cells (llr_from_cells: ValueError for a cell no LLR gives)
     junk: an rng (numpy Generator) that fills the bits of every byte which the DEVICE does not read -- bits 1..7 of a bit byte, bits
           2..7 of a dibit byte or dibit cell, the bits of the last packed byte behind burst_bits.  Such bursts are what the device
           calls mask; mbx_burst_validate and the session submits refuse them.
@@ -158,6 +210,8 @@ def to_form(schedule, packed_bursts, soft=False, junk=None):
     B = s.burst_bits
     if soft:
         cells = np.ascontiguousarray(packed_bursts, dtype=np.uint8).reshape(-1, B, 2)
+        if s.form in LLR_DTYPE:
+            return llr_from_cells(cells, s.form)
         if s.form != FORM_DIBITS:
             return cells.copy()
         pairs = cells.reshape(-1, B // 2, 2, 2)
@@ -167,6 +221,8 @@ def to_form(schedule, packed_bursts, soft=False, junk=None):
         if junk is not None:
             d = d | (junk.integers(0, 64, size=d.shape, dtype=np.uint8) << 2)
         return np.stack([d, pairs[:, :, 0, 1]], axis=-1)
+    if s.form in LLR_DTYPE:
+        raise ValueError("an LLR schedule has soft bursts only")
     raw = np.ascontiguousarray(packed_bursts, dtype=np.uint8)
     raw = raw.reshape(-1, s.packed_bytes) if raw.ndim != 2 else raw[:, :s.packed_bytes]
     bits = np.unpackbits(raw, axis=1)
@@ -218,17 +274,19 @@ def gap_schedule(codec, frames_per_burst, gap=48, device=False):
 def deinterleave(schedule, bursts, soft=False, mixed_rows=False, burst_stride=None, out=None):
     """The gather alone, on the device (mbx_deinterleave / mbx_deinterleave_soft on the current torch stream).  bursts: uint8 device
     tensor (or host array, uploaded) of n bursts in the schedule's form -- hard: burst_stride bytes each (default
-    schedule.burst_bytes); soft: [n, schedule.soft_cells, 2].  Returns uint8 [n * F, row] wire frames (soft: [n * F, row, 2] cells); mixed_rows=True: rows of
+    schedule.burst_bytes); soft: [n, schedule.soft_cells, 2], of an LLR schedule [n, burst_bits] int16 / int8 (array or tensor, or their
+    bytes as uint8).  Returns uint8 [n * F, row] wire frames (soft: [n * F, row, 2] cells); mixed_rows=True: rows of
     MIXED_ROW_BYTES bytes / MIXED_ROW_CELLS cells, as mbx_process_batch_mixed takes them (bytes 9..17 of an AMBE wire row are not
     written: zero in a tensor made here, kept in `out`)."""
     import torch
 
     s = schedule
+    bursts = as_bytes(s, bursts, soft)
     if isinstance(bursts, np.ndarray):
-        bursts = torch.from_numpy(np.ascontiguousarray(bursts, dtype=np.uint8).reshape(-1)).cuda()
+        bursts = torch.from_numpy(bursts.reshape(-1)).cuda()
     if bursts.dtype != torch.uint8 or not bursts.is_contiguous():
         raise ValueError("bursts must be a contiguous uint8 tensor")
-    per = s.soft_cells * 2 if soft else (s.burst_bytes if burst_stride is None else int(burst_stride))
+    per = s.soft_bytes if soft else (s.burst_bytes if burst_stride is None else int(burst_stride))
     if per < 1 or bursts.numel() % per:
         raise ValueError("bursts must hold whole bursts")
     n = bursts.numel() // per

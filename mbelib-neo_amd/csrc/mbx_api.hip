@@ -21,6 +21,8 @@
 #include "mbx_host.h"
 #include "mbx_kernels.h"
 #include "mbx_launch_plan.h"
+#include "mbx_llr.h"
+#include "mbx_llr_cell.h"
 
 namespace {
 
@@ -507,9 +509,9 @@ int mbx_soft_bits_from_llr(const int16_t* llr, mbe_soft_bit* soft, size_t count)
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     for (size_t i = 0; i < count; ++i) {
-        const int v = llr[i], mag = v < 0 ? -v : v;
-        soft[i].bit = (uint8_t)(v > 0 ? 1u : 0u);
-        soft[i].reliability = (uint8_t)(mag > 255 ? 255 : mag);
+        const uint32_t cell = mbx::soft_cell_from_llr(llr[i]);
+        soft[i].bit = (uint8_t)(cell & 1u);
+        soft[i].reliability = (uint8_t)(cell >> 8);
     }
     return 0;
 }
@@ -1408,7 +1410,7 @@ static int process_bursts(const char* who, bool soft, const mbx_burst_schedule* 
     char text[160];
     // (alignment first: it needs neither the schedule nor a device)
     if (!batch_pointers_aligned(d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, d_stream_index, d_resident, nullptr) ||
-        !aligned_to(d_bursts, soft ? 2 : 1)) {
+        !aligned_to(d_bursts, soft ? (sched ? mbx::burst_shape(sched).soft_align() : 2) : 1)) {
         return misaligned(who);
     }
     if (!sched || !d_bursts || !d_records || !d_state_pool || !d_rng_pool || S < 0) {
@@ -1416,6 +1418,10 @@ static int process_bursts(const char* who, bool soft, const mbx_burst_schedule* 
         return fail(MBE_STATUS_INVALID_ARGUMENT, text);
     }
     const mbx::BurstShape sh = mbx::burst_shape(sched);
+    if (!soft && sh.llr()) {
+        snprintf(text, sizeof(text), "%s: an LLR schedule has soft bursts only", who);
+        return fail(MBE_STATUS_INVALID_ARGUMENT, text);
+    }
     if (!soft && burst_stride < sh.bytes) {
         snprintf(text, sizeof(text), "%s: burst_stride is below mbx_burst_schedule_bytes()", who);
         return fail(MBE_STATUS_INVALID_ARGUMENT, text);
@@ -1551,6 +1557,25 @@ int mbx_floattoshort(const float* d_in, int16_t* d_out, size_t nframes, void* st
     const unsigned grid = (unsigned)((nsamples / 2 + 255) / 256);
     hipLaunchKernelGGL(mbx::floattoshort_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, d_in, d_out, nsamples);
     return check_launch("floattoshort_kernel");
+}
+
+// (include/mbx_llr.h)  One launch: a grid-stride over chunks of mbx::kLlrChunk LLRs (mbx_kernels.h), at most 2,048 workgroups.
+int mbx_soft_from_llr(const void* d_llr, int llr_bytes, size_t count, mbe_soft_bit* d_soft, void* stream) {
+    if (!d_llr || !d_soft || (llr_bytes != 1 && llr_bytes != 2)) {
+        return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_soft_from_llr: d_llr and d_soft are needed, llr_bytes is 2 (int16) or 1 (int8)");
+    }
+    if (!aligned_to(d_llr, (uintptr_t)llr_bytes) || !aligned_to(d_soft, 2)) {
+        return mbx::misaligned("mbx_soft_from_llr", "mbx_llr.h");
+    }
+    REQUIRE_CTX(c);
+    if (count == 0) {
+        return 0;
+    }
+    const size_t chunks = (count + mbx::kLlrChunk - 1) / mbx::kLlrChunk;
+    const unsigned grid = (unsigned)(chunks < 2048 ? chunks : 2048);
+    const auto kernel = llr_bytes == 2 ? mbx::soft_from_llr_kernel<2> : mbx::soft_from_llr_kernel<1>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, static_cast<const uint8_t*>(d_llr), count, d_soft);
+    return check_launch("soft_from_llr_kernel");
 }
 
 int mbx_result_histogram(const mbe_process_result* d_results, size_t n, mbx_result_hist* d_hist, void* stream) {

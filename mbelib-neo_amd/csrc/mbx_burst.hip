@@ -1,9 +1,9 @@
 // mbx_burst.hip -- burst input (include/mbx_burst.h): the caller's de-interleave schedule, folded once on the host into two tables,
 // and the gather kernels that apply them to every burst on the device: received bursts -> packed wire frames (hard) or the
 // reference's cell arrays (soft), i.e. what the batch launchers of mbx_api.hip start from.  One kernel template per kind,
-// burst_gather_kernel<form, invert> and burst_gather_soft_kernel<dibits, flip>, serves every form a receiver holds its bursts in --
-// packed bits, one byte per bit, one byte per dibit; soft per-bit cells, soft {dibit, reliability} pairs -- with or without a fixed
-// inversion sequence.  The launchers that chain a gather in
+// burst_gather_kernel<form, invert> and burst_gather_soft_kernel<cell, flip>, serves every form a receiver holds its bursts in --
+// packed bits, one byte per bit, one byte per dibit; soft per-bit cells, soft {dibit, reliability} pairs, one signed LLR per bit as
+// int16 or int8 (converted in the gather: mbx_llr_cell.h) -- with or without a fixed inversion sequence.  The launchers that chain a gather in
 // front of a batch step are in mbx_api.hip (they need the stream's workspace), the session submits in mbx_session.hip.
 //
 // No air-interface table is written here: F, B, the strides and the tables are kernel arguments, one code object serves every
@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "mbx.h"
@@ -21,6 +22,7 @@
 #include "mbx_gather.h"
 #include "mbx_host.h"
 #include "mbx_kernels.h"
+#include "mbx_llr_cell.h"
 
 namespace mbx {
 
@@ -28,6 +30,7 @@ constexpr int      kGatherBursts = 64;     // hard gather: bursts per workgroup,
 constexpr int      kSoftStageBytes = 32768;   // soft gather: a workgroup stages at most this much of soft bursts (and at most 16 bursts)
 constexpr uint32_t kNoBit = 0xffffu;       // table entry of a frame bit / cell no received bit goes to
 constexpr int      kSoftDibitBursts = 32;  // soft gather of dibit pairs: half the bytes per burst, twice the bursts of a workgroup at most
+constexpr int      kSoftLlr8Bursts = 32;   // soft gather of int8 LLRs: likewise
 constexpr uint32_t kInverted = 0x8000u;    // cell table: the received bit arrives inverted (entries are below MBX_BURST_MAX_BITS = 0x1000) ...
 constexpr uint32_t kBitOf = 0x0fffu;       // ... and the received bit of an entry
 
@@ -177,23 +180,30 @@ burst_gather_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride, siz
 }
 
 // ---- soft bursts -> cell arrays ----------------------------------------------------------------------------------------------------
-// A workgroup takes nb consecutive bursts (a contiguous range of cells, C per burst) into LDS as they come, with dword loads from
-// the first aligned pair on, then every wave takes rows of the output: a lane owns the two cells of one aligned output dword, looks
-// each up in the schedule's table (cell -> burst bit, in LDS), fetches it with one 16-bit LDS read and stores the pair; cells
+// A workgroup takes nb consecutive bursts (a contiguous range of staged cells, C per burst) into LDS as they come, with dword loads
+// from the first aligned dword on, then every wave takes rows of the output: a lane owns the two cells of one aligned output dword,
+// looks each up in the schedule's table (cell -> burst bit, in LDS), fetches it with one LDS read and stores the pair; cells
 // without a received bit, and the cells of a mixed row behind the codec's array, are {0, 0}.
-//   kDibits    a staged cell is a {dibit, reliability} pair, C = B / 2 of them per burst -- half the bytes, so up to
-//              kSoftDibitBursts bursts per workgroup -- and not one of C = B per-bit cells.  Entry j gives pair j >> 1 as
-//              ((dibit >> (1 - (j & 1))) & 1) ^ flip | reliability << 8, i.e. of a dibit `& 3` counts.
+//   kCell      what a staged cell is (SoftCell, mbx_kernels.h):
+//              kCellBit    one of C = B per-bit {bit, reliability} cells, 16 bits.
+//              kCellDibit  a {dibit, reliability} pair, C = B / 2 of them per burst -- half the bytes, so up to kSoftDibitBursts
+//                          bursts per workgroup.  Entry j gives pair j >> 1 as
+//                          ((dibit >> (1 - (j & 1))) & 1) ^ flip | reliability << 8, i.e. of a dibit `& 3` counts.
+//              kCellLlr16  one of C = B signed 16-bit LLRs, staged like per-bit cells; entry j gives soft_cell_from_llr(LLR j)
+//                          (mbx_llr_cell.h) with the hard decision flipped where the entry carries kInverted.
+//              kCellLlr8   one of C = B signed 8-bit LLRs: a staged piece is ONE byte -- half the bytes, up to kSoftLlr8Bursts
+//                          bursts per workgroup -- so the range starts at any of four byte phases (16-bit cells: two); the LDS
+//                          image keeps the source's dword alignment all the same.  One 8-bit LDS read per entry, then as LLR16.
 //   kFlip      the table's entries carry kInverted where the received bit arrives inverted: per-bit cells give cell j with its
 //              hard decision flipped.  Without it an entry is the received bit alone (a schedule without a sequence has no such
 //              entry) and the fetch is the plain read of cell j: no mask, no shift.  (Only per-bit cells are launched without.)
 //   cell_tab   [F][cells] burst bit of each cell of the reference's array, kNoBit for a cell that is not on the wire
-// dynamic LDS: table | nb * C cells (+ one pair of slack for the alignment phase)
-template <bool kDibits, bool kFlip>
+// dynamic LDS: table | nb * C staged cells (+ one dword of slack for the alignment phase)
+template <SoftCell kCell, bool kFlip>
 __global__ void __launch_bounds__(256)
 burst_gather_soft_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, int F, int C, int cells, const uint16_t* __restrict__ cell_tab,
                          mbe_soft_bit* __restrict__ rows_out, int row_cells, int nb) {
-    static_assert(kFlip || !kDibits, "not an instance that mbx::burst_gather launches");
+    static_assert(kFlip || kCell == kCellBit, "not an instance that mbx::burst_gather launches");
     extern __shared__ uint32_t lds[];
     const int tab_dwords = (F * cells) >> 1;   // (every codec has an even number of cells)
     const uint16_t* tab = reinterpret_cast<const uint16_t*>(lds);
@@ -204,12 +214,35 @@ burst_gather_soft_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, int F,
     for (int i = tid; i < tab_dwords; i += 256) {
         lds[i] = reinterpret_cast<const uint32_t*>(cell_tab)[i];
     }
-    // cell i of the range sits at in16[i + head]: an aligned dword of the source is an aligned dword of LDS
-    const uint16_t* src = reinterpret_cast<const uint16_t*>(soft) + first * (size_t)C;
-    const int ncells = here * C;
-    const int head = (int)((reinterpret_cast<uintptr_t>(src) >> 1) & 1u);
-    const int ndw = (ncells - head) >> 1;
-    {
+    // staged cell i of the range sits at in[i + head] (Piece: what a staged cell is read as): an aligned dword of the source is an
+    // aligned dword of LDS
+    using Piece = std::conditional_t<kCell == kCellLlr8, uint8_t, uint16_t>;
+    const Piece* in = reinterpret_cast<const Piece*>(in16);
+    int head;
+    if constexpr (kCell == kCellLlr8) {
+        const uint8_t* src = reinterpret_cast<const uint8_t*>(soft) + first * (size_t)C;
+        const int ncells = here * C;
+        uint8_t* in8 = reinterpret_cast<uint8_t*>(in16);
+        head = (int)(reinterpret_cast<uintptr_t>(src) & 3u);
+        const int lead = (4 - head) & 3;   // bytes in front of the first aligned dword ...
+        const int edge = lead < ncells ? lead : ncells;   // ... as far as the range has them
+        const int ndw = (ncells - edge) >> 2;
+        const int tail = edge + 4 * ndw;   // the bytes behind the last whole dword: fewer than four
+        const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src + edge);   // (aligned wherever ndw > 0: then edge == lead)
+        uint32_t* d32 = reinterpret_cast<uint32_t*>(in8 + head + edge);
+        for (int m = tid; m < ndw; m += 256) {
+            d32[m] = s32[m];
+        }
+        if (tid < edge) {
+            in8[head + tid] = src[tid];
+        } else if (tid >= 4 && tid - 4 < ncells - tail) {
+            in8[head + tail + tid - 4] = src[tail + tid - 4];
+        }
+    } else {
+        const uint16_t* src = reinterpret_cast<const uint16_t*>(soft) + first * (size_t)C;
+        const int ncells = here * C;
+        head = (int)((reinterpret_cast<uintptr_t>(src) >> 1) & 1u);
+        const int ndw = (ncells - head) >> 1;
         const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src + head);
         uint32_t* d32 = reinterpret_cast<uint32_t*>(in16) + head;
         for (int m = tid; m < ndw; m += 256) {
@@ -225,14 +258,18 @@ burst_gather_soft_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, int F,
         }
     }
     __syncthreads();
-    const auto fetch = [](const uint16_t* b, uint32_t e) -> uint32_t {
+    const auto fetch = [](const Piece* b, uint32_t e) -> uint32_t {
         if constexpr (!kFlip) {
             return b[e];
         } else {
             const uint32_t j = e & kBitOf, flip = e >> 15;
-            if constexpr (kDibits) {
+            if constexpr (kCell == kCellDibit) {
                 const uint32_t c = b[j >> 1];
                 return ((((c & 0xffu) >> (1u - (j & 1u))) & 1u) ^ flip) | (c & 0xff00u);
+            } else if constexpr (kCell == kCellLlr16) {
+                return soft_cell_from_llr((int16_t)b[j]) ^ flip;
+            } else if constexpr (kCell == kCellLlr8) {
+                return soft_cell_from_llr((int8_t)b[j]) ^ flip;
             } else {
                 return (uint32_t)b[j] ^ flip;
             }
@@ -245,7 +282,7 @@ burst_gather_soft_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, int F,
     for (int r = wave; r < nrows; r += 4) {
         const int j = r / F, k = r - j * F;
         const uint16_t* t = tab + k * cells;
-        const uint16_t* b = in16 + head + j * C;
+        const Piece* b = in + head + j * C;
         uint16_t* o = dst + (size_t)r * (size_t)row_cells;
         for (int p = lane; p < pairs; p += 64) {
             const int c0 = 2 * p - a, c1 = c0 + 1;
@@ -281,6 +318,7 @@ struct mbx_burst_schedule {
     int       lstride = 0;      // hard gather: bytes between two bursts in LDS (a whole, odd number of dwords)
     unsigned  hard_lds = 0;     // dynamic LDS of the two kernels
     int       soft_bursts = 0;  // soft gather: bursts per workgroup
+    int       staged_cells = 0; // soft gather: staged cells of one burst (cells, dibit pairs or LLRs)
     unsigned  soft_lds = 0;
     uint16_t* d_wire_tab = nullptr;   // [frames][frame_bytes * 8]
     uint16_t* d_cell_tab = nullptr;   // [frames][cells], kInverted on the inverted bits; the same allocation, behind the wire table
@@ -319,11 +357,11 @@ void launch_hard(const mbx_burst_schedule* s, const uint8_t* in, size_t burst_st
                        (int)sh.frame_bytes, s->d_wire_tab, s->d_xor_tab, out, frame_stride, s->lstride);
 }
 
-template <bool kDibits, bool kFlip>
+template <mbx::SoftCell kCell, bool kFlip>
 void launch_soft(const mbx_burst_schedule* s, const mbe_soft_bit* in, size_t n, mbe_soft_bit* out, int row_cells, hipStream_t strm) {
     const mbx::BurstShape& sh = s->shape;
     const unsigned grid = (unsigned)((n + (size_t)s->soft_bursts - 1) / (size_t)s->soft_bursts);
-    hipLaunchKernelGGL((mbx::burst_gather_soft_kernel<kDibits, kFlip>), dim3(grid), dim3(256), s->soft_lds, strm, in, n, sh.frames, (int)sh.soft_cells,
+    hipLaunchKernelGGL((mbx::burst_gather_soft_kernel<kCell, kFlip>), dim3(grid), dim3(256), s->soft_lds, strm, in, n, sh.frames, s->staged_cells,
                        (int)sh.cells, s->d_cell_tab, out, row_cells, s->soft_bursts);
 }
 
@@ -335,12 +373,16 @@ BurstShape burst_shape(const mbx_burst_schedule* sched) { return sched->shape; }
 
 int burst_gather(const mbx_burst_schedule* sched, bool soft, const void* d_in, size_t burst_stride, size_t n, void* d_out, size_t row,
                  void* stream) {
-    // the seven instances, by (soft, form, inverts): BITS and DIBITS bursts always read their inversion table, dibit pairs always
-    // look for kInverted; a packed schedule (soft: a per-bit one) does so only where its sequence inverts a bit
+    // the nine instances, by (soft, form, inverts): BITS and DIBITS bursts always read their inversion table, dibit pairs and LLRs
+    // always look for kInverted; a packed schedule (soft: a per-bit one) does so only where its sequence inverts a bit
     const int form = sched->shape.form;
     const bool inverts = sched->inverts;
     if (soft) {
-        const auto launch = form == MBX_BURST_FORM_DIBITS ? launch_soft<true, true> : inverts ? launch_soft<false, true> : launch_soft<false, false>;
+        const auto launch = form == MBX_BURST_FORM_LLR16    ? launch_soft<kCellLlr16, true>
+                            : form == MBX_BURST_FORM_LLR8   ? launch_soft<kCellLlr8, true>
+                            : form == MBX_BURST_FORM_DIBITS ? launch_soft<kCellDibit, true>
+                            : inverts                       ? launch_soft<kCellBit, true>
+                                                            : launch_soft<kCellBit, false>;
         launch(sched, static_cast<const mbe_soft_bit*>(d_in), n, static_cast<mbe_soft_bit*>(d_out), (int)row, (hipStream_t)stream);
     } else {
         const auto launch = form == MBX_BURST_FORM_DIBITS ? launch_hard<MBX_BURST_FORM_DIBITS, true>
@@ -387,8 +429,9 @@ int channel_bits(const mbx::CodecShape* sh) {   // of one frame
 }
 
 // what of mbx_burst_schedule_create_form's arguments can be refused before their tables are read: the text, or nullptr
+// (mbx_burst_schedule_create_llr: `form` is the LLR form of its llr_bytes, 0 for a width there is none of)
 const char* schedule_args_refused(const mbx::CodecShape* sh, int frames_per_burst, int burst_bits, const int* src_bit, const int* cell_row,
-                                  const int* cell_col, int form, const uint8_t* invert) {
+                                  const int* cell_col, int form, const uint8_t* invert, bool llr) {
     if (!sh) {
         return "no such codec";
     }
@@ -401,7 +444,11 @@ const char* schedule_args_refused(const mbx::CodecShape* sh, int frames_per_burs
     if (burst_bits < 1 || burst_bits > MBX_BURST_MAX_BITS) {
         return "burst_bits must be 1 .. MBX_BURST_MAX_BITS";
     }
-    if (form != MBX_BURST_FORM_PACKED && form != MBX_BURST_FORM_BITS && form != MBX_BURST_FORM_DIBITS) {
+    if (llr) {
+        if (form != MBX_BURST_FORM_LLR16 && form != MBX_BURST_FORM_LLR8) {
+            return "llr_bytes must be 2 (int16) or 1 (int8)";
+        }
+    } else if (form != MBX_BURST_FORM_PACKED && form != MBX_BURST_FORM_BITS && form != MBX_BURST_FORM_DIBITS) {
         return "form must be one of MBX_BURST_FORM_*";
     }
     if (form == MBX_BURST_FORM_DIBITS && (burst_bits & 1)) {
@@ -489,8 +536,9 @@ int mbx_burst_schedule_create(mbx_burst_schedule** out, int codec, int frames_pe
     return mbx_burst_schedule_create_form(out, codec, frames_per_burst, burst_bits, src_bit, cell_row, cell_col, MBX_BURST_FORM_PACKED, nullptr);
 }
 
-int mbx_burst_schedule_create_form(mbx_burst_schedule** out, int codec, int frames_per_burst, int burst_bits, const int* src_bit,
-                                   const int* cell_row, const int* cell_col, int form, const uint8_t* invert) {
+// the two creators: every refusal first, then the device
+static int create_schedule(mbx_burst_schedule** out, int codec, int frames_per_burst, int burst_bits, const int* src_bit, const int* cell_row,
+                           const int* cell_col, int form, const uint8_t* invert, bool llr) {
     if (!out) {
         return refuse("no place for the handle");
     }
@@ -498,7 +546,7 @@ int mbx_burst_schedule_create_form(mbx_burst_schedule** out, int codec, int fram
     const mbx::CodecShape* sh = mbx::codec_shape(codec);
     const int F = frames_per_burst;
     FoldedSchedule folded;
-    const char* why = schedule_args_refused(sh, F, burst_bits, src_bit, cell_row, cell_col, form, invert);
+    const char* why = schedule_args_refused(sh, F, burst_bits, src_bit, cell_row, cell_col, form, invert, llr);
     if (!why) {
         why = fold_schedule(&folded, codec, sh, F, burst_bits, src_bit, cell_row, cell_col, invert);
     }
@@ -517,18 +565,22 @@ int mbx_burst_schedule_create_form(mbx_burst_schedule** out, int codec, int fram
     }
     const size_t items = (size_t)F * (size_t)sh->frame_bytes;
     const size_t packed_bytes = ((size_t)burst_bits + 7) / 8;
-    const size_t bytes = form == MBX_BURST_FORM_BITS ? (size_t)burst_bits : (form == MBX_BURST_FORM_DIBITS ? (size_t)burst_bits / 2 : packed_bytes);
-    const size_t soft_cells = form == MBX_BURST_FORM_DIBITS ? (size_t)burst_bits / 2 : (size_t)burst_bits;
-    s->shape = mbx::BurstShape{codec, F, burst_bits, dev, bytes, (size_t)sh->frame_bytes, (size_t)sh->cells, form, soft_cells};
+    // an LLR schedule has no hard bursts (bytes 0), and its int8 bursts need not be a whole number of cells (soft_cells 0)
+    const size_t bytes = llr ? 0 : form == MBX_BURST_FORM_BITS ? (size_t)burst_bits : (form == MBX_BURST_FORM_DIBITS ? (size_t)burst_bits / 2 : packed_bytes);
+    const size_t soft_cells = form == MBX_BURST_FORM_LLR8 ? 0 : form == MBX_BURST_FORM_DIBITS ? (size_t)burst_bits / 2 : (size_t)burst_bits;
+    const size_t soft_bytes = form == MBX_BURST_FORM_LLR8 ? (size_t)burst_bits : soft_cells * sizeof(mbe_soft_bit);
+    s->shape = mbx::BurstShape{codec, F, burst_bits, dev, bytes, (size_t)sh->frame_bytes, (size_t)sh->cells, form, soft_cells, soft_bytes};
     s->inverts = folded.inverts;
     // the hard gather works on the PACKED image of the bursts whatever their form: lstride and the dynamic LDS do not depend on it
     const int bdw = (int)((packed_bytes + 3) / 4);
     s->lstride = 4 * (bdw | 1);
     s->hard_lds = (unsigned)(items * 16 + (size_t)mbx::kGatherBursts * (size_t)s->lstride + ((mbx::kGatherBursts * items + 3) & ~(size_t)3));
-    const int nb = mbx::kSoftStageBytes / ((int)soft_cells * (int)sizeof(mbe_soft_bit));
-    const int most = form == MBX_BURST_FORM_DIBITS ? mbx::kSoftDibitBursts : 16;
+    const int nb = mbx::kSoftStageBytes / (int)soft_bytes;
+    const int most = form == MBX_BURST_FORM_DIBITS ? mbx::kSoftDibitBursts : form == MBX_BURST_FORM_LLR8 ? mbx::kSoftLlr8Bursts : 16;
     s->soft_bursts = nb < 1 ? 1 : (nb > most ? most : nb);
-    s->soft_lds = (unsigned)((size_t)F * (size_t)sh->cells * 2 + ((size_t)s->soft_bursts * soft_cells + 2) * 2 + 3) & ~3u;
+    s->staged_cells = form == MBX_BURST_FORM_DIBITS ? burst_bits / 2 : burst_bits;
+    // (the staged range and one dword of slack for its alignment phase: up to one 16-bit cell, or three int8 LLRs)
+    s->soft_lds = (unsigned)((size_t)F * (size_t)sh->cells * 2 + (size_t)s->soft_bursts * soft_bytes + 4 + 3) & ~3u;
     const std::vector<uint16_t>& tabs = folded.tabs;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->d_wire_tab), tabs.size() * sizeof(uint16_t));
     if (e == hipSuccess) {
@@ -543,6 +595,17 @@ int mbx_burst_schedule_create_form(mbx_burst_schedule** out, int codec, int fram
     s->d_xor_tab = reinterpret_cast<uint8_t*>(s->d_wire_tab + folded.tab_entries);
     *out = s;
     return 0;
+}
+
+int mbx_burst_schedule_create_form(mbx_burst_schedule** out, int codec, int frames_per_burst, int burst_bits, const int* src_bit,
+                                   const int* cell_row, const int* cell_col, int form, const uint8_t* invert) {
+    return create_schedule(out, codec, frames_per_burst, burst_bits, src_bit, cell_row, cell_col, form, invert, false);
+}
+
+int mbx_burst_schedule_create_llr(mbx_burst_schedule** out, int codec, int frames_per_burst, int burst_bits, const int* src_bit,
+                                  const int* cell_row, const int* cell_col, int llr_bytes, const uint8_t* invert) {
+    const int form = llr_bytes == 2 ? MBX_BURST_FORM_LLR16 : llr_bytes == 1 ? MBX_BURST_FORM_LLR8 : 0;
+    return create_schedule(out, codec, frames_per_burst, burst_bits, src_bit, cell_row, cell_col, form, invert, true);
 }
 
 int mbx_burst_schedule_destroy(mbx_burst_schedule* sched) {
@@ -560,12 +623,19 @@ int mbx_burst_schedule_bits(const mbx_burst_schedule* sched) { return sched ? sc
 int mbx_burst_schedule_form(const mbx_burst_schedule* sched) { return sched ? sched->shape.form : MBE_STATUS_INVALID_ARGUMENT; }
 size_t mbx_burst_schedule_bytes(const mbx_burst_schedule* sched) { return sched ? sched->shape.bytes : 0; }
 size_t mbx_burst_schedule_soft_cells(const mbx_burst_schedule* sched) { return sched ? sched->shape.soft_cells : 0; }
+size_t mbx_burst_schedule_soft_bytes(const mbx_burst_schedule* sched) { return sched ? sched->shape.soft_bytes : 0; }
 
 int mbx_burst_validate(const mbx_burst_schedule* sched, const void* bursts, size_t burst_stride, size_t n, int soft) {
     if (!sched || !bursts) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     const mbx::BurstShape& sh = sched->shape;
+    if (sh.llr()) {   // every LLR is a valid one; hard bursts of an LLR schedule there are none
+        if (!soft) {
+            mbx_set_error_text("mbx_burst_validate: an LLR schedule has soft bursts only");
+        }
+        return soft ? 0 : MBE_STATUS_INVALID_ARGUMENT;
+    }
     if (soft) {
         if (sh.form != MBX_BURST_FORM_DIBITS) {
             return mbx_validate_soft_bits(static_cast<const mbe_soft_bit*>(bursts), n * sh.soft_cells);
@@ -607,6 +677,10 @@ int mbx_deinterleave(const mbx_burst_schedule* sched, const uint8_t* d_bursts, s
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     const mbx::BurstShape& sh = sched->shape;
+    if (sh.llr()) {
+        mbx_set_error_text("mbx_deinterleave: an LLR schedule has soft bursts only (mbx_deinterleave_soft)");
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
     if (burst_stride < sh.bytes || (frame_stride != sh.frame_bytes && frame_stride != (size_t)MBX_MIXED_ROW_BYTES)) {
         mbx_set_error_text("mbx_deinterleave: burst_stride below mbx_burst_schedule_bytes(), or frame_stride neither the codec's frame size nor the mixed row");
         return MBE_STATUS_INVALID_ARGUMENT;
@@ -621,7 +695,8 @@ int mbx_deinterleave(const mbx_burst_schedule* sched, const uint8_t* d_bursts, s
 
 int mbx_deinterleave_soft(const mbx_burst_schedule* sched, const mbe_soft_bit* d_soft, size_t n, mbe_soft_bit* d_cells, size_t row_cells,
                           void* stream) {
-    if (!mbx::aligned_to(d_soft, 2) || !mbx::aligned_to(d_cells, 2)) {   // (first: it needs neither the schedule nor a device)
+    // (first: it needs no device, and of the schedule only whether its soft bursts are int8 LLRs)
+    if (!mbx::aligned_to(d_soft, sched ? sched->shape.soft_align() : 2) || !mbx::aligned_to(d_cells, 2)) {
         return mbx::misaligned("mbx_deinterleave_soft", "mbx_burst.h");
     }
     if (!sched || !d_soft || !d_cells) {

@@ -14,6 +14,7 @@
 #include "mbx_fec_frame.h"
 #include "mbx_fec_soft.h"
 #include "mbx_kernels.h"
+#include "mbx_llr_cell.h"
 
 namespace mbx {
 
@@ -119,6 +120,75 @@ stage_in_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, size
         }
     }
 }
+
+// LLRs -> soft cells (mbx_soft_from_llr; the conversion: mbx_llr_cell.h).  A workgroup takes chunks of kLlrChunk LLRs, grid-stride: the
+// chunk goes to LDS as it comes, with dword loads from the first aligned dword on and single pieces at the edges (an aligned dword
+// of the source is an aligned dword of LDS), then a lane owns the two cells of one aligned output dword, reads their LLRs from LDS
+// and stores the pair -- a single cell where the dword is not wholly inside the chunk.  A chunk is a whole number of dwords on
+// both sides, so every chunk has the alignment phases of the first.
+template <int kLlrBytes>
+__global__ void __launch_bounds__(256)
+soft_from_llr_kernel(const uint8_t* __restrict__ llr, size_t count, mbe_soft_bit* __restrict__ soft) {
+    static_assert(kLlrBytes == 1 || kLlrBytes == 2, "int8 or int16");
+    __shared__ uint32_t stage[kLlrChunk * kLlrBytes / 4 + 1];   // (+ one dword for the phase)
+    uint8_t* in8 = reinterpret_cast<uint8_t*>(stage);
+    const int tid = (int)threadIdx.x;
+    const int head = (int)(reinterpret_cast<uintptr_t>(llr) & 3u);   // byte i of a chunk sits at in8[head + i]
+    const int lead = (4 - head) & 3;                                 // bytes in front of the first aligned dword
+    uint16_t* out = reinterpret_cast<uint16_t*>(soft);
+    const int a = (int)((reinterpret_cast<uintptr_t>(out) >> 1) & 1u);
+    for (size_t first = (size_t)blockIdx.x * kLlrChunk; first < count; first += (size_t)gridDim.x * kLlrChunk) {
+        const int here = (int)(count - first < (size_t)kLlrChunk ? count - first : (size_t)kLlrChunk);
+        const int nbytes = here * kLlrBytes;
+        const uint8_t* src = llr + first * kLlrBytes;
+        const int edge = lead < nbytes ? lead : nbytes;
+        const int ndw = (nbytes - edge) >> 2;
+        const int tail = edge + 4 * ndw;   // the bytes behind the last whole dword: fewer than four
+        const uint32_t* s32 = reinterpret_cast<const uint32_t*>(src + edge);   // (aligned wherever ndw > 0: then edge == lead)
+        uint32_t* d32 = reinterpret_cast<uint32_t*>(in8 + head + edge);
+        for (int m = tid; m < ndw; m += 256) {
+            d32[m] = s32[m];
+        }
+        // the edges in pieces of one LLR (an int16 array is 2-aligned: its edges are whole LLRs)
+        if (tid * kLlrBytes < edge) {
+            if constexpr (kLlrBytes == 2) {
+                *reinterpret_cast<uint16_t*>(in8 + head + 2 * tid) = *reinterpret_cast<const uint16_t*>(src + 2 * tid);
+            } else {
+                in8[head + tid] = src[tid];
+            }
+        } else if (tid >= 4 && (tid - 4) * kLlrBytes < nbytes - tail) {
+            const int at = tail + (tid - 4) * kLlrBytes;
+            if constexpr (kLlrBytes == 2) {
+                *reinterpret_cast<uint16_t*>(in8 + head + at) = *reinterpret_cast<const uint16_t*>(src + at);
+            } else {
+                in8[head + at] = src[at];
+            }
+        }
+        __syncthreads();
+        const auto cell = [&](int i) -> uint32_t {
+            if constexpr (kLlrBytes == 2) {
+                return soft_cell_from_llr(*reinterpret_cast<const int16_t*>(in8 + head + 2 * i));
+            } else {
+                return soft_cell_from_llr(*reinterpret_cast<const int8_t*>(in8 + head + i));
+            }
+        };
+        uint16_t* o = out + first;
+        const int pairs = (here + 1 + a) >> 1;
+        for (int p = tid; p < pairs; p += 256) {
+            const int c0 = 2 * p - a, c1 = c0 + 1;
+            if (c0 >= 0 && c1 < here) {
+                *reinterpret_cast<uint32_t*>(o + c0) = cell(c0) | (cell(c1) << 16);
+            } else if (c0 >= 0) {
+                o[c0] = (uint16_t)cell(c0);
+            } else if (c1 < here) {
+                o[c1] = (uint16_t)cell(c1);
+            }
+        }
+        __syncthreads();   // the next chunk overwrites the stage
+    }
+}
+template __global__ void soft_from_llr_kernel<1>(const uint8_t*, size_t, mbe_soft_bit*);
+template __global__ void soft_from_llr_kernel<2>(const uint8_t*, size_t, mbe_soft_bit*);
 
 __global__ void __launch_bounds__(256)
 floattoshort_kernel(const float* __restrict__ in, int16_t* __restrict__ out, size_t nsamples) {

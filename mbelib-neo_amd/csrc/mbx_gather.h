@@ -12,11 +12,15 @@ namespace mbx {
 // what a schedule is, as far as its users look: the folded tables stay inside mbx_burst.hip
 struct BurstShape {
     int    codec, frames, bits, device;
-    size_t bytes;          // the smallest burst_stride of a hard burst in the schedule's form (mbx_burst_schedule_bytes)
+    size_t bytes;          // the smallest burst_stride of a hard burst in the schedule's form (mbx_burst_schedule_bytes); an LLR form: 0
     size_t frame_bytes;    // one gathered wire frame
     size_t cells;          // one gathered cell array (mbe_soft_bit cells)
     int    form;           // MBX_BURST_FORM_*
     size_t soft_cells;     // cells of one soft burst in the schedule's form (mbx_burst_schedule_soft_cells)
+    size_t soft_bytes;     // bytes of one soft burst in the schedule's form (mbx_burst_schedule_soft_bytes)
+    // an LLR schedule is soft-only: the hard calls refuse it; its soft bursts are aligned to one LLR (2 | 1), not to a cell
+    bool   llr() const { return form == MBX_BURST_FORM_LLR16 || form == MBX_BURST_FORM_LLR8; }
+    size_t soft_align() const { return form == MBX_BURST_FORM_LLR8 ? 1 : 2; }
 };
 BurstShape burst_shape(const mbx_burst_schedule* sched);   // sched != nullptr
 

@@ -102,6 +102,9 @@ __global__ void fec_ambe3600x2450_kernel(const uint8_t*, size_t, mbx_param_recor
 __global__ void fec_imbe7100x4400_kernel(const uint8_t*, size_t, mbx_param_record*, DeviceTables);
 __global__ void stage_in_kernel(const uint8_t*, uint8_t*, size_t);
 __global__ void floattoshort_kernel(const float*, int16_t*, size_t);
+constexpr int kLlrChunk = 2048;   // LLRs a workgroup of soft_from_llr_kernel converts at a time
+template <int kLlrBytes>
+__global__ void soft_from_llr_kernel(const uint8_t*, size_t, mbe_soft_bit*);
 __global__ void result_histogram_kernel(const mbe_process_result*, size_t, unsigned long long*);
 __global__ void fec_stage_kernel(int, int, const uint8_t*, size_t, uint8_t*, mbx_param_record*, DeviceTables);
 __global__ void pack_cells_kernel(int, const char*, size_t, uint8_t*, int32_t*);
@@ -122,11 +125,12 @@ __global__ void expand_ambe_kernel(const mbx_param_record*, size_t, FrameParams*
 __global__ void expand_ambe2400_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);
 
 // ---- mbx_burst.hip: burst input, in front of a batch step -- received bursts -> wire frames / cell arrays by a caller's schedule -----------
-// (one template per kind over the forms of mbx_burst_schedule_create_form: packed bits, bit bytes, dibit bytes; per-bit cells, dibit
-// pairs; with or without an inversion sequence)
+// (one template per kind over the forms of mbx_burst_schedule_create_form / _create_llr: packed bits, bit bytes, dibit bytes; per-bit
+// cells, dibit pairs, int16 and int8 LLRs; with or without an inversion sequence)
 template <int kForm, bool kInvert>
 __global__ void burst_gather_kernel(const uint8_t*, size_t, size_t, int, int, int, const uint16_t*, const uint8_t*, uint8_t*, int, int);
-template <bool kDibits, bool kFlip>
+enum SoftCell { kCellBit, kCellDibit, kCellLlr16, kCellLlr8 };   // what a staged cell of a soft burst is
+template <SoftCell kCell, bool kFlip>
 __global__ void burst_gather_soft_kernel(const mbe_soft_bit*, size_t, int, int, int, const uint16_t*, mbe_soft_bit*, int, int);
 
 // ---- mbx_api.hip ---------------------------------------------------------------------------------------------------------------

@@ -166,7 +166,7 @@ bool range_ok(const mbx_session* s, int first, int count) {
 struct BurstIn {
     const mbx_burst_schedule* sched;
     size_t                    stride;   // hard bursts: the caller's burst_stride
-    size_t                    bytes;    // one burst in the input: burst_stride, or the soft cells of the schedule's form
+    size_t                    bytes;    // one burst in the input: burst_stride, or mbx_burst_schedule_soft_bytes()
 };
 
 // `soft`: frames are mbe_soft_bit cells (soft_bytes per frame) instead of wire frames (frame_bytes)
@@ -185,7 +185,9 @@ int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frame
     if (n == 0 || T == 0) {
         return 0;
     }
-    if (burst) {   // bursts of a form that can be invalid: a bit byte > 1, a dibit > 3, a soft hard decision > 1 (mbx_burst_validate)
+    if (burst && mbx::burst_shape(burst->sched).llr()) {
+        // every LLR is a valid one: nothing to check
+    } else if (burst) {   // bursts of a form that can be invalid: a bit byte > 1, a dibit > 3, a soft hard decision > 1 (mbx_burst_validate)
         const int rc = mbx_burst_validate(burst->sched, frames, burst->stride, (size_t)n, soft ? 1 : 0);
         if (rc < 0) {
             return rc;
@@ -619,6 +621,11 @@ static int submit_bursts(const char* who, mbx_session* s, const mbx_burst_schedu
         mbx_set_error_text(text);
         return MBE_STATUS_INVALID_ARGUMENT;
     }
+    if (!soft && sh.llr()) {
+        snprintf(text, sizeof(text), "%s: an LLR schedule has soft bursts only", who);
+        mbx_set_error_text(text);
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
     if (!soft && burst_stride < sh.bytes) {
         snprintf(text, sizeof(text), "%s: burst_stride is below mbx_burst_schedule_bytes()", who);
         mbx_set_error_text(text);
@@ -629,7 +636,7 @@ static int submit_bursts(const char* who, mbx_session* s, const mbx_burst_schedu
         mbx_set_error_text(text);
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    const BurstIn in{sched, burst_stride, soft ? sh.soft_cells * sizeof(mbe_soft_bit) : burst_stride};
+    const BurstIn in{sched, burst_stride, soft ? mbx_burst_schedule_soft_bytes(sched) : burst_stride};
     return submit(s, n, sh.frames, stream_index, bursts, soft, pcm16, pcmf, results, nullptr, &in);
 }
 

@@ -13,6 +13,7 @@ Reference interface mirrored (include/mbelib-neo/mbelib.h):
 import numpy as np
 
 from . import _native
+from . import bursts as _bursts
 from .layout import (
     CODEC_IMBE7200X4400,
     FRAME_BYTES,
@@ -163,22 +164,23 @@ class BatchDecoder:
         the F frames of a burst sit; burst row i carries the next F frames of stream i (stream_index[i]).  One mbx_process_bursts /
         _soft call: the gather on the device, then the step decode(frames, T=F) / decode_soft run, on this decoder's state, resident
         or not.  bursts: uint8 tensor or array in the schedule's form -- hard: n bursts of burst_stride bytes (default
-        schedule.burst_bytes); soft=True: [n, schedule.soft_cells, 2] (bit or dibit, reliability).  A host array is checked with
+        schedule.burst_bytes); soft=True: [n, schedule.soft_cells, 2] (bit or dibit, reliability), of an LLR schedule [n, burst_bits]
+        int16 / int8.  A host array is checked with
         mbx_burst_validate; a device tensor is the caller's to check.  Returns the dict of decode at T = F."""
         torch = _torch()
         if schedule.codec != self.codec:
             raise ValueError("the schedule is of another codec than the decoder")
         stride = schedule.burst_bytes if burst_stride is None else int(burst_stride)
+        bursts = _bursts.as_bytes(schedule, bursts, soft)
         if isinstance(bursts, np.ndarray):
-            bursts = np.ascontiguousarray(bursts, dtype=np.uint8)
-            per = schedule.soft_cells * 2 if soft else stride
+            per = schedule.soft_bytes if soft else stride
             if per > 0 and bursts.size % per == 0 and _native.lib().mbx_burst_validate(schedule.handle, bursts.ctypes.data, stride, bursts.size // per, int(soft)) == -2:
                 raise ValueError("soft bursts: a hard decision is not 0 or 1 (a dibit not 0 .. 3)" if soft else "bursts: a bit byte is not 0 or 1, or a dibit byte not 0 .. 3")
-        d_bursts = self.to_device(np.ascontiguousarray(bursts, dtype=np.uint8) if isinstance(bursts, np.ndarray) else bursts)
+        d_bursts = self.to_device(bursts)
         if d_bursts.dtype != torch.uint8 or not d_bursts.is_contiguous():
             raise ValueError("bursts must be a contiguous uint8 tensor")
         n = self.streams if stream_index is None else int(stream_index.numel())
-        if d_bursts.numel() != n * (schedule.soft_cells * 2 if soft else stride):
+        if d_bursts.numel() != n * (schedule.soft_bytes if soft else stride):
             raise ValueError("bursts must hold one burst per batch row")
         if stream_index is not None:
             if stream_index.dtype != torch.int32 or stream_index.device != self.device:
@@ -476,6 +478,23 @@ def ecc_soft_words_host(kind, soft, device=0):
     rc = _native.lib().mbx_ecc_soft_words_host(kind, soft.ctypes.data, n, out.ctypes.data, errs.ctypes.data)
     _native.check(rc, "mbx_ecc_soft_words_host")
     return out, errs
+
+
+def soft_from_llr(llr, out=None):
+    """mbx_soft_from_llr on the current torch stream: an int16 or int8 device tensor of LLRs, any shape -> uint8 [..., 2] cells
+    (bit, reliability), the bytes soft_bits_from_llr gives on the host.  For callers that hold frame-shaped LLR arrays and go on
+    to decode_soft; bursts of LLRs need no such call (bursts.FORM_LLR16 / FORM_LLR8)."""
+    torch = _torch()
+    if llr.dtype not in (torch.int16, torch.int8) or not llr.is_contiguous():
+        raise ValueError("llr must be a contiguous int16 or int8 tensor")
+    if out is None:
+        out = torch.empty(tuple(llr.shape) + (2,), dtype=torch.uint8, device=llr.device)
+    elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != 2 * llr.numel():
+        raise ValueError("out must be a contiguous uint8 tensor of two bytes per LLR")
+    with torch.cuda.device(llr.device):
+        rc = _native.lib().mbx_soft_from_llr(llr.data_ptr(), llr.element_size(), llr.numel(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+    _native.check(rc, "mbx_soft_from_llr")
+    return out
 
 
 def soft_bits_from_llr(llr):

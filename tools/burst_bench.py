@@ -7,7 +7,7 @@ Two SHAPES, random bijections with the right frame count and burst length (no ai
 --kernels   per shape: HIP-event time of one mbx_process_bursts[_soft] step against the mbx_process_batch[_soft]_resident step on
             frames that are already there.  Run it under `rocprofv3 --kernel-trace --stats -- python tools/burst_bench.py --kernels`
             for the gather kernels' own times next to their step's kernels (instances of burst_gather_kernel<form, invert> and
-            burst_gather_soft_kernel<dibits, flip>).
+            burst_gather_soft_kernel<cell, flip>).  Soft bursts as LLRs: tools/llr_gather_bench.py.
 --sessions  frames/s of sessions fed with bursts (mbx_session_submit_bursts[_soft]) against the same sessions fed with frames the
             host scatters first (numpy apply_schedule, vectorised over the batch -- kinder to the host than the per-bit C loop of
             INTEGRATION.md), 1 and 8 host threads, each thread with its own session of S / threads streams; pinned input, int16 PCM out.
