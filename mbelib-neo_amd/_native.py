@@ -1,4 +1,5 @@
-"""ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h).  Fails loudly when the library
+"""ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h,
+include/mbx_burst_groups.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -146,6 +147,21 @@ _LLR_SIGNATURES = {
     "mbx_soft_from_llr": (C.c_int, [_vp, C.c_int, _sz, _vp, _vp]),
 }
 LLR_SYMBOLS = tuple(_LLR_SIGNATURES)
+# burst groups (include/mbx_burst_groups.h): the bursts of several schedules in one call
+_GROUP_SIGNATURES = {
+    "mbx_process_burst_groups": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mbx_burst_groups_workspace_frames": (_sz, [_vp, C.c_int, C.c_int]),
+    "mbx_burst_groups_rows": (C.c_int, [_vp, C.c_int, _vp]),
+    "mbx_session_create_mixed": (C.c_int, [_vp, C.c_int, _vp, _sz, C.c_uint]),
+    "mbx_session_submit_burst_groups": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+}
+GROUP_SYMBOLS = tuple(_GROUP_SIGNATURES)
+
+
+class BurstGroupStruct(C.Structure):
+    """mbx_burst_group"""
+    _fields_ = [("sched", _vp), ("bursts", _vp), ("burst_stride", _sz), ("n_streams", C.c_int), ("bursts_per_stream", C.c_int),
+                ("stream_index", _vp), ("first_slot", C.c_int)]
 
 
 def lib():
@@ -168,7 +184,7 @@ def lib():
             handle = C.CDLL(path)
         except OSError as e:  # e.g. libamdhip64 not found
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
-        for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

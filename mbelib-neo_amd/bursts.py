@@ -15,6 +15,10 @@ emits them; the gather converts them (``cells_from_llr`` is the conversion in nu
 
 ``apply_schedule`` is the same thing in numpy, on the host: the definition, and what the tests expect of the kernels.  No
 air-interface table of any standard is written here; ``random_schedule`` and ``gap_schedule`` make schedules of a given SHAPE.
+
+``BurstGroup`` (include/mbx_burst_groups.h) is the bursts of ONE schedule in one tick -- n_streams streams with bursts_per_stream
+consecutive bursts each, every stream named by a pool slot; ``BatchDecoder.decode_burst_groups`` decodes up to MAX_GROUPS of them in
+one call, and ``apply_groups`` is its numpy definition: the mixed rows, offsets, codecs and index that one mixed ragged step takes.
 """
 import ctypes as C
 
@@ -25,6 +29,7 @@ from .layout import FRAME_BYTES, FRAME_CELLS, ROW_WIDTHS
 
 MAX_FRAMES, MAX_BITS = 18, 4096          # MBX_BURST_MAX_FRAMES, MBX_BURST_MAX_BITS
 MIXED_ROW_BYTES, MIXED_ROW_CELLS = 18, 184
+MAX_GROUPS = 8                           # MBX_BURST_MAX_GROUPS (include/mbx_burst_groups.h)
 FORM_PACKED, FORM_BITS, FORM_DIBITS = 0, 1, 2   # MBX_BURST_FORM_*
 FORM_LLR16, FORM_LLR8 = 16, 8                   # MBX_BURST_FORM_LLR*: soft bursts of one int16 / int8 LLR per received bit
 LLR_DTYPE = {FORM_LLR16: np.int16, FORM_LLR8: np.int8}
@@ -303,3 +308,85 @@ def deinterleave(schedule, bursts, soft=False, mixed_rows=False, burst_stride=No
             out = torch.zeros((n * s.frames_per_burst, row), dtype=torch.uint8, device=bursts.device)
         _native.check(L.mbx_deinterleave(s.handle, bursts.data_ptr(), per, n, out.data_ptr(), row, strm), "mbx_deinterleave")
     return out
+
+
+class BurstGroup:
+    """The bursts of ONE schedule in one tick (mbx_burst_group): n_streams streams x bursts_per_stream consecutive bursts, stream-major.
+    bursts: uint8 array or device tensor in the schedule's form -- hard: burst_stride bytes each (default schedule.burst_bytes); soft:
+    dense, schedule.soft_bytes each (LLRs may come as int16 / int8).  stream_index: the pool slot of each stream (sequence, int32
+    array or int32 device tensor); None: slots first_slot .. first_slot + n_streams - 1."""
+
+    def __init__(self, schedule, bursts, n_streams, bursts_per_stream=1, stream_index=None, first_slot=0, burst_stride=None):
+        self.schedule, self.bursts = schedule, bursts
+        self.n_streams, self.bursts_per_stream, self.first_slot = int(n_streams), int(bursts_per_stream), int(first_slot)
+        self.stream_index = stream_index
+        self.burst_stride = schedule.burst_bytes if burst_stride is None else int(burst_stride)
+
+    @property
+    def n_bursts(self):
+        return self.n_streams * self.bursts_per_stream
+
+    @property
+    def frames(self):
+        return self.n_bursts * self.schedule.frames_per_burst
+
+    def slots(self):
+        """the pool slots of the group's streams, int32 on the host"""
+        if self.stream_index is None:
+            return np.arange(self.first_slot, self.first_slot + self.n_streams, dtype=np.int32)
+        idx = self.stream_index
+        if not isinstance(idx, (np.ndarray, list, tuple, range)):
+            idx = idx.cpu().numpy()
+        return np.ascontiguousarray(idx, dtype=np.int32).reshape(-1)
+
+
+def group_rows(groups):
+    """first frame row of every group and the total behind them (mbx_burst_groups_rows): int32 [len(groups) + 1]"""
+    rows = np.zeros(len(groups) + 1, dtype=np.int64)
+    np.cumsum([g.frames for g in groups], out=rows[1:])
+    if rows[-1] > 0x7FFFFFFF:
+        raise ValueError("more than 2^31-1 frames in one call")
+    return rows.astype(np.int32)
+
+
+def apply_groups(groups, soft=False):
+    """What one burst-groups call decodes, in numpy: the numpy gather (apply_schedule) of every group into mixed rows, group after
+    group, and the layout of the ONE mixed ragged step over them.  groups: BurstGroups with HOST bursts.  Returns a dict:
+      rows          uint8 [total, MIXED_ROW_BYTES] wire rows (bytes behind an AMBE frame zero); soft: [total, MIXED_ROW_CELLS, 2]
+      frame_offset  int32 [S + 1]: stream row s owns rows frame_offset[s] .. frame_offset[s + 1] - 1, bursts_per_stream * F of them
+      stream_codec  uint8 [S]: the codec of the stream's group's schedule
+      stream_index  int32 [S]: its pool slot
+      row_of_group  int32 [len(groups) + 1]"""
+    if len(groups) > MAX_GROUPS:
+        raise ValueError("at most MAX_GROUPS groups in one call")
+    row_of_group = group_rows(groups)
+    total = int(row_of_group[-1])
+    rows = np.zeros((total, MIXED_ROW_CELLS, 2) if soft else (total, MIXED_ROW_BYTES), dtype=np.uint8)
+    counts, codecs, index = [], [], []
+    for g, first in zip(groups, row_of_group[:-1]):
+        s = g.schedule
+        if g.n_streams < 0 or g.bursts_per_stream < 1:
+            raise ValueError("a group has n_streams >= 0 streams of bursts_per_stream >= 1 bursts")
+        slots = g.slots()
+        if slots.size != g.n_streams:
+            raise ValueError("stream_index must hold one slot per stream of the group")
+        if g.n_streams:
+            raw = as_bytes(s, np.asarray(g.bursts), soft).reshape(-1)[:g.n_bursts * (s.soft_bytes if soft else g.burst_stride)]
+            got = apply_schedule(s, raw, soft=True) if soft else apply_schedule(s, raw, burst_stride=g.burst_stride)
+            rows[first:first + g.frames, :got.shape[1]] = got
+        counts += [g.bursts_per_stream * s.frames_per_burst] * g.n_streams
+        codecs += [s.codec] * g.n_streams
+        index.append(slots)
+    frame_offset = np.zeros(len(counts) + 1, dtype=np.int32)
+    np.cumsum(counts, out=frame_offset[1:])
+    return {"rows": rows, "frame_offset": frame_offset, "stream_codec": np.asarray(codecs, dtype=np.uint8),
+            "stream_index": np.concatenate(index).astype(np.int32) if index else np.zeros(0, dtype=np.int32), "row_of_group": row_of_group}
+
+
+def group_structs(groups, pointers):
+    """the ctypes array of mbx_burst_group for `groups`; pointers: one (bursts, stream_index) address pair per group (0 / None: NULL)"""
+    arr = (_native.BurstGroupStruct * max(len(groups), 1))()
+    for a, g, (bursts, index) in zip(arr, groups, pointers):
+        a.sched, a.bursts, a.burst_stride = g.schedule.handle, bursts or None, g.burst_stride
+        a.n_streams, a.bursts_per_stream, a.stream_index, a.first_slot = g.n_streams, g.bursts_per_stream, index or None, g.first_slot
+    return arr

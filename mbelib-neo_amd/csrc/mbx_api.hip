@@ -1471,6 +1471,100 @@ int mbx_process_bursts_soft(const mbx_burst_schedule* sched, int S, const int32_
                           d_results, d_records, stream);
 }
 
+// ---- burst groups (include/mbx_burst_groups.h): ONE gather over the bursts of up to eight schedules, then ONE mixed step -------------
+// As process_bursts: check, a mixed StepShape, plan_on_stream, c->mu held from the ONE growth of the workspace (to
+// mbx_burst_groups_workspace_frames, which covers the step's own rows) to the last launch.  The workspace (mbx_group_plan.h): the
+// step's rows | the gathered mixed rows | the layout words frame_offset, stream_index, stream_codec, which the gather launch itself
+// writes -- nothing is uploaded, and the mixed step (run_mixed_stages) runs unchanged on those arrays.
+static StepShape groups_step_shape(const mbx::GroupPlan& gp, bool soft, bool resident) {
+    StepShape q;
+    q.S = gp.total_streams, q.total = (size_t)gp.total_rows;
+    q.kind = soft ? kSoft : kFrames;
+    q.resident = resident;
+    q.ragged = q.mixed = true;
+    q.aligned = true;   // (the gathered rows: 256-byte aligned)
+    q.own_workspace = q.slices_allowed = true;
+    return q;
+}
+static mbx::GroupWorkspace groups_workspace(const Context* c, const mbx::GroupPlan& gp, const StepShape& q, bool soft) {
+    const size_t row = soft ? (size_t)MBX_MIXED_ROW_CELLS * sizeof(mbe_soft_bit) : (size_t)MBX_MIXED_ROW_BYTES;
+    return mbx::group_workspace(gp, plan_of(c, q).workspace_frames, sizeof(mbx::FrameParams), row);
+}
+
+size_t mbx_burst_groups_workspace_frames(const mbx_burst_group* groups, int n_groups, int soft) {
+    mbx::GroupShape shapes[MBX_BURST_MAX_GROUPS];
+    mbx::GroupPlan gp;
+    if (mbx::burst_groups_plan("mbx_burst_groups_workspace_frames", groups, n_groups, soft != 0, shapes, &gp) < 0 || gp.total_rows == 0) {
+        return 0;
+    }
+    // (the workspace of a step does not depend on the device or on the elision words: no context is asked for)
+    return groups_workspace(nullptr, gp, groups_step_shape(gp, soft != 0, false), soft != 0).frames;
+}
+
+int mbx_process_burst_groups(const mbx_burst_group* groups, int n_groups, int soft_in, mbe_parms* d_state_pool, uint32_t* d_resident,
+                             mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results,
+                             mbx_param_record* d_records, void* stream) {
+    const char* const who = "mbx_process_burst_groups";
+    const bool soft = soft_in != 0;
+    char text[160];
+    if (!batch_pointers_aligned(d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, nullptr, d_resident, nullptr)) {
+        return mbx::misaligned(who, "mbx_burst_groups.h");
+    }
+    mbx::GroupShape shapes[MBX_BURST_MAX_GROUPS];
+    mbx::GroupPlan gp;
+    int rc = mbx::burst_groups_plan(who, groups, n_groups, soft, shapes, &gp);
+    if (rc < 0) {
+        return rc;
+    }
+    if (!d_state_pool || !d_rng_pool || (gp.total_rows > 0 && !d_records)) {
+        snprintf(text, sizeof(text), "%s: state, RNG state and records are all needed", who);
+        return fail(MBE_STATUS_INVALID_ARGUMENT, text);
+    }
+    REQUIRE_CTX(c);
+    for (int i = 0; i < n_groups; ++i) {
+        const int dev = mbx::burst_shape(groups[i].sched).device;
+        if (dev != c->device) {
+            snprintf(text, sizeof(text), "%s: a schedule was made on device %d, the current device is %d", who, dev, c->device);
+            return fail(MBE_STATUS_INVALID_ARGUMENT, text);
+        }
+    }
+    if (gp.total_rows == 0) {
+        return 0;
+    }
+    StepShape q = groups_step_shape(gp, soft, d_resident != nullptr);
+    const StepPlan plan = plan_on_stream(c, q, stream);
+    const mbx::GroupWorkspace w = groups_workspace(c, gp, q, soft);
+    mbx::GroupGather gather[MBX_BURST_MAX_GROUPS];
+    int count = 0;
+    for (int i = 0; i < n_groups; ++i) {   // the groups that have a workgroup, in grid order
+        const mbx::GroupPlace& p = gp.place[i];
+        if (p.bursts) {
+            gather[count++] = mbx::GroupGather{groups[i].sched, groups[i].bursts, groups[i].burst_stride, p.bursts, groups[i].bursts_per_stream,
+                                               groups[i].stream_index, groups[i].first_slot, p.first_wg, p.first_row, p.first_stream};
+        }
+    }
+    std::lock_guard<std::mutex> lock(c->mu);
+    StreamSlot& slot = c->slots[stream];
+    rc = ensure_workspace(c, slot, w.frames, stream);
+    if (rc < 0) {
+        return rc;
+    }
+    slot.exp_codec = -1;   // rows an earlier mbx_expand_records() left behind the step's own are being replaced
+    uint8_t* const base = reinterpret_cast<uint8_t*>(slot.workspace);
+    void* const gathered = base + w.gathered;
+    const mbx::GroupLayout layout{gp.total_streams, gp.total_rows, reinterpret_cast<int32_t*>(base + w.frame_offset),
+                                  reinterpret_cast<int32_t*>(base + w.stream_index), base + w.stream_codec};
+    rc = mbx::burst_gather_groups(gather, count, soft, gp.grid, gp.lds, layout, gathered, stream);
+    if (rc < 0) {
+        return rc;
+    }
+    BatchCall b{0, gp.total_streams, 0, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, layout.d_stream_index, d_resident};
+    b.frame_offset = layout.d_frame_offset;
+    b.total = (size_t)gp.total_rows;
+    b.stream_codec = layout.d_stream_codec;
+    return issue_on_slot(c, slot, b, q, plan, gathered);
+}
+
 // ---- ragged batches: run_batch with BatchCall::frame_offset ---------------------------------------------------------------------------
 // (what can be refused without a device is refused before one is asked for, as mbx_process_batch does)
 // (`mixed`: d_stream_codec is the codec of every stream row and `codec` is not looked at)

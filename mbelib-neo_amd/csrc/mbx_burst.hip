@@ -5,6 +5,8 @@
 // packed bits, one byte per bit, one byte per dibit; soft per-bit cells, soft {dibit, reliability} pairs, one signed LLR per bit as
 // int16 or int8 (converted in the gather: mbx_llr_cell.h) -- with or without a fixed inversion sequence.  The launchers that chain a gather in
 // front of a batch step are in mbx_api.hip (they need the stream's workspace), the session submits in mbx_session.hip.
+// Burst groups (include/mbx_burst_groups.h): burst_gather_groups_kernel and burst_gather_soft_groups_kernel run the same bodies over
+// the bursts of up to eight schedules in ONE launch and write the layout words of the mixed step behind it.
 //
 // No air-interface table is written here: F, B, the strides and the tables are kernel arguments, one code object serves every
 // schedule.  The frame shapes come from the one table in mbx_codec.h (through mbx_wire_bit_of_cell for the wire order).
@@ -56,11 +58,13 @@ constexpr uint32_t kBitOf = 0x0fffu;       // ... and the received bit of an ent
 //   xor_tab    [F * fbytes] a 1 where the wire bit's received bit arrives inverted (0 for the bits that pad the last byte)
 //   lstride    bytes between two bursts in LDS
 // dynamic LDS: table | 64 * lstride | 64 * F * fbytes
+// (the body: `block` is the workgroup's place among those of ITS bursts -- blockIdx.x in burst_gather_kernel, the place inside its
+// group in burst_gather_groups_kernel)
 template <int kForm, bool kInvert>
-__global__ void __launch_bounds__(256)
-burst_gather_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride, size_t n, int F, int B, int fbytes,
-                    const uint16_t* __restrict__ wire_tab, const uint8_t* __restrict__ xor_tab, uint8_t* __restrict__ frames,
-                    int frame_stride, int lstride) {
+__device__ __forceinline__ void
+burst_gather_body(const uint8_t* __restrict__ bursts, size_t burst_stride, size_t n, int F, int B, int fbytes,
+                  const uint16_t* __restrict__ wire_tab, const uint8_t* __restrict__ xor_tab, uint8_t* __restrict__ frames,
+                  int frame_stride, int lstride, unsigned block) {
     static_assert(kInvert || kForm == MBX_BURST_FORM_PACKED, "not an instance that mbx::burst_gather launches");
     extern __shared__ uint32_t lds[];
     const int items = F * fbytes;   // output bytes of one burst; eight table entries each
@@ -69,7 +73,7 @@ burst_gather_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride, siz
     uint8_t* in = reinterpret_cast<uint8_t*>(lds + tab_dwords);
     uint8_t* out = in + kGatherBursts * lstride;
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const size_t first = (size_t)blockIdx.x * kGatherBursts;
+    const size_t first = (size_t)block * kGatherBursts;
     const int here = (int)((n - first) < (size_t)kGatherBursts ? (n - first) : (size_t)kGatherBursts);
     for (int i = tid; i < tab_dwords; i += 256) {
         lds[i] = reinterpret_cast<const uint32_t*>(wire_tab)[i];
@@ -179,6 +183,14 @@ burst_gather_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride, siz
     }
 }
 
+template <int kForm, bool kInvert>
+__global__ void __launch_bounds__(256)
+burst_gather_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride, size_t n, int F, int B, int fbytes,
+                    const uint16_t* __restrict__ wire_tab, const uint8_t* __restrict__ xor_tab, uint8_t* __restrict__ frames,
+                    int frame_stride, int lstride) {
+    burst_gather_body<kForm, kInvert>(bursts, burst_stride, n, F, B, fbytes, wire_tab, xor_tab, frames, frame_stride, lstride, blockIdx.x);
+}
+
 // ---- soft bursts -> cell arrays ----------------------------------------------------------------------------------------------------
 // A workgroup takes nb consecutive bursts (a contiguous range of staged cells, C per burst) into LDS as they come, with dword loads
 // from the first aligned dword on, then every wave takes rows of the output: a lane owns the two cells of one aligned output dword,
@@ -200,16 +212,16 @@ burst_gather_kernel(const uint8_t* __restrict__ bursts, size_t burst_stride, siz
 //   cell_tab   [F][cells] burst bit of each cell of the reference's array, kNoBit for a cell that is not on the wire
 // dynamic LDS: table | nb * C staged cells (+ one dword of slack for the alignment phase)
 template <SoftCell kCell, bool kFlip>
-__global__ void __launch_bounds__(256)
-burst_gather_soft_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, int F, int C, int cells, const uint16_t* __restrict__ cell_tab,
-                         mbe_soft_bit* __restrict__ rows_out, int row_cells, int nb) {
+__device__ __forceinline__ void
+burst_gather_soft_body(const mbe_soft_bit* __restrict__ soft, size_t n, int F, int C, int cells, const uint16_t* __restrict__ cell_tab,
+                       mbe_soft_bit* __restrict__ rows_out, int row_cells, int nb, unsigned block) {
     static_assert(kFlip || kCell == kCellBit, "not an instance that mbx::burst_gather launches");
     extern __shared__ uint32_t lds[];
     const int tab_dwords = (F * cells) >> 1;   // (every codec has an even number of cells)
     const uint16_t* tab = reinterpret_cast<const uint16_t*>(lds);
     uint16_t* in16 = reinterpret_cast<uint16_t*>(lds + tab_dwords);
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const size_t first = (size_t)blockIdx.x * (size_t)nb;
+    const size_t first = (size_t)block * (size_t)nb;
     const int here = (int)((n - first) < (size_t)nb ? (n - first) : (size_t)nb);
     for (int i = tid; i < tab_dwords; i += 256) {
         lds[i] = reinterpret_cast<const uint32_t*>(cell_tab)[i];
@@ -310,6 +322,85 @@ burst_gather_soft_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, int F,
     }
 }
 
+template <SoftCell kCell, bool kFlip>
+__global__ void __launch_bounds__(256)
+burst_gather_soft_kernel(const mbe_soft_bit* __restrict__ soft, size_t n, int F, int C, int cells, const uint16_t* __restrict__ cell_tab,
+                         mbe_soft_bit* __restrict__ rows_out, int row_cells, int nb) {
+    burst_gather_soft_body<kCell, kFlip>(soft, n, F, C, cells, cell_tab, rows_out, row_cells, nb, blockIdx.x);
+}
+
+// ---- burst groups: the bursts of several schedules in one launch (include/mbx_burst_groups.h) ----------------------------------------
+// The grid is the concatenation of the groups' workgroups.  A workgroup finds its group with a scalar loop over the (at most eight)
+// first-workgroup values of the descriptors in the kernel arguments, then enters that group's instance of the body above by a scalar
+// branch, as mixed_stream_kernel_ragged picks its codec body; its rows are written at the mixed row size from the group's first row.
+// Dynamic LDS is the largest group's.  The same launch writes the layout words of the mixed step behind it into the workspace, with
+// vector stores: the lanes that own a stream's FIRST burst write that stream's frame_offset, stream_index and stream_codec, the last
+// workgroup writes frame_offset[S].  (Every stream has a first burst and every burst a lane: each word is written exactly once.)
+__device__ __forceinline__ int group_of_workgroup(const GatherGroups& d) {
+    int g = 0;
+#pragma unroll
+    for (int i = 1; i < 8; ++i) {
+        if (i < d.count && blockIdx.x >= d.g[i].first_wg) {
+            g = i;
+        }
+    }
+    return __builtin_amdgcn_readfirstlane(g);
+}
+// `per_wg`: bursts a workgroup of this group takes
+__device__ __forceinline__ void write_group_layout(const GatherGroups& d, const GatherGroup& e, unsigned block, int per_wg) {
+    const int tid = (int)threadIdx.x;
+    if (tid < per_wg) {
+        const uint32_t burst = block * (uint32_t)per_wg + (uint32_t)tid;
+        if (burst < e.n) {
+            const uint32_t j = burst / (uint32_t)e.bursts_per_stream;
+            if (burst == j * (uint32_t)e.bursts_per_stream) {
+                const int s = e.first_stream + (int)j;
+                d.frame_offset[s] = e.first_row + (int)(burst * (uint32_t)e.F);
+                d.stream_index[s] = e.index ? e.index[j] : e.first_slot + (int)j;
+                d.stream_codec[s] = (uint8_t)e.codec;
+            }
+        }
+    }
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) {
+        d.frame_offset[d.S] = d.total;
+    }
+}
+
+__global__ void __launch_bounds__(256) burst_gather_groups_kernel(GatherGroups d, uint8_t* __restrict__ rows) {
+    const GatherGroup& e = d.g[group_of_workgroup(d)];
+    const unsigned block = blockIdx.x - e.first_wg;
+    write_group_layout(d, e, block, kGatherBursts);
+    const uint8_t* in = static_cast<const uint8_t*>(e.in);
+    uint8_t* out = rows + (size_t)e.first_row * (size_t)MBX_MIXED_ROW_BYTES;
+#define MBX_GROUP_HARD(form, invert) \
+    burst_gather_body<form, invert>(in, e.stride, (size_t)e.n, e.F, e.B, e.unit, e.tab, e.xor_tab, out, MBX_MIXED_ROW_BYTES, e.per, block)
+    switch (e.instance) {
+    case kHardPacked: MBX_GROUP_HARD(MBX_BURST_FORM_PACKED, false); break;
+    case kHardPackedInvert: MBX_GROUP_HARD(MBX_BURST_FORM_PACKED, true); break;
+    case kHardBits: MBX_GROUP_HARD(MBX_BURST_FORM_BITS, true); break;
+    default: MBX_GROUP_HARD(MBX_BURST_FORM_DIBITS, true); break;
+    }
+#undef MBX_GROUP_HARD
+}
+
+__global__ void __launch_bounds__(256) burst_gather_soft_groups_kernel(GatherGroups d, mbe_soft_bit* __restrict__ rows) {
+    const GatherGroup& e = d.g[group_of_workgroup(d)];
+    const unsigned block = blockIdx.x - e.first_wg;
+    write_group_layout(d, e, block, e.per);
+    const mbe_soft_bit* in = static_cast<const mbe_soft_bit*>(e.in);
+    mbe_soft_bit* out = rows + (size_t)e.first_row * (size_t)MBX_MIXED_ROW_CELLS;
+#define MBX_GROUP_SOFT(cell, flip) \
+    burst_gather_soft_body<cell, flip>(in, (size_t)e.n, e.F, e.staged, e.unit, e.tab, out, MBX_MIXED_ROW_CELLS, e.per, block)
+    switch (e.instance) {
+    case kSoftBit: MBX_GROUP_SOFT(kCellBit, false); break;
+    case kSoftBitFlip: MBX_GROUP_SOFT(kCellBit, true); break;
+    case kSoftDibit: MBX_GROUP_SOFT(kCellDibit, true); break;
+    case kSoftLlr16: MBX_GROUP_SOFT(kCellLlr16, true); break;
+    default: MBX_GROUP_SOFT(kCellLlr8, true); break;
+    }
+#undef MBX_GROUP_SOFT
+}
+
 }  // namespace mbx
 
 // ---- the schedule (host) -----------------------------------------------------------------------------------------------------------
@@ -393,6 +484,103 @@ int burst_gather(const mbx_burst_schedule* sched, bool soft, const void* d_in, s
     }
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : hip_failed("", soft ? "the soft burst gather" : "the burst gather", e);
+}
+
+int burst_gather_per_workgroup(const mbx_burst_schedule* sched, bool soft) { return soft ? sched->soft_bursts : kGatherBursts; }
+unsigned burst_gather_lds(const mbx_burst_schedule* sched, bool soft) { return soft ? sched->soft_lds : sched->hard_lds; }
+
+int burst_groups_plan(const char* who, const mbx_burst_group* groups, int n_groups, bool soft, GroupShape* shapes, GroupPlan* plan) {
+    char text[200];
+    const auto refused = [&](const char* why) {
+        snprintf(text, sizeof(text), "%s: %s", who, why);
+        mbx_set_error_text(text);
+        return MBE_STATUS_INVALID_ARGUMENT;
+    };
+    if (n_groups < 0 || n_groups > MBX_BURST_MAX_GROUPS) {
+        return refused(group_refusal_text(kGroupCount));
+    }
+    if (n_groups > 0 && !groups) {
+        return refused("groups is NULL");
+    }
+    for (int i = 0; i < n_groups; ++i) {
+        const mbx_burst_group& g = groups[i];
+        // (counts and alignment first: they need no schedule -- of one only whether its soft bursts are int8 LLRs)
+        if (g.n_streams < 0) {
+            return refused(group_refusal_text(kGroupNegative));
+        }
+        if (g.bursts_per_stream < 1) {
+            return refused(group_refusal_text(kGroupBurstsPer));
+        }
+        // (of a group without streams neither pointer is looked at)
+        if (g.n_streams > 0 && (!aligned_to(g.bursts, soft ? (g.sched ? g.sched->shape.soft_align() : 2) : 1) || !aligned_to(g.stream_index, 4))) {
+            return misaligned(who, "mbx_burst_groups.h");
+        }
+        if (!g.sched) {
+            return refused("a group without a schedule");
+        }
+        const BurstShape& sh = g.sched->shape;
+        if (!soft && sh.llr()) {
+            return refused("an LLR schedule has soft bursts only");
+        }
+        if (g.n_streams > 0 && !g.bursts) {
+            return refused("a group without bursts");
+        }
+        if (!soft && g.burst_stride < sh.bytes) {
+            return refused("a burst_stride below mbx_burst_schedule_bytes()");
+        }
+        GroupShape& q = shapes[i];
+        q.codec = sh.codec, q.form = sh.form, q.frames = sh.frames;
+        q.n_streams = g.n_streams, q.bursts_per_stream = g.bursts_per_stream;
+        q.bursts_per_wg = burst_gather_per_workgroup(g.sched, soft);
+        q.lds = burst_gather_lds(g.sched, soft);
+    }
+    const GroupRefusal r = plan_groups(shapes, n_groups, plan);
+    return r == kGroupsOk ? 0 : refused(group_refusal_text(r));
+}
+
+int burst_gather_groups(const GroupGather* groups, int count, bool soft, unsigned grid, unsigned lds, const GroupLayout& layout, void* d_rows,
+                        void* stream) {
+    GatherGroups d{};
+    d.count = count;
+    d.S = layout.S, d.total = layout.total;
+    d.frame_offset = layout.d_frame_offset, d.stream_index = layout.d_stream_index, d.stream_codec = layout.d_stream_codec;
+    for (int i = 0; i < count; ++i) {
+        const GroupGather& g = groups[i];
+        const mbx_burst_schedule* s = g.sched;
+        const BurstShape& sh = s->shape;
+        GatherGroup& e = d.g[i];
+        e.in = g.d_in, e.stride = g.burst_stride;
+        e.tab = soft ? s->d_cell_tab : s->d_wire_tab;
+        e.xor_tab = s->d_xor_tab;
+        e.index = g.d_index;
+        e.n = g.bursts;
+        e.F = sh.frames, e.B = sh.bits;
+        e.unit = soft ? (int)sh.cells : (int)sh.frame_bytes;
+        e.staged = s->staged_cells;
+        e.per = soft ? s->soft_bursts : s->lstride;
+        // (the instance burst_gather launches for this schedule)
+        if (soft) {
+            e.instance = sh.form == MBX_BURST_FORM_LLR16    ? kSoftLlr16
+                         : sh.form == MBX_BURST_FORM_LLR8   ? kSoftLlr8
+                         : sh.form == MBX_BURST_FORM_DIBITS ? kSoftDibit
+                         : s->inverts                       ? kSoftBitFlip
+                                                            : kSoftBit;
+        } else {
+            e.instance = sh.form == MBX_BURST_FORM_DIBITS ? kHardDibits
+                         : sh.form == MBX_BURST_FORM_BITS ? kHardBits
+                         : s->inverts                     ? kHardPackedInvert
+                                                          : kHardPacked;
+        }
+        e.first_wg = g.first_wg, e.first_row = g.first_row, e.first_stream = g.first_stream;
+        e.bursts_per_stream = g.bursts_per_stream, e.codec = sh.codec, e.first_slot = g.first_slot;
+    }
+    if (soft) {
+        hipLaunchKernelGGL(burst_gather_soft_groups_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, d, static_cast<mbe_soft_bit*>(d_rows));
+    } else {
+        hipLaunchKernelGGL(burst_gather_groups_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, d, static_cast<uint8_t*>(d_rows));
+    }
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : hip_failed("", soft ? "the soft gather of the burst groups" : "the gather of the burst groups", e);
 }
 
 }  // namespace mbx
@@ -657,6 +845,40 @@ int mbx_burst_validate(const mbx_burst_schedule* sched, const void* bursts, size
             return MBE_STATUS_INVALID_BITS;
         }
     }
+    return 0;
+}
+
+int mbx_burst_groups_rows(const mbx_burst_group* groups, int n_groups, int32_t* row_of_group) {
+    mbx::GroupShape shapes[MBX_BURST_MAX_GROUPS];
+    mbx::GroupPlan plan;
+    if (!row_of_group) {
+        mbx_set_error_text("mbx_burst_groups_rows: row_of_group is NULL");
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    // (soft: neither the stride nor the hard-only rule is this call's to judge; a NULL bursts pointer is the launcher's)
+    if (n_groups < 0 || n_groups > MBX_BURST_MAX_GROUPS || (n_groups > 0 && !groups)) {
+        mbx_set_error_text("mbx_burst_groups_rows: n_groups must be 0 .. MBX_BURST_MAX_GROUPS, with groups");
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    for (int i = 0; i < n_groups; ++i) {
+        if (!groups[i].sched) {
+            mbx_set_error_text("mbx_burst_groups_rows: a group without a schedule");
+            return MBE_STATUS_INVALID_ARGUMENT;
+        }
+        shapes[i].frames = groups[i].sched->shape.frames;
+        shapes[i].n_streams = groups[i].n_streams, shapes[i].bursts_per_stream = groups[i].bursts_per_stream;
+    }
+    const mbx::GroupRefusal r = mbx::plan_groups(shapes, n_groups, &plan);
+    if (r != mbx::kGroupsOk) {
+        char text[160];
+        snprintf(text, sizeof(text), "mbx_burst_groups_rows: %s", mbx::group_refusal_text(r));
+        mbx_set_error_text(text);
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    for (int i = 0; i < n_groups; ++i) {
+        row_of_group[i] = plan.place[i].first_row;
+    }
+    row_of_group[n_groups] = plan.total_rows;
     return 0;
 }
 

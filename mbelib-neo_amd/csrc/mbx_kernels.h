@@ -132,6 +132,38 @@ __global__ void burst_gather_kernel(const uint8_t*, size_t, size_t, int, int, in
 enum SoftCell { kCellBit, kCellDibit, kCellLlr16, kCellLlr8 };   // what a staged cell of a soft burst is
 template <SoftCell kCell, bool kFlip>
 __global__ void burst_gather_soft_kernel(const mbe_soft_bit*, size_t, int, int, int, const uint16_t*, mbe_soft_bit*, int, int);
+// Burst groups (include/mbx_burst_groups.h): ONE gather launch over the bursts of up to eight schedules, its grid the concatenation
+// of the groups' workgroups.  The descriptors travel BY VALUE in the kernel arguments -- every field a scalar load, nothing uploaded
+// per call, the launch capturable.  The same launch writes the layout words of the mixed step behind it.
+enum HardGather { kHardPacked, kHardPackedInvert, kHardBits, kHardDibits };              // the instances burst_gather launches, hard ...
+enum SoftGather { kSoftBit, kSoftBitFlip, kSoftDibit, kSoftLlr16, kSoftLlr8 };           // ... and soft
+struct GatherGroup {
+    const void*     in;          // the group's bursts ...
+    size_t          stride;      // ... hard: this many bytes apart; soft: dense
+    const uint16_t* tab;         // wire table (hard) | cell table (soft)
+    const uint8_t*  xor_tab;     // hard: the inversion sequence per output byte
+    const int32_t*  index;       // pool slot of each stream of the group, or nullptr: first_slot + j
+    uint32_t        n;           // bursts
+    int             F, B;        // frames per burst, burst bits
+    int             unit;        // frame bytes (hard) | cells (soft) of the codec
+    int             staged;      // soft: staged cells of one burst
+    int             per;         // hard: lstride; soft: bursts per workgroup
+    int             instance;    // HardGather | SoftGather: form and inversion
+    uint32_t        first_wg;    // of the grid
+    int             first_row;   // frame row of the step
+    int             first_stream;   // stream row of the step
+    int             bursts_per_stream, codec, first_slot;
+};
+struct GatherGroups {
+    GatherGroup g[8];            // (MBX_BURST_MAX_GROUPS) the groups that have a workgroup, in grid order
+    int         count;
+    int         S, total;        // stream rows and frame rows of the step
+    int32_t*    frame_offset;    // [S + 1] ...
+    int32_t*    stream_index;    // [S] ...
+    uint8_t*    stream_codec;    // [S]: the layout words, in the workspace
+};
+__global__ void burst_gather_groups_kernel(GatherGroups, uint8_t*);
+__global__ void burst_gather_soft_groups_kernel(GatherGroups, mbe_soft_bit*);
 
 // ---- mbx_api.hip ---------------------------------------------------------------------------------------------------------------
 // (C linkage: defined inside the extern "C" block of the entry points, so the profiler prints the bare name)

@@ -26,6 +26,7 @@
 
 #include "mbx.h"
 #include "mbx_burst.h"
+#include "mbx_burst_groups.h"
 #include "mbx_codec.h"
 #include "mbx_gather.h"
 #include "mbx_host.h"
@@ -102,6 +103,8 @@ struct mbx_session {
     Slot     slot[kDepth];
     unsigned long long submitted = 0;
     std::vector<uint8_t> seen;   // submit_indexed: one mark per stream, to refuse an index that names a stream twice
+    std::vector<uint8_t> stream_codec;   // a MIXED session (mbx_session_create_mixed): the codec of every stream; empty: all of `codec`
+    bool mixed() const { return !stream_codec.empty(); }
 };
 
 namespace {
@@ -173,8 +176,24 @@ struct BurstIn {
 int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
             mbe_process_result* results, mbx_param_record* records, const BurstIn* burst);
 
+int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records);
+
+// a mixed session takes burst groups only
+int refuse_mixed(const mbx_session* s, const char* who) {
+    if (s && s->mixed()) {
+        char text[160];
+        snprintf(text, sizeof(text), "%s: a mixed session takes burst groups only (mbx_session_submit_burst_groups)", who);
+        mbx_set_error_text(text);
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    return 0;
+}
+
 int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst = nullptr) {
+    if (refuse_mixed(s, "mbx_session_submit") < 0) {
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
     if (!s || !frames || n < 0 || T < 0 || n > s->streams || (size_t)n * (size_t)T > s->max_frames) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
@@ -320,8 +339,13 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
     if (rc < 0) {
         return rc;
     }
+    return copy_out(s, sl, nf, pcm16, pcmf, results, records);
+}
+
+// ---- out ----: behind the compute stream's launches of a submit of nf frames, the outputs to the caller (or to the slot's staging)
+int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records) {
+    int rc = 0;
     S_TRY(hipEventRecord(sl.comp, s->s_comp));
-    // ---- out ----
     S_TRY(hipStreamWaitEvent(s->s_out, sl.comp, 0));
     sl.nout = 0;
     auto out = [&](void* user, const void* dev, auto*& stage, size_t per_frame) -> int {   // per_frame elements of *stage per frame
@@ -364,11 +388,18 @@ void mbx_host_free(void* p) {
     }
 }
 
-int mbx_session_create(mbx_session** out, int codec, int streams, size_t max_frames_per_submit, unsigned outputs) {
+// (stream_codec: a mixed session -- `codec` is then none (-1), and the slot buffers are sized for mixed rows)
+static int create_session(mbx_session** out, int codec, const uint8_t* stream_codec, int streams, size_t max_frames_per_submit, unsigned outputs) {
     const mbx::CodecShape* shape = mbx::codec_shape(codec);
-    if (!out || streams <= 0 || max_frames_per_submit == 0 || !shape
+    if (!out || streams <= 0 || max_frames_per_submit == 0 || (!shape && !stream_codec)
         || (outputs & ~(MBX_SESSION_PCM16 | MBX_SESSION_PCMF | MBX_SESSION_RESULTS)) != 0u) {
         return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    for (int i = 0; stream_codec && i < streams; ++i) {
+        if (!mbx::codec_shape(stream_codec[i])) {
+            mbx_set_error_text("mbx_session_create_mixed: a stream_codec byte is not one of MBX_CODEC_*");
+            return MBE_STATUS_INVALID_ARGUMENT;
+        }
     }
     int dev = -1;
     S_TRY(hipGetDevice(&dev));
@@ -385,8 +416,11 @@ int mbx_session_create(mbx_session** out, int codec, int streams, size_t max_fra
     s->streams = streams;
     s->max_frames = max_frames_per_submit;
     s->outputs = outputs ? outputs : MBX_SESSION_PCM16;
-    s->frame_bytes = (size_t)shape->frame_bytes;
-    s->soft_bytes = sizeof(mbe_soft_bit) * (size_t)shape->cells;
+    s->frame_bytes = stream_codec ? (size_t)MBX_MIXED_ROW_BYTES : (size_t)shape->frame_bytes;
+    s->soft_bytes = sizeof(mbe_soft_bit) * (stream_codec ? (size_t)MBX_MIXED_ROW_CELLS : (size_t)shape->cells);
+    if (stream_codec) {
+        s->stream_codec.assign(stream_codec, stream_codec + streams);
+    }
     *out = s;
     auto bail = [&](int rc) {
         mbx_session_destroy(s);
@@ -438,6 +472,18 @@ int mbx_session_create(mbx_session** out, int codec, int streams, size_t max_fra
     }
     rc = mbx_session_reset(s, 0, streams);
     return rc < 0 ? bail(rc) : 0;
+}
+
+int mbx_session_create(mbx_session** out, int codec, int streams, size_t max_frames_per_submit, unsigned outputs) {
+    return create_session(out, codec, nullptr, streams, max_frames_per_submit, outputs);
+}
+
+int mbx_session_create_mixed(mbx_session** out, int streams, const uint8_t* stream_codec, size_t max_frames_per_submit, unsigned outputs) {
+    if (!stream_codec) {
+        mbx_set_error_text("mbx_session_create_mixed: stream_codec is NULL");
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    return create_session(out, -1, stream_codec, streams, max_frames_per_submit, outputs);
 }
 
 int mbx_session_destroy(mbx_session* s) {
@@ -612,7 +658,7 @@ int mbx_session_submit_soft_indexed(mbx_session* s, int n, int T, const int32_t*
 static int submit_bursts(const char* who, mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index, const void* bursts,
                          size_t burst_stride, bool soft, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
     char text[160];
-    if (!s || !sched || !bursts || n < 0) {
+    if (!s || !sched || !bursts || n < 0 || refuse_mixed(s, who) < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     const mbx::BurstShape sh = mbx::burst_shape(sched);
@@ -648,6 +694,163 @@ int mbx_session_submit_bursts(mbx_session* s, const mbx_burst_schedule* sched, i
 int mbx_session_submit_bursts_soft(mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index, const mbe_soft_bit* soft,
                                    int16_t* pcm16, float* pcmf, mbe_process_result* results) {
     return submit_bursts("mbx_session_submit_bursts_soft", s, sched, n, stream_index, soft, 0, true, pcm16, pcmf, results);
+}
+
+// ---- burst groups (include/mbx_burst_groups.h) --------------------------------------------------------------------------------------
+// The groups' bursts into the slot's burst buffer, each group at a 16-byte aligned offset (pinned 16-byte aligned buffers read in
+// place, others through the slot's pinned staging at the same offsets), their indices into the slot's index words, then
+// mbx_process_burst_groups on the compute stream with the groups rewritten to those device addresses, and the outputs out.
+static int enqueue_groups(mbx_session* s, Slot& sl, const mbx_burst_group* groups, int n_groups, bool soft, const mbx::GroupPlan& gp,
+                          int16_t* pcm16, float* pcmf, mbe_process_result* results) {
+    size_t at[MBX_BURST_MAX_GROUPS], bytes[MBX_BURST_MAX_GROUPS], total = 0;
+    bool staged = false, indexed = false;
+    for (int i = 0; i < n_groups; ++i) {
+        const size_t per = soft ? mbx_burst_schedule_soft_bytes(groups[i].sched) : groups[i].burst_stride;
+        at[i] = total;
+        // (of the last hard burst only the schedule's bytes are there to read, not its whole stride)
+        bytes[i] = gp.place[i].bursts ? ((size_t)gp.place[i].bursts - 1) * per + (soft ? per : mbx_burst_schedule_bytes(groups[i].sched)) : 0;
+        total = (total + bytes[i] + 15) & ~(size_t)15;
+        if (bytes[i] && (!is_pinned(groups[i].bursts) || (reinterpret_cast<uintptr_t>(groups[i].bursts) & 15u))) {
+            staged = true;
+        }
+        indexed = indexed || (gp.place[i].bursts && groups[i].stream_index);
+    }
+    if (sl.bursts_cap < total) {
+        (void)hipFree(sl.d_bursts);
+        sl.d_bursts = nullptr;
+        sl.bursts_cap = 0;
+        S_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_bursts), total));
+        sl.bursts_cap = total;
+    }
+    if (staged && sl.h_bursts_cap < total) {
+        (void)hipHostFree(sl.h_bursts);
+        sl.h_bursts = nullptr;
+        sl.h_bursts_cap = 0;
+        S_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.h_bursts), total, hipHostMallocDefault));
+        sl.h_bursts_cap = total;
+    }
+    int rc = 0;
+    if (indexed) {
+        rc = pinned(sl.h_index, (size_t)s->streams);
+        if (rc < 0) {
+            return rc;
+        }
+    }
+    mbx_burst_group dev[MBX_BURST_MAX_GROUPS];
+    for (int i = 0; i < n_groups; ++i) {
+        dev[i] = groups[i];
+        dev[i].bursts = sl.d_bursts + at[i];
+        dev[i].stream_index = nullptr;
+        if (!bytes[i]) {
+            continue;
+        }
+        const uint8_t* src = static_cast<const uint8_t*>(groups[i].bursts);
+        if (!is_pinned(src) || (reinterpret_cast<uintptr_t>(src) & 15u)) {
+            memcpy(sl.h_bursts + at[i], src, bytes[i]);
+            src = sl.h_bursts + at[i];
+        }
+        const void* dev_view = src;
+        void* mapped = nullptr;
+        if (hipHostGetDevicePointer(&mapped, const_cast<uint8_t*>(src), 0) == hipSuccess && mapped) {
+            dev_view = mapped;
+        } else {
+            (void)hipGetLastError();
+        }
+        rc = mbx_stage_in(sl.d_bursts + at[i], dev_view, bytes[i], s->s_comp);
+        if (rc < 0) {
+            return rc;
+        }
+        if (groups[i].stream_index) {   // (the groups name every stream once: their indices fit the slot's `streams` words, at their stream rows)
+            memcpy(sl.h_index + gp.place[i].first_stream, groups[i].stream_index, (size_t)groups[i].n_streams * sizeof(int32_t));
+            dev[i].stream_index = sl.d_index + gp.place[i].first_stream;
+        }
+    }
+    if (indexed) {
+        rc = mbx_stage_in(sl.d_index, sl.h_index, (size_t)gp.total_streams * sizeof(int32_t), s->s_comp);
+        if (rc < 0) {
+            return rc;
+        }
+    }
+    rc = mbx_process_burst_groups(dev, n_groups, soft ? 1 : 0, s->d_state, s->d_resident, s->d_rng, pcm16 ? sl.d_pcm16 : nullptr,
+                                  pcmf ? sl.d_pcmf : nullptr, results ? sl.d_results : nullptr, sl.d_records, s->s_comp);
+    if (rc < 0) {
+        return rc;
+    }
+    return copy_out(s, sl, (size_t)gp.total_rows, pcm16, pcmf, results, nullptr);
+}
+
+int mbx_session_submit_burst_groups(mbx_session* s, const mbx_burst_group* groups, int n_groups, int soft_in, int16_t* pcm16, float* pcmf,
+                                    mbe_process_result* results) {
+    const char* const who = "mbx_session_submit_burst_groups";
+    const bool soft = soft_in != 0;
+    char text[200];
+    const auto refused = [&](const char* why) {
+        snprintf(text, sizeof(text), "%s: %s", who, why);
+        mbx_set_error_text(text);
+        return MBE_STATUS_INVALID_ARGUMENT;
+    };
+    if (!s) {
+        return refused("no session");
+    }
+    mbx::GroupShape shapes[MBX_BURST_MAX_GROUPS];
+    mbx::GroupPlan gp;
+    int rc = mbx::burst_groups_plan(who, groups, n_groups, soft, shapes, &gp);
+    if (rc < 0) {
+        return rc;
+    }
+    if ((pcm16 && !(s->outputs & MBX_SESSION_PCM16)) || (pcmf && !(s->outputs & MBX_SESSION_PCMF)) || (results && !(s->outputs & MBX_SESSION_RESULTS))) {
+        return refused("an output the session was not created for");
+    }
+    if ((size_t)gp.total_rows > s->max_frames) {
+        return refused("more frames than max_frames_per_submit");
+    }
+    // every group's schedule is of the codec of every stream the group names; slots in range, none named twice across the groups
+    s->seen.assign((size_t)s->streams, 0);
+    for (int i = 0; i < n_groups; ++i) {
+        const mbx_burst_group& g = groups[i];
+        const mbx::BurstShape sh = mbx::burst_shape(g.sched);
+        if (sh.device != s->device) {
+            return refused("a schedule of another device than the session");
+        }
+        for (int j = 0; j < g.n_streams; ++j) {
+            const long long slot = g.stream_index ? (long long)g.stream_index[j] : (long long)g.first_slot + j;
+            if (slot < 0 || slot >= s->streams || s->seen[(size_t)slot]) {
+                return refused("stream index out of range or listed twice");
+            }
+            s->seen[(size_t)slot] = 1;
+            if ((s->mixed() ? (int)s->stream_codec[(size_t)slot] : s->codec) != sh.codec) {
+                return refused("a schedule of another codec than a stream its group names");
+            }
+        }
+    }
+    for (int i = 0; i < n_groups; ++i) {   // bursts of a form that can be invalid (mbx_burst_validate)
+        if (gp.place[i].bursts && !mbx::burst_shape(groups[i].sched).llr()) {
+            rc = mbx_burst_validate(groups[i].sched, groups[i].bursts, groups[i].burst_stride, (size_t)gp.place[i].bursts, soft ? 1 : 0);
+            if (rc < 0) {
+                return rc;
+            }
+        }
+    }
+    if (gp.total_rows == 0) {
+        return 0;
+    }
+    DeviceGuard guard(s->device);
+    Slot& sl = s->slot[s->submitted % kDepth];
+    rc = finish_slot(sl);
+    if (rc < 0) {
+        return rc;
+    }
+    rc = enqueue_groups(s, sl, groups, n_groups, soft, gp, pcm16, pcmf, results);
+    if (rc < 0) {   // (as submit: drain, so that the next submit may reuse the slot at once)
+        (void)hipStreamSynchronize(s->s_comp);
+        (void)hipStreamSynchronize(s->s_out);
+        (void)hipGetLastError();
+        sl.nout = 0;
+        return rc;
+    }
+    sl.busy = true;
+    ++s->submitted;
+    return 0;
 }
 
 }  // extern "C"

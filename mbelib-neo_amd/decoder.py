@@ -205,6 +205,60 @@ class BatchDecoder:
         _native.check(rc, "mbx_process_bursts")
         return out
 
+    def decode_burst_groups(self, groups, soft=False, want_pcm16=True, want_float=False, want_results=True, out=None):
+        """Burst groups (bursts.BurstGroup, up to bursts.MAX_GROUPS, all hard or all soft): the bursts of several schedules, of any
+        codecs, decoded by ONE mbx_process_burst_groups call on this decoder's state pool, resident or not, whatever the decoder's own
+        codec is -- one gather launch over all groups, then one mixed ragged step.  Rows run group after group, inside a group stream
+        after stream, burst after burst, frame after frame.  Host bursts are checked with mbx_burst_validate and uploaded, device
+        tensors are the caller's to check; the slots the groups name are checked here (in range, none twice).  The codec of a slot
+        stays what it was in its earlier calls: that is the caller's to keep.  Returns the dict of decode plus "row_of_group"
+        (int32 host array, len(groups) + 1)."""
+        torch = _torch()
+        groups = list(groups)
+        if len(groups) > _bursts.MAX_GROUPS:
+            raise ValueError("at most MAX_GROUPS groups in one call")
+        row_of_group = _bursts.group_rows(groups)
+        slots = np.concatenate([g.slots() for g in groups]) if groups else np.zeros(0, dtype=np.int32)
+        if slots.size and (np.unique(slots).size != slots.size or slots.min() < 0 or slots.max() >= self.streams):
+            raise ValueError("stream_index: out of range, or a slot named twice (two rows would race on one state)")
+        L = _native.lib()
+        keep, pointers = [], []
+        for g in groups:
+            s = g.schedule
+            b = _bursts.as_bytes(s, g.bursts, soft)
+            if not isinstance(b, np.ndarray) and (b.dtype != torch.uint8 or not b.is_contiguous()):
+                raise ValueError("bursts must be a contiguous uint8 tensor")
+            # of the last hard burst the schedule's bytes are read, not its whole stride
+            per = s.soft_bytes if soft else g.burst_stride
+            need = (g.n_bursts - 1) * per + (per if soft else s.burst_bytes) if g.n_bursts else 0
+            if (b.size if isinstance(b, np.ndarray) else b.numel()) < need:
+                raise ValueError("bursts must hold n_streams * bursts_per_stream bursts")
+            if isinstance(b, np.ndarray) and g.n_bursts and L.mbx_burst_validate(s.handle, b.ctypes.data, g.burst_stride, g.n_bursts, int(soft)) == -2:
+                raise ValueError("burst groups: a bit byte, dibit or hard decision above its range")
+            d_b = self.to_device(b)
+            idx = g.stream_index
+            if idx is not None and not isinstance(idx, torch.Tensor):
+                idx = torch.from_numpy(g.slots()).to(self.device)
+            if idx is not None and (idx.dtype != torch.int32 or idx.device != self.device or idx.numel() != g.n_streams):
+                raise ValueError("stream_index must be an int32 tensor of n_streams slots on the decoder's device")
+            keep.append((d_b, idx))
+            pointers.append((d_b.data_ptr() if d_b.numel() else 0, idx.data_ptr() if idx is not None and idx.numel() else 0))
+        if out is None:
+            out = self.make_outputs(0, want_pcm16, want_float, want_results, total=int(row_of_group[-1]))
+        out["row_of_group"] = row_of_group
+
+        def ptr(t):
+            return t.data_ptr() if t is not None else None
+
+        arr = _bursts.group_structs(groups, pointers)
+        with torch.cuda.device(self.device):
+            rc = L.mbx_process_burst_groups(arr, len(groups), int(soft), self.state.data_ptr(), ptr(self.resident), self.rng.data_ptr(),
+                                            ptr(out["pcm16"]), ptr(out["pcmf"]), ptr(out["results"]), out["records"].data_ptr(),
+                                            torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_process_burst_groups")
+        out["_inputs"] = keep   # the launch is asynchronous: the uploaded bursts live as long as the outputs
+        return out
+
     def decode_ragged(self, frames, counts, soft=False, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None,
                       codec=None):
         """A frame count per stream: row i of the batch brings counts[i] >= 0 frames (host sequence or array), its rows of `frames`
