@@ -10,7 +10,8 @@
  * ecc -> demodulate -> ecc -> process*Data sequence, tones, and the stderr dump helpers -- so the library can stand
  * in for libmbe-neo.so.2 at link or load time.
  *
- * There is no CPU compute path: the first call initialises the GPU (device $MBX_DEVICE or 0,
+ * There is no CPU compute path: the first call initialises the GPU (device $MBX_DEVICE or 0 -- or the devices listed in
+ * $MBX_DEVICES, over which threads and queued channels are then spread: mbe_neo_shards.h --,
  * tables from $MBX_TABLES or <library dir>/data/mbx_tables.bin) and the process aborts with a
  * message on stderr if that fails.  Like the reference (mbelib.h:28-30) the processing functions are re-entrant per
  * stream: each host thread has its own HIP stream, device scratch and RNG state.

@@ -11,18 +11,22 @@
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_map>
 #include <algorithm>
 #include <vector>
 
+#include "mbe_device_list.h"
 #include "mbe_flush_plan.h"
 #include "mbe_neo_amd.h"
+#include "mbe_neo_shards.h"
 #include "mbx.h"
 #include "mbx_cells.h"
 #include "mbx_codec.h"
@@ -35,7 +39,14 @@ namespace {
 }
 
 std::once_flag g_once;
-int g_device = 0;   // MBX_DEVICE: the one device the per-frame API runs on
+// MBX_DEVICES (mbe_device_list.h): the shards the per-frame API runs on, each on its device.  Unset: ONE shard on MBX_DEVICE (or 0).
+// A thread lives on its HOME shard's device -- its Slot, so every synchronous call --; queue mode spreads the channels of a
+// thread's batch over all shards.  Run on one card only so far (a device named several times); DESIGN.md §6.
+mbx::DeviceList g_shards;
+std::atomic<int> g_threads{0};   // threads that have made their Slot: the next one's ordinal
+// pinned arrays of queue mode: with several shards they are allocated with the shard's device current and must be visible to it
+// whichever device that is -- portable and mapped, said explicitly (the zero-copy flush has the kernels read and write them)
+unsigned g_pin_flags = hipHostMallocDefault;
 // MBE_NEO_FRAME_SERVER=1: synchronous calls are served by a resident wavefront (mbx_frame_server_start) instead of a launch each.
 // OPT-IN: measured 20.9 us per call against 22.5 us (the state still crosses PCIe both ways in every call, which is what
 // bounds it), and a kernel that stays on the device occupies one of HIP's few hardware queues while it lives -- other streams
@@ -67,15 +78,31 @@ void init_once() {
     const size_t n = fread(blob.data(), 1, blob.size(), f);
     fclose(f);
     const char* dev = getenv("MBX_DEVICE");
-    g_device = dev ? atoi(dev) : 0;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess) {
+        count = 0;
+        (void)hipGetLastError();
+    }
+    const char* why = nullptr;
+    if (!mbx::parse_device_list(getenv("MBX_DEVICES"), count, dev ? atoi(dev) : 0, &g_shards, &why)) {   // MBX_DEVICES wins over MBX_DEVICE
+        fprintf(stderr, "libmbe_neo_amd: %s (MBX_DEVICES: 'all', or device indices separated by commas; %d device%s here)\n", why, count,
+                count == 1 ? "" : "s");
+        abort();
+    }
+    if (g_shards.n > 1) {
+        g_pin_flags = hipHostMallocPortable | hipHostMallocMapped;
+    }
     if (const char* fs = getenv("MBE_NEO_FRAME_SERVER")) {
         g_frame_server = atoi(fs) != 0;
     }
     if (const char* sh = getenv("MBE_NEO_FRAME_SHADOW")) {
         g_frame_shadow = atoi(sh) != 0;
     }
-    if (mbx_init(g_device, blob.data(), n) != 0) {
-        die("mbx_init");
+    for (int i = 0; i < g_shards.n; ++i) {   // once per DISTINCT device
+        if (std::find(g_shards.device, g_shards.device + i, g_shards.device[i]) == g_shards.device + i
+            && mbx_init(g_shards.device[i], blob.data(), n) != 0) {
+            die("mbx_init");
+        }
     }
 }
 
@@ -128,9 +155,13 @@ struct Slot {
         size_t      n;
     } pending[12];
     int npending = 0;
+    int ordinal = 0, home = 0, device = 0;   // the thread's number, its home shard (mbe_device_list.h) and that shard's device
     Slot() {
         std::call_once(g_once, init_once);
-        HIP_OK(hipSetDevice(g_device));   // HIP's current device is per thread: every thread that decodes selects the library's
+        ordinal = g_threads.fetch_add(1, std::memory_order_relaxed);
+        home = mbx::home_shard(ordinal, g_shards.n);
+        device = g_shards.device[home];
+        HIP_OK(hipSetDevice(device));   // HIP's current device is per thread: every thread that decodes selects its home device
         HIP_OK(hipStreamCreate(&stream));
         size_t off = 0;
         auto take = [&](size_t bytes) {
@@ -281,11 +312,11 @@ struct SlotHolder {
     Slot* p = nullptr;
     ~SlotHolder() {
         if (p) {
-            // the stream's workspace slot lives in the context of g_device: a host that has switched devices on this thread must
+            // the stream's workspace slot lives in the context of the thread's home device: a host that has switched devices on this thread must
             // not have the release resolved against another device's context (the slot would leak, keyed by a dead hipStream_t)
             int before = -1;
             (void)hipGetDevice(&before);
-            (void)hipSetDevice(g_device);
+            (void)hipSetDevice(p->device);
             p->stop_server();
             if (p->server_stream) {
                 (void)hipStreamDestroy(p->server_stream);
@@ -300,7 +331,7 @@ struct SlotHolder {
             (void)hipStreamDestroy(p->stream);
             (void)hipFree(p->d_shadow);
             (void)hipHostFree(p->block);
-            if (before >= 0 && before != g_device) {
+            if (before >= 0 && before != p->device) {
                 (void)hipSetDevice(before);
             }
             (void)hipGetLastError();
@@ -316,8 +347,8 @@ Slot& slot() {
     }
     Slot* s = holder.p;
     int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != g_device) {   // the host application switched devices on this thread
-        HIP_OK(hipSetDevice(g_device));
+    if (hipGetDevice(&dev) != hipSuccess || dev != s->device) {   // the host application switched devices on this thread
+        HIP_OK(hipSetDevice(s->device));
     }
     return *s;
 }
@@ -628,21 +659,111 @@ struct PinArr {   // grow-only pinned host array
                 HIP_OK(hipHostFree(p));
             }
             cap = n + n / 2 + 64;
-            HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&p), cap * sizeof(U), hipHostMallocDefault));
+            HIP_OK(hipHostMalloc(reinterpret_cast<void**>(&p), cap * sizeof(U), g_pin_flags));
         }
     }
 };
 
-struct Batch {
-    bool active = false;
-    bool queue_soft = false;                              // MBE_BATCH_QUEUE_SOFT: mbe_process*SoftFrame[f] queue as well
-    int  mode = MBE_BATCH_STATE_WRITEBACK;
+// How one flush runs, decided once its inputs are staged: where the kernels read and write -- the shard's PINNED arrays themselves
+// (zero-copy) or their device twins -- and how the PCM comes back.
+struct FlushRun {
+    bool   zero_copy;
+    int    chunks;        // PCM chunks of the copy-out: 4 from 8,192 rows on
+    size_t per_chunk;     // rows of a chunk (the last may be shorter)
+    const uint8_t* frames;
+    const int32_t* index;
+    const int32_t* offsets;
+    const uint8_t* codecs;
+    int16_t*            pcm16;     // nullptr: no queued call wants it
+    float*              pcmf;
+    mbe_process_result* results;
+    mbx_param_record*   records;
+};
+constexpr int kMaxChunks = 4;
+
+// The stream a (thread, shard) pair flushes on, with the five events of the copy-out and the copy helpers of the flush steps.
+// With ONE shard the lane IS the thread's Slot -- its stream, its events, its up / down / sync --, as before there were shards;
+// otherwise a stream of its own on the shard's device, made with the shard and given back with the thread.
+struct Lane {
+    Slot*       slot = nullptr;     // one shard: everything below is the Slot's
+    int         device = 0;
+    hipStream_t stream = nullptr;
+    hipEvent_t  own_events[1 + kMaxChunks] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t* chunk_done = own_events;   // mbe_flush: small outputs, then four PCM chunks
+    Lane() = default;
+    Lane(const Lane&) = delete;
+    Lane& operator=(const Lane&) = delete;
+    void open(int dev, Slot* home_slot) {   // home_slot: the thread's Slot when the list has one entry, else nullptr (`dev` is current)
+        device = dev;
+        slot = home_slot;
+        if (slot) {
+            stream = slot->stream;
+            chunk_done = slot->chunk_done;
+        } else {
+            HIP_OK(hipStreamCreate(&stream));
+        }
+    }
+    void up(void* dst, const void* src, size_t n) {
+        if (slot) {
+            slot->up(dst, src, n);
+        } else {
+            HIP_OK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, stream));
+        }
+    }
+    void down(void* dst, const void* src, size_t n) {
+        if (slot) {
+            slot->down(dst, src, n);
+        } else {
+            HIP_OK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, stream));
+        }
+    }
+    void sync() {
+        if (slot) {
+            slot->sync();
+        } else {
+            HIP_OK(hipStreamSynchronize(stream));
+        }
+    }
+    void forget_pending() {   // (deferred copies exist on a Slot alone)
+        if (slot) {
+            slot->npending = 0;
+        }
+    }
+    ~Lane() {
+        if (slot || !stream) {
+            return;   // the Slot's own: SlotHolder gives it back
+        }
+        // as SlotHolder does for the Slot: the stream's workspace slot lives in the context of the lane's device
+        int before = -1;
+        (void)hipGetDevice(&before);
+        (void)hipSetDevice(device);
+        (void)hipStreamSynchronize(stream);
+        (void)mbx_release_stream(stream);
+        for (hipEvent_t e : own_events) {
+            if (e) {
+                (void)hipEventDestroy(e);
+            }
+        }
+        (void)hipStreamDestroy(stream);
+        if (before >= 0 && before != device) {
+            (void)hipSetDevice(before);
+        }
+        (void)hipGetLastError();
+    }
+};
+
+// One entry of MBX_DEVICES as a thread's batch sees it: a whole queue of its own -- entries, channels, pools, staging arrays, plan --
+// on the entry's device, flushed on the thread's lane for it.  Made at the first channel placed on it; kept, like the arrays'
+// capacity, until the thread ends.
+struct Shard {
+    int  mode = MBE_BATCH_STATE_WRITEBACK;                // Batch::mode, handed down by mbe_batchBegin
+    Lane lane;                                            // (declared before the arrays: they are freed first, then the stream goes)
+    long passes = 0, rows = 0;                            // since mbe_batchBegin: flush passes that launched something here, rows launched
+    FlushRun run = {};                                    // the flush under way, between its two passes
     std::vector<QEntry>   q;
     std::vector<mbe_soft_bit> soft_cells;                 // cells of the queued soft frames, in call order; gathered into
                                                           // h_frames (pinned, group order) by the flush like packed frames
     std::vector<QChannel> channels;                       // pool slot = index
-    std::unordered_map<const mbe_parms*, int> index;      // cur_mp -> channel
-    std::unordered_map<const mbe_parms*, int> aux;        // prev_mp / prev_mp_enhanced -> channel (direct use of either struct)
     DevArr<mbe_parms>      d_state;                       // [channels][3]
     DevArr<mbx_stream_rng> d_rng;
     DevArr<uint32_t>       d_elided;                      // resident mode: prev_mp_enhanced of the slot is elided (mbx_process_batch_resident)
@@ -669,6 +790,52 @@ struct Batch {
     std::vector<int>           upload;                    // ... and the channels whose state went up for it, in slot order
 };
 
+struct ChannelAt {
+    int shard, channel;   // channel: index into Shard::channels
+};
+
+// What is global to a thread's batch; everything a flush works on is in the shards.
+struct Batch {
+    bool active = false;
+    bool queue_soft = false;                              // MBE_BATCH_QUEUE_SOFT: mbe_process*SoftFrame[f] queue as well
+    int  mode = MBE_BATCH_STATE_WRITEBACK;
+    int  home = 0;                                        // the thread's home shard ...
+    int  created = 0;                                     // ... and the channels it has created since mbe_batchBegin: the next one
+                                                          // goes to channel_shard(home, created, shards) (mbe_device_list.h)
+    std::unordered_map<const mbe_parms*, ChannelAt> index;   // cur_mp -> channel
+    std::unordered_map<const mbe_parms*, ChannelAt> aux;     // prev_mp / prev_mp_enhanced -> channel (direct use of either struct)
+    std::unique_ptr<Shard> shards[mbx::kMaxShards];       // [list entry]; null until its first channel
+
+    size_t pending() const {
+        size_t n = 0;
+        for (int i = 0; i < g_shards.n; ++i) {
+            n += shards[i] ? shards[i]->q.size() : 0;
+        }
+        return n;
+    }
+};
+
+// HIP's current device while a shard is worked on.  One shard: the thread's home device is current already (slot()), nothing is called.
+void use_device(int device) {
+    if (g_shards.n > 1) {
+        HIP_OK(hipSetDevice(device));
+    }
+}
+
+// the shard of list entry `at`, made now if this is its first channel (the home device is current before and after)
+Shard& shard_at(Batch& b, int at) {
+    if (!b.shards[at]) {
+        Slot& home = slot();
+        b.shards[at].reset(new Shard());
+        Shard& sh = *b.shards[at];
+        sh.mode = b.mode;
+        use_device(g_shards.device[at]);
+        sh.lane.open(g_shards.device[at], g_shards.n == 1 ? &home : nullptr);
+        use_device(home.device);
+    }
+    return *b.shards[at];
+}
+
 struct BatchHolder {   // freed with the thread (the arrays' destructors return the device and pinned memory)
     Batch* p = nullptr;
     ~BatchHolder() { delete p; }
@@ -683,7 +850,7 @@ Batch& batch() {
 }
 
 // grow the device pool to `n` channels, keeping what is resident
-void pool_reserve(Batch& b, Slot& s, size_t n) {
+void pool_reserve(Shard& b, Lane& s, size_t n) {
     if (n <= b.d_state.cap / 3 && n <= b.d_rng.cap) {
         return;
     }
@@ -716,7 +883,7 @@ void pool_reserve(Batch& b, Slot& s, size_t n) {
 
 // bring the state held in pool slots [first, first + count) back into the host structs of the channels that own them
 // (`owners[i]` = channel of slot first + i); with_rng: the per-channel RNG state as well
-void pool_download(Batch& b, Slot& s, size_t first, const std::vector<int>& owners, bool with_rng) {
+void pool_download(Shard& b, Lane& s, size_t first, const std::vector<int>& owners, bool with_rng) {
     const size_t count = owners.size();
     if (count == 0) {
         return;
@@ -788,23 +955,6 @@ static const bool g_trace_flush = [] {
 }();
 thread_local FlushTrace t_flush_trace;
 
-// How one flush runs, decided once its inputs are staged: where the kernels read and write -- the thread's PINNED arrays themselves
-// (zero-copy) or their device twins -- and how the PCM comes back.
-struct FlushRun {
-    bool   zero_copy;
-    int    chunks;        // PCM chunks of the copy-out: 4 from 8,192 rows on
-    size_t per_chunk;     // rows of a chunk (the last may be shorter)
-    const uint8_t* frames;
-    const int32_t* index;
-    const int32_t* offsets;
-    const uint8_t* codecs;
-    int16_t*            pcm16;     // nullptr: no queued call wants it
-    float*              pcmf;
-    mbe_process_result* results;
-    mbx_param_record*   records;
-};
-constexpr int kMaxChunks = 4;
-
 template <class U>
 U* flush_view(bool zero_copy, const PinArr<U>& h, const DevArr<U>& d) {
     return zero_copy ? h.p : d.p;
@@ -812,7 +962,7 @@ U* flush_view(bool zero_copy, const PinArr<U>& h, const DevArr<U>& d) {
 
 // ---- state upload.  Resident mode: the channels first seen since the last flush, appended at slots [resident, total).
 //      Write-back mode: every channel that has frames this time, at slots [0, k); nothing stays afterwards. ----
-void flush_upload_state(Batch& b, Slot& s) {
+void flush_upload_state(Shard& b, Lane& s) {
     const size_t total = b.channels.size();
     std::vector<int>& upload = b.upload;
     upload.clear();
@@ -868,7 +1018,7 @@ bool flush_zero_copy(size_t rows) {
 
 // ---- inputs: the queued frames gathered into h_frames where the plan puts them, the plan's channels as pool slots, the offsets and
 //      codecs of the mixed forms; every array sized; the views chosen; the inputs uploaded unless the kernels read them in place ----
-FlushRun flush_stage_inputs(Batch& b, Slot& s) {
+FlushRun flush_stage_inputs(Shard& b, Lane& s) {
     const mbx::FlushPlan& p = b.plan;
     const size_t total = b.channels.size(), rows = p.rows;
     b.h_frames.need(p.bytes);
@@ -927,7 +1077,7 @@ FlushRun flush_stage_inputs(Batch& b, Slot& s) {
 
 // ---- launches: a mixed form as ONE launch set at its first group; a group alone in its form by the single-codec launcher of its
 //      input form and state mode ----
-void flush_launch(Batch& b, Slot& s, const FlushRun& r) {
+void flush_launch(Shard& b, Lane& s, const FlushRun& r) {
     const mbx::FlushPlan& p = b.plan;
     const bool resident = b.mode == MBE_BATCH_STATE_RESIDENT;
     uint32_t* const elided = resident ? b.d_elided.p : nullptr;   // (no elision words in write-back mode)
@@ -967,7 +1117,7 @@ void flush_launch(Batch& b, Slot& s, const FlushRun& r) {
 
 // ---- outputs: the small arrays first, then the PCM in chunks -- the host hands chunk k to the callers' buffers while
 //      chunk k + 1 is still crossing PCIe (the scatter is as long as the copy: 5 MB per 16,384 frames each) ----
-void flush_copy_out(Batch& b, Slot& s, const FlushRun& r) {
+void flush_copy_out(Shard& b, Lane& s, const FlushRun& r) {
     const size_t rows = b.plan.rows;
     if (!s.chunk_done[0]) {
         HIP_OK(hipEventCreateWithFlags(&s.chunk_done[0], hipEventDisableTiming | hipEventBlockingSync));   // the long wait sleeps
@@ -997,7 +1147,7 @@ void flush_copy_out(Batch& b, Slot& s, const FlushRun& r) {
 }
 
 // ---- scatter into the callers' buffers: results and parameter bits, then the PCM chunk by chunk as it arrives ----
-void flush_scatter(Batch& b, Slot& s, const FlushRun& r) {
+void flush_scatter(Shard& b, Lane& s, const FlushRun& r) {
     const mbx::FlushPlan& p = b.plan;
     for (size_t e = 0; e < b.q.size(); ++e) {
         const QEntry& qe = b.q[e];
@@ -1024,8 +1174,8 @@ void flush_scatter(Batch& b, Slot& s, const FlushRun& r) {
 }
 
 // ---- the queue is empty again; write-back mode: the host structs are current again, nothing stays on the device ----
-void flush_finish(Batch& b, Slot& s) {
-    s.npending = 0;
+void flush_finish(Shard& b, Lane& s) {
+    s.forget_pending();
     b.q.clear();
     b.soft_cells.clear();
     for (QChannel& ch : b.channels) {
@@ -1043,47 +1193,84 @@ void flush_finish(Batch& b, Slot& s) {
 }
 
 // One flush: where everything goes is planned on the host alone (mbe_flush_plan.h); the steps above carry the plan out.
-int flush_batch(Batch& b) {
-    const size_t n = b.q.size();
+// A shard's flush is a whole flush as it was before there were shards; with several, every shard with queued entries gets its work
+// issued first (pass 1) and is waited for and scattered afterwards (pass 2), so that the devices work at the same time.
+int flush_batch(Batch& all) {
+    const size_t n = all.pending();
     if (n == 0) {
         return 0;
     }
-    Slot& s = slot();
-    const double tr0 = g_trace_flush ? trace_now() : 0.0;
-    flush_upload_state(b, s);
-    b.plan.build(b.channels.data(), b.channels.size(), b.q.data(), n);
-    const FlushRun r = flush_stage_inputs(b, s);
-    const double tr1 = g_trace_flush ? trace_now() : 0.0;
-    flush_launch(b, s, r);
-    flush_copy_out(b, s, r);
-    b.plan.invert_rows();   // (host work behind the launches: the device is busy)
-    const double tr2 = g_trace_flush ? trace_now() : 0.0;
-    if (b.plan.rows < 256) {
-        HIP_OK(hipStreamSynchronize(s.stream));   // a small flush: spin, the sleeping wait's wake-up would be most of it
-    } else {
-        HIP_OK(hipEventSynchronize(s.chunk_done[0]));
-    }
-    const double tr3 = g_trace_flush ? trace_now() : 0.0;
-    flush_scatter(b, s, r);
-    if (g_trace_flush) {
-        FlushTrace& t = t_flush_trace;
-        const double tr4 = trace_now();
-        if (++t.seen > 2) {   // (the first flushes of a thread allocate and upload: not the steady state)
-            t.prep += tr1 - tr0;
-            t.issue += tr2 - tr1;
-            t.wait += tr3 - tr2;
-            t.scatter += tr4 - tr3;
-            t.flushes += 1;
-            t.rows += (long)b.plan.rows;
+    Slot& home = slot();
+    const bool trace = g_trace_flush;
+    double prep = 0, issue = 0, wait = 0, scatter = 0;   // summed over the shards
+    long rows = 0;
+    for (int i = 0; i < g_shards.n; ++i) {
+        if (!all.shards[i] || all.shards[i]->q.empty()) {
+            continue;
+        }
+        Shard& b = *all.shards[i];
+        Lane& s = b.lane;
+        use_device(s.device);
+        const double tr0 = trace ? trace_now() : 0.0;
+        flush_upload_state(b, s);
+        b.plan.build(b.channels.data(), b.channels.size(), b.q.data(), b.q.size());
+        b.run = flush_stage_inputs(b, s);
+        const double tr1 = trace ? trace_now() : 0.0;
+        flush_launch(b, s, b.run);
+        flush_copy_out(b, s, b.run);
+        b.plan.invert_rows();   // (host work behind the launches: the device is busy)
+        b.passes += 1;
+        b.rows += (long)b.plan.rows;
+        if (trace) {
+            const double tr2 = trace_now();
+            prep += tr1 - tr0;
+            issue += tr2 - tr1;
+            rows += (long)b.plan.rows;
         }
     }
-    flush_finish(b, s);
+    for (int i = 0; i < g_shards.n; ++i) {   // (a shard of pass 1 still has its entries: flush_finish clears them)
+        if (!all.shards[i] || all.shards[i]->q.empty()) {
+            continue;
+        }
+        Shard& b = *all.shards[i];
+        Lane& s = b.lane;
+        use_device(s.device);
+        const double tr2 = trace ? trace_now() : 0.0;
+        if (b.plan.rows < 256) {
+            HIP_OK(hipStreamSynchronize(s.stream));   // a small flush: spin, the sleeping wait's wake-up would be most of it
+        } else {
+            HIP_OK(hipEventSynchronize(s.chunk_done[0]));
+        }
+        const double tr3 = trace ? trace_now() : 0.0;
+        flush_scatter(b, s, b.run);
+        if (trace) {
+            wait += tr3 - tr2;
+            scatter += trace_now() - tr3;
+        }
+        flush_finish(b, s);
+    }
+    use_device(home.device);
+    if (trace) {
+        FlushTrace& t = t_flush_trace;
+        if (++t.seen > 2) {   // (the first flushes of a thread allocate and upload: not the steady state)
+            t.prep += prep;
+            t.issue += issue;
+            t.wait += wait;
+            t.scatter += scatter;
+            t.flushes += 1;
+            t.rows += rows;
+        }
+    }
     return (int)n;
 }
 
-// forget one channel after bringing its state home (resident mode: the last channel takes its pool slot)
-void release_channel(Batch& b, int c) {
-    Slot& s = slot();
+// forget one channel after bringing its state home (resident mode: the last channel of its shard takes its pool slot)
+void release_channel(Batch& all, ChannelAt at) {
+    Shard& b = *all.shards[at.shard];
+    Lane& s = b.lane;
+    const int c = at.channel;
+    Slot& home = slot();
+    use_device(s.device);
     QChannel& ch = b.channels[(size_t)c];
     const size_t last = b.channels.size() - 1;
     if (ch.on_device) {   // resident mode: slot == channel index
@@ -1097,17 +1284,18 @@ void release_channel(Batch& b, int c) {
         }
         b.resident = last;
     }
-    b.index.erase(ch.cur);
-    b.aux.erase(ch.prev);
-    b.aux.erase(ch.enh);
+    use_device(home.device);
+    all.index.erase(ch.cur);
+    all.aux.erase(ch.prev);
+    all.aux.erase(ch.enh);
     if ((size_t)c != last) {
         b.channels[(size_t)c] = b.channels[last];
         if (b.channels[(size_t)c].on_device) {
             b.channels[(size_t)c].slot = c;
         }
-        b.index[b.channels[(size_t)c].cur] = c;
-        b.aux[b.channels[(size_t)c].prev] = c;
-        b.aux[b.channels[(size_t)c].enh] = c;
+        all.index[b.channels[(size_t)c].cur] = at;   // the maps of the whole batch follow the move
+        all.aux[b.channels[(size_t)c].prev] = at;
+        all.aux[b.channels[(size_t)c].enh] = at;
     }
     b.channels.pop_back();
 }
@@ -1120,18 +1308,18 @@ void sync_channel_for_direct_use(const mbe_parms* any) {
         return;
     }
     auto it = b.index.find(any);
-    int c = -1;
+    const ChannelAt* at = nullptr;
     if (it != b.index.end()) {
-        c = it->second;
+        at = &it->second;
     } else {
         auto ia = b.aux.find(any);
         if (ia != b.aux.end()) {
-            c = ia->second;
+            at = &ia->second;
         }
     }
-    if (c >= 0) {
-        const mbe_parms* cur = b.channels[(size_t)c].cur;
-        (void)flush_batch(b);
+    if (at) {
+        const mbe_parms* cur = b.shards[at->shard]->channels[(size_t)at->channel].cur;
+        (void)flush_batch(b);   // the WHOLE batch, every shard
         release_channel(b, b.index.find(cur)->second);
     }
 }
@@ -1147,31 +1335,35 @@ int queue_frame(int codec, float* aout_f, short* aout_s, mbe_process_result* res
     if (rc < 0) {
         return rc;
     }
-    Batch& b = batch();
-    auto it = b.index.find(cur);
-    int c;
-    if (it == b.index.end()) {
-        c = (int)b.channels.size();
+    Batch& all = batch();
+    auto it = all.index.find(cur);
+    ChannelAt at;
+    if (it == all.index.end()) {   // a new channel: placed now, and there it stays until it is released or the batch ends
+        at.shard = mbx::channel_shard(all.home, all.created++, g_shards.n);
+        Shard& b = shard_at(all, at.shard);
+        at.channel = (int)b.channels.size();
         QChannel ch;
         ch.cur = cur;
         ch.prev = prev;
         ch.enh = enh;
         ch.rng = t_rng.r;
         b.channels.push_back(ch);
-        b.index.emplace(cur, c);
-        b.aux[prev] = c;
-        b.aux[enh] = c;
+        all.index.emplace(cur, at);
+        all.aux[prev] = at;
+        all.aux[enh] = at;
     } else {
-        c = it->second;
-        QChannel& ch = b.channels[(size_t)c];
+        at = it->second;
+        QChannel& ch = all.shards[at.shard]->channels[(size_t)at.channel];
         if (ch.prev != prev || ch.enh != enh) {
             return MBE_STATUS_INVALID_ARGUMENT;   // a channel is its three structs; they cannot change while it is queued / resident
         }
         if (ch.pending && (ch.codec != codec || ch.soft != (soft != nullptr))) {   // one codec and one input form per channel and flush: run what is queued first
-            (void)flush_batch(b);
+            (void)flush_batch(all);
             return queue_frame(codec, aout_f, aout_s, result, cells, bits_out, cur, prev, enh, soft);
         }
     }
+    Shard& b = *all.shards[at.shard];
+    const int c = at.channel;
     QChannel& ch = b.channels[(size_t)c];
     ch.codec = codec;
     ch.soft = soft != nullptr;
@@ -1616,10 +1808,17 @@ int mbe_batchBegin(int state_mode) {
     if (b.active || (state_mode != MBE_BATCH_STATE_WRITEBACK && state_mode != MBE_BATCH_STATE_RESIDENT)) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    (void)slot();   // the thread's device scratch and stream exist from here on
+    b.home = slot().home;   // the thread's device scratch and stream exist from here on
+    b.created = 0;
     b.active = true;
     b.queue_soft = queue_soft;
     b.mode = state_mode;
+    for (int i = 0; i < g_shards.n; ++i) {
+        if (b.shards[i]) {
+            b.shards[i]->mode = state_mode;
+            b.shards[i]->passes = b.shards[i]->rows = 0;
+        }
+    }
     return 0;
 }
 
@@ -1628,7 +1827,7 @@ int mbe_flush(void) {
     return b.active ? flush_batch(b) : 0;
 }
 
-int mbe_batchPending(void) { return (int)batch().q.size(); }
+int mbe_batchPending(void) { return (int)batch().pending(); }
 
 int mbe_batchRelease(mbe_parms* cur_mp) {
     Batch& b = batch();
@@ -1649,13 +1848,24 @@ int mbe_batchEnd(void) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     const int ran = flush_batch(b);
-    if (b.resident) {   // resident mode: slot == channel index
-        std::vector<int> owners(b.resident);
-        for (size_t c = 0; c < b.resident; ++c) {
-            owners[c] = (int)c;
+    Slot& home = slot();
+    for (int i = 0; i < g_shards.n; ++i) {
+        if (!b.shards[i]) {
+            continue;
         }
-        pool_download(b, slot(), 0, owners, false);
+        Shard& sh = *b.shards[i];
+        if (sh.resident) {   // resident mode: slot == channel index
+            std::vector<int> owners(sh.resident);
+            for (size_t c = 0; c < sh.resident; ++c) {
+                owners[c] = (int)c;
+            }
+            use_device(sh.lane.device);
+            pool_download(sh, sh.lane, 0, owners, false);
+        }
+        sh.channels.clear();
+        sh.resident = 0;
     }
+    use_device(home.device);
     if (g_trace_flush && t_flush_trace.flushes) {
         const FlushTrace& t = t_flush_trace;
         fprintf(stderr, "[flush trace] %ld flushes, %.0f rows each: prep %.1f us, issue %.1f us, wait %.1f us, scatter %.1f us per flush\n", t.flushes,
@@ -1663,12 +1873,40 @@ int mbe_batchEnd(void) {
                 1e6 * t.scatter / t.flushes);
         t_flush_trace = FlushTrace{};
     }
-    b.channels.clear();
     b.index.clear();
     b.aux.clear();
-    b.resident = 0;
     b.active = false;
     return ran;
+}
+
+// ---- the shards from outside (include/mbe_neo_shards.h) ---------------------------------------------------------------
+int mbq_shard_count(void) {
+    std::call_once(g_once, init_once);
+    return g_shards.n;
+}
+
+int mbq_shard_device(int shard) { return shard >= 0 && shard < mbq_shard_count() ? g_shards.device[shard] : -1; }
+
+int mbq_thread_home(void) { return slot().home; }
+
+int mbq_channel_shard(const void* cur_mp) {
+    const Batch& b = batch();
+    auto it = b.index.find(static_cast<const mbe_parms*>(cur_mp));
+    return b.active && it != b.index.end() ? it->second.shard : -1;
+}
+
+int mbq_shard_census(int shard, mbq_census* out) {
+    if (!out || shard < 0 || shard >= mbq_shard_count()) {
+        return -1;
+    }
+    memset(out, 0, sizeof(*out));
+    if (const Shard* sh = batch().shards[shard].get()) {
+        out->flush_passes = sh->passes;
+        out->rows = sh->rows;
+        out->channels = (int)sh->channels.size();
+        out->resident = (int)sh->resident;
+    }
+    return 0;
 }
 
 // ---- frame decode ---------------------------------------------------------------------------
