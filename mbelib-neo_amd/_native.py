@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h,
-include/mbx_burst_groups.h).  Fails loudly when the library
+include/mbx_burst_groups.h, include/mbx_keystream.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -156,6 +156,15 @@ _GROUP_SIGNATURES = {
     "mbx_session_submit_burst_groups": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
 }
 GROUP_SYMBOLS = tuple(_GROUP_SIGNATURES)
+# keystream input (include/mbx_keystream.h): encrypted channels on the batched paths
+_KEYSTREAM_SIGNATURES = {
+    "mbx_keystream_apply_host": (C.c_int, [C.c_int, _vp, _sz, _vp]),
+    "mbx_apply_keystream": (C.c_int, [C.c_int, _vp, _sz, _vp, _vp]),
+    "mbx_process_batch_keyed": (C.c_int, [C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mbx_process_batch_ragged_keyed": (C.c_int, [C.c_int, _vp, C.c_int, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mbx_session_submit_keyed": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+KEYSTREAM_SYMBOLS = tuple(_KEYSTREAM_SIGNATURES)
 
 
 class BurstGroupStruct(C.Structure):
@@ -184,7 +193,7 @@ def lib():
             handle = C.CDLL(path)
         except OSError as e:  # e.g. libamdhip64 not found
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
-        for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES, **_KEYSTREAM_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

@@ -20,6 +20,8 @@
 #include "mbx_gather.h"
 #include "mbx_host.h"
 #include "mbx_kernels.h"
+#include "mbx_keystream.h"
+#include "mbx_keystream_words.h"
 #include "mbx_launch_plan.h"
 #include "mbx_llr.h"
 #include "mbx_llr_cell.h"
@@ -705,10 +707,13 @@ struct BatchCall {
     size_t              total = 0;                // the host's copy of frame_offset[S]: rows of every batch array
     // a MIXED ragged step (mbx_process_batch_mixed): stream row i is of codec stream_codec[i]; `codec` is unused
     const uint8_t*      stream_codec = nullptr;   // S bytes on the device, or nullptr: every stream is of `codec`
+    // a KEYED step (include/mbx_keystream.h): the front launch XORs row r of the keystream onto the record of batch row r
+    const uint8_t*      keystream = nullptr;      // MBX_KEYSTREAM_ROW_BYTES per batch row on the device, or nullptr: the unkeyed step
 };
 static bool call_args_ok(const BatchCall& b) { return b.records && b.state && b.rng && b.S >= 0 && b.T >= 0; }
 static bool call_aligned(const BatchCall& b) {
-    return batch_pointers_aligned(b.records, b.state, b.rng, b.pcm16, b.pcmf, b.results, b.stream_index, b.resident, b.frame_offset);
+    return batch_pointers_aligned(b.records, b.state, b.rng, b.pcm16, b.pcmf, b.results, b.stream_index, b.resident, b.frame_offset) &&
+           aligned_to(b.keystream, 4);   // (kind `keystream`, include/mbx_keystream.h: the kernels load a row as three dwords)
 }
 static size_t batch_rows(const BatchCall& b) { return b.frame_offset ? b.total : (size_t)b.S * (size_t)b.T; }
 // the tables of a launch: the context's + what this launch walks (`reverse`: see launch_stream)
@@ -743,6 +748,7 @@ static StepShape step_shape(const BatchCall& b, InputKind kind, const void* d_in
     q.mixed = b.stream_codec != nullptr;
     q.aligned = (reinterpret_cast<uintptr_t>(d_input) & 3u) == 0;
     q.own_workspace = q.slices_allowed = own_workspace;
+    q.keyed = b.keystream != nullptr;
     return q;
 }
 // THE plan of a step on `stream`.  A plan that needs the slot's flag words (a captured launch would be replayed with the same epoch,
@@ -1056,6 +1062,21 @@ struct CallerWorkspace {
     void*  p;
     size_t bytes;
 };
+// The front launch of a KEYED step (BatchCall::keystream; mbx_keystream.hip): the hard or the soft front of the unkeyed step of the same
+// form -- frames a codec's own size apart and a uniform codec, or the rows and row codecs of a mixed step -- with the keystream row of
+// every frame XORed onto its record before the record's one store.  Everything behind it is the unkeyed step's.
+static int launch_keyed_front(Context* c, bool soft, const BatchCall& b, const uint8_t* row_codec, const void* d_input, size_t n) {
+    const mbx::CodecShape* sh = row_codec ? nullptr : &mbx::kCodecs[b.codec];
+    const hipStream_t st = (hipStream_t)b.stream;
+    if (soft) {
+        hipLaunchKernelGGL(mbx::soft_front_keyed_kernel, dim3((unsigned)n), dim3(64), 0, st, static_cast<const mbe_soft_bit*>(d_input), n,
+                           sh ? sh->cells : MBX_MIXED_ROW_CELLS, b.codec, row_codec, b.keystream, b.records, c->tabs);
+        return check_launch("soft_front_keyed_kernel");
+    }
+    hipLaunchKernelGGL(mbx::fec_keyed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const uint8_t*>(d_input), n,
+                       sh ? sh->frame_bytes : MBX_MIXED_ROW_BYTES, b.codec, row_codec, b.keystream, b.records, c->tabs);
+    return check_launch("fec_keyed_kernel");
+}
 // The staged launches of a MIXED step (BatchCall::stream_codec): the codec of every batch row into the step's own workspace (behind
 // the rows and the order words, at plan.codec_offset), then what a ragged step launches, by kernels that look the codec of a row or a
 // stream up -- one front launch and one expand launch over all rows, (the order,) one stream-stage launch, whatever the mix.
@@ -1065,7 +1086,9 @@ static int run_mixed_stages(Context* c, const BatchCall& b, const StepPlan& plan
     uint8_t* const row_codec = reinterpret_cast<uint8_t*>(ws + plan.codec_offset);
     hipLaunchKernelGGL(mbx::mixed_row_codec_kernel, dim3((unsigned)((b.S + 3) / 4)), dim3(256), 0, st, b.S, (int)n, b.frame_offset, b.stream_codec, row_codec);
     int rc = check_launch("mixed_row_codec_kernel");
-    if (rc >= 0 && plan.front == mbx::kFecFront) {
+    if (rc >= 0 && b.keystream) {   // a keyed step: the keyed front over the same rows and row codecs
+        rc = launch_keyed_front(c, plan.front == mbx::kSoftFront, b, row_codec, d_input, n);
+    } else if (rc >= 0 && plan.front == mbx::kFecFront) {
         hipLaunchKernelGGL(mbx::fec_mixed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, static_cast<const uint8_t*>(d_input), n, row_codec,
                            b.records, c->tabs);
         rc = check_launch("fec_mixed_kernel");
@@ -1086,7 +1109,9 @@ static int run_stages(Context* c, unsigned order, const BatchCall& b, const Step
                       StreamSlot* slot) {
     const size_t n = batch_rows(b);
     int rc = 0;
-    if (plan.front == mbx::kFecFront) {
+    if (b.keystream && plan.front != mbx::kNoFront) {
+        rc = launch_keyed_front(c, plan.front == mbx::kSoftFront, b, nullptr, d_input, n);
+    } else if (plan.front == mbx::kFecFront) {
         rc = launch_fec(c, b.codec, static_cast<const uint8_t*>(d_input), n, b.records, b.stream);
     } else if (plan.front == mbx::kSoftFront) {
         rc = launch_soft_fec(c, b.codec, true, static_cast<const mbe_soft_bit*>(d_input), n, b.records, b.stream);
@@ -1133,7 +1158,7 @@ static int run_batch(Context* c, const char* who, const BatchCall& b, InputKind 
     }
     if (!call_aligned(b) || (kind == kSoft && !aligned_to(d_input, 2)) || (kind == kFrames && !frames_aligned(d_input, mixed || imbe_codec(b.codec))) ||
         (caller_ws && !aligned_to(caller_ws->p, 16))) {
-        return misaligned(who);
+        return !aligned_to(b.keystream, 4) ? mbx::misaligned(who, "mbx_keystream.h") : misaligned(who);   // (the table that has the pointer's row)
     }
     const size_t n = batch_rows(b);
     if (b.S == 0 || n == 0) {
@@ -1571,15 +1596,16 @@ int mbx_process_burst_groups(const mbx_burst_group* groups, int n_groups, int so
 static int process_batch_ragged(const char* who, InputKind kind, bool mixed, int codec, int S, const uint8_t* d_stream_codec,
                                 const int32_t* d_frame_offset, size_t total_frames, const int32_t* d_stream_index, const void* d_input,
                                 mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16, float* d_pcmf,
-                                mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
+                                mbe_process_result* d_results, mbx_param_record* d_records, void* stream, const uint8_t* d_keystream = nullptr) {
     const bool empty = S == 0 || total_frames == 0;   // (a batch without frames has no frame and no record array to name)
     if (!d_frame_offset || !d_state_pool || !d_rng_pool || S < 0 || (mixed ? !d_stream_codec : !mbx::codec_shape(codec)) ||
         (!empty && (!d_input || !d_records))) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     if (!batch_pointers_aligned(d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, d_stream_index, d_resident, d_frame_offset) ||
-        (kind == kSoft && !aligned_to(d_input, 2)) || (kind == kFrames && !frames_aligned(d_input, mixed || imbe_codec(codec)))) {
-        return misaligned(who);
+        (kind == kSoft && !aligned_to(d_input, 2)) || (kind == kFrames && !frames_aligned(d_input, mixed || imbe_codec(codec))) ||
+        !aligned_to(d_keystream, 4)) {
+        return !aligned_to(d_keystream, 4) ? mbx::misaligned(who, "mbx_keystream.h") : misaligned(who);
     }
     REQUIRE_CTX(c);
     if (empty) {
@@ -1589,6 +1615,7 @@ static int process_batch_ragged(const char* who, InputKind kind, bool mixed, int
     b.frame_offset = d_frame_offset;
     b.total = total_frames;
     b.stream_codec = mixed ? d_stream_codec : nullptr;
+    b.keystream = d_keystream;
     return run_batch(c, who, b, kind, d_input, nullptr);
 }
 int mbx_process_batch_ragged(int codec, int S, const int32_t* d_frame_offset, size_t total_frames, const int32_t* d_stream_index,
@@ -1617,6 +1644,74 @@ int mbx_process_batch_soft_mixed(int S, const uint8_t* d_stream_codec, const int
                                  mbx_param_record* d_records, void* stream) {
     return process_batch_ragged("mbx_process_batch_soft_mixed", kSoft, true, 0, S, d_stream_codec, d_frame_offset, total_frames, d_stream_index, d_soft,
                                 d_state_pool, d_resident, d_rng_pool, d_pcm16, d_pcmf, d_results, d_records, stream);
+}
+
+// ---- keystream input (include/mbx_keystream.h): run_batch with BatchCall::keystream --------------------------------------------------
+// The caller steps in where the reference's callers do, between mbe_decodeImbe7200x4400Frame / mbe_decodeAmbe3600x2450Frame and
+// mbe_processImbe4400Dataf / mbe_processAmbe2450Dataf (ref src/imbe/imbe7200x4400.c:935-948, src/ambe/ambe3600x2450.c:684-714).
+int mbx_keystream_apply_host(int codec, mbx_param_record* records, size_t n, const uint8_t* keystream) {
+    const int nbits = mbx::keystream_nbits(codec);
+    if (!records || !keystream || nbits == 0) {
+        return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_keystream_apply_host: records and keystream are needed, codec is one of MBX_CODEC_*");
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const mbx::KeystreamWords k = mbx::keystream_words_of_row(keystream + i * (size_t)MBX_KEYSTREAM_ROW_BYTES, nbits);
+        records[i].w[0] ^= k.x;
+        records[i].w[1] ^= k.y;
+        records[i].w[2] ^= k.z;
+    }
+    return 0;
+}
+
+int mbx_apply_keystream(int codec, mbx_param_record* d_records, size_t n, const uint8_t* d_keystream, void* stream) {
+    static_assert(MBX_KEYSTREAM_ROW_BYTES == mbx::kKeystreamRowBytes, "one row size, stated in the public header and in the words header");
+    const int nbits = mbx::keystream_nbits(codec);
+    if (!d_records || !d_keystream || nbits == 0) {
+        return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_apply_keystream: d_records and d_keystream are needed, codec is one of MBX_CODEC_*");
+    }
+    if (!aligned_to(d_records, 16)) {
+        return misaligned("mbx_apply_keystream");
+    }
+    if (!aligned_to(d_keystream, 4)) {
+        return mbx::misaligned("mbx_apply_keystream", "mbx_keystream.h");
+    }
+    REQUIRE_CTX(c);
+    (void)c;
+    if (n == 0) {
+        return 0;
+    }
+    if (n > 0x7fffffffu) {
+        return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_apply_keystream: more than 2^31-1 records in one launch");
+    }
+    hipLaunchKernelGGL(mbx::keystream_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nbits, d_records, n, d_keystream);
+    return check_launch("keystream_apply_kernel");
+}
+
+// S x T: every uniform form in one entry point -- index or none, resident words or ABI triplets, hard frames or soft cells.  Without
+// a keystream it is the unkeyed call of the same form, launch for launch.
+int mbx_process_batch_keyed(int codec, int S, int T, const int32_t* d_stream_index, const uint8_t* d_frames, const mbe_soft_bit* d_soft,
+                            const uint8_t* d_keystream, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool,
+                            int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
+    if ((d_frames != nullptr) == (d_soft != nullptr)) {
+        return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_process_batch_keyed: exactly one of d_frames and d_soft is given");
+    }
+    REQUIRE_CTX(c);
+    BatchCall b{codec, S, T, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index, d_resident};
+    b.keystream = d_keystream;
+    return d_soft ? run_batch(c, "mbx_process_batch_keyed", b, kSoft, d_soft, nullptr) : run_batch(c, "mbx_process_batch_keyed", b, kFrames, d_frames, nullptr);
+}
+
+// ragged, and mixed where d_stream_codec is given (rows of MBX_MIXED_ROW_BYTES / MBX_MIXED_ROW_CELLS, `codec` unused)
+int mbx_process_batch_ragged_keyed(int codec, const uint8_t* d_stream_codec, int S, const int32_t* d_frame_offset, size_t total_frames,
+                                   const int32_t* d_stream_index, const uint8_t* d_frames, const mbe_soft_bit* d_soft,
+                                   const uint8_t* d_keystream, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool,
+                                   int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, void* stream) {
+    if ((d_frames != nullptr) == (d_soft != nullptr)) {
+        return fail(MBE_STATUS_INVALID_ARGUMENT, "mbx_process_batch_ragged_keyed: exactly one of d_frames and d_soft is given");
+    }
+    return process_batch_ragged("mbx_process_batch_ragged_keyed", d_soft ? kSoft : kFrames, d_stream_codec != nullptr, d_stream_codec ? 0 : codec, S,
+                                d_stream_codec, d_frame_offset, total_frames, d_stream_index, d_soft ? static_cast<const void*>(d_soft) : d_frames,
+                                d_state_pool, d_resident, d_rng_pool, d_pcm16, d_pcmf, d_results, d_records, stream, d_keystream);
 }
 
 int mbx_synthesize_speech(int S, mbe_parms* d_cur, mbe_parms* d_prev, mbx_stream_rng* d_rng, float* d_pcmf,

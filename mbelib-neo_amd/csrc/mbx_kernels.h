@@ -1,5 +1,5 @@
 // mbx_kernels.h -- every __global__ kernel of libmbx_hip.so, declared exactly once.
-// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
+// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
 // one that launches it (mbx_api.hip), so a parameter list that drifts from its definition is a compile error (an unmatched
 // overload at the launch site or in the instance table), not an unresolved symbol when the library is loaded.
 // A new kernel: declare it here, define it, and -- a stream-stage instance -- give it its row in kInstances (mbx_api.hip).
@@ -118,6 +118,12 @@ __global__ void ecc_soft_words_kernel(int, const mbe_soft_bit*, size_t, uint32_t
 __global__ void soft_front_imbe_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
 __global__ void soft_front_imbe7100_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
 __global__ void soft_front_ambe_kernel(const mbe_soft_bit*, size_t, mbx_param_record*, DeviceTables);
+
+// ---- mbx_keystream.hip: keystream input (include/mbx_keystream.h) -- the stage alone on records, and the hard and the soft front of a
+// keyed step (frame stride, uniform codec or row codecs, keystream rows) ---------------------------------------------------------------
+__global__ void keystream_apply_kernel(int, mbx_param_record*, size_t, const uint8_t*);
+__global__ void fec_keyed_kernel(const uint8_t*, size_t, int, int, const uint8_t*, const uint8_t*, mbx_param_record*, DeviceTables);
+__global__ void soft_front_keyed_kernel(const mbe_soft_bit*, size_t, int, int, const uint8_t*, const uint8_t*, mbx_param_record*, DeviceTables);
 
 // ---- mbx_expand.hip ------------------------------------------------------------------------------------------------------------
 __global__ void expand_imbe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);

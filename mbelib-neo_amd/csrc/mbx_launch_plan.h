@@ -102,6 +102,7 @@ struct StepShape {
     bool      own_workspace = false;     // the rows may go through the stream slot's own workspace and flag words
     bool      slices_allowed = false;    // the launch may be issued slice by slice on the slot's side streams
     bool      capturing = false;         // the stream is being captured into a graph
+    bool      keyed = false;             // a keystream row per frame is XORed onto the record by the front launch (mbx_keystream.hip)
 };
 
 // ---- ... and everything the launcher then does without asking again -----------------------------------------------------------------
@@ -216,7 +217,10 @@ static inline StepPlan plan_step(const StepShape& q, const LaunchSwitches& sw, c
     // (the default): 0.2229 -- and with the front blocks at a raised wave priority 0.2259 / 0.2253 against 0.2194: what a front block
     // costs is the wave SLOT it holds for the ~10 us of its table-read chain, not its instructions, and slots are what an interleaved
     // front block takes away from stream blocks that could use them.
-    if (q.kind == kFrames && q.T == 1 && q.S > kSmallBatchFrames && sw.fuse_one != 0) {
+    // A KEYED step takes neither form, as with MBX_FUSE_ONE=0: the stream blocks of both re-run the front end from the wire frame (the
+    // fall-back path; the in-wave form always), so a keyed instance would have to reach into the stream bodies.  It takes the staged
+    // launches, whose front launch is the keyed one.
+    if (q.kind == kFrames && q.T == 1 && q.S > kSmallBatchFrames && sw.fuse_one != 0 && !q.keyed) {
         // AMBE, 9-byte frames: byte loads, any alignment; no in-wave form: without a workspace the staged kernels.  IMBE: dword loads.
         const bool takes_frames = sh && (!imbe || q.aligned);
         if (takes_frames && sw.fuse_one == 2 && !imbe7100 && q.own_workspace) {

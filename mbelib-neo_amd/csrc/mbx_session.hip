@@ -30,6 +30,7 @@
 #include "mbx_codec.h"
 #include "mbx_gather.h"
 #include "mbx_host.h"
+#include "mbx_keystream.h"
 
 namespace {
 
@@ -70,11 +71,13 @@ struct Slot {
     void*               d_workspace = nullptr;
     uint8_t*            d_bursts = nullptr;   // bursts (hard or soft), grown by the burst submits that need more
     size_t              bursts_cap = 0;
+    uint8_t*            d_keystream = nullptr;   // keystream rows (include/mbx_keystream.h), allocated (as h_keystream) by the slot's first keyed submit
     // pinned staging, allocated on first need
     uint8_t*            h_in = nullptr;
     uint8_t*            h_soft = nullptr;
     uint8_t*            h_bursts = nullptr;   // ... and their pinned staging
     size_t              h_bursts_cap = 0;
+    uint8_t*            h_keystream = nullptr;
     int32_t*            h_index = nullptr;
     int16_t*            h_pcm16 = nullptr;
     float*              h_pcmf = nullptr;
@@ -174,7 +177,7 @@ struct BurstIn {
 
 // `soft`: frames are mbe_soft_bit cells (soft_bytes per frame) instead of wire frames (frame_bytes)
 int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst);
+            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst, const uint8_t* keystream);
 
 int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records);
 
@@ -190,7 +193,7 @@ int refuse_mixed(const mbx_session* s, const char* who) {
 }
 
 int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-           mbe_process_result* results, mbx_param_record* records, const BurstIn* burst = nullptr) {
+           mbe_process_result* results, mbx_param_record* records, const BurstIn* burst = nullptr, const uint8_t* keystream = nullptr) {
     if (refuse_mixed(s, "mbx_session_submit") < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
@@ -235,7 +238,7 @@ int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frame
     }
     // From here on work is queued on the three streams against this slot's buffers.  If anything fails halfway the slot is
     // NOT marked busy, so before the error goes back the streams are drained: the next submit may reuse the slot at once.
-    rc = enqueue(s, sl, n, T, index, frames, soft, pcm16, pcmf, results, records, burst);
+    rc = enqueue(s, sl, n, T, index, frames, soft, pcm16, pcmf, results, records, burst, keystream);
     if (rc < 0) {
         (void)hipStreamSynchronize(s->s_comp);
         (void)hipStreamSynchronize(s->s_out);
@@ -249,7 +252,7 @@ int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frame
 }
 
 int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst) {
+            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst, const uint8_t* keystream) {
     int rc = 0;
     const size_t nf = (size_t)n * (size_t)T;
     // ---- in ----
@@ -313,11 +316,40 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
             return rc;
         }
     }
+    if (keystream) {   // the keystream rows take the road the frames take: pinned 16-byte aligned rows in place, others staged
+        const size_t ks_total = nf * (size_t)MBX_KEYSTREAM_ROW_BYTES;
+        if (!sl.d_keystream) {
+            S_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_keystream), s->max_frames * (size_t)MBX_KEYSTREAM_ROW_BYTES));
+        }
+        const uint8_t* ks = keystream;
+        if (!is_pinned(keystream) || (reinterpret_cast<uintptr_t>(ks) & 15u)) {
+            rc = pinned(sl.h_keystream, s->max_frames * (size_t)MBX_KEYSTREAM_ROW_BYTES);
+            if (rc < 0) {
+                return rc;
+            }
+            memcpy(sl.h_keystream, keystream, ks_total);
+            ks = sl.h_keystream;
+        }
+        const void* ks_view = ks;
+        void* ks_mapped = nullptr;
+        if (hipHostGetDevicePointer(&ks_mapped, const_cast<uint8_t*>(ks), 0) == hipSuccess && ks_mapped) {
+            ks_view = ks_mapped;
+        } else {
+            (void)hipGetLastError();
+        }
+        rc = mbx_stage_in(sl.d_keystream, ks_view, ks_total, s->s_comp);
+        if (rc < 0) {
+            return rc;
+        }
+    }
     // ---- compute ----
     int16_t* d16 = pcm16 ? sl.d_pcm16 : nullptr;
     float*   dfl = pcmf ? sl.d_pcmf : nullptr;
     mbe_process_result* dres = results ? sl.d_results : nullptr;
-    if (burst && soft) {   // the gather in front of the step the frames submits run: resident words or plain triplets, index or none
+    if (keystream) {   // the keyed call takes every form: hard or soft, index or none, resident words or plain triplets
+        rc = mbx_process_batch_keyed(s->codec, n, T, index ? sl.d_index : nullptr, soft ? nullptr : sl.d_frames, soft ? sl.d_soft : nullptr,
+                                     sl.d_keystream, s->d_state, s->d_resident, s->d_rng, d16, dfl, dres, sl.d_records, s->s_comp);
+    } else if (burst && soft) {   // the gather in front of the step the frames submits run: resident words or plain triplets, index or none
         rc = mbx_process_bursts_soft(burst->sched, n, index ? sl.d_index : nullptr, reinterpret_cast<const mbe_soft_bit*>(sl.d_bursts), s->d_state,
                                      s->d_resident, s->d_rng, d16, dfl, dres, sl.d_records, s->s_comp);
     } else if (burst) {
@@ -508,6 +540,8 @@ int mbx_session_destroy(mbx_session* s) {
         (void)hipFree(sl.d_index);
         (void)hipFree(sl.d_workspace);
         (void)hipFree(sl.d_bursts);
+        (void)hipFree(sl.d_keystream);
+        (void)hipHostFree(sl.h_keystream);
         (void)hipHostFree(sl.h_bursts);
         (void)hipHostFree(sl.h_in);
         (void)hipHostFree(sl.h_soft);
@@ -652,6 +686,19 @@ int mbx_session_submit_soft_indexed(mbx_session* s, int n, int T, const int32_t*
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     return submit(s, n, T, stream_index, soft, true, pcm16, pcmf, results, records);
+}
+
+// ---- keyed submits (include/mbx_keystream.h): a frames submit of either kind with a keystream row per frame ---------------------------
+int mbx_session_submit_keyed(mbx_session* s, int n, int T, const int32_t* stream_index, const uint8_t* frames, const mbe_soft_bit* soft,
+                             const uint8_t* keystream, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records) {
+    if (refuse_mixed(s, "mbx_session_submit_keyed") < 0) {
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (!s || (frames != nullptr) == (soft != nullptr) || (!stream_index && n != s->streams)) {
+        mbx_set_error_text("mbx_session_submit_keyed: a session, exactly one of frames and soft, and without an index n = the session's stream count");
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    return submit(s, n, T, stream_index, soft ? static_cast<const void*>(soft) : frames, soft != nullptr, pcm16, pcmf, results, records, nullptr, keystream);
 }
 
 // ---- burst submits (include/mbx_burst.h) ---------------------------------------------------------------------------------------------

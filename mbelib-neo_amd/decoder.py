@@ -9,11 +9,13 @@ Reference interface mirrored (include/mbelib-neo/mbelib.h):
   mbe_processImbe7200x4400Frame[f]      -> decode(frames, T)            codec=IMBE
   mbe_processAmbe3600x2450Frame[f]      -> decode(frames, T)            codec=AMBE
   mbe_decode*Frame                      -> fec(frames)
+  mbe_decode*Frame, the caller's keystream XOR, mbe_process*Dataf -> decode / decode_soft / decode_ragged(..., keystream=rows)
 """
 import numpy as np
 
 from . import _native
 from . import bursts as _bursts
+from . import keystream as _keystream
 from .layout import (
     CODEC_IMBE7200X4400,
     FRAME_BYTES,
@@ -67,6 +69,7 @@ class BatchDecoder:
         self.state = torch.from_numpy(st.view(np.uint8).reshape(-1)).to(self.device)
         self.rng = torch.from_numpy(rg.view(np.uint8).reshape(-1)).to(self.device)
         self.resident = torch.zeros(self.streams, dtype=torch.int32, device=self.device) if resident else None
+        self._keystream = None   # the rows of the last keyed call
 
     # -- state access (host copies) --------------------------------------------------------
     def materialize(self):
@@ -98,6 +101,17 @@ class BatchDecoder:
             return torch.from_numpy(np.ascontiguousarray(frames).reshape(-1)).to(self.device)
         return frames
 
+    def keystream_rows(self, keystream, rows):
+        """The keystream of a keyed call (include/mbx_keystream.h; keystream.rows_from_bits makes it) as a device tensor: uint8
+        [rows, 12], one row per batch row, torch tensor or array."""
+        torch = _torch()
+        if isinstance(keystream, np.ndarray) and keystream.dtype != np.uint8:
+            raise ValueError("keystream must be uint8 rows of KEYSTREAM_ROW_BYTES bytes")
+        d = self.to_device(keystream)
+        if d.dtype != torch.uint8 or not d.is_contiguous() or d.numel() != int(rows) * _keystream.ROW_BYTES:
+            raise ValueError(f"keystream must hold {int(rows)} contiguous uint8 rows of {_keystream.ROW_BYTES} bytes, one per batch row")
+        return d
+
     # -- launches ----------------------------------------------------------------------------
     def fec(self, frames):
         """FEC stage only: wire frames -> parameter records (device tensor of uint32 [n, 4])."""
@@ -122,11 +136,13 @@ class BatchDecoder:
         out["results"] = torch.empty((n, 5), dtype=torch.int32, device=self.device) if want_results else None
         return out
 
-    def decode_soft(self, soft, T, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None):
+    def decode_soft(self, soft, T, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None, keystream=None):
         """Soft-decision frames: `soft` = torch tensor (or array) uint8 [n*T, cells, 2] = (bit, reliability), cells = 184 / 96 /
         168 / 96 for codecs 0..3, stream-major.  Runs mbx_process_batch_soft_resident on this decoder's state, resident or not.
         stream_index (int32 tensor [n]): batch row i belongs to stream stream_index[i] of this decoder (no stream twice); without
-        it n = streams.  Hard decisions must be 0/1 (checked here only for host arrays).  Hard and soft calls may alternate."""
+        it n = streams.  Hard decisions must be 0/1 (checked here only for host arrays).  Hard and soft calls may alternate.
+        keystream (uint8 [n*T, 12]): a keyed call, mbx_process_batch_keyed -- row r is XORed onto the parameter bits of batch row r
+        between FEC and parameter decode; out["records"] holds the bits after it."""
         torch = _torch()
         if isinstance(soft, np.ndarray):
             soft = _soft_array(self.codec, soft, soft.size // (SOFT_CELLS[self.codec] * 2))
@@ -149,13 +165,22 @@ class BatchDecoder:
         def ptr(t):
             return t.data_ptr() if t is not None else None
 
+        d_key = self.keystream_rows(keystream, n * int(T)) if keystream is not None else None
         with torch.cuda.device(self.device):
-            rc = _native.lib().mbx_process_batch_soft_resident(
-                self.codec, n, int(T), ptr(stream_index), d_soft.data_ptr(), self.state.data_ptr(), ptr(self.resident),
-                self.rng.data_ptr(), ptr(out["pcm16"]), ptr(out["pcmf"]), ptr(out["results"]), out["records"].data_ptr(),
-                torch.cuda.current_stream().cuda_stream,
-            )
-        _native.check(rc, "mbx_process_batch_soft_resident")
+            if d_key is not None:
+                rc = _native.lib().mbx_process_batch_keyed(
+                    self.codec, n, int(T), ptr(stream_index), None, d_soft.data_ptr(), d_key.data_ptr(), self.state.data_ptr(),
+                    ptr(self.resident), self.rng.data_ptr(), ptr(out["pcm16"]), ptr(out["pcmf"]), ptr(out["results"]),
+                    out["records"].data_ptr(), torch.cuda.current_stream().cuda_stream,
+                )
+                self._keystream = d_key   # the launch is asynchronous: the decoder holds the uploaded rows until its next keyed call
+            else:
+                rc = _native.lib().mbx_process_batch_soft_resident(
+                    self.codec, n, int(T), ptr(stream_index), d_soft.data_ptr(), self.state.data_ptr(), ptr(self.resident),
+                    self.rng.data_ptr(), ptr(out["pcm16"]), ptr(out["pcmf"]), ptr(out["results"]), out["records"].data_ptr(),
+                    torch.cuda.current_stream().cuda_stream,
+                )
+        _native.check(rc, "mbx_process_batch_keyed" if d_key is not None else "mbx_process_batch_soft_resident")
         return out
 
     def decode_bursts(self, schedule, bursts, soft=False, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None,
@@ -260,7 +285,7 @@ class BatchDecoder:
         return out
 
     def decode_ragged(self, frames, counts, soft=False, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None,
-                      codec=None):
+                      codec=None, keystream=None):
         """A frame count per stream: row i of the batch brings counts[i] >= 0 frames (host sequence or array), its rows of `frames`
         and of every output are offsets[i] .. offsets[i + 1] - 1 with offsets = [0, cumsum(counts)], in time order.  One
         mbx_process_batch_ragged / _soft_ragged call on this decoder's state, resident or not; soft=True: `frames` holds
@@ -270,7 +295,9 @@ class BatchDecoder:
         codec (array of n MBX_CODEC_* values): a MIXED batch, row i of codec[i], decoded by one mbx_process_batch_mixed /
         _soft_mixed call whatever the decoder's own codec is; `frames` then holds rows of ONE size, MIXED_ROW_BYTES bytes
         (soft: MIXED_ROW_CELLS cells), as pack_mixed_rows makes them from each stream's own frames -- or is the list of per-stream
-        arrays itself.  The codec of a stream stays what it was in the stream's earlier calls: that is the caller's to keep."""
+        arrays itself.  The codec of a stream stays what it was in the stream's earlier calls: that is the caller's to keep.
+        keystream (uint8 [sum(counts), 12]): a keyed call, mbx_process_batch_ragged_keyed -- row r onto the parameter bits of
+        batch row r, whatever its codec."""
         counts = np.ascontiguousarray(counts, dtype=np.int64).reshape(-1)
         n = self.streams if stream_index is None else int(stream_index.numel())
         if counts.size != n or (n and counts.min() < 0):
@@ -317,7 +344,16 @@ class BatchDecoder:
         L = _native.lib()
         tail = (d_offsets.data_ptr(), total, ptr(stream_index), d_frames.data_ptr(), self.state.data_ptr(), ptr(self.resident),
                 self.rng.data_ptr(), ptr(out["pcm16"]), ptr(out["pcmf"]), ptr(out["results"]), out["records"].data_ptr())
+        d_key = self.keystream_rows(keystream, total) if keystream is not None else None
         with torch.cuda.device(self.device):
+            if d_key is not None:
+                d_codec = torch.from_numpy(codec).to(self.device) if mixed else None
+                rc = L.mbx_process_batch_ragged_keyed(self.codec, ptr(d_codec), n, d_offsets.data_ptr(), total, ptr(stream_index),
+                                                      None if soft else d_frames.data_ptr(), d_frames.data_ptr() if soft else None,
+                                                      d_key.data_ptr(), *tail[4:], torch.cuda.current_stream().cuda_stream)
+                self._keystream = d_key   # the launch is asynchronous: the decoder holds the uploaded rows until its next keyed call
+                _native.check(rc, "mbx_process_batch_ragged_keyed")
+                return out
             if mixed:
                 d_codec = torch.from_numpy(codec).to(self.device)
                 rc = (L.mbx_process_batch_soft_mixed if soft else L.mbx_process_batch_mixed)(
@@ -328,12 +364,15 @@ class BatchDecoder:
         _native.check(rc, "mbx_process_batch_mixed" if mixed else "mbx_process_batch_ragged")
         return out
 
-    def decode(self, frames, T, want_pcm16=True, want_float=False, want_results=True, out=None, staged=False):
+    def decode(self, frames, T, want_pcm16=True, want_float=False, want_results=True, out=None, staged=False, keystream=None):
         """S x T frames, stream-major (stream s, frame t at index s*T + t).  Asynchronous on the
         current torch stream; returns device tensors.
         staged=True: the stages as separate calls (mbx_fec_* then mbx_process_records) instead of mbx_process_batch -- the
         same results by contract; the IMBE codecs at T = 1 take one fused launch in mbx_process_batch and the FEC /
-        expansion / stream launches here (tests compare the two)."""
+        expansion / stream launches here (tests compare the two).
+        keystream (uint8 [streams*T, 12]): a keyed call, mbx_process_batch_keyed -- row r is XORed onto the parameter bits of
+        batch row r between FEC and parameter decode (staged=True: mbx_apply_keystream between the two calls); out["records"]
+        holds the bits after it."""
         torch = _torch()
         d_frames = self.to_device(frames)
         n = self.streams * int(T)
@@ -345,14 +384,25 @@ class BatchDecoder:
         def ptr(t):
             return t.data_ptr() if t is not None else None
 
+        d_key = self.keystream_rows(keystream, n) if keystream is not None else None
+        if d_key is not None:
+            self._keystream = d_key   # the launch is asynchronous: the decoder holds the uploaded rows until its next keyed call
         with torch.cuda.device(self.device):   # the launcher works on the current device's context
-            if staged:
+            if d_key is not None and not staged:
+                rc = _native.lib().mbx_process_batch_keyed(
+                    self.codec, self.streams, int(T), None, d_frames.data_ptr(), None, d_key.data_ptr(), self.state.data_ptr(),
+                    ptr(self.resident), self.rng.data_ptr(), ptr(out["pcm16"]), ptr(out["pcmf"]), ptr(out["results"]),
+                    out["records"].data_ptr(), torch.cuda.current_stream().cuda_stream,
+                )
+            elif staged:
                 if self.resident is not None:
                     raise ValueError("staged decoding is for the ABI-triplet form")
                 L = _native.lib()
                 strm = torch.cuda.current_stream().cuda_stream
                 fn = {0: L.mbx_fec_imbe7200x4400, 1: L.mbx_fec_ambe3600x2450, 2: L.mbx_fec_imbe7100x4400, 3: L.mbx_fec_ambe3600x2450}[self.codec]
                 _native.check(fn(d_frames.data_ptr(), n, out["records"].data_ptr(), strm), "mbx_fec")
+                if d_key is not None:
+                    _native.check(L.mbx_apply_keystream(self.codec, out["records"].data_ptr(), n, d_key.data_ptr(), strm), "mbx_apply_keystream")
                 rc = L.mbx_process_records(0 if self.codec == 2 else self.codec, self.streams, int(T), out["records"].data_ptr(),
                                            self.state.data_ptr(), self.rng.data_ptr(), ptr(out["pcm16"]), ptr(out["pcmf"]),
                                            ptr(out["results"]), strm)
