@@ -559,10 +559,21 @@ int mbx_session_submit_soft_indexed(mbx_session* s, int n, int T, const int32_t*
                                     float* pcmf, mbe_process_result* results, mbx_param_record* records);
 /* every batch submitted so far is complete and its outputs are in the caller's buffers */
 int mbx_session_wait(mbx_session* s);
-/* state of streams [first, first + count): ref mbe_initMbeParms / mbe_setThreadRngSeed / direct access.  These wait. */
+/* state of streams [first, first + count): ref mbe_initMbeParms / mbe_setThreadRngSeed / direct access.  All four wait for every
+ * submit in flight (and hand its outputs to pageable buffers) before they touch the state, so a submit before the call ran on the
+ * state before it and the next submit runs on the state after it.  count = 0 returns 0 and changes nothing; first < 0,
+ * first + count > streams, a NULL seeds, or state and rng both NULL return MBE_STATUS_INVALID_ARGUMENT and change nothing.
+ * tests/test_gpu_session_churn.py holds them to this. */
+/* reset: the slots' triplets and noise generators are the defaults of mbe_initMbeParms (the IMBE defaults, for every codec), whole. */
 int mbx_session_reset(mbx_session* s, int first, int count);
+/* seed: set_state without a state -- new noise generators; the slots' models, and the elision of their third struct, stay as they are.
+ * (As in the reference a new seed of the unvoiced noise is taken up when the stream's noise state is next initialised: after a reset.) */
 int mbx_session_seed(mbx_session* s, int first, int count, const uint32_t* seeds);
+/* get_state: the slots' triplets come back whole, in their ABI form (what mbx_process_batch would have left), and / or their noise
+ * generators; the session goes on unaffected, the slots outside the range keep their resident form. */
 int mbx_session_get_state(mbx_session* s, int first, int count, mbe_parms* state /* count*3, or NULL */, mbx_stream_rng* rng /* or NULL */);
+/* set_state: with a state the slots' triplets are the caller's, whole (ABI form: nothing of them is elided any more); without one
+ * (rng alone) the models and their elision stay as they are.  The slots outside the range are not touched. */
 int mbx_session_set_state(mbx_session* s, int first, int count, const mbe_parms* state, const mbx_stream_rng* rng);
 /* pinned host memory for zero-copy DMA of frames / PCM */
 void* mbx_host_alloc(size_t bytes);

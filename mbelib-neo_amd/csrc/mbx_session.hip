@@ -600,7 +600,9 @@ int mbx_session_set_state(mbx_session* s, int first, int count, const mbe_parms*
     if (state) {
         S_TRY(hipMemcpy(s->d_state + 3 * (size_t)first, state, (size_t)count * 3 * sizeof(mbe_parms), hipMemcpyHostToDevice));
         if (s->d_resident) {   // the caller's triplets are whole: nothing is elided any more
-            S_TRY(hipMemset(s->d_resident + first, 0, (size_t)count * sizeof(uint32_t)));
+            // On the compute stream, not the null stream: s_comp is non-blocking, so a null-stream memset is not ordered in front of the
+            // next submit's launches (the workspace flags of mbx_api.hip, same reasoning).  By the API's contract; no race was observed.
+            S_TRY(hipMemsetAsync(s->d_resident + first, 0, (size_t)count * sizeof(uint32_t), s->s_comp));
         }
     }
     if (rng) {
@@ -655,6 +657,9 @@ int mbx_session_reset(mbx_session* s, int first, int count) {
 int mbx_session_seed(mbx_session* s, int first, int count, const uint32_t* seeds) {
     if (!range_ok(s, first, count) || !seeds) {
         return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (count == 0) {   // (as reset: an empty vector's data() is NULL, which set_state refuses)
+        return 0;
     }
     std::vector<mbx_stream_rng> rg((size_t)count);
     for (int i = 0; i < count; ++i) {
