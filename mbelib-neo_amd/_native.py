@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h,
-include/mbx_burst_groups.h, include/mbx_keystream.h).  Fails loudly when the library
+include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -165,6 +165,13 @@ _KEYSTREAM_SIGNATURES = {
     "mbx_session_submit_keyed": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 KEYSTREAM_SYMBOLS = tuple(_KEYSTREAM_SIGNATURES)
+# companded PCM out (include/mbx_pcm8.h): G.711 bytes, converted on the device
+_PCM8_SIGNATURES = {
+    "mbx_pcm_compand_host": (C.c_int, [C.c_int, _vp, _sz, _vp]),
+    "mbx_pcm_compand": (C.c_int, [C.c_int, _vp, _sz, _vp, _vp]),
+    "mbx_session_next_pcm8": (C.c_int, [_vp, C.c_int, _vp]),
+}
+PCM8_SYMBOLS = tuple(_PCM8_SIGNATURES)
 
 
 class BurstGroupStruct(C.Structure):
@@ -193,7 +200,7 @@ def lib():
             handle = C.CDLL(path)
         except OSError as e:  # e.g. libamdhip64 not found
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
-        for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES, **_KEYSTREAM_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES, **_KEYSTREAM_SIGNATURES, **_PCM8_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

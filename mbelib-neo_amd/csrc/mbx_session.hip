@@ -2,7 +2,8 @@
 // device and takes batches of wire frames from HOST memory, returning PCM to HOST memory (include/mbx.h, "sessions").
 //
 // What crosses PCIe per 20 ms frame is the wire frame in (18 B / 9 B) and the PCM out (320 B int16, + 20 B when the
-// mbe_process_result is asked for) -- not the 15.6 KB of state the per-call conveniences (mbx_process_batch_host) move.
+// mbe_process_result is asked for; 160 B where the host takes G.711 bytes, include/mbx_pcm8.h: one compand launch behind the step)
+// -- not the 15.6 KB of state the per-call conveniences (mbx_process_batch_host) move.
 //
 // Pipeline: kDepth slots of device buffers, two HIP streams.  Batch k uses slot k % kDepth:
 //     compute stream   stage-in kernel (frames(k) read from pinned host memory), FEC + stream kernels -> event comp(k)
@@ -21,7 +22,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <new>
+#include <unordered_map>
 #include <vector>
 
 #include "mbx.h"
@@ -31,6 +34,7 @@
 #include "mbx_gather.h"
 #include "mbx_host.h"
 #include "mbx_keystream.h"
+#include "mbx_pcm8.h"
 
 namespace {
 
@@ -67,6 +71,7 @@ struct Slot {
     int16_t*            d_pcm16 = nullptr;
     float*              d_pcmf = nullptr;
     mbe_process_result* d_results = nullptr;
+    uint8_t*            d_pcm8 = nullptr;   // companded bytes (include/mbx_pcm8.h): a session created with MBX_SESSION_PCM8
     int32_t*            d_index = nullptr;
     void*               d_workspace = nullptr;
     uint8_t*            d_bursts = nullptr;   // bursts (hard or soft), grown by the burst submits that need more
@@ -81,11 +86,12 @@ struct Slot {
     int32_t*            h_index = nullptr;
     int16_t*            h_pcm16 = nullptr;
     float*              h_pcmf = nullptr;
+    uint8_t*            h_pcm8 = nullptr;
     mbe_process_result* h_results = nullptr;
     mbx_param_record*   h_records = nullptr;
     hipEvent_t          comp = nullptr, done = nullptr;
     bool                busy = false;
-    CopyOut             out[4];
+    CopyOut             out[5];
     int                 nout = 0;
 };
 
@@ -164,6 +170,28 @@ void default_parms(mbe_parms& p) {   // ref mbe_initMbeParms, src/core/mbelib.c:
     p.noiseSeed = -1.0f;
 }
 
+// mbx_session_next_pcm8: where the NEXT submit of a session also delivers its PCM as companded bytes (include/mbx_pcm8.h).  The
+// attachment lasts for one submit call, whether that call queues or refuses, so every public submit takes it as its first act --
+// by the session's ADDRESS, out of a table beside the sessions: a submit refuses some arguments before it looks at its session, and
+// must not dereference a pointer it has not checked to use the attachment up.
+struct Pcm8Out {
+    uint8_t* dst = nullptr;   // host memory, rows * 160 bytes; nullptr: nothing attached
+    int      law = 0;         // MBX_LAW_*
+};
+std::mutex g_pcm8_mu;
+std::unordered_map<const mbx_session*, Pcm8Out> g_pcm8;
+
+Pcm8Out take_pcm8(const mbx_session* s) {
+    std::lock_guard<std::mutex> lock(g_pcm8_mu);
+    Pcm8Out out;
+    const auto it = g_pcm8.find(s);
+    if (it != g_pcm8.end()) {
+        out = it->second;
+        g_pcm8.erase(it);
+    }
+    return out;
+}
+
 bool range_ok(const mbx_session* s, int first, int count) {
     return s && first >= 0 && count >= 0 && (long long)first + count <= s->streams;
 }
@@ -177,9 +205,14 @@ struct BurstIn {
 
 // `soft`: frames are mbe_soft_bit cells (soft_bytes per frame) instead of wire frames (frame_bytes)
 int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst, const uint8_t* keystream);
+            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst, const uint8_t* keystream, const Pcm8Out& pcm8);
 
-int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records);
+int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records, uint8_t* pcm8);
+
+// behind the step of a submit of nf frames that has a destination attached: the slot's int16 rows -> its bytes, on the compute stream
+int compand_step(mbx_session* s, Slot& sl, size_t nf, const Pcm8Out& pcm8) {
+    return pcm8.dst ? mbx_pcm_compand(pcm8.law, sl.d_pcm16, nf, sl.d_pcm8, s->s_comp) : 0;
+}
 
 // a mixed session takes burst groups only
 int refuse_mixed(const mbx_session* s, const char* who) {
@@ -192,7 +225,7 @@ int refuse_mixed(const mbx_session* s, const char* who) {
     return 0;
 }
 
-int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
+int submit(const Pcm8Out& pcm8, mbx_session* s, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst = nullptr, const uint8_t* keystream = nullptr) {
     if (refuse_mixed(s, "mbx_session_submit") < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
@@ -238,7 +271,7 @@ int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frame
     }
     // From here on work is queued on the three streams against this slot's buffers.  If anything fails halfway the slot is
     // NOT marked busy, so before the error goes back the streams are drained: the next submit may reuse the slot at once.
-    rc = enqueue(s, sl, n, T, index, frames, soft, pcm16, pcmf, results, records, burst, keystream);
+    rc = enqueue(s, sl, n, T, index, frames, soft, pcm16, pcmf, results, records, burst, keystream, pcm8);
     if (rc < 0) {
         (void)hipStreamSynchronize(s->s_comp);
         (void)hipStreamSynchronize(s->s_out);
@@ -252,7 +285,7 @@ int submit(mbx_session* s, int n, int T, const int32_t* index, const void* frame
 }
 
 int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst, const uint8_t* keystream) {
+            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst, const uint8_t* keystream, const Pcm8Out& pcm8) {
     int rc = 0;
     const size_t nf = (size_t)n * (size_t)T;
     // ---- in ----
@@ -343,7 +376,7 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
         }
     }
     // ---- compute ----
-    int16_t* d16 = pcm16 ? sl.d_pcm16 : nullptr;
+    int16_t* d16 = pcm16 || pcm8.dst ? sl.d_pcm16 : nullptr;   // (the compand behind the step reads the int16 rows)
     float*   dfl = pcmf ? sl.d_pcmf : nullptr;
     mbe_process_result* dres = results ? sl.d_results : nullptr;
     if (keystream) {   // the keyed call takes every form: hard or soft, index or none, resident words or plain triplets
@@ -368,14 +401,14 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
         rc = mbx_process_batch_ws(s->codec, n, T, sl.d_frames, s->d_state, s->d_rng, d16, dfl, dres, sl.d_records, sl.d_workspace,
                                   mbx_workspace_bytes(s->max_frames), s->s_comp);
     }
-    if (rc < 0) {
+    if (rc < 0 || (rc = compand_step(s, sl, nf, pcm8)) < 0) {
         return rc;
     }
-    return copy_out(s, sl, nf, pcm16, pcmf, results, records);
+    return copy_out(s, sl, nf, pcm16, pcmf, results, records, pcm8.dst);
 }
 
 // ---- out ----: behind the compute stream's launches of a submit of nf frames, the outputs to the caller (or to the slot's staging)
-int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records) {
+int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records, uint8_t* pcm8) {
     int rc = 0;
     S_TRY(hipEventRecord(sl.comp, s->s_comp));
     S_TRY(hipStreamWaitEvent(s->s_out, sl.comp, 0));
@@ -398,7 +431,8 @@ int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, m
         return e == hipSuccess ? 0 : mbx::hip_failed("session: ", "hipMemcpyAsync (device to host)", e);
     };
     if ((rc = out(pcm16, sl.d_pcm16, sl.h_pcm16, 160)) < 0 || (rc = out(pcmf, sl.d_pcmf, sl.h_pcmf, 160)) < 0
-        || (rc = out(results, sl.d_results, sl.h_results, 1)) < 0 || (rc = out(records, sl.d_records, sl.h_records, 1)) < 0) {
+        || (rc = out(results, sl.d_results, sl.h_results, 1)) < 0 || (rc = out(records, sl.d_records, sl.h_records, 1)) < 0
+        || (rc = out(pcm8, sl.d_pcm8, sl.h_pcm8, 160)) < 0) {
         return rc;
     }
     S_TRY(hipEventRecord(sl.done, s->s_out));
@@ -424,7 +458,7 @@ void mbx_host_free(void* p) {
 static int create_session(mbx_session** out, int codec, const uint8_t* stream_codec, int streams, size_t max_frames_per_submit, unsigned outputs) {
     const mbx::CodecShape* shape = mbx::codec_shape(codec);
     if (!out || streams <= 0 || max_frames_per_submit == 0 || (!shape && !stream_codec)
-        || (outputs & ~(MBX_SESSION_PCM16 | MBX_SESSION_PCMF | MBX_SESSION_RESULTS)) != 0u) {
+        || (outputs & ~(MBX_SESSION_PCM16 | MBX_SESSION_PCMF | MBX_SESSION_RESULTS | MBX_SESSION_PCM8)) != 0u) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     for (int i = 0; stream_codec && i < streams; ++i) {
@@ -482,8 +516,11 @@ static int create_session(mbx_session** out, int codec, const uint8_t* stream_co
         if (!s->d_resident) {   // (the resident entry point uses the workspace the launcher keeps for the compute stream, reserved below)
             C_TRY(hipMalloc(&sl.d_workspace, mbx_workspace_bytes(mf)));
         }
-        if (s->outputs & MBX_SESSION_PCM16) {
+        if (s->outputs & (MBX_SESSION_PCM16 | MBX_SESSION_PCM8)) {   // (the step writes int16 and the compand reads it)
             C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_pcm16), mf * 160 * sizeof(int16_t)));
+        }
+        if (s->outputs & MBX_SESSION_PCM8) {
+            C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_pcm8), mf * 160));
         }
         if (s->outputs & MBX_SESSION_PCMF) {
             C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_pcmf), mf * 160 * sizeof(float)));
@@ -522,6 +559,7 @@ int mbx_session_destroy(mbx_session* s) {
     if (!s) {
         return 0;
     }
+    (void)take_pcm8(s);   // (an attachment no submit used)
     DeviceGuard guard(s->device);
     if (s->s_comp) {
         (void)hipStreamSynchronize(s->s_comp);
@@ -537,6 +575,7 @@ int mbx_session_destroy(mbx_session* s) {
         (void)hipFree(sl.d_pcm16);
         (void)hipFree(sl.d_pcmf);
         (void)hipFree(sl.d_results);
+        (void)hipFree(sl.d_pcm8);
         (void)hipFree(sl.d_index);
         (void)hipFree(sl.d_workspace);
         (void)hipFree(sl.d_bursts);
@@ -548,6 +587,7 @@ int mbx_session_destroy(mbx_session* s) {
         (void)hipHostFree(sl.h_index);
         (void)hipHostFree(sl.h_pcm16);
         (void)hipHostFree(sl.h_pcmf);
+        (void)hipHostFree(sl.h_pcm8);
         (void)hipHostFree(sl.h_results);
         (void)hipHostFree(sl.h_records);
         if (sl.comp) {
@@ -670,32 +710,58 @@ int mbx_session_seed(mbx_session* s, int first, int count, const uint32_t* seeds
 }
 
 int mbx_session_submit(mbx_session* s, int T, const uint8_t* frames, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
-    return submit(s, s ? s->streams : 0, T, nullptr, frames, false, pcm16, pcmf, results, nullptr);
+    return submit(take_pcm8(s), s, s ? s->streams : 0, T, nullptr, frames, false, pcm16, pcmf, results, nullptr);
 }
 
 int mbx_session_submit_indexed(mbx_session* s, int n, int T, const int32_t* stream_index, const uint8_t* frames, int16_t* pcm16,
                                float* pcmf, mbe_process_result* results, mbx_param_record* records) {
+    const Pcm8Out pcm8 = take_pcm8(s);
     if (!stream_index) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    return submit(s, n, T, stream_index, frames, false, pcm16, pcmf, results, records);
+    return submit(pcm8, s, n, T, stream_index, frames, false, pcm16, pcmf, results, records);
 }
 
 int mbx_session_submit_soft(mbx_session* s, int T, const mbe_soft_bit* soft, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
-    return submit(s, s ? s->streams : 0, T, nullptr, soft, true, pcm16, pcmf, results, nullptr);
+    return submit(take_pcm8(s), s, s ? s->streams : 0, T, nullptr, soft, true, pcm16, pcmf, results, nullptr);
 }
 
 int mbx_session_submit_soft_indexed(mbx_session* s, int n, int T, const int32_t* stream_index, const mbe_soft_bit* soft, int16_t* pcm16,
                                     float* pcmf, mbe_process_result* results, mbx_param_record* records) {
+    const Pcm8Out pcm8 = take_pcm8(s);
     if (!stream_index) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    return submit(s, n, T, stream_index, soft, true, pcm16, pcmf, results, records);
+    return submit(pcm8, s, n, T, stream_index, soft, true, pcm16, pcmf, results, records);
+}
+
+// ---- companded bytes out (include/mbx_pcm8.h): the destination of the next submit ----------------------------------------------------
+int mbx_session_next_pcm8(mbx_session* s, int law, uint8_t* pcm8) {
+    if (!s) {
+        mbx_set_error_text("mbx_session_next_pcm8: no session");
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (!pcm8) {
+        (void)take_pcm8(s);
+        return 0;
+    }
+    if (!(s->outputs & MBX_SESSION_PCM8)) {
+        mbx_set_error_text("mbx_session_next_pcm8: the session was created without MBX_SESSION_PCM8");
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (law != MBX_LAW_ULAW && law != MBX_LAW_ALAW) {
+        mbx_set_error_text("mbx_session_next_pcm8: law is MBX_LAW_ULAW or MBX_LAW_ALAW");
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    std::lock_guard<std::mutex> lock(g_pcm8_mu);
+    g_pcm8[s] = Pcm8Out{pcm8, law};
+    return 0;
 }
 
 // ---- keyed submits (include/mbx_keystream.h): a frames submit of either kind with a keystream row per frame ---------------------------
 int mbx_session_submit_keyed(mbx_session* s, int n, int T, const int32_t* stream_index, const uint8_t* frames, const mbe_soft_bit* soft,
                              const uint8_t* keystream, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records) {
+    const Pcm8Out pcm8 = take_pcm8(s);
     if (refuse_mixed(s, "mbx_session_submit_keyed") < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
@@ -703,12 +769,13 @@ int mbx_session_submit_keyed(mbx_session* s, int n, int T, const int32_t* stream
         mbx_set_error_text("mbx_session_submit_keyed: a session, exactly one of frames and soft, and without an index n = the session's stream count");
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    return submit(s, n, T, stream_index, soft ? static_cast<const void*>(soft) : frames, soft != nullptr, pcm16, pcmf, results, records, nullptr, keystream);
+    return submit(pcm8, s, n, T, stream_index, soft ? static_cast<const void*>(soft) : frames, soft != nullptr, pcm16, pcmf, results, records, nullptr, keystream);
 }
 
 // ---- burst submits (include/mbx_burst.h) ---------------------------------------------------------------------------------------------
 static int submit_bursts(const char* who, mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index, const void* bursts,
                          size_t burst_stride, bool soft, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
+    const Pcm8Out pcm8 = take_pcm8(s);
     char text[160];
     if (!s || !sched || !bursts || n < 0 || refuse_mixed(s, who) < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
@@ -735,7 +802,7 @@ static int submit_bursts(const char* who, mbx_session* s, const mbx_burst_schedu
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     const BurstIn in{sched, burst_stride, soft ? mbx_burst_schedule_soft_bytes(sched) : burst_stride};
-    return submit(s, n, sh.frames, stream_index, bursts, soft, pcm16, pcmf, results, nullptr, &in);
+    return submit(pcm8, s, n, sh.frames, stream_index, bursts, soft, pcm16, pcmf, results, nullptr, &in);
 }
 
 int mbx_session_submit_bursts(mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index, const uint8_t* bursts,
@@ -753,7 +820,7 @@ int mbx_session_submit_bursts_soft(mbx_session* s, const mbx_burst_schedule* sch
 // place, others through the slot's pinned staging at the same offsets), their indices into the slot's index words, then
 // mbx_process_burst_groups on the compute stream with the groups rewritten to those device addresses, and the outputs out.
 static int enqueue_groups(mbx_session* s, Slot& sl, const mbx_burst_group* groups, int n_groups, bool soft, const mbx::GroupPlan& gp,
-                          int16_t* pcm16, float* pcmf, mbe_process_result* results) {
+                          int16_t* pcm16, float* pcmf, mbe_process_result* results, const Pcm8Out& pcm8) {
     size_t at[MBX_BURST_MAX_GROUPS], bytes[MBX_BURST_MAX_GROUPS], total = 0;
     bool staged = false, indexed = false;
     for (int i = 0; i < n_groups; ++i) {
@@ -823,17 +890,18 @@ static int enqueue_groups(mbx_session* s, Slot& sl, const mbx_burst_group* group
             return rc;
         }
     }
-    rc = mbx_process_burst_groups(dev, n_groups, soft ? 1 : 0, s->d_state, s->d_resident, s->d_rng, pcm16 ? sl.d_pcm16 : nullptr,
+    rc = mbx_process_burst_groups(dev, n_groups, soft ? 1 : 0, s->d_state, s->d_resident, s->d_rng, pcm16 || pcm8.dst ? sl.d_pcm16 : nullptr,
                                   pcmf ? sl.d_pcmf : nullptr, results ? sl.d_results : nullptr, sl.d_records, s->s_comp);
-    if (rc < 0) {
+    if (rc < 0 || (rc = compand_step(s, sl, (size_t)gp.total_rows, pcm8)) < 0) {
         return rc;
     }
-    return copy_out(s, sl, (size_t)gp.total_rows, pcm16, pcmf, results, nullptr);
+    return copy_out(s, sl, (size_t)gp.total_rows, pcm16, pcmf, results, nullptr, pcm8.dst);
 }
 
 int mbx_session_submit_burst_groups(mbx_session* s, const mbx_burst_group* groups, int n_groups, int soft_in, int16_t* pcm16, float* pcmf,
                                     mbe_process_result* results) {
     const char* const who = "mbx_session_submit_burst_groups";
+    const Pcm8Out pcm8 = take_pcm8(s);
     const bool soft = soft_in != 0;
     char text[200];
     const auto refused = [&](const char* why) {
@@ -892,7 +960,7 @@ int mbx_session_submit_burst_groups(mbx_session* s, const mbx_burst_group* group
     if (rc < 0) {
         return rc;
     }
-    rc = enqueue_groups(s, sl, groups, n_groups, soft, gp, pcm16, pcmf, results);
+    rc = enqueue_groups(s, sl, groups, n_groups, soft, gp, pcm16, pcmf, results, pcm8);
     if (rc < 0) {   // (as submit: drain, so that the next submit may reuse the slot at once)
         (void)hipStreamSynchronize(s->s_comp);
         (void)hipStreamSynchronize(s->s_out);

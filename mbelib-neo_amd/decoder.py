@@ -10,6 +10,7 @@ Reference interface mirrored (include/mbelib-neo/mbelib.h):
   mbe_processAmbe3600x2450Frame[f]      -> decode(frames, T)            codec=AMBE
   mbe_decode*Frame                      -> fec(frames)
   mbe_decode*Frame, the caller's keystream XOR, mbe_process*Dataf -> decode / decode_soft / decode_ragged(..., keystream=rows)
+Beyond the reference: compand(pcm16, law) -- the int16 rows of a decode as G.711 bytes (include/mbx_pcm8.h).
 """
 import numpy as np
 
@@ -134,6 +135,22 @@ class BatchDecoder:
         out["pcm16"] = torch.empty((n, 160), dtype=torch.int16, device=self.device) if want_pcm16 else None
         out["pcmf"] = torch.empty((n, 160), dtype=torch.float32, device=self.device) if want_float else None
         out["results"] = torch.empty((n, 5), dtype=torch.int32, device=self.device) if want_results else None
+        return out
+
+    def compand(self, pcm16, law, out=None):
+        """Companded PCM out (include/mbx_pcm8.h): mbx_pcm_compand behind a decode on the current torch stream -- the int16 rows
+        [n, 160] a decode returned (a contiguous device tensor) -> uint8 [n, 160], G.711 mu-law (pcm8.LAW_ULAW) or A-law
+        (pcm8.LAW_ALAW), the bytes pcm8.ulaw / pcm8.alaw give on the host.  out: a contiguous uint8 tensor of as many elements."""
+        torch = _torch()
+        if pcm16.dtype != torch.int16 or not pcm16.is_contiguous() or pcm16.numel() % 160:
+            raise ValueError("pcm16 must be a contiguous int16 tensor of rows of 160 samples")
+        if out is None:
+            out = torch.empty(tuple(pcm16.shape), dtype=torch.uint8, device=pcm16.device)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != pcm16.numel() or out.device != pcm16.device:
+            raise ValueError("out must be a contiguous uint8 tensor of one byte per sample on the device of pcm16")
+        with torch.cuda.device(pcm16.device):
+            rc = _native.lib().mbx_pcm_compand(int(law), pcm16.data_ptr(), pcm16.numel() // 160, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_pcm_compand")
         return out
 
     def decode_soft(self, soft, T, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None, keystream=None):
