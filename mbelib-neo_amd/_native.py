@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h,
-include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h).  Fails loudly when the library
+include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -172,6 +172,19 @@ _PCM8_SIGNATURES = {
     "mbx_session_next_pcm8": (C.c_int, [_vp, C.c_int, _vp]),
 }
 PCM8_SYMBOLS = tuple(_PCM8_SIGNATURES)
+# mix-down out (include/mbx_mixdown.h): talkgroup buses summed on the device
+_MIXDOWN_SIGNATURES = {
+    "mbx_mixdown_plan_create": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp]),
+    "mbx_mixdown_plan_create_split": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int]),
+    "mbx_mixdown_plan_destroy": (C.c_int, [_vp]),
+    "mbx_mixdown_plan_buses": (C.c_int, [_vp]),
+    "mbx_mixdown_plan_rows": (C.c_int, [_vp]),
+    "mbx_mixdown_plan_long_buses": (C.c_int, [_vp]),
+    "mbx_mixdown_host": (C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mbx_mixdown": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, _vp]),
+    "mbx_session_next_mixdown": (C.c_int, [_vp, _vp, C.c_int, _vp]),
+}
+MIXDOWN_SYMBOLS = tuple(_MIXDOWN_SIGNATURES)
 
 
 class BurstGroupStruct(C.Structure):
@@ -200,7 +213,8 @@ def lib():
             handle = C.CDLL(path)
         except OSError as e:  # e.g. libamdhip64 not found
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
-        for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES, **_KEYSTREAM_SIGNATURES, **_PCM8_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES, **_KEYSTREAM_SIGNATURES, **_PCM8_SIGNATURES,
+                                   **_MIXDOWN_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

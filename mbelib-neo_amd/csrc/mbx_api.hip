@@ -447,6 +447,10 @@ int mbx_reserve(size_t max_frames) {
 int mbx_release_stream(void* stream) {
     REQUIRE_CTX(c);
     std::lock_guard<std::mutex> lock(c->mu);
+    {   // what mbx_last_kernel_name knows of the stream goes with it: a later stream may be given the same handle
+        std::lock_guard<std::mutex> names(c->name_mu);
+        c->last_kernel.erase(stream);
+    }
     auto it = c->slots.find(stream);
     if (it == c->slots.end()) {
         return 0;

@@ -12,7 +12,11 @@
 
 void mbx_set_error_text(const char* text);   // mbx_api.hip: sets the calling thread's mbx_last_error()
 
+struct mbx_mixdown_plan;
+
 namespace mbx {
+
+int mixdown_plan_device(const mbx_mixdown_plan* plan);   // mbx_mixdown.hip: the device a plan's tables are on (-1: no plan)
 
 static inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
 

@@ -1,6 +1,6 @@
 // mbx_kernels.h -- every __global__ kernel of libmbx_hip.so, declared exactly once.
-// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
-// one that launches it (mbx_api.hip; mbx_burst.hip and mbx_pcm8.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
+// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
+// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip and mbx_mixdown.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
 // overload at the launch site or in the instance table), not an unresolved symbol when the library is loaded.
 // A new kernel: declare it here, define it, and -- a stream-stage instance -- give it its row in kInstances (mbx_api.hip).
 #pragma once
@@ -129,6 +129,15 @@ __global__ void soft_front_keyed_kernel(const mbe_soft_bit*, size_t, int, int, c
 // whether the pieces are 16-byte aligned in the input: samples, bytes, their count, whole pieces, samples in front and behind --------------
 template <int kLaw, bool kAligned>
 __global__ void pcm_compand_kernel(const int16_t*, uint8_t*, size_t, size_t, int, int);
+
+// ---- mbx_mixdown.hip: mix-down out (include/mbx_mixdown.h) -- behind a step, its int16 rows -> talkgroup buses in one of three output
+// forms (mbx_mixdown.h): the rows, bus_offset, the buses of the slots (short form: and their count) or of the workgroups (long form),
+// the inputs (mbx_mixdown_plan.h), the bus rows ----------------------------------------------------------------------------------------
+struct MixdownInput;
+template <int kOut>
+__global__ void mixdown_kernel(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, void*);
+template <int kOut>
+__global__ void mixdown_long_kernel(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, void*);
 
 // ---- mbx_expand.hip ------------------------------------------------------------------------------------------------------------
 __global__ void expand_imbe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);

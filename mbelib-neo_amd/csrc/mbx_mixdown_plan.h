@@ -1,0 +1,192 @@
+// mbx_mixdown_plan.h -- what a mix-down plan (include/mbx_mixdown.h) is before it reaches a device: the caller's CSR arrays checked,
+// rows_needed, the split of the buses into SHORT ones (flat lanes, mixdown_kernel) and LONG ones (one workgroup each,
+// mixdown_long_kernel), the two grid sizes, the words of the tables the kernels read, and what mbx_mixdown refuses of its arguments.
+// Integer work on the host alone: no HIP, no locks, no globals -- so that a CPU program can check it under a sanitizer
+// (tests/mixdown_check.cpp), in the manner of mbx_group_plan.h, mbx_launch_plan.h and mbe_flush_plan.h.  Private to mbx_mixdown.hip;
+// nothing here is exported.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+#include "mbx_mixdown.h"
+
+namespace mbx {
+
+// A bus with MORE inputs than this takes the long form, unless the caller states the split (mbx_mixdown_plan_create_split).  The long
+// form spreads the inputs over 12 slices and pays a barrier and a pass through LDS for it, so below a couple of trips per slice there
+// is nothing to win.  MEASURED on one MI355X (EXPERIMENTS.md, "Mix-down out"): 65,536 rows dealt into equal buses, the short form is
+// ahead up to 20 inputs, the two are level at 22 and the long form is ahead from 24 (two trips per slice) on.
+constexpr int kMixdownLongAbove = 22;
+
+constexpr int kMixdownBlock = 256;   // lanes of a workgroup, both forms
+
+enum MixdownRefusal {
+    kMixdownOk = 0,
+    kMixdownNoHandle,     // no place for the handle
+    kMixdownBuses,        // n_buses < 1
+    kMixdownNull,         // bus_offset is NULL, or src_row is NULL while a bus has an input
+    kMixdownFirst,        // bus_offset[0] != 0
+    kMixdownDecreasing,   // bus_offset decreases
+    kMixdownTooLong,      // a bus with more than kMixdownMaxInputs inputs (the total fits int32 by its type: bus_offset is int32)
+    kMixdownRow,          // a negative src_row
+    kMixdownRowMost,      // a src_row of 2^31 - 1: rows_needed would not fit int32
+    kMixdownSplit,        // a negative long_above
+    // mbx_mixdown's arguments
+    kMixdownForm,
+    kMixdownPointers,
+    kMixdownAlign,
+    kMixdownRows,
+    kMixdownOverlap,
+};
+static inline const char* mixdown_refusal_text(MixdownRefusal r) {
+    switch (r) {
+    case kMixdownNoHandle: return "no place for the handle";
+    case kMixdownBuses: return "n_buses must be at least 1";
+    case kMixdownNull: return "bus_offset and src_row are needed (only gain_q12 may be NULL: unity)";
+    case kMixdownFirst: return "bus_offset[0] must be 0";
+    case kMixdownDecreasing: return "bus_offset must not decrease";
+    case kMixdownTooLong: return "a bus has more than MBX_MIXDOWN_MAX_INPUTS inputs";
+    case kMixdownRow: return "a negative src_row";
+    case kMixdownRowMost: return "a src_row of 2^31-1: the rows needed must fit int32";
+    case kMixdownSplit: return "long_above must not be negative (0: the library's default)";
+    case kMixdownForm: return "form is MBX_MIXDOWN_PCM16, MBX_MIXDOWN_ULAW or MBX_MIXDOWN_ALAW";
+    case kMixdownPointers: return "a plan, d_pcm16 and d_out are needed";
+    case kMixdownAlign: return "a pointer is below the alignment of its kind (include/mbx_mixdown.h, Alignment)";
+    case kMixdownRows: return "nrows is below mbx_mixdown_plan_rows(): an input would lie outside d_pcm16";
+    case kMixdownOverlap: return "d_pcm16 and d_out overlap";
+    default: return "";
+    }
+}
+
+// one input as the kernels read it: 8 bytes, one load
+struct alignas(8) MixdownInput {
+    int32_t row;    // src_row
+    int32_t gain;   // gain_q12, sign-extended
+};
+
+// The plan.  The tables are ONE array of int32 words (the device copy is one allocation):
+//   bus_offset[n_buses + 1] | short_bus[n_short] | long_bus[n_long] | (one word of padding where the inputs would start odd) |
+//   input[inputs] (MixdownInput, 8-byte aligned in an 8-byte aligned array)
+// short_bus[slot] / long_bus[workgroup] name the bus a slot of the short launch / a workgroup of the long launch sums, both in the
+// caller's bus order; every bus is in exactly one of them, so the two launches together write every bus row once.
+struct MixdownPlan {
+    int      n_buses = 0;
+    int32_t  inputs = 0;        // bus_offset[n_buses]
+    int32_t  rows_needed = 0;   // 1 + the largest src_row; 0: no bus has an input
+    int      long_above = 0;    // the split in force
+    int      n_short = 0, n_long = 0;
+    uint32_t short_grid = 0;    // workgroups of kMixdownBlock lanes: 20 lanes per short bus, flat
+    uint32_t long_grid = 0;     // one workgroup per long bus
+    size_t   at_short = 0, at_long = 0, at_inputs = 0, words = 0;   // word offsets into the tables, and their length
+};
+
+// THE check and the counts.  long_above: 0 takes kMixdownLongAbove; any value >= kMixdownMaxInputs makes every bus short.
+static inline MixdownRefusal plan_mixdown(int n_buses, const int32_t* bus_offset, const int32_t* src_row, int long_above, MixdownPlan* out) {
+    *out = MixdownPlan();
+    if (n_buses < 1) {
+        return kMixdownBuses;
+    }
+    if (!bus_offset) {
+        return kMixdownNull;
+    }
+    if (long_above < 0) {
+        return kMixdownSplit;
+    }
+    if (bus_offset[0] != 0) {
+        return kMixdownFirst;
+    }
+    const int above = long_above ? long_above : kMixdownLongAbove;
+    int n_long = 0;
+    for (int b = 0; b < n_buses; ++b) {
+        const int64_t count = (int64_t)bus_offset[b + 1] - (int64_t)bus_offset[b];
+        if (count < 0) {
+            return kMixdownDecreasing;
+        }
+        if (count > kMixdownMaxInputs) {
+            return kMixdownTooLong;
+        }
+        n_long += count > above;
+    }
+    const int32_t total = bus_offset[n_buses];   // (non-decreasing from 0 in int32: it fits)
+    if (total > 0 && !src_row) {
+        return kMixdownNull;
+    }
+    int32_t most = -1;
+    for (int32_t k = 0; k < total; ++k) {
+        if (src_row[k] < 0) {
+            return kMixdownRow;
+        }
+        if (src_row[k] == INT32_MAX) {
+            return kMixdownRowMost;
+        }
+        most = src_row[k] > most ? src_row[k] : most;
+    }
+    out->n_buses = n_buses;
+    out->inputs = total;
+    out->rows_needed = most + 1;
+    out->long_above = above;
+    out->n_long = n_long;
+    out->n_short = n_buses - n_long;
+    out->short_grid = (uint32_t)(((uint64_t)out->n_short * kMixdownPieces + kMixdownBlock - 1) / kMixdownBlock);
+    out->long_grid = (uint32_t)n_long;
+    out->at_short = (size_t)n_buses + 1;
+    out->at_long = out->at_short + (size_t)out->n_short;
+    out->at_inputs = (out->at_long + (size_t)n_long + 1) & ~(size_t)1;
+    out->words = out->at_inputs + 2 * (size_t)total;
+    return kMixdownOk;
+}
+
+// the words of the tables: `words` has plan.words of them; the arrays are those plan_mixdown accepted
+static inline void fill_mixdown_tables(const MixdownPlan& plan, const int32_t* bus_offset, const int32_t* src_row, const int16_t* gain_q12,
+                                       int32_t* words) {
+    size_t ns = plan.at_short, nl = plan.at_long;
+    for (int b = 0; b < plan.n_buses; ++b) {
+        words[b] = bus_offset[b];
+        const int32_t count = bus_offset[b + 1] - bus_offset[b];
+        if (count > plan.long_above) {
+            words[nl++] = b;
+        } else {
+            words[ns++] = b;
+        }
+    }
+    words[plan.n_buses] = plan.inputs;
+    if (plan.at_inputs > plan.at_long + (size_t)plan.n_long) {
+        words[plan.at_inputs - 1] = 0;   // the padding word
+    }
+    for (int32_t k = 0; k < plan.inputs; ++k) {
+        words[plan.at_inputs + 2 * (size_t)k] = src_row[k];
+        words[plan.at_inputs + 2 * (size_t)k + 1] = gain_q12 ? (int32_t)gain_q12[k] : kMixdownUnity;
+    }
+}
+
+static inline size_t mixdown_sample_bytes(int form) { return form == kMixdownPcm16 ? 2 : 1; }
+
+// what mbx_mixdown refuses of its arguments, before a device is asked for.  The pointers are never dereferenced.
+// Alignment: d_pcm16 16 (a piece of 8 samples is one 16-byte load), d_out 16 as int16 and 8 as bytes (a piece is one store).
+static inline MixdownRefusal mixdown_launch_refused(const MixdownPlan* plan, int form, const void* d_pcm16, size_t nrows, const void* d_out) {
+    if (!mixdown_form_ok(form)) {
+        return kMixdownForm;
+    }
+    if (!d_pcm16 || !d_out) {
+        return kMixdownPointers;
+    }
+    const uintptr_t in = reinterpret_cast<uintptr_t>(d_pcm16), to = reinterpret_cast<uintptr_t>(d_out);
+    if ((in & 15u) != 0 || (to & (form == kMixdownPcm16 ? 15u : 7u)) != 0) {
+        return kMixdownAlign;
+    }
+    if (!plan) {   // (behind the pointers' own checks: those need no plan, and a host without a device can make none)
+        return kMixdownPointers;
+    }
+    if (nrows < (size_t)plan->rows_needed) {
+        return kMixdownRows;
+    }
+    // (the caller's nrows rows, whether the plan reads them all or not, and the output as far as it is written)
+    const uintptr_t in_bytes = (uintptr_t)nrows * 320u, to_bytes = (uintptr_t)plan->n_buses * 160u * mixdown_sample_bytes(form);
+    if (in < to + to_bytes && to < in + in_bytes) {
+        return kMixdownOverlap;
+    }
+    return kMixdownOk;
+}
+
+}  // namespace mbx

@@ -2,7 +2,8 @@
 // device and takes batches of wire frames from HOST memory, returning PCM to HOST memory (include/mbx.h, "sessions").
 //
 // What crosses PCIe per 20 ms frame is the wire frame in (18 B / 9 B) and the PCM out (320 B int16, + 20 B when the
-// mbe_process_result is asked for; 160 B where the host takes G.711 bytes, include/mbx_pcm8.h: one compand launch behind the step)
+// mbe_process_result is asked for; 160 B where the host takes G.711 bytes, include/mbx_pcm8.h: one compand launch behind the step;
+// a few bus rows in place of them all where the host takes talkgroup buses, include/mbx_mixdown.h: the mix-down launches behind the step)
 // -- not the 15.6 KB of state the per-call conveniences (mbx_process_batch_host) move.
 //
 // Pipeline: kDepth slots of device buffers, two HIP streams.  Batch k uses slot k % kDepth:
@@ -34,6 +35,7 @@
 #include "mbx_gather.h"
 #include "mbx_host.h"
 #include "mbx_keystream.h"
+#include <mbx_mixdown.h>   // (the public header: include/ is first on the include path; "mbx_mixdown.h" would be this directory's)
 #include "mbx_pcm8.h"
 
 namespace {
@@ -72,6 +74,7 @@ struct Slot {
     float*              d_pcmf = nullptr;
     mbe_process_result* d_results = nullptr;
     uint8_t*            d_pcm8 = nullptr;   // companded bytes (include/mbx_pcm8.h): a session created with MBX_SESSION_PCM8
+    uint8_t*            d_mix = nullptr;    // bus rows (include/mbx_mixdown.h), max_frames of 320 B: a session created with MBX_SESSION_MIXDOWN
     int32_t*            d_index = nullptr;
     void*               d_workspace = nullptr;
     uint8_t*            d_bursts = nullptr;   // bursts (hard or soft), grown by the burst submits that need more
@@ -87,11 +90,12 @@ struct Slot {
     int16_t*            h_pcm16 = nullptr;
     float*              h_pcmf = nullptr;
     uint8_t*            h_pcm8 = nullptr;
+    uint8_t*            h_mix = nullptr;
     mbe_process_result* h_results = nullptr;
     mbx_param_record*   h_records = nullptr;
     hipEvent_t          comp = nullptr, done = nullptr;
     bool                busy = false;
-    CopyOut             out[5];
+    CopyOut             out[6];
     int                 nout = 0;
 };
 
@@ -174,20 +178,24 @@ void default_parms(mbe_parms& p) {   // ref mbe_initMbeParms, src/core/mbelib.c:
 // attachment lasts for one submit call, whether that call queues or refuses, so every public submit takes it as its first act --
 // by the session's ADDRESS, out of a table beside the sessions: a submit refuses some arguments before it looks at its session, and
 // must not dereference a pointer it has not checked to use the attachment up.
-struct Pcm8Out {
+// mbx_session_next_mixdown (include/mbx_mixdown.h) attaches the buses of a plan in the same way, in the same record: one submit uses both up.
+struct NextOut {
     uint8_t* dst = nullptr;   // host memory, rows * 160 bytes; nullptr: nothing attached
     int      law = 0;         // MBX_LAW_*
+    void*                   buses = nullptr;   // host memory, the plan's buses * 160 samples of `form`; nullptr: nothing attached
+    const mbx_mixdown_plan* plan = nullptr;
+    int                     form = 0;          // MBX_MIXDOWN_*
 };
-std::mutex g_pcm8_mu;
-std::unordered_map<const mbx_session*, Pcm8Out> g_pcm8;
+std::mutex g_next_mu;
+std::unordered_map<const mbx_session*, NextOut> g_next;
 
-Pcm8Out take_pcm8(const mbx_session* s) {
-    std::lock_guard<std::mutex> lock(g_pcm8_mu);
-    Pcm8Out out;
-    const auto it = g_pcm8.find(s);
-    if (it != g_pcm8.end()) {
+NextOut take_next(const mbx_session* s) {
+    std::lock_guard<std::mutex> lock(g_next_mu);
+    NextOut out;
+    const auto it = g_next.find(s);
+    if (it != g_next.end()) {
         out = it->second;
-        g_pcm8.erase(it);
+        g_next.erase(it);
     }
     return out;
 }
@@ -205,13 +213,30 @@ struct BurstIn {
 
 // `soft`: frames are mbe_soft_bit cells (soft_bytes per frame) instead of wire frames (frame_bytes)
 int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst, const uint8_t* keystream, const Pcm8Out& pcm8);
+            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst, const uint8_t* keystream, const NextOut& next);
 
-int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records, uint8_t* pcm8);
+int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records, const NextOut& next);
 
 // behind the step of a submit of nf frames that has a destination attached: the slot's int16 rows -> its bytes, on the compute stream
-int compand_step(mbx_session* s, Slot& sl, size_t nf, const Pcm8Out& pcm8) {
-    return pcm8.dst ? mbx_pcm_compand(pcm8.law, sl.d_pcm16, nf, sl.d_pcm8, s->s_comp) : 0;
+int compand_step(mbx_session* s, Slot& sl, size_t nf, const NextOut& next) {
+    return next.dst ? mbx_pcm_compand(next.law, sl.d_pcm16, nf, sl.d_pcm8, s->s_comp) : 0;
+}
+
+// ... and the plan's buses of those rows, nf of them: one or two more launches on the compute stream
+int mixdown_step(mbx_session* s, Slot& sl, size_t nf, const NextOut& next) {
+    return next.buses ? mbx_mixdown(next.plan, next.form, sl.d_pcm16, nf, sl.d_mix, s->s_comp) : 0;
+}
+
+// a submit of `rows` rows with buses attached: every row the plan names must be among them, or nothing is queued
+int refuse_rows_short_of_the_plan(const NextOut& next, size_t rows) {
+    if (next.buses && rows < (size_t)mbx_mixdown_plan_rows(next.plan)) {
+        char text[200];
+        snprintf(text, sizeof(text), "session: the submit has %zu rows, the mix-down plan attached to it needs %d (mbx_session_next_mixdown)", rows,
+                 mbx_mixdown_plan_rows(next.plan));
+        mbx_set_error_text(text);
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    return 0;
 }
 
 // a mixed session takes burst groups only
@@ -225,7 +250,7 @@ int refuse_mixed(const mbx_session* s, const char* who) {
     return 0;
 }
 
-int submit(const Pcm8Out& pcm8, mbx_session* s, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
+int submit(const NextOut& next, mbx_session* s, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst = nullptr, const uint8_t* keystream = nullptr) {
     if (refuse_mixed(s, "mbx_session_submit") < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
@@ -236,6 +261,9 @@ int submit(const Pcm8Out& pcm8, mbx_session* s, int n, int T, const int32_t* ind
     if ((pcm16 && !(s->outputs & MBX_SESSION_PCM16)) || (pcmf && !(s->outputs & MBX_SESSION_PCMF))
         || (results && !(s->outputs & MBX_SESSION_RESULTS))) {
         return MBE_STATUS_INVALID_ARGUMENT;   // an output the session was not created for
+    }
+    if (refuse_rows_short_of_the_plan(next, (size_t)n * (size_t)T) < 0) {
+        return MBE_STATUS_INVALID_ARGUMENT;
     }
     if (n == 0 || T == 0) {
         return 0;
@@ -271,7 +299,7 @@ int submit(const Pcm8Out& pcm8, mbx_session* s, int n, int T, const int32_t* ind
     }
     // From here on work is queued on the three streams against this slot's buffers.  If anything fails halfway the slot is
     // NOT marked busy, so before the error goes back the streams are drained: the next submit may reuse the slot at once.
-    rc = enqueue(s, sl, n, T, index, frames, soft, pcm16, pcmf, results, records, burst, keystream, pcm8);
+    rc = enqueue(s, sl, n, T, index, frames, soft, pcm16, pcmf, results, records, burst, keystream, next);
     if (rc < 0) {
         (void)hipStreamSynchronize(s->s_comp);
         (void)hipStreamSynchronize(s->s_out);
@@ -285,7 +313,7 @@ int submit(const Pcm8Out& pcm8, mbx_session* s, int n, int T, const int32_t* ind
 }
 
 int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst, const uint8_t* keystream, const Pcm8Out& pcm8) {
+            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst, const uint8_t* keystream, const NextOut& next) {
     int rc = 0;
     const size_t nf = (size_t)n * (size_t)T;
     // ---- in ----
@@ -376,7 +404,7 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
         }
     }
     // ---- compute ----
-    int16_t* d16 = pcm16 || pcm8.dst ? sl.d_pcm16 : nullptr;   // (the compand behind the step reads the int16 rows)
+    int16_t* d16 = pcm16 || next.dst || next.buses ? sl.d_pcm16 : nullptr;   // (the compand and the mix-down behind the step read the int16 rows)
     float*   dfl = pcmf ? sl.d_pcmf : nullptr;
     mbe_process_result* dres = results ? sl.d_results : nullptr;
     if (keystream) {   // the keyed call takes every form: hard or soft, index or none, resident words or plain triplets
@@ -401,26 +429,28 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
         rc = mbx_process_batch_ws(s->codec, n, T, sl.d_frames, s->d_state, s->d_rng, d16, dfl, dres, sl.d_records, sl.d_workspace,
                                   mbx_workspace_bytes(s->max_frames), s->s_comp);
     }
-    if (rc < 0 || (rc = compand_step(s, sl, nf, pcm8)) < 0) {
+    if (rc < 0 || (rc = compand_step(s, sl, nf, next)) < 0 || (rc = mixdown_step(s, sl, nf, next)) < 0) {
         return rc;
     }
-    return copy_out(s, sl, nf, pcm16, pcmf, results, records, pcm8.dst);
+    return copy_out(s, sl, nf, pcm16, pcmf, results, records, next);
 }
 
 // ---- out ----: behind the compute stream's launches of a submit of nf frames, the outputs to the caller (or to the slot's staging)
-int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records, uint8_t* pcm8) {
+int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records, const NextOut& next) {
     int rc = 0;
     S_TRY(hipEventRecord(sl.comp, s->s_comp));
     S_TRY(hipStreamWaitEvent(s->s_out, sl.comp, 0));
     sl.nout = 0;
-    auto out = [&](void* user, const void* dev, auto*& stage, size_t per_frame) -> int {   // per_frame elements of *stage per frame
+    // per_frame elements of *stage per row (the staging, made on first need, holds most_per_frame); rows: nf, but the buses of a mix-down
+    // plan (at most max_frames of them)
+    auto out = [&](void* user, const void* dev, auto*& stage, size_t per_frame, size_t rows, size_t most_per_frame) -> int {
         if (!user) {
             return 0;
         }
-        const size_t bytes = nf * per_frame * sizeof(*stage);
+        const size_t bytes = rows * per_frame * sizeof(*stage);
         void* dst = user;
         if (!is_pinned(user)) {
-            int r = pinned(stage, s->max_frames * per_frame);
+            int r = pinned(stage, s->max_frames * most_per_frame);
             if (r < 0) {
                 return r;
             }
@@ -430,9 +460,11 @@ int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, m
         hipError_t e = hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, s->s_out);
         return e == hipSuccess ? 0 : mbx::hip_failed("session: ", "hipMemcpyAsync (device to host)", e);
     };
-    if ((rc = out(pcm16, sl.d_pcm16, sl.h_pcm16, 160)) < 0 || (rc = out(pcmf, sl.d_pcmf, sl.h_pcmf, 160)) < 0
-        || (rc = out(results, sl.d_results, sl.h_results, 1)) < 0 || (rc = out(records, sl.d_records, sl.h_records, 1)) < 0
-        || (rc = out(pcm8, sl.d_pcm8, sl.h_pcm8, 160)) < 0) {
+    const size_t buses = next.buses ? (size_t)mbx_mixdown_plan_buses(next.plan) : 0;
+    if ((rc = out(pcm16, sl.d_pcm16, sl.h_pcm16, 160, nf, 160)) < 0 || (rc = out(pcmf, sl.d_pcmf, sl.h_pcmf, 160, nf, 160)) < 0
+        || (rc = out(results, sl.d_results, sl.h_results, 1, nf, 1)) < 0 || (rc = out(records, sl.d_records, sl.h_records, 1, nf, 1)) < 0
+        || (rc = out(next.dst, sl.d_pcm8, sl.h_pcm8, 160, nf, 160)) < 0
+        || (rc = out(next.buses, sl.d_mix, sl.h_mix, next.form == MBX_MIXDOWN_PCM16 ? 320 : 160, buses, 320)) < 0) {
         return rc;
     }
     S_TRY(hipEventRecord(sl.done, s->s_out));
@@ -458,7 +490,7 @@ void mbx_host_free(void* p) {
 static int create_session(mbx_session** out, int codec, const uint8_t* stream_codec, int streams, size_t max_frames_per_submit, unsigned outputs) {
     const mbx::CodecShape* shape = mbx::codec_shape(codec);
     if (!out || streams <= 0 || max_frames_per_submit == 0 || (!shape && !stream_codec)
-        || (outputs & ~(MBX_SESSION_PCM16 | MBX_SESSION_PCMF | MBX_SESSION_RESULTS | MBX_SESSION_PCM8)) != 0u) {
+        || (outputs & ~(MBX_SESSION_PCM16 | MBX_SESSION_PCMF | MBX_SESSION_RESULTS | MBX_SESSION_PCM8 | MBX_SESSION_MIXDOWN)) != 0u) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     for (int i = 0; stream_codec && i < streams; ++i) {
@@ -516,11 +548,14 @@ static int create_session(mbx_session** out, int codec, const uint8_t* stream_co
         if (!s->d_resident) {   // (the resident entry point uses the workspace the launcher keeps for the compute stream, reserved below)
             C_TRY(hipMalloc(&sl.d_workspace, mbx_workspace_bytes(mf)));
         }
-        if (s->outputs & (MBX_SESSION_PCM16 | MBX_SESSION_PCM8)) {   // (the step writes int16 and the compand reads it)
+        if (s->outputs & (MBX_SESSION_PCM16 | MBX_SESSION_PCM8 | MBX_SESSION_MIXDOWN)) {   // (the step writes int16, the compand and the mix-down read it)
             C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_pcm16), mf * 160 * sizeof(int16_t)));
         }
         if (s->outputs & MBX_SESSION_PCM8) {
             C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_pcm8), mf * 160));
+        }
+        if (s->outputs & MBX_SESSION_MIXDOWN) {
+            C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_mix), mf * 160 * sizeof(int16_t)));
         }
         if (s->outputs & MBX_SESSION_PCMF) {
             C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_pcmf), mf * 160 * sizeof(float)));
@@ -559,7 +594,7 @@ int mbx_session_destroy(mbx_session* s) {
     if (!s) {
         return 0;
     }
-    (void)take_pcm8(s);   // (an attachment no submit used)
+    (void)take_next(s);   // (an attachment no submit used)
     DeviceGuard guard(s->device);
     if (s->s_comp) {
         (void)hipStreamSynchronize(s->s_comp);
@@ -576,6 +611,7 @@ int mbx_session_destroy(mbx_session* s) {
         (void)hipFree(sl.d_pcmf);
         (void)hipFree(sl.d_results);
         (void)hipFree(sl.d_pcm8);
+        (void)hipFree(sl.d_mix);
         (void)hipFree(sl.d_index);
         (void)hipFree(sl.d_workspace);
         (void)hipFree(sl.d_bursts);
@@ -588,6 +624,7 @@ int mbx_session_destroy(mbx_session* s) {
         (void)hipHostFree(sl.h_pcm16);
         (void)hipHostFree(sl.h_pcmf);
         (void)hipHostFree(sl.h_pcm8);
+        (void)hipHostFree(sl.h_mix);
         (void)hipHostFree(sl.h_results);
         (void)hipHostFree(sl.h_records);
         if (sl.comp) {
@@ -710,29 +747,29 @@ int mbx_session_seed(mbx_session* s, int first, int count, const uint32_t* seeds
 }
 
 int mbx_session_submit(mbx_session* s, int T, const uint8_t* frames, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
-    return submit(take_pcm8(s), s, s ? s->streams : 0, T, nullptr, frames, false, pcm16, pcmf, results, nullptr);
+    return submit(take_next(s), s, s ? s->streams : 0, T, nullptr, frames, false, pcm16, pcmf, results, nullptr);
 }
 
 int mbx_session_submit_indexed(mbx_session* s, int n, int T, const int32_t* stream_index, const uint8_t* frames, int16_t* pcm16,
                                float* pcmf, mbe_process_result* results, mbx_param_record* records) {
-    const Pcm8Out pcm8 = take_pcm8(s);
+    const NextOut next = take_next(s);
     if (!stream_index) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    return submit(pcm8, s, n, T, stream_index, frames, false, pcm16, pcmf, results, records);
+    return submit(next, s, n, T, stream_index, frames, false, pcm16, pcmf, results, records);
 }
 
 int mbx_session_submit_soft(mbx_session* s, int T, const mbe_soft_bit* soft, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
-    return submit(take_pcm8(s), s, s ? s->streams : 0, T, nullptr, soft, true, pcm16, pcmf, results, nullptr);
+    return submit(take_next(s), s, s ? s->streams : 0, T, nullptr, soft, true, pcm16, pcmf, results, nullptr);
 }
 
 int mbx_session_submit_soft_indexed(mbx_session* s, int n, int T, const int32_t* stream_index, const mbe_soft_bit* soft, int16_t* pcm16,
                                     float* pcmf, mbe_process_result* results, mbx_param_record* records) {
-    const Pcm8Out pcm8 = take_pcm8(s);
+    const NextOut next = take_next(s);
     if (!stream_index) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    return submit(pcm8, s, n, T, stream_index, soft, true, pcm16, pcmf, results, records);
+    return submit(next, s, n, T, stream_index, soft, true, pcm16, pcmf, results, records);
 }
 
 // ---- companded bytes out (include/mbx_pcm8.h): the destination of the next submit ----------------------------------------------------
@@ -742,7 +779,11 @@ int mbx_session_next_pcm8(mbx_session* s, int law, uint8_t* pcm8) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     if (!pcm8) {
-        (void)take_pcm8(s);
+        std::lock_guard<std::mutex> lock(g_next_mu);
+        const auto it = g_next.find(s);
+        if (it != g_next.end()) {
+            it->second.dst = nullptr;   // (buses attached beside it stay)
+        }
         return 0;
     }
     if (!(s->outputs & MBX_SESSION_PCM8)) {
@@ -753,15 +794,59 @@ int mbx_session_next_pcm8(mbx_session* s, int law, uint8_t* pcm8) {
         mbx_set_error_text("mbx_session_next_pcm8: law is MBX_LAW_ULAW or MBX_LAW_ALAW");
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    std::lock_guard<std::mutex> lock(g_pcm8_mu);
-    g_pcm8[s] = Pcm8Out{pcm8, law};
+    std::lock_guard<std::mutex> lock(g_next_mu);
+    NextOut& next = g_next[s];
+    next.dst = pcm8;
+    next.law = law;
+    return 0;
+}
+
+// ---- mix-down out (include/mbx_mixdown.h): the buses of the next submit -----------------------------------------------------------------
+int mbx_session_next_mixdown(mbx_session* s, const mbx_mixdown_plan* plan, int form, void* out) {
+    const auto refused = [](const char* why) {
+        char text[200];
+        snprintf(text, sizeof(text), "mbx_session_next_mixdown: %s", why);
+        mbx_set_error_text(text);
+        return MBE_STATUS_INVALID_ARGUMENT;
+    };
+    if (!s) {
+        return refused("no session");
+    }
+    if (!out) {
+        std::lock_guard<std::mutex> lock(g_next_mu);
+        const auto it = g_next.find(s);
+        if (it != g_next.end()) {
+            it->second.buses = nullptr;   // (bytes attached beside it stay)
+        }
+        return 0;
+    }
+    if (!(s->outputs & MBX_SESSION_MIXDOWN)) {
+        return refused("the session was created without MBX_SESSION_MIXDOWN");
+    }
+    if (!plan) {
+        return refused("no plan");
+    }
+    if (form != MBX_MIXDOWN_PCM16 && form != MBX_MIXDOWN_ULAW && form != MBX_MIXDOWN_ALAW) {
+        return refused("form is MBX_MIXDOWN_PCM16, MBX_MIXDOWN_ULAW or MBX_MIXDOWN_ALAW");
+    }
+    if ((size_t)mbx_mixdown_plan_buses(plan) > s->max_frames) {
+        return refused("the plan has more buses than max_frames_per_submit");
+    }
+    if (mbx::mixdown_plan_device(plan) != s->device) {
+        return refused("a plan of another device than the session");
+    }
+    std::lock_guard<std::mutex> lock(g_next_mu);
+    NextOut& next = g_next[s];
+    next.buses = out;
+    next.plan = plan;
+    next.form = form;
     return 0;
 }
 
 // ---- keyed submits (include/mbx_keystream.h): a frames submit of either kind with a keystream row per frame ---------------------------
 int mbx_session_submit_keyed(mbx_session* s, int n, int T, const int32_t* stream_index, const uint8_t* frames, const mbe_soft_bit* soft,
                              const uint8_t* keystream, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records) {
-    const Pcm8Out pcm8 = take_pcm8(s);
+    const NextOut next = take_next(s);
     if (refuse_mixed(s, "mbx_session_submit_keyed") < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
@@ -769,13 +854,13 @@ int mbx_session_submit_keyed(mbx_session* s, int n, int T, const int32_t* stream
         mbx_set_error_text("mbx_session_submit_keyed: a session, exactly one of frames and soft, and without an index n = the session's stream count");
         return MBE_STATUS_INVALID_ARGUMENT;
     }
-    return submit(pcm8, s, n, T, stream_index, soft ? static_cast<const void*>(soft) : frames, soft != nullptr, pcm16, pcmf, results, records, nullptr, keystream);
+    return submit(next, s, n, T, stream_index, soft ? static_cast<const void*>(soft) : frames, soft != nullptr, pcm16, pcmf, results, records, nullptr, keystream);
 }
 
 // ---- burst submits (include/mbx_burst.h) ---------------------------------------------------------------------------------------------
 static int submit_bursts(const char* who, mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index, const void* bursts,
                          size_t burst_stride, bool soft, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
-    const Pcm8Out pcm8 = take_pcm8(s);
+    const NextOut next = take_next(s);
     char text[160];
     if (!s || !sched || !bursts || n < 0 || refuse_mixed(s, who) < 0) {
         return MBE_STATUS_INVALID_ARGUMENT;
@@ -802,7 +887,7 @@ static int submit_bursts(const char* who, mbx_session* s, const mbx_burst_schedu
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     const BurstIn in{sched, burst_stride, soft ? mbx_burst_schedule_soft_bytes(sched) : burst_stride};
-    return submit(pcm8, s, n, sh.frames, stream_index, bursts, soft, pcm16, pcmf, results, nullptr, &in);
+    return submit(next, s, n, sh.frames, stream_index, bursts, soft, pcm16, pcmf, results, nullptr, &in);
 }
 
 int mbx_session_submit_bursts(mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index, const uint8_t* bursts,
@@ -820,7 +905,7 @@ int mbx_session_submit_bursts_soft(mbx_session* s, const mbx_burst_schedule* sch
 // place, others through the slot's pinned staging at the same offsets), their indices into the slot's index words, then
 // mbx_process_burst_groups on the compute stream with the groups rewritten to those device addresses, and the outputs out.
 static int enqueue_groups(mbx_session* s, Slot& sl, const mbx_burst_group* groups, int n_groups, bool soft, const mbx::GroupPlan& gp,
-                          int16_t* pcm16, float* pcmf, mbe_process_result* results, const Pcm8Out& pcm8) {
+                          int16_t* pcm16, float* pcmf, mbe_process_result* results, const NextOut& next) {
     size_t at[MBX_BURST_MAX_GROUPS], bytes[MBX_BURST_MAX_GROUPS], total = 0;
     bool staged = false, indexed = false;
     for (int i = 0; i < n_groups; ++i) {
@@ -890,18 +975,18 @@ static int enqueue_groups(mbx_session* s, Slot& sl, const mbx_burst_group* group
             return rc;
         }
     }
-    rc = mbx_process_burst_groups(dev, n_groups, soft ? 1 : 0, s->d_state, s->d_resident, s->d_rng, pcm16 || pcm8.dst ? sl.d_pcm16 : nullptr,
+    rc = mbx_process_burst_groups(dev, n_groups, soft ? 1 : 0, s->d_state, s->d_resident, s->d_rng, pcm16 || next.dst || next.buses ? sl.d_pcm16 : nullptr,
                                   pcmf ? sl.d_pcmf : nullptr, results ? sl.d_results : nullptr, sl.d_records, s->s_comp);
-    if (rc < 0 || (rc = compand_step(s, sl, (size_t)gp.total_rows, pcm8)) < 0) {
+    if (rc < 0 || (rc = compand_step(s, sl, (size_t)gp.total_rows, next)) < 0 || (rc = mixdown_step(s, sl, (size_t)gp.total_rows, next)) < 0) {
         return rc;
     }
-    return copy_out(s, sl, (size_t)gp.total_rows, pcm16, pcmf, results, nullptr, pcm8.dst);
+    return copy_out(s, sl, (size_t)gp.total_rows, pcm16, pcmf, results, nullptr, next);
 }
 
 int mbx_session_submit_burst_groups(mbx_session* s, const mbx_burst_group* groups, int n_groups, int soft_in, int16_t* pcm16, float* pcmf,
                                     mbe_process_result* results) {
     const char* const who = "mbx_session_submit_burst_groups";
-    const Pcm8Out pcm8 = take_pcm8(s);
+    const NextOut next = take_next(s);
     const bool soft = soft_in != 0;
     char text[200];
     const auto refused = [&](const char* why) {
@@ -923,6 +1008,9 @@ int mbx_session_submit_burst_groups(mbx_session* s, const mbx_burst_group* group
     }
     if ((size_t)gp.total_rows > s->max_frames) {
         return refused("more frames than max_frames_per_submit");
+    }
+    if (refuse_rows_short_of_the_plan(next, (size_t)gp.total_rows) < 0) {
+        return MBE_STATUS_INVALID_ARGUMENT;
     }
     // every group's schedule is of the codec of every stream the group names; slots in range, none named twice across the groups
     s->seen.assign((size_t)s->streams, 0);
@@ -960,7 +1048,7 @@ int mbx_session_submit_burst_groups(mbx_session* s, const mbx_burst_group* group
     if (rc < 0) {
         return rc;
     }
-    rc = enqueue_groups(s, sl, groups, n_groups, soft, gp, pcm16, pcmf, results, pcm8);
+    rc = enqueue_groups(s, sl, groups, n_groups, soft, gp, pcm16, pcmf, results, next);
     if (rc < 0) {   // (as submit: drain, so that the next submit may reuse the slot at once)
         (void)hipStreamSynchronize(s->s_comp);
         (void)hipStreamSynchronize(s->s_out);

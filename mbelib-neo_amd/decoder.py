@@ -10,7 +10,8 @@ Reference interface mirrored (include/mbelib-neo/mbelib.h):
   mbe_processAmbe3600x2450Frame[f]      -> decode(frames, T)            codec=AMBE
   mbe_decode*Frame                      -> fec(frames)
   mbe_decode*Frame, the caller's keystream XOR, mbe_process*Dataf -> decode / decode_soft / decode_ragged(..., keystream=rows)
-Beyond the reference: compand(pcm16, law) -- the int16 rows of a decode as G.711 bytes (include/mbx_pcm8.h).
+Beyond the reference: compand(pcm16, law) -- the int16 rows of a decode as G.711 bytes (include/mbx_pcm8.h);
+mixdown(pcm16, plan, form) -- the rows summed into talkgroup buses, a gain per input (include/mbx_mixdown.h).
 """
 import numpy as np
 
@@ -151,6 +152,25 @@ class BatchDecoder:
         with torch.cuda.device(pcm16.device):
             rc = _native.lib().mbx_pcm_compand(int(law), pcm16.data_ptr(), pcm16.numel() // 160, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(rc, "mbx_pcm_compand")
+        return out
+
+    def mixdown(self, pcm16, plan, form=0, out=None):
+        """Mix-down out (include/mbx_mixdown.h): mbx_mixdown behind a decode on the current torch stream -- the int16 rows [n, 160] a
+        decode returned (a contiguous device tensor) -> the buses of `plan` (a mixdown.Plan made on that device) [plan.buses, 160]:
+        int16 (mixdown.PCM16) or G.711 bytes (mixdown.ULAW, mixdown.ALAW), the values mixdown.mix gives on the host.  out: a contiguous
+        tensor of that shape's element count and dtype."""
+        torch = _torch()
+        if pcm16.dtype != torch.int16 or not pcm16.is_contiguous() or pcm16.numel() % 160:
+            raise ValueError("pcm16 must be a contiguous int16 tensor of rows of 160 samples")
+        dtype = torch.int16 if int(form) == 0 else torch.uint8
+        if out is None:
+            out = torch.empty((plan.buses, 160), dtype=dtype, device=pcm16.device)
+        elif out.dtype != dtype or not out.is_contiguous() or out.numel() != plan.buses * 160 or out.device != pcm16.device:
+            raise ValueError("out must be a contiguous tensor of 160 samples per bus, int16 or uint8 by the form, on the device of pcm16")
+        with torch.cuda.device(pcm16.device):
+            rc = _native.lib().mbx_mixdown(plan.handle, int(form), pcm16.data_ptr(), pcm16.numel() // 160, out.data_ptr(),
+                                           torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_mixdown")
         return out
 
     def decode_soft(self, soft, T, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None, keystream=None):
