@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h,
-include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h).  Fails loudly when the library
+include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -185,6 +185,16 @@ _MIXDOWN_SIGNATURES = {
     "mbx_session_next_mixdown": (C.c_int, [_vp, _vp, C.c_int, _vp]),
 }
 MIXDOWN_SYMBOLS = tuple(_MIXDOWN_SIGNATURES)
+# levels out and the gated mix-down (include/mbx_levels.h): a level record per row, buses of the open / the N loudest inputs
+_LEVELS_SIGNATURES = {
+    "mbx_pcm_levels": (C.c_int, [_vp, _sz, _vp, _vp]),
+    "mbx_pcm_levels_host": (C.c_int, [_vp, _sz, _vp]),
+    "mbx_mixdown_gated": (C.c_int, [_vp, _vp, C.c_int, _vp, _sz, _vp, _vp, _vp]),
+    "mbx_mixdown_gated_host": (C.c_int, [C.c_int, _vp, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mbx_session_next_levels": (C.c_int, [_vp, _vp]),
+    "mbx_session_next_mixdown_gated": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp]),
+}
+LEVELS_SYMBOLS = tuple(_LEVELS_SIGNATURES)
 
 
 class BurstGroupStruct(C.Structure):
@@ -214,7 +224,7 @@ def lib():
         except OSError as e:  # e.g. libamdhip64 not found
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
         for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES, **_KEYSTREAM_SIGNATURES, **_PCM8_SIGNATURES,
-                                   **_MIXDOWN_SIGNATURES}.items():
+                                   **_MIXDOWN_SIGNATURES, **_LEVELS_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

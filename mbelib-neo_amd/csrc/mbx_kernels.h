@@ -1,10 +1,12 @@
 // mbx_kernels.h -- every __global__ kernel of libmbx_hip.so, declared exactly once.
-// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
-// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip and mbx_mixdown.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
+// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
+// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip, mbx_mixdown.hip and mbx_levels.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
 // overload at the launch site or in the instance table), not an unresolved symbol when the library is loaded.
 // A new kernel: declare it here, define it, and -- a stream-stage instance -- give it its row in kInstances (mbx_api.hip).
 #pragma once
 #include "mbx_device.h"
+
+struct mbx_row_level;   // include/mbx_levels.h
 
 // The four argument families of the stream-stage instances, written once: the declarations below, the definitions
 // (mbx_stream.hip, MBX_*_KERNEL) and the launcher's function pointer types (mbx_api.hip, Instance) all take them from here.
@@ -138,6 +140,15 @@ template <int kOut>
 __global__ void mixdown_kernel(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, void*);
 template <int kOut>
 __global__ void mixdown_long_kernel(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, void*);
+
+// ---- mbx_levels.hip: levels out and the gated mix-down (include/mbx_levels.h) -- behind a step, its int16 rows -> one level record per
+// row (rows, their count, records); and the two mix-down kernels under a gate: their arguments with the records of the rows behind
+// the rows and the gate (open_peak, loudest_n) in front of the bus rows -------------------------------------------------------------------
+__global__ void pcm_levels_kernel(const int16_t*, size_t, ::mbx_row_level*);
+template <int kOut>
+__global__ void mixdown_gated_kernel(const int16_t*, const ::mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, int, uint32_t, int, void*);
+template <int kOut>
+__global__ void mixdown_gated_long_kernel(const int16_t*, const ::mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, uint32_t, int, void*);
 
 // ---- mbx_expand.hip ------------------------------------------------------------------------------------------------------------
 __global__ void expand_imbe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);

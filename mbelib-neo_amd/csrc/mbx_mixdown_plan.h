@@ -190,3 +190,11 @@ static inline MixdownRefusal mixdown_launch_refused(const MixdownPlan* plan, int
 }
 
 }  // namespace mbx
+
+// the handle of the public header: the plan and where its tables are.  Made and destroyed by mbx_mixdown.hip; mbx_levels.hip launches
+// the gated kernels from the same tables.
+struct mbx_mixdown_plan {
+    mbx::MixdownPlan plan;
+    int      device = -1;
+    int32_t* d_words = nullptr;   // the tables, one allocation on `device`
+};

@@ -3,7 +3,8 @@
 //
 // What crosses PCIe per 20 ms frame is the wire frame in (18 B / 9 B) and the PCM out (320 B int16, + 20 B when the
 // mbe_process_result is asked for; 160 B where the host takes G.711 bytes, include/mbx_pcm8.h: one compand launch behind the step;
-// a few bus rows in place of them all where the host takes talkgroup buses, include/mbx_mixdown.h: the mix-down launches behind the step)
+// a few bus rows in place of them all where the host takes talkgroup buses, include/mbx_mixdown.h: the mix-down launches behind the step;
+// 16 B where it takes level records, include/mbx_levels.h: the levels launch behind the step, in front of a gated mix-down)
 // -- not the 15.6 KB of state the per-call conveniences (mbx_process_batch_host) move.
 //
 // Pipeline: kDepth slots of device buffers, two HIP streams.  Batch k uses slot k % kDepth:
@@ -35,6 +36,8 @@
 #include "mbx_gather.h"
 #include "mbx_host.h"
 #include "mbx_keystream.h"
+#include <mbx_levels.h>    // (the public headers of these two names: include/ is first on the include path)
+#include "mbx_levels_plan.h"   // (what a gate is refused for)
 #include <mbx_mixdown.h>   // (the public header: include/ is first on the include path; "mbx_mixdown.h" would be this directory's)
 #include "mbx_pcm8.h"
 
@@ -75,6 +78,7 @@ struct Slot {
     mbe_process_result* d_results = nullptr;
     uint8_t*            d_pcm8 = nullptr;   // companded bytes (include/mbx_pcm8.h): a session created with MBX_SESSION_PCM8
     uint8_t*            d_mix = nullptr;    // bus rows (include/mbx_mixdown.h), max_frames of 320 B: a session created with MBX_SESSION_MIXDOWN
+    mbx_row_level*      d_levels = nullptr; // level records (include/mbx_levels.h), max_frames of them: a session created with MBX_SESSION_LEVELS
     int32_t*            d_index = nullptr;
     void*               d_workspace = nullptr;
     uint8_t*            d_bursts = nullptr;   // bursts (hard or soft), grown by the burst submits that need more
@@ -91,11 +95,12 @@ struct Slot {
     float*              h_pcmf = nullptr;
     uint8_t*            h_pcm8 = nullptr;
     uint8_t*            h_mix = nullptr;
+    mbx_row_level*      h_levels = nullptr;
     mbe_process_result* h_results = nullptr;
     mbx_param_record*   h_records = nullptr;
     hipEvent_t          comp = nullptr, done = nullptr;
     bool                busy = false;
-    CopyOut             out[6];
+    CopyOut             out[7];
     int                 nout = 0;
 };
 
@@ -185,6 +190,10 @@ struct NextOut {
     void*                   buses = nullptr;   // host memory, the plan's buses * 160 samples of `form`; nullptr: nothing attached
     const mbx_mixdown_plan* plan = nullptr;
     int                     form = 0;          // MBX_MIXDOWN_*
+    bool                    gated = false;     // the buses under `gate` (mbx_session_next_mixdown_gated, include/mbx_levels.h): the same slot, whichever call came last
+    mbx_mixdown_gate        gate = {0, 0};
+    mbx_row_level*          levels = nullptr;  // host memory, one record per row (mbx_session_next_levels); nullptr: nothing attached
+    bool wants_levels() const { return levels || (buses && gated); }
 };
 std::mutex g_next_mu;
 std::unordered_map<const mbx_session*, NextOut> g_next;
@@ -222,8 +231,16 @@ int compand_step(mbx_session* s, Slot& sl, size_t nf, const NextOut& next) {
     return next.dst ? mbx_pcm_compand(next.law, sl.d_pcm16, nf, sl.d_pcm8, s->s_comp) : 0;
 }
 
+// ... the level records of those rows, once per submit, for the caller or for the gate of its buses or both
+int levels_step(mbx_session* s, Slot& sl, size_t nf, const NextOut& next) {
+    return next.wants_levels() ? mbx_pcm_levels(sl.d_pcm16, nf, sl.d_levels, s->s_comp) : 0;
+}
+
 // ... and the plan's buses of those rows, nf of them: one or two more launches on the compute stream
 int mixdown_step(mbx_session* s, Slot& sl, size_t nf, const NextOut& next) {
+    if (next.buses && next.gated) {
+        return mbx_mixdown_gated(next.plan, &next.gate, next.form, sl.d_pcm16, nf, sl.d_levels, sl.d_mix, s->s_comp);
+    }
     return next.buses ? mbx_mixdown(next.plan, next.form, sl.d_pcm16, nf, sl.d_mix, s->s_comp) : 0;
 }
 
@@ -404,7 +421,7 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
         }
     }
     // ---- compute ----
-    int16_t* d16 = pcm16 || next.dst || next.buses ? sl.d_pcm16 : nullptr;   // (the compand and the mix-down behind the step read the int16 rows)
+    int16_t* d16 = pcm16 || next.dst || next.buses || next.levels ? sl.d_pcm16 : nullptr;   // (the compand, the levels and the mix-down behind the step read the int16 rows)
     float*   dfl = pcmf ? sl.d_pcmf : nullptr;
     mbe_process_result* dres = results ? sl.d_results : nullptr;
     if (keystream) {   // the keyed call takes every form: hard or soft, index or none, resident words or plain triplets
@@ -429,7 +446,7 @@ int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const 
         rc = mbx_process_batch_ws(s->codec, n, T, sl.d_frames, s->d_state, s->d_rng, d16, dfl, dres, sl.d_records, sl.d_workspace,
                                   mbx_workspace_bytes(s->max_frames), s->s_comp);
     }
-    if (rc < 0 || (rc = compand_step(s, sl, nf, next)) < 0 || (rc = mixdown_step(s, sl, nf, next)) < 0) {
+    if (rc < 0 || (rc = compand_step(s, sl, nf, next)) < 0 || (rc = levels_step(s, sl, nf, next)) < 0 || (rc = mixdown_step(s, sl, nf, next)) < 0) {
         return rc;
     }
     return copy_out(s, sl, nf, pcm16, pcmf, results, records, next);
@@ -464,7 +481,8 @@ int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, m
     if ((rc = out(pcm16, sl.d_pcm16, sl.h_pcm16, 160, nf, 160)) < 0 || (rc = out(pcmf, sl.d_pcmf, sl.h_pcmf, 160, nf, 160)) < 0
         || (rc = out(results, sl.d_results, sl.h_results, 1, nf, 1)) < 0 || (rc = out(records, sl.d_records, sl.h_records, 1, nf, 1)) < 0
         || (rc = out(next.dst, sl.d_pcm8, sl.h_pcm8, 160, nf, 160)) < 0
-        || (rc = out(next.buses, sl.d_mix, sl.h_mix, next.form == MBX_MIXDOWN_PCM16 ? 320 : 160, buses, 320)) < 0) {
+        || (rc = out(next.buses, sl.d_mix, sl.h_mix, next.form == MBX_MIXDOWN_PCM16 ? 320 : 160, buses, 320)) < 0
+        || (rc = out(next.levels, sl.d_levels, sl.h_levels, 1, nf, 1)) < 0) {
         return rc;
     }
     S_TRY(hipEventRecord(sl.done, s->s_out));
@@ -490,7 +508,7 @@ void mbx_host_free(void* p) {
 static int create_session(mbx_session** out, int codec, const uint8_t* stream_codec, int streams, size_t max_frames_per_submit, unsigned outputs) {
     const mbx::CodecShape* shape = mbx::codec_shape(codec);
     if (!out || streams <= 0 || max_frames_per_submit == 0 || (!shape && !stream_codec)
-        || (outputs & ~(MBX_SESSION_PCM16 | MBX_SESSION_PCMF | MBX_SESSION_RESULTS | MBX_SESSION_PCM8 | MBX_SESSION_MIXDOWN)) != 0u) {
+        || (outputs & ~(MBX_SESSION_PCM16 | MBX_SESSION_PCMF | MBX_SESSION_RESULTS | MBX_SESSION_PCM8 | MBX_SESSION_MIXDOWN | MBX_SESSION_LEVELS)) != 0u) {
         return MBE_STATUS_INVALID_ARGUMENT;
     }
     for (int i = 0; stream_codec && i < streams; ++i) {
@@ -548,7 +566,7 @@ static int create_session(mbx_session** out, int codec, const uint8_t* stream_co
         if (!s->d_resident) {   // (the resident entry point uses the workspace the launcher keeps for the compute stream, reserved below)
             C_TRY(hipMalloc(&sl.d_workspace, mbx_workspace_bytes(mf)));
         }
-        if (s->outputs & (MBX_SESSION_PCM16 | MBX_SESSION_PCM8 | MBX_SESSION_MIXDOWN)) {   // (the step writes int16, the compand and the mix-down read it)
+        if (s->outputs & (MBX_SESSION_PCM16 | MBX_SESSION_PCM8 | MBX_SESSION_MIXDOWN | MBX_SESSION_LEVELS)) {   // (the step writes int16; the compand, the mix-down and the levels read it)
             C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_pcm16), mf * 160 * sizeof(int16_t)));
         }
         if (s->outputs & MBX_SESSION_PCM8) {
@@ -556,6 +574,9 @@ static int create_session(mbx_session** out, int codec, const uint8_t* stream_co
         }
         if (s->outputs & MBX_SESSION_MIXDOWN) {
             C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_mix), mf * 160 * sizeof(int16_t)));
+        }
+        if (s->outputs & MBX_SESSION_LEVELS) {
+            C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_levels), mf * sizeof(mbx_row_level)));
         }
         if (s->outputs & MBX_SESSION_PCMF) {
             C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_pcmf), mf * 160 * sizeof(float)));
@@ -612,6 +633,7 @@ int mbx_session_destroy(mbx_session* s) {
         (void)hipFree(sl.d_results);
         (void)hipFree(sl.d_pcm8);
         (void)hipFree(sl.d_mix);
+        (void)hipFree(sl.d_levels);
         (void)hipFree(sl.d_index);
         (void)hipFree(sl.d_workspace);
         (void)hipFree(sl.d_bursts);
@@ -625,6 +647,7 @@ int mbx_session_destroy(mbx_session* s) {
         (void)hipHostFree(sl.h_pcmf);
         (void)hipHostFree(sl.h_pcm8);
         (void)hipHostFree(sl.h_mix);
+        (void)hipHostFree(sl.h_levels);
         (void)hipHostFree(sl.h_results);
         (void)hipHostFree(sl.h_records);
         if (sl.comp) {
@@ -802,10 +825,11 @@ int mbx_session_next_pcm8(mbx_session* s, int law, uint8_t* pcm8) {
 }
 
 // ---- mix-down out (include/mbx_mixdown.h): the buses of the next submit -----------------------------------------------------------------
-int mbx_session_next_mixdown(mbx_session* s, const mbx_mixdown_plan* plan, int form, void* out) {
-    const auto refused = [](const char* why) {
+// (gate: the gated call of include/mbx_levels.h, which shares the buses slot of the record; nullptr: mbx_session_next_mixdown itself)
+static int next_mixdown(const char* who, mbx_session* s, const mbx_mixdown_plan* plan, int form, const mbx_mixdown_gate* gate, bool gated, void* out) {
+    const auto refused = [who](const char* why) {
         char text[200];
-        snprintf(text, sizeof(text), "mbx_session_next_mixdown: %s", why);
+        snprintf(text, sizeof(text), "%s: %s", who, why);
         mbx_set_error_text(text);
         return MBE_STATUS_INVALID_ARGUMENT;
     };
@@ -823,8 +847,17 @@ int mbx_session_next_mixdown(mbx_session* s, const mbx_mixdown_plan* plan, int f
     if (!(s->outputs & MBX_SESSION_MIXDOWN)) {
         return refused("the session was created without MBX_SESSION_MIXDOWN");
     }
+    if (gated && !(s->outputs & MBX_SESSION_LEVELS)) {
+        return refused("the session was created without MBX_SESSION_LEVELS");
+    }
     if (!plan) {
         return refused("no plan");
+    }
+    if (gated) {
+        const mbx::LevelsRefusal why = mbx::gate_refused(gate != nullptr, gate ? gate->open_peak : 0u, gate ? gate->loudest_n : 0u);
+        if (why != mbx::kLevelsOk) {
+            return refused(mbx::levels_refusal_text(why));
+        }
     }
     if (form != MBX_MIXDOWN_PCM16 && form != MBX_MIXDOWN_ULAW && form != MBX_MIXDOWN_ALAW) {
         return refused("form is MBX_MIXDOWN_PCM16, MBX_MIXDOWN_ULAW or MBX_MIXDOWN_ALAW");
@@ -840,6 +873,39 @@ int mbx_session_next_mixdown(mbx_session* s, const mbx_mixdown_plan* plan, int f
     next.buses = out;
     next.plan = plan;
     next.form = form;
+    next.gated = gated;
+    next.gate = gated ? *gate : mbx_mixdown_gate{0, 0};
+    return 0;
+}
+
+int mbx_session_next_mixdown(mbx_session* s, const mbx_mixdown_plan* plan, int form, void* out) {
+    return next_mixdown("mbx_session_next_mixdown", s, plan, form, nullptr, false, out);
+}
+
+// ---- levels out and the gated mix-down (include/mbx_levels.h): the records and the gated buses of the next submit ------------------------
+int mbx_session_next_mixdown_gated(mbx_session* s, const mbx_mixdown_plan* plan, int form, const mbx_mixdown_gate* gate, void* out) {
+    return next_mixdown("mbx_session_next_mixdown_gated", s, plan, form, gate, true, out);
+}
+
+int mbx_session_next_levels(mbx_session* s, mbx_row_level* out) {
+    if (!s) {
+        mbx_set_error_text("mbx_session_next_levels: no session");
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    if (!out) {
+        std::lock_guard<std::mutex> lock(g_next_mu);
+        const auto it = g_next.find(s);
+        if (it != g_next.end()) {
+            it->second.levels = nullptr;   // (bytes and buses attached beside it stay)
+        }
+        return 0;
+    }
+    if (!(s->outputs & MBX_SESSION_LEVELS)) {
+        mbx_set_error_text("mbx_session_next_levels: the session was created without MBX_SESSION_LEVELS");
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    std::lock_guard<std::mutex> lock(g_next_mu);
+    g_next[s].levels = out;
     return 0;
 }
 
@@ -975,9 +1041,10 @@ static int enqueue_groups(mbx_session* s, Slot& sl, const mbx_burst_group* group
             return rc;
         }
     }
-    rc = mbx_process_burst_groups(dev, n_groups, soft ? 1 : 0, s->d_state, s->d_resident, s->d_rng, pcm16 || next.dst || next.buses ? sl.d_pcm16 : nullptr,
+    rc = mbx_process_burst_groups(dev, n_groups, soft ? 1 : 0, s->d_state, s->d_resident, s->d_rng, pcm16 || next.dst || next.buses || next.levels ? sl.d_pcm16 : nullptr,
                                   pcmf ? sl.d_pcmf : nullptr, results ? sl.d_results : nullptr, sl.d_records, s->s_comp);
-    if (rc < 0 || (rc = compand_step(s, sl, (size_t)gp.total_rows, next)) < 0 || (rc = mixdown_step(s, sl, (size_t)gp.total_rows, next)) < 0) {
+    if (rc < 0 || (rc = compand_step(s, sl, (size_t)gp.total_rows, next)) < 0 || (rc = levels_step(s, sl, (size_t)gp.total_rows, next)) < 0
+        || (rc = mixdown_step(s, sl, (size_t)gp.total_rows, next)) < 0) {
         return rc;
     }
     return copy_out(s, sl, (size_t)gp.total_rows, pcm16, pcmf, results, nullptr, next);

@@ -11,7 +11,9 @@ Reference interface mirrored (include/mbelib-neo/mbelib.h):
   mbe_decode*Frame                      -> fec(frames)
   mbe_decode*Frame, the caller's keystream XOR, mbe_process*Dataf -> decode / decode_soft / decode_ragged(..., keystream=rows)
 Beyond the reference: compand(pcm16, law) -- the int16 rows of a decode as G.711 bytes (include/mbx_pcm8.h);
-mixdown(pcm16, plan, form) -- the rows summed into talkgroup buses, a gain per input (include/mbx_mixdown.h).
+mixdown(pcm16, plan, form) -- the rows summed into talkgroup buses, a gain per input (include/mbx_mixdown.h);
+levels(pcm16) -- a level record per row, and mixdown_gated(pcm16, plan, form, open_peak, loudest_n) -- the buses of the open / the N
+loudest inputs (include/mbx_levels.h).
 """
 import numpy as np
 
@@ -171,6 +173,51 @@ class BatchDecoder:
             rc = _native.lib().mbx_mixdown(plan.handle, int(form), pcm16.data_ptr(), pcm16.numel() // 160, out.data_ptr(),
                                            torch.cuda.current_stream().cuda_stream)
         _native.check(rc, "mbx_mixdown")
+        return out
+
+    def levels(self, pcm16, out=None):
+        """Levels out (include/mbx_levels.h): mbx_pcm_levels behind a decode on the current torch stream -- the int16 rows [n, 160] a
+        decode returned (a contiguous device tensor) -> their level records as uint8 [n, 16]; ``.cpu().numpy().view(levels.LEVEL_DTYPE)``
+        gives the records levels.measure gives on the host.  out: a contiguous uint8 tensor of 16 bytes per row."""
+        torch = _torch()
+        if pcm16.dtype != torch.int16 or not pcm16.is_contiguous() or pcm16.numel() % 160:
+            raise ValueError("pcm16 must be a contiguous int16 tensor of rows of 160 samples")
+        n = pcm16.numel() // 160
+        if out is None:
+            out = torch.empty((n, 16), dtype=torch.uint8, device=pcm16.device)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != n * 16 or out.device != pcm16.device:
+            raise ValueError("out must be a contiguous uint8 tensor of 16 bytes per row on the device of pcm16")
+        with torch.cuda.device(pcm16.device):
+            rc = _native.lib().mbx_pcm_levels(pcm16.data_ptr(), n, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_pcm_levels")
+        return out
+
+    def mixdown_gated(self, pcm16, plan, form=0, open_peak=0, loudest_n=0, levels=None, out=None):
+        """The gated mix-down (include/mbx_levels.h): mbx_mixdown_gated on the current torch stream -- the buses of `plan` summing only
+        the inputs whose row's peak is at least open_peak, and with loudest_n = N > 0 only the N loudest of those, the values
+        levels.mix_gated gives on the host.  levels: what self.levels(pcm16) returned; None: measured here first.  out: as for mixdown."""
+        import ctypes
+
+        from . import levels as _levels
+
+        torch = _torch()
+        if levels is None:
+            levels = self.levels(pcm16)
+        n = pcm16.numel() // 160
+        if levels.dtype != torch.uint8 or not levels.is_contiguous() or levels.numel() != n * 16 or levels.device != pcm16.device:
+            raise ValueError("levels must be the contiguous uint8 tensor of 16 bytes per row that levels() returns for pcm16")
+        dtype = torch.int16 if int(form) == 0 else torch.uint8
+        if out is None:
+            out = torch.empty((plan.buses, 160), dtype=dtype, device=pcm16.device)
+        elif out.dtype != dtype or not out.is_contiguous() or out.numel() != plan.buses * 160 or out.device != pcm16.device:
+            raise ValueError("out must be a contiguous tensor of 160 samples per bus, int16 or uint8 by the form, on the device of pcm16")
+        if not (0 <= int(open_peak) <= 0xFFFF and 0 <= int(loudest_n) <= 0xFFFF):
+            raise ValueError("open_peak and loudest_n are uint16 fields of the gate")
+        gate = _levels.Gate(int(open_peak), int(loudest_n))
+        with torch.cuda.device(pcm16.device):
+            rc = _native.lib().mbx_mixdown_gated(plan.handle, ctypes.addressof(gate), int(form), pcm16.data_ptr(), n, levels.data_ptr(), out.data_ptr(),
+                                                 torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_mixdown_gated")
         return out
 
     def decode_soft(self, soft, T, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None, keystream=None):
