@@ -7,7 +7,7 @@
  * bus of mbx_mixdown.h sums everything it is given: right for a talkgroup of four, wrong for an unselect or an all-call bus of hundreds
  * of inputs, which adds up every idle channel's comfort noise and hits the rails as soon as a few talkers overlap.  Bridges and consoles
  * mix the inputs that are open (a level gate), usually only the N loudest of them, N = 3 the classic figure.  Both decisions are exact
- * in integers.  They are stateless per frame: no hang time, no hysteresis, no ramps.
+ * in integers.  They are stateless per frame: no hang time, no hysteresis, no ramps (the gate that has all three is in mbx_hold.h).
  *
  * Conventions are those of mbx_mixdown.h: `stream` is a hipStream_t passed as void*, launchers are asynchronous on `stream`, never
  * synchronise, and return 0 or a negative MBE_STATUS_* / MBX_E* code with the reason in mbx_last_error(); every refusal comes before a

@@ -23,7 +23,7 @@
  * and the output is y as int16 (MBX_MIXDOWN_PCM16) or the G.711 byte of y exactly as mbx_pcm8.h defines it (MBX_MIXDOWN_ULAW: silence
  * is 0xFF; MBX_MIXDOWN_ALAW: silence is 0xD5).  A sum of integers does not depend on its order, so the device's bits are those of
  * mbx_mixdown_host and of mbelib-neo_amd/mixdown.py (mix), whatever the split over lanes.  No limiter, no AGC, no gain ramps, no
- * resampling.
+ * resampling (a gate that fades its inputs in and out is in mbx_hold.h).
  *
  * Alignment, in the style of the table in mbx.h (kinds not named here keep their row there):
  *   kind        bytes  which pointers

@@ -1,6 +1,6 @@
 // mbx_kernels.h -- every __global__ kernel of libmbx_hip.so, declared exactly once.
-// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
-// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip, mbx_mixdown.hip and mbx_levels.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
+// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
+// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip and mbx_hold.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
 // overload at the launch site or in the instance table), not an unresolved symbol when the library is loaded.
 // A new kernel: declare it here, define it, and -- a stream-stage instance -- give it its row in kInstances (mbx_api.hip).
 #pragma once
@@ -149,6 +149,16 @@ template <int kOut>
 __global__ void mixdown_gated_kernel(const int16_t*, const ::mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, int, uint32_t, int, void*);
 template <int kOut>
 __global__ void mixdown_gated_long_kernel(const int16_t*, const ::mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, uint32_t, int, void*);
+
+// ---- mbx_hold.hip: the held gate (include/mbx_hold.h) -- the gated mix-down with a state record per input: one lane per short bus
+// decides (records, the plan's tables, the hold, the state in place, a code byte per input), the short sum reads the codes, and one
+// workgroup per long bus decides and sums (the hold: mbx_hold_plan.h) -----------------------------------------------------------------
+struct HoldParams;
+__global__ void hold_decide_kernel(const ::mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, int, HoldParams, uint32_t*, uint8_t*);
+template <int kOut>
+__global__ void hold_sum_kernel(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, const uint8_t*, int, void*);
+template <int kOut>
+__global__ void hold_long_kernel(const int16_t*, const ::mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, HoldParams, uint32_t*, void*);
 
 // ---- mbx_expand.hip ------------------------------------------------------------------------------------------------------------
 __global__ void expand_imbe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);

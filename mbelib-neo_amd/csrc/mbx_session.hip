@@ -38,6 +38,8 @@
 #include "mbx_keystream.h"
 #include <mbx_levels.h>    // (the public headers of these two names: include/ is first on the include path)
 #include "mbx_levels_plan.h"   // (what a gate is refused for)
+#include <mbx_hold.h>      // (the held gate: the public header)
+#include "mbx_hold_plan.h"     // (what a hold is refused for, and the plan a state is tied to)
 #include <mbx_mixdown.h>   // (the public header: include/ is first on the include path; "mbx_mixdown.h" would be this directory's)
 #include "mbx_pcm8.h"
 
@@ -192,8 +194,10 @@ struct NextOut {
     int                     form = 0;          // MBX_MIXDOWN_*
     bool                    gated = false;     // the buses under `gate` (mbx_session_next_mixdown_gated, include/mbx_levels.h): the same slot, whichever call came last
     mbx_mixdown_gate        gate = {0, 0};
+    mbx_gate_state*         held = nullptr;    // the buses under `hold` with this state (mbx_session_next_mixdown_held, include/mbx_hold.h): the same slot again
+    mbx_mixdown_hold        hold = {0, 0, 0, 0, 0};
     mbx_row_level*          levels = nullptr;  // host memory, one record per row (mbx_session_next_levels); nullptr: nothing attached
-    bool wants_levels() const { return levels || (buses && gated); }
+    bool wants_levels() const { return levels || (buses && (gated || held)); }
 };
 std::mutex g_next_mu;
 std::unordered_map<const mbx_session*, NextOut> g_next;
@@ -238,6 +242,9 @@ int levels_step(mbx_session* s, Slot& sl, size_t nf, const NextOut& next) {
 
 // ... and the plan's buses of those rows, nf of them: one or two more launches on the compute stream
 int mixdown_step(mbx_session* s, Slot& sl, size_t nf, const NextOut& next) {
+    if (next.buses && next.held) {
+        return mbx_mixdown_held(next.plan, &next.hold, next.held, next.form, sl.d_pcm16, nf, sl.d_levels, sl.d_mix, s->s_comp);
+    }
     if (next.buses && next.gated) {
         return mbx_mixdown_gated(next.plan, &next.gate, next.form, sl.d_pcm16, nf, sl.d_levels, sl.d_mix, s->s_comp);
     }
@@ -825,8 +832,10 @@ int mbx_session_next_pcm8(mbx_session* s, int law, uint8_t* pcm8) {
 }
 
 // ---- mix-down out (include/mbx_mixdown.h): the buses of the next submit -----------------------------------------------------------------
-// (gate: the gated call of include/mbx_levels.h, which shares the buses slot of the record; nullptr: mbx_session_next_mixdown itself)
-static int next_mixdown(const char* who, mbx_session* s, const mbx_mixdown_plan* plan, int form, const mbx_mixdown_gate* gate, bool gated, void* out) {
+// (gate: the gated call of include/mbx_levels.h, which shares the buses slot of the record; nullptr: mbx_session_next_mixdown itself.
+// held: the held call of include/mbx_hold.h, the same slot again, with its hold and its state)
+static int next_mixdown(const char* who, mbx_session* s, const mbx_mixdown_plan* plan, int form, const mbx_mixdown_gate* gate, bool gated, void* out,
+                        bool held = false, const mbx_mixdown_hold* hold = nullptr, mbx_gate_state* state = nullptr) {
     const auto refused = [who](const char* why) {
         char text[200];
         snprintf(text, sizeof(text), "%s: %s", who, why);
@@ -847,7 +856,7 @@ static int next_mixdown(const char* who, mbx_session* s, const mbx_mixdown_plan*
     if (!(s->outputs & MBX_SESSION_MIXDOWN)) {
         return refused("the session was created without MBX_SESSION_MIXDOWN");
     }
-    if (gated && !(s->outputs & MBX_SESSION_LEVELS)) {
+    if ((gated || held) && !(s->outputs & MBX_SESSION_LEVELS)) {
         return refused("the session was created without MBX_SESSION_LEVELS");
     }
     if (!plan) {
@@ -857,6 +866,16 @@ static int next_mixdown(const char* who, mbx_session* s, const mbx_mixdown_plan*
         const mbx::LevelsRefusal why = mbx::gate_refused(gate != nullptr, gate ? gate->open_peak : 0u, gate ? gate->loudest_n : 0u);
         if (why != mbx::kLevelsOk) {
             return refused(mbx::levels_refusal_text(why));
+        }
+    }
+    if (held) {
+        mbx::HoldRefusal why = mbx::hold_refused(hold != nullptr, hold ? hold->open_peak : 0u, hold ? hold->close_peak : 0u, hold ? hold->loudest_n : 0u,
+                                                 hold ? hold->ramp_log2 : 0u);
+        if (why == mbx::kHoldOk) {
+            why = mbx::hold_state_refused(state != nullptr, state ? state->plan : nullptr, plan);
+        }
+        if (why != mbx::kHoldOk) {
+            return refused(mbx::hold_refusal_text(why));
         }
     }
     if (form != MBX_MIXDOWN_PCM16 && form != MBX_MIXDOWN_ULAW && form != MBX_MIXDOWN_ALAW) {
@@ -875,6 +894,8 @@ static int next_mixdown(const char* who, mbx_session* s, const mbx_mixdown_plan*
     next.form = form;
     next.gated = gated;
     next.gate = gated ? *gate : mbx_mixdown_gate{0, 0};
+    next.held = held ? state : nullptr;
+    next.hold = held ? *hold : mbx_mixdown_hold{0, 0, 0, 0, 0};
     return 0;
 }
 
@@ -885,6 +906,11 @@ int mbx_session_next_mixdown(mbx_session* s, const mbx_mixdown_plan* plan, int f
 // ---- levels out and the gated mix-down (include/mbx_levels.h): the records and the gated buses of the next submit ------------------------
 int mbx_session_next_mixdown_gated(mbx_session* s, const mbx_mixdown_plan* plan, int form, const mbx_mixdown_gate* gate, void* out) {
     return next_mixdown("mbx_session_next_mixdown_gated", s, plan, form, gate, true, out);
+}
+
+// ---- the held gate (include/mbx_hold.h): the buses of the next submit under a hold, the caller's state advanced by one frame ------------
+int mbx_session_next_mixdown_held(mbx_session* s, const mbx_mixdown_plan* plan, int form, const mbx_mixdown_hold* hold, mbx_gate_state* state, void* out) {
+    return next_mixdown("mbx_session_next_mixdown_held", s, plan, form, nullptr, false, out, true, hold, state);
 }
 
 int mbx_session_next_levels(mbx_session* s, mbx_row_level* out) {

@@ -13,7 +13,8 @@ Reference interface mirrored (include/mbelib-neo/mbelib.h):
 Beyond the reference: compand(pcm16, law) -- the int16 rows of a decode as G.711 bytes (include/mbx_pcm8.h);
 mixdown(pcm16, plan, form) -- the rows summed into talkgroup buses, a gain per input (include/mbx_mixdown.h);
 levels(pcm16) -- a level record per row, and mixdown_gated(pcm16, plan, form, open_peak, loudest_n) -- the buses of the open / the N
-loudest inputs (include/mbx_levels.h).
+loudest inputs (include/mbx_levels.h); mixdown_held(pcm16, plan, state, hold, form) -- the same with hysteresis, hang time and ramps,
+a state record per input kept on the device (include/mbx_hold.h).
 """
 import numpy as np
 
@@ -218,6 +219,29 @@ class BatchDecoder:
             rc = _native.lib().mbx_mixdown_gated(plan.handle, ctypes.addressof(gate), int(form), pcm16.data_ptr(), n, levels.data_ptr(), out.data_ptr(),
                                                  torch.cuda.current_stream().cuda_stream)
         _native.check(rc, "mbx_mixdown_gated")
+        return out
+
+    def mixdown_held(self, pcm16, plan, state, hold, form=0, levels=None, out=None):
+        """The held gate (include/mbx_hold.h): mbx_mixdown_held on the current torch stream -- the buses of `plan` under `hold` (a
+        hold.Hold: hysteresis, hang time, the N loudest, ramps) and `state` (a hold.GateState made for `plan`) advanced by one frame, the
+        values hold.step gives on the host.  levels: what self.levels(pcm16) returned; None: measured here first.  out: as for mixdown."""
+        import ctypes
+
+        torch = _torch()
+        if levels is None:
+            levels = self.levels(pcm16)
+        n = pcm16.numel() // 160
+        if levels.dtype != torch.uint8 or not levels.is_contiguous() or levels.numel() != n * 16 or levels.device != pcm16.device:
+            raise ValueError("levels must be the contiguous uint8 tensor of 16 bytes per row that levels() returns for pcm16")
+        dtype = torch.int16 if int(form) == 0 else torch.uint8
+        if out is None:
+            out = torch.empty((plan.buses, 160), dtype=dtype, device=pcm16.device)
+        elif out.dtype != dtype or not out.is_contiguous() or out.numel() != plan.buses * 160 or out.device != pcm16.device:
+            raise ValueError("out must be a contiguous tensor of 160 samples per bus, int16 or uint8 by the form, on the device of pcm16")
+        with torch.cuda.device(pcm16.device):
+            rc = _native.lib().mbx_mixdown_held(plan.handle, ctypes.addressof(hold), state.handle, int(form), pcm16.data_ptr(), n, levels.data_ptr(),
+                                                out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_mixdown_held")
         return out
 
     def decode_soft(self, soft, T, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None, keystream=None):
