@@ -419,25 +419,9 @@ struct mbx_burst_schedule {
 
 namespace {
 
-int refuse(const char* why) {
-    char text[200];
-    snprintf(text, sizeof(text), "mbx_burst_schedule_create: %s", why);
-    mbx_set_error_text(text);
-    return MBE_STATUS_INVALID_ARGUMENT;
-}
+int refuse(const char* why) { return mbx::refuse("mbx_burst_schedule_create", why); }
 
-// the current device, after mbx_init() for it
-int ready_device(int* dev) {
-    const hipError_t e = hipGetDevice(dev);
-    if (e != hipSuccess) {
-        return mbx::hip_failed("", "hipGetDevice", e);
-    }
-    if (!mbx_device_ready(*dev)) {
-        mbx_set_error_text("mbx_init() has not been called for the current device");
-        return MBX_ENOTINIT;
-    }
-    return 0;
-}
+using mbx::ready_device;
 
 // the argument list of each kind, once
 template <int kForm, bool kInvert>
@@ -490,12 +474,7 @@ int burst_gather_per_workgroup(const mbx_burst_schedule* sched, bool soft) { ret
 unsigned burst_gather_lds(const mbx_burst_schedule* sched, bool soft) { return soft ? sched->soft_lds : sched->hard_lds; }
 
 int burst_groups_plan(const char* who, const mbx_burst_group* groups, int n_groups, bool soft, GroupShape* shapes, GroupPlan* plan) {
-    char text[200];
-    const auto refused = [&](const char* why) {
-        snprintf(text, sizeof(text), "%s: %s", who, why);
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
-    };
+    const auto refused = [&](const char* why) { return mbx::refuse(who, why); };
     if (n_groups < 0 || n_groups > MBX_BURST_MAX_GROUPS) {
         return refused(group_refusal_text(kGroupCount));
     }
@@ -596,14 +575,11 @@ int gather_ready(const char* who, const mbx_burst_schedule* sched, size_t n) {
         return rc;
     }
     if (dev != sched->shape.device) {
-        snprintf(text, sizeof(text), "%s: the schedule was made on device %d, the current device is %d", who, sched->shape.device, dev);
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
+        snprintf(text, sizeof(text), "the schedule was made on device %d, the current device is %d", sched->shape.device, dev);
+        return mbx::refuse(who, text);
     }
     if (n > (size_t)0x7fffffff / (size_t)MBX_BURST_MAX_FRAMES) {
-        snprintf(text, sizeof(text), "%s: too many bursts in one launch", who);
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
+        return mbx::refuse(who, "too many bursts in one launch");
     }
     return 0;
 }
@@ -870,10 +846,7 @@ int mbx_burst_groups_rows(const mbx_burst_group* groups, int n_groups, int32_t* 
     }
     const mbx::GroupRefusal r = mbx::plan_groups(shapes, n_groups, &plan);
     if (r != mbx::kGroupsOk) {
-        char text[160];
-        snprintf(text, sizeof(text), "mbx_burst_groups_rows: %s", mbx::group_refusal_text(r));
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
+        return mbx::refuse("mbx_burst_groups_rows", mbx::group_refusal_text(r));
     }
     for (int i = 0; i < n_groups; ++i) {
         row_of_group[i] = plan.place[i].first_row;

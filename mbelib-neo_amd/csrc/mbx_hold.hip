@@ -1,8 +1,9 @@
 // mbx_hold.hip -- the held gate (include/mbx_hold.h): mbx_mixdown_gated with memory -- hysteresis, hang time and click-free ramps --
 // behind mbx_pcm_levels, in two or three launches, with one 4-byte state record per input kept on the device between calls.  The
-// arithmetic and the checks are mbx_hold_plan.h, host-only and shared with the host definition below; the plan and its tables are
-// those of mbx_mixdown.hip, a lane's add and store are mbx_mixdown_lanes.h, the rank key is mbx_levels.h.  No kernel of another unit
-// changes.
+// arithmetic and the checks are mbx_hold_plan.h, host-only and shared with the host definition below; the plan, its tables, the way
+// from its handle to a launch and the prelude of the host definition are those of mbx_mixdown.hip (mbx_mixdown_plan.h); a lane's bus,
+// row load, add, long tail and store are mbx_mixdown_lanes.h, shared with mbx_mixdown.hip and mbx_levels.hip; the rank key is
+// mbx_levels.h.
 //
 // Two rules shape the launches.  REPLAY: a captured graph that holds one call must advance the state once per replay, so nothing
 // about the state is decided on the host -- the kernels read the record of the last frame and write the record of this one IN PLACE.
@@ -61,8 +62,7 @@ hold_decide_kernel(const mbx_row_level* __restrict__ levels, const int32_t* __re
     if (g >= (size_t)n_short) {
         return;
     }
-    const int bus = short_bus[g];
-    const int32_t lo = bus_offset[bus], count = bus_offset[bus + 1] - lo;
+    const auto [bus, lo, count] = mixdown_bus_at(bus_offset, short_bus, g);
     // FOUR inputs at a time, as mixdown_sum has them: four input words and four state words, then four records, in flight together --
     // the lane is alone with its bus, and one dependent load pair after another is all its time.  A short batch is filled up with
     // the batch's first input, whose key is not used and whose record is not written.
@@ -121,9 +121,8 @@ __device__ __forceinline__ void hold_add_input(const int16_t* __restrict__ pcm16
     if (mode == kHoldPieceSteady) {
         mixdown_add_input(pcm16, in, piece, acc);
     } else if (mode == kHoldPieceRamp) {
-        const uint4 v = *reinterpret_cast<const uint4*>(pcm16 + (size_t)in.row * 160u + (size_t)(piece * kMixdownPiece));
-        const int16_t x[kMixdownPiece] = {(int16_t)(v.x & 0xFFFFu), (int16_t)(v.x >> 16), (int16_t)(v.y & 0xFFFFu), (int16_t)(v.y >> 16),
-                                          (int16_t)(v.z & 0xFFFFu), (int16_t)(v.z >> 16), (int16_t)(v.w & 0xFFFFu), (int16_t)(v.w >> 16)};
+        int16_t x[kMixdownPiece];
+        mixdown_load_piece(pcm16, in, piece, x);
 #pragma unroll
         for (int i = 0; i < kMixdownPiece; ++i) {
             acc[i] += hold_ramped(mixdown_term(x[i], (int16_t)in.gain), hold_weight(code, piece * kMixdownPiece + i, ramp_log2), ramp_log2);
@@ -136,14 +135,11 @@ template <int kOut>
 __global__ void __launch_bounds__(256)
 hold_sum_kernel(const int16_t* __restrict__ pcm16, const int32_t* __restrict__ bus_offset, const int32_t* __restrict__ short_bus,
                 const MixdownInput* __restrict__ input, int n_short, const uint8_t* __restrict__ code, int ramp_log2, void* __restrict__ out) {
-    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t slot = g / kMixdownPieces;
+    const auto [slot, piece] = mixdown_short_slot();
     if (slot >= (size_t)n_short) {
         return;
     }
-    const int piece = (int)(g - slot * kMixdownPieces);
-    const int bus = short_bus[slot];
-    const int32_t lo = bus_offset[bus], count = bus_offset[bus + 1] - lo;
+    const auto [bus, lo, count] = mixdown_bus_at(bus_offset, short_bus, slot);
     int32_t acc[kMixdownPiece] = {0, 0, 0, 0, 0, 0, 0, 0};
     constexpr int kBatch = 4;   // four codes and four input words in flight together, as mixdown_sum has them
     for (int32_t i = 0; i < count; i += kBatch) {
@@ -166,9 +162,6 @@ template __global__ void hold_sum_kernel<kMixdownPcm16>(const int16_t*, const in
 template __global__ void hold_sum_kernel<kMixdownUlaw>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, const uint8_t*, int, void*);
 template __global__ void hold_sum_kernel<kMixdownAlaw>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, const uint8_t*, int, void*);
 
-constexpr int kHoldKeysPerLane = kMixdownMaxInputs / kMixdownBlock;   // 16
-constexpr int kHoldWaves = kMixdownBlock / 64;                        // 4: the kernels of this library are built for 64-lane waves
-static_assert(kHoldKeysPerLane * kMixdownBlock == kMixdownMaxInputs, "the lanes of a workgroup hold the keys of a full bus");
 static_assert(kMixdownMaxInputs <= (1 << 12) && kHoldFalling < 4, "a list entry, position | code << 12, fits 16 bits");
 
 // one workgroup per long bus: long_bus[blockIdx.x] is its bus
@@ -176,21 +169,20 @@ template <int kOut>
 __global__ void __launch_bounds__(256)
 hold_long_kernel(const int16_t* __restrict__ pcm16, const mbx_row_level* __restrict__ levels, const int32_t* __restrict__ bus_offset,
                  const int32_t* __restrict__ long_bus, const MixdownInput* __restrict__ input, HoldParams hp, uint32_t* state, void* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) int32_t part[kMixdownSlices][160];
-    __shared__ uint64_t wave_max[kHoldWaves];
+    __shared__ __attribute__((aligned(16))) MixdownPart part;
+    __shared__ uint64_t wave_max[kGateWaves];
     __shared__ uint16_t list[kMixdownMaxInputs];
     __shared__ int n_list;
-    const int bus = long_bus[blockIdx.x];
-    const int32_t lo = bus_offset[bus], count = bus_offset[bus + 1] - lo;
+    const auto [bus, lo, count] = mixdown_bus_at(bus_offset, long_bus, blockIdx.x);
     const int tid = (int)threadIdx.x;
     if (tid == 0) {
         n_list = 0;
     }
     uint64_t threshold = 1u;   // every open input; a closed one has the key 0
     if (hp.loudest_n > 0) {    // (uniform: the barriers inside are reached by all 256 lanes or by none)
-        uint64_t key[kHoldKeysPerLane];
+        uint64_t key[kGateKeysPerLane];
 #pragma unroll
-        for (int j = 0; j < kHoldKeysPerLane; ++j) {
+        for (int j = 0; j < kGateKeysPerLane; ++j) {
             const int32_t k = tid + j * kMixdownBlock;
             uint32_t next;
             key[j] = k < count ? hold_key_of(levels, input[lo + k], k, state[lo + k], hp, &next) : 0u;
@@ -203,7 +195,7 @@ hold_long_kernel(const int16_t* __restrict__ pcm16, const mbx_row_level* __restr
             if (r < hp.loudest_n && more) {
                 uint64_t m = 0;
 #pragma unroll
-                for (int j = 0; j < kHoldKeysPerLane; ++j) {
+                for (int j = 0; j < kGateKeysPerLane; ++j) {
                     m = (key[j] < below && key[j] > m) ? key[j] : m;
                 }
 #pragma unroll
@@ -217,7 +209,7 @@ hold_long_kernel(const int16_t* __restrict__ pcm16, const mbx_row_level* __restr
                 __syncthreads();
                 m = wave_max[0];
 #pragma unroll
-                for (int w = 1; w < kHoldWaves; ++w) {
+                for (int w = 1; w < kGateWaves; ++w) {
                     m = wave_max[w] > m ? wave_max[w] : m;
                 }
                 __syncthreads();   // (the next round writes wave_max again)
@@ -232,7 +224,7 @@ hold_long_kernel(const int16_t* __restrict__ pcm16, const mbx_row_level* __restr
     // (four at a time, the loads of a batch in flight together and in front of its stores: a bus of 4,096 is ONE workgroup's work, and
     // sixteen dependent load pairs one after another were most of its time)
     constexpr int kPass = 4;
-    for (int j0 = 0; j0 < kHoldKeysPerLane && tid + j0 * kMixdownBlock < count; j0 += kPass) {
+    for (int j0 = 0; j0 < kGateKeysPerLane && tid + j0 * kMixdownBlock < count; j0 += kPass) {
         MixdownInput in[kPass];
         uint32_t old[kPass], next[kPass];
         uint64_t key[kPass];
@@ -281,18 +273,14 @@ hold_long_kernel(const int16_t* __restrict__ pcm16, const mbx_row_level* __restr
                 hold_add_input(pcm16, in[j], piece, c[j], hp.ramp_log2, acc);
             }
         }
-        int4* const to = reinterpret_cast<int4*>(&part[slice][piece * kMixdownPiece]);
-        to[0] = int4{acc[0], acc[1], acc[2], acc[3]};
-        to[1] = int4{acc[4], acc[5], acc[6], acc[7]};
+        mixdown_part_put(part, slice, piece, acc);
     }
     __syncthreads();
     if (tid < kMixdownPieces) {
         int32_t acc[kMixdownPiece] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int j = 0; j < kMixdownSlices; ++j) {
-            const int4* const from = reinterpret_cast<const int4*>(&part[j][tid * kMixdownPiece]);
-            const int4 a = from[0], b = from[1];
-            acc[0] += a.x, acc[1] += a.y, acc[2] += a.z, acc[3] += a.w, acc[4] += b.x, acc[5] += b.y, acc[6] += b.z, acc[7] += b.w;
+            mixdown_part_add(part, j, tid, acc);
         }
         mixdown_store<kOut>(out, bus, tid, acc);
     }
@@ -305,12 +293,7 @@ template __global__ void hold_long_kernel<kMixdownAlaw>(const int16_t*, const mb
 
 namespace {
 
-int refuse(const char* who, const char* why) {
-    char text[240];
-    snprintf(text, sizeof(text), "%s: %s", who, why);
-    mbx_set_error_text(text);
-    return MBE_STATUS_INVALID_ARGUMENT;
-}
+using mbx::refuse;
 
 int refuse(const char* who, mbx::HoldRefusal why, mbx::LevelsRefusal levels = mbx::kLevelsOk, mbx::MixdownRefusal mix = mbx::kMixdownOk) {
     if (why != mbx::kHoldGated) {
@@ -322,41 +305,18 @@ int refuse(const char* who, mbx::HoldRefusal why, mbx::LevelsRefusal levels = mb
     return refuse(who, levels == mbx::kGateMixdown ? mbx::mixdown_refusal_text(mix) : mbx::levels_refusal_text(levels));
 }
 
-// the current device, after mbx_init() for it
-int ready_device(int* dev) {
-    const hipError_t e = hipGetDevice(dev);
-    if (e != hipSuccess) {
-        return mbx::hip_failed("", "hipGetDevice", e);
-    }
-    if (!mbx_device_ready(*dev)) {
-        mbx_set_error_text("mbx_init() has not been called for the current device");
-        return MBX_ENOTINIT;
-    }
-    return 0;
-}
-
 mbx::HoldParams params_of(const mbx_mixdown_hold& h) {
     return mbx::HoldParams{h.open_peak, h.close_peak, h.hang_frames, (int)h.loudest_n, (int)h.ramp_log2};
 }
 
-template <int kOut>
-void launch_held(const mbx_mixdown_plan* p, const mbx::HoldParams& hp, mbx_gate_state* st, const int16_t* d_pcm16, const mbx_row_level* d_levels,
-                 void* d_out, hipStream_t strm) {
-    const mbx::MixdownPlan& plan = p->plan;
-    const mbx::MixdownInput* const input = reinterpret_cast<const mbx::MixdownInput*>(p->d_words + plan.at_inputs);
-    if (plan.short_grid) {
-        hipLaunchKernelGGL(mbx::hold_decide_kernel, dim3(mbx::hold_decide_grid(plan)), dim3(mbx::kHoldDecideBlock), 0, strm, d_levels, p->d_words,
-                           p->d_words + plan.at_short, input, plan.n_short, hp, st->d_state, st->d_code);
-        hipLaunchKernelGGL(mbx::hold_sum_kernel<kOut>, dim3(plan.short_grid), dim3(mbx::kMixdownBlock), 0, strm, d_pcm16, p->d_words,
-                           p->d_words + plan.at_short, input, plan.n_short, st->d_code, hp.ramp_log2, d_out);
+// what hold_records_refused says of n records a caller gave
+mbx::HoldRefusal records_refused(const mbx_gate_input_state* r, int32_t n) {
+    std::vector<uint32_t> words((size_t)n);
+    for (int32_t k = 0; k < n; ++k) {
+        words[(size_t)k] = mbx::hold_state_word(r[k].hang_left, r[k].open, r[k].on);
     }
-    if (plan.long_grid) {
-        hipLaunchKernelGGL(mbx::hold_long_kernel<kOut>, dim3(plan.long_grid), dim3(mbx::kMixdownBlock), 0, strm, d_pcm16, d_levels, p->d_words,
-                           p->d_words + plan.at_long, input, hp, st->d_state, d_out);
-    }
+    return mbx::hold_records_refused(words.data(), words.size());
 }
-
-uint32_t word_of(const mbx_gate_input_state& r) { return mbx::hold_state_word(r.hang_left, r.open, r.on); }
 
 }  // namespace
 
@@ -371,22 +331,16 @@ int mbx_gate_state_create(mbx_gate_state** out, const mbx_mixdown_plan* plan) {
     if (!plan) {
         return refuse(who, "a plan is needed");
     }
-    int dev = -1;
-    const int rc = ready_device(&dev);
+    const int rc = mbx::mixdown_tables(who, plan, nullptr);   // (the check alone: the current device ready, and the plan's own)
     if (rc < 0) {
         return rc;
-    }
-    if (dev != plan->device) {
-        char text[160];
-        snprintf(text, sizeof(text), "the plan was made on device %d, the current device is %d", plan->device, dev);
-        return refuse(who, text);
     }
     mbx_gate_state* st = new (std::nothrow) mbx_gate_state();
     if (!st) {
         return refuse(who, "out of memory");
     }
     st->plan = plan;
-    st->device = dev;
+    st->device = plan->device;
     st->inputs = plan->plan.inputs;
     const size_t bytes = mbx::hold_alloc_bytes(st->inputs);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&st->d_state), bytes);
@@ -451,10 +405,8 @@ int mbx_gate_state_set(mbx_gate_state* st, const mbx_gate_input_state* host, voi
     if (!host && st->inputs > 0) {
         return refuse(who, "host memory for the records is needed");
     }
-    for (int32_t k = 0; k < st->inputs; ++k) {
-        if (!mbx::hold_word_ok(word_of(host[k]))) {
-            return refuse(who, mbx::kHoldRecord);
-        }
+    if (records_refused(host, st->inputs) != mbx::kHoldOk) {
+        return refuse(who, mbx::kHoldRecord);
     }
     hipError_t e = hipSuccess;
     if (st->inputs > 0) {
@@ -474,27 +426,15 @@ int mbx_mixdown_held_host(int form, const mbx_mixdown_hold* hold, int n_buses, c
     if (bad_hold != mbx::kHoldOk) {
         return refuse(who, bad_hold);
     }
-    if (!mbx::mixdown_form_ok(form)) {
-        return refuse(who, mbx::mixdown_refusal_text(mbx::kMixdownForm));
-    }
     mbx::MixdownPlan plan;
-    const mbx::MixdownRefusal why = mbx::plan_mixdown(n_buses, bus_offset, src_row, 0, &plan);
-    if (why != mbx::kMixdownOk) {
-        return refuse(who, mbx::mixdown_refusal_text(why));
-    }
-    if (!out || (!pcm16 && plan.rows_needed > 0)) {
-        return refuse(who, "pcm16 and out are needed");
-    }
-    if (nrows < (size_t)plan.rows_needed) {
-        return refuse(who, mbx::mixdown_refusal_text(mbx::kMixdownRows));
+    if (const char* const why = mbx::mixdown_host_refused(form, n_buses, bus_offset, src_row, pcm16, nrows, out, &plan)) {
+        return refuse(who, why);
     }
     if (!state && plan.inputs > 0) {
         return refuse(who, mbx::kHoldNoState);
     }
-    for (int32_t k = 0; k < plan.inputs; ++k) {
-        if (!mbx::hold_word_ok(word_of(state[k]))) {
-            return refuse(who, mbx::kHoldRecord);
-        }
+    if (records_refused(state, plan.inputs) != mbx::kHoldOk) {
+        return refuse(who, mbx::kHoldRecord);
     }
     const mbx::HoldParams hp = params_of(*hold);
     std::vector<uint64_t> keys;
@@ -521,13 +461,7 @@ int mbx_mixdown_held_host(int form, const mbx_mixdown_hold* hold, int n_buses, c
             }
             state[lo + k] = mbx_gate_input_state{(uint16_t)decided[(size_t)k].hang, (uint8_t)decided[(size_t)k].open, (uint8_t)on};
         }
-        for (int n = 0; n < 160; ++n) {
-            if (form == MBX_MIXDOWN_PCM16) {
-                static_cast<int16_t*>(out)[(size_t)b * 160u + n] = mbx::mixdown_clamp(acc[n]);
-            } else {
-                static_cast<uint8_t*>(out)[(size_t)b * 160u + n] = mbx::mixdown_byte(form, acc[n]);
-            }
-        }
+        mbx::mixdown_put_row(form, acc, b, out);
     }
     return 0;
 }
@@ -544,25 +478,26 @@ int mbx_mixdown_held(const mbx_mixdown_plan* plan, const mbx_mixdown_hold* hold,
     if (why != mbx::kHoldOk) {
         return refuse(who, why, levels, mix);
     }
-    int dev = -1;
-    const int rc = ready_device(&dev);
+    mbx::MixdownTables t;
+    const int rc = mbx::mixdown_tables(who, plan, &t);
     if (rc < 0) {
         return rc;
     }
-    if (dev != plan->device) {
-        char text[160];
-        snprintf(text, sizeof(text), "the plan was made on device %d, the current device is %d", plan->device, dev);
-        return refuse(who, text);
-    }
-    const hipStream_t strm = (hipStream_t)stream;
+    const mbx::MixdownPlan& p = plan->plan;
     const mbx::HoldParams hp = params_of(*hold);
-    if (form == MBX_MIXDOWN_PCM16) {
-        launch_held<mbx::kMixdownPcm16>(plan, hp, state, d_pcm16, d_levels, d_out, strm);
-    } else if (form == MBX_MIXDOWN_ULAW) {
-        launch_held<mbx::kMixdownUlaw>(plan, hp, state, d_pcm16, d_levels, d_out, strm);
-    } else {
-        launch_held<mbx::kMixdownAlaw>(plan, hp, state, d_pcm16, d_levels, d_out, strm);
-    }
+    const hipStream_t strm = (hipStream_t)stream;
+    mbx::mixdown_by_form(form, [&](auto k) {
+        if (p.short_grid) {
+            hipLaunchKernelGGL(mbx::hold_decide_kernel, dim3(mbx::hold_decide_grid(p)), dim3(mbx::kHoldDecideBlock), 0, strm, d_levels, t.bus_offset,
+                               t.short_bus, t.input, p.n_short, hp, state->d_state, state->d_code);
+            hipLaunchKernelGGL(mbx::hold_sum_kernel<k()>, dim3(p.short_grid), dim3(mbx::kMixdownBlock), 0, strm, d_pcm16, t.bus_offset, t.short_bus,
+                               t.input, p.n_short, state->d_code, hp.ramp_log2, d_out);
+        }
+        if (p.long_grid) {
+            hipLaunchKernelGGL(mbx::hold_long_kernel<k()>, dim3(p.long_grid), dim3(mbx::kMixdownBlock), 0, strm, d_pcm16, d_levels, t.bus_offset,
+                               t.long_bus, t.input, hp, state->d_state, d_out);
+        }
+    });
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : mbx::hip_failed("", "hold kernels", e);
 }

@@ -1,6 +1,7 @@
-// mbx_host.h -- what the host units of libmbx_hip.so (mbx_api.hip, mbx_session.hip, mbx_burst.hip, mbx_collective.hip) share to
-// refuse a call: the per-thread text behind mbx_last_error(), the failed-HIP-call text, the alignment refusal.  Host-only and
-// private; the inlines have internal linkage, nothing here is exported.  Only what at least two units use belongs here.
+// mbx_host.h -- what the host units of libmbx_hip.so (mbx_api.hip, mbx_session.hip, mbx_burst.hip, mbx_collective.hip, mbx_pcm8.hip,
+// mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip) share to refuse a call: the per-thread text behind mbx_last_error(), the "who: why"
+// refusal, the failed-HIP-call text, the alignment refusal, the current device after mbx_init().  Host-only and private; the inlines
+// have internal linkage, nothing here is exported.  Only what at least two units use belongs here.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -20,6 +21,14 @@ int mixdown_plan_device(const mbx_mixdown_plan* plan);   // mbx_mixdown.hip: the
 
 static inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
 
+// an argument is refused: "<who>: <why>", MBE_STATUS_INVALID_ARGUMENT
+static inline int refuse(const char* who, const char* why) {
+    char text[240];
+    snprintf(text, sizeof(text), "%s: %s", who, why);
+    mbx_set_error_text(text);
+    return MBE_STATUS_INVALID_ARGUMENT;
+}
+
 // a HIP call failed: "<prefix><what>: <HIP's text>", MBX_ENODEVICE
 static inline int hip_failed(const char* prefix, const char* what, hipError_t e) {
     char text[256];
@@ -34,6 +43,19 @@ static inline int misaligned(const char* who, const char* header) {
     snprintf(text, sizeof(text), "%s: a pointer is below the alignment of its kind (include/%s, Alignment)", who, header);
     mbx_set_error_text(text);
     return MBE_STATUS_INVALID_ARGUMENT;
+}
+
+// the current device, after mbx_init() for it
+static inline int ready_device(int* dev) {
+    const hipError_t e = hipGetDevice(dev);
+    if (e != hipSuccess) {
+        return hip_failed("", "hipGetDevice", e);
+    }
+    if (!mbx_device_ready(*dev)) {
+        mbx_set_error_text("mbx_init() has not been called for the current device");
+        return MBX_ENOTINIT;
+    }
+    return 0;
 }
 
 }  // namespace mbx

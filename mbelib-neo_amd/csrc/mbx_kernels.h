@@ -134,7 +134,8 @@ __global__ void pcm_compand_kernel(const int16_t*, uint8_t*, size_t, size_t, int
 
 // ---- mbx_mixdown.hip: mix-down out (include/mbx_mixdown.h) -- behind a step, its int16 rows -> talkgroup buses in one of three output
 // forms (mbx_mixdown.h): the rows, bus_offset, the buses of the slots (short form: and their count) or of the workgroups (long form),
-// the inputs (mbx_mixdown_plan.h), the bus rows ----------------------------------------------------------------------------------------
+// the inputs (mbx_mixdown_plan.h), the bus rows.  What a lane of these and of the next two units' bus kernels does -- its bus, one
+// input's piece, the walk, the tail of a long bus, the store -- is mbx_mixdown_lanes.h -----------------------------------------------
 struct MixdownInput;
 template <int kOut>
 __global__ void mixdown_kernel(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, void*);
@@ -143,7 +144,7 @@ __global__ void mixdown_long_kernel(const int16_t*, const int32_t*, const int32_
 
 // ---- mbx_levels.hip: levels out and the gated mix-down (include/mbx_levels.h) -- behind a step, its int16 rows -> one level record per
 // row (rows, their count, records); and the two mix-down kernels under a gate: their arguments with the records of the rows behind
-// the rows and the gate (open_peak, loudest_n) in front of the bus rows -------------------------------------------------------------------
+// the rows and the gate (open_peak, loudest_n) in front of the bus rows (the lanes' pieces: mbx_mixdown_lanes.h) -------------------------
 __global__ void pcm_levels_kernel(const int16_t*, size_t, ::mbx_row_level*);
 template <int kOut>
 __global__ void mixdown_gated_kernel(const int16_t*, const ::mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, int, uint32_t, int, void*);
@@ -152,7 +153,7 @@ __global__ void mixdown_gated_long_kernel(const int16_t*, const ::mbx_row_level*
 
 // ---- mbx_hold.hip: the held gate (include/mbx_hold.h) -- the gated mix-down with a state record per input: one lane per short bus
 // decides (records, the plan's tables, the hold, the state in place, a code byte per input), the short sum reads the codes, and one
-// workgroup per long bus decides and sums (the hold: mbx_hold_plan.h) -----------------------------------------------------------------
+// workgroup per long bus decides and sums (the hold: mbx_hold_plan.h; the lanes' pieces: mbx_mixdown_lanes.h) -------------------------
 struct HoldParams;
 __global__ void hold_decide_kernel(const ::mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, int, HoldParams, uint32_t*, uint8_t*);
 template <int kOut>

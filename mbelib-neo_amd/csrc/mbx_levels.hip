@@ -1,8 +1,9 @@
 // mbx_levels.hip -- levels out and the gated mix-down (include/mbx_levels.h): the int16 rows a step wrote -> one 16-byte level record
 // per row (energy, peak, clipped), and talkgroup buses that sum only the inputs a gate CHOOSES by those records, in one launch for the
 // levels and one or two for the buses, BEHIND the step.  The arithmetic is mbx_levels.h, shared with the host definitions below; the
-// checks are mbx_levels_plan.h, host-only; the plan and its tables are those of mbx_mixdown.hip, untouched, and a lane's add, walk and
-// store are mbx_mixdown_lanes.h, shared with the kernels there.
+// checks are mbx_levels_plan.h, host-only; the plan, its tables, the way from its handle to a launch and the prelude of the host
+// definition are those of mbx_mixdown.hip (mbx_mixdown_plan.h), and a lane's bus, add, walk, long tail and store are
+// mbx_mixdown_lanes.h, shared with the kernels there and in mbx_hold.hip.
 //
 // pcm_levels_kernel.  A row is 320 B, and its level is a reduction over the lanes that share it.  The partition: 16 LANES PER ROW of
 // TEN SAMPLES each, 4 rows per 64-lane wave.  Why: the kernel is bound by vector issue, not by bytes (a first build with lane j on the
@@ -147,14 +148,11 @@ __global__ void __launch_bounds__(256)
 mixdown_gated_kernel(const int16_t* __restrict__ pcm16, const mbx_row_level* __restrict__ levels, const int32_t* __restrict__ bus_offset,
                      const int32_t* __restrict__ short_bus, const MixdownInput* __restrict__ input, int n_short, uint32_t open_peak, int loudest_n,
                      void* __restrict__ out) {
-    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t slot = g / kMixdownPieces;
+    const auto [slot, piece] = mixdown_short_slot();
     if (slot >= (size_t)n_short) {
         return;
     }
-    const int piece = (int)(g - slot * kMixdownPieces);
-    const int bus = short_bus[slot];
-    const int32_t lo = bus_offset[bus], count = bus_offset[bus + 1] - lo;
+    const auto [bus, lo, count] = mixdown_bus_at(bus_offset, short_bus, slot);
     uint64_t top[kGateMaxLoudest] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int32_t k = 0; loudest_n > 0 && k < count; ++k) {   // (a plan may make any bus short: correct for every count up to 4,096)
         gate_insert(top, gate_key_of(levels, input[lo + k], k, open_peak));
@@ -168,38 +166,29 @@ template __global__ void mixdown_gated_kernel<kMixdownPcm16>(const int16_t*, con
 template __global__ void mixdown_gated_kernel<kMixdownUlaw>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, int, uint32_t, int, void*);
 template __global__ void mixdown_gated_kernel<kMixdownAlaw>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, int, uint32_t, int, void*);
 
-constexpr int kGateKeysPerLane = kMixdownMaxInputs / kMixdownBlock;   // 16
-constexpr int kGateWaves = kMixdownBlock / 64;                        // 4: the kernels of this library are built for 64-lane waves
-static_assert(kGateKeysPerLane * kMixdownBlock == kMixdownMaxInputs, "the lanes of a workgroup hold the keys of a full bus");
-
 // one workgroup per long bus: long_bus[blockIdx.x] is its bus
 template <int kOut>
 __global__ void __launch_bounds__(256)
 mixdown_gated_long_kernel(const int16_t* __restrict__ pcm16, const mbx_row_level* __restrict__ levels, const int32_t* __restrict__ bus_offset,
                           const int32_t* __restrict__ long_bus, const MixdownInput* __restrict__ input, uint32_t open_peak, int loudest_n,
                           void* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) int32_t part[kMixdownSlices][160];
+    __shared__ __attribute__((aligned(16))) MixdownPart part;
     __shared__ uint64_t wave_max[kGateWaves];
-    const int bus = long_bus[blockIdx.x];
-    const int32_t lo = bus_offset[bus], count = bus_offset[bus + 1] - lo;
+    const auto [bus, lo, count] = mixdown_bus_at(bus_offset, long_bus, blockIdx.x);
     const int tid = (int)threadIdx.x;
     if (loudest_n == 0) {   // every open input: mixdown_long_kernel's slice pass, closed inputs skipped
         const int slice = tid / kMixdownPieces, piece = tid - slice * kMixdownPieces;
         if (slice < kMixdownSlices) {
             int32_t acc[kMixdownPiece] = {0, 0, 0, 0, 0, 0, 0, 0};
             mixdown_gated_sum<kMixdownSlices>(pcm16, levels, input + lo, slice, count, piece, open_peak, 1u, acc);
-            int4* const to = reinterpret_cast<int4*>(&part[slice][piece * kMixdownPiece]);
-            to[0] = int4{acc[0], acc[1], acc[2], acc[3]};
-            to[1] = int4{acc[4], acc[5], acc[6], acc[7]};
+            mixdown_part_put(part, slice, piece, acc);
         }
         __syncthreads();
         if (tid < kMixdownPieces) {
             int32_t acc[kMixdownPiece] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
             for (int j = 0; j < kMixdownSlices; ++j) {
-                const int4* const from = reinterpret_cast<const int4*>(&part[j][tid * kMixdownPiece]);
-                const int4 a = from[0], b = from[1];
-                acc[0] += a.x, acc[1] += a.y, acc[2] += a.z, acc[3] += a.w, acc[4] += b.x, acc[5] += b.y, acc[6] += b.z, acc[7] += b.w;
+                mixdown_part_add(part, j, tid, acc);
             }
             mixdown_store<kOut>(out, bus, tid, acc);
         }
@@ -214,7 +203,7 @@ mixdown_gated_long_kernel(const int16_t* __restrict__ pcm16, const mbx_row_level
     }
     // N rounds: the largest key below the previous round's winner.  Keys are unique within a bus, so a round names one input; a round
     // that finds 0 has run out of open inputs, and so have all behind it.  Every lane reads the same winner, so `more` is uniform and
-    // the barriers below are reached by all 256 lanes or by none.
+    // the barriers below are reached by all 256 lanes or by none.  (hold_long_kernel has the same rounds: mbx_mixdown_lanes.h says why.)
     uint64_t chosen[kGateMaxLoudest] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t below = ~(uint64_t)0;
     bool more = true;
@@ -270,46 +259,13 @@ template __global__ void mixdown_gated_long_kernel<kMixdownAlaw>(const int16_t*,
 
 namespace {
 
-int refuse(const char* who, const char* why) {
-    char text[240];
-    snprintf(text, sizeof(text), "%s: %s", who, why);
-    mbx_set_error_text(text);
-    return MBE_STATUS_INVALID_ARGUMENT;
-}
+using mbx::refuse;
 
 int refuse(const char* who, mbx::LevelsRefusal why, mbx::MixdownRefusal mix = mbx::kMixdownOk) {
     if (why == mbx::kLevelsAlign || (why == mbx::kGateMixdown && mix == mbx::kMixdownAlign)) {
         return mbx::misaligned(who, "mbx_levels.h");
     }
     return refuse(who, why == mbx::kGateMixdown ? mbx::mixdown_refusal_text(mix) : mbx::levels_refusal_text(why));
-}
-
-// the current device, after mbx_init() for it
-int ready_device(int* dev) {
-    const hipError_t e = hipGetDevice(dev);
-    if (e != hipSuccess) {
-        return mbx::hip_failed("", "hipGetDevice", e);
-    }
-    if (!mbx_device_ready(*dev)) {
-        mbx_set_error_text("mbx_init() has not been called for the current device");
-        return MBX_ENOTINIT;
-    }
-    return 0;
-}
-
-template <int kOut>
-void launch_gated(const mbx_mixdown_plan* p, const mbx_mixdown_gate& gate, const int16_t* d_pcm16, const mbx_row_level* d_levels, void* d_out,
-                  hipStream_t strm) {
-    const mbx::MixdownPlan& plan = p->plan;
-    const mbx::MixdownInput* const input = reinterpret_cast<const mbx::MixdownInput*>(p->d_words + plan.at_inputs);
-    if (plan.short_grid) {
-        hipLaunchKernelGGL(mbx::mixdown_gated_kernel<kOut>, dim3(plan.short_grid), dim3(mbx::kMixdownBlock), 0, strm, d_pcm16, d_levels, p->d_words,
-                           p->d_words + plan.at_short, input, plan.n_short, (uint32_t)gate.open_peak, (int)gate.loudest_n, d_out);
-    }
-    if (plan.long_grid) {
-        hipLaunchKernelGGL(mbx::mixdown_gated_long_kernel<kOut>, dim3(plan.long_grid), dim3(mbx::kMixdownBlock), 0, strm, d_pcm16, d_levels, p->d_words,
-                           p->d_words + plan.at_long, input, (uint32_t)gate.open_peak, (int)gate.loudest_n, d_out);
-    }
 }
 
 }  // namespace
@@ -339,7 +295,7 @@ int mbx_pcm_levels(const int16_t* d_pcm16, size_t nrows, mbx_row_level* d_levels
         return 0;
     }
     int dev = -1;
-    const int rc = ready_device(&dev);
+    const int rc = mbx::ready_device(&dev);
     if (rc < 0) {
         return rc;
     }
@@ -355,19 +311,9 @@ int mbx_mixdown_gated_host(int form, const mbx_mixdown_gate* gate, int n_buses, 
     if (bad_gate != mbx::kLevelsOk) {
         return refuse(who, bad_gate);
     }
-    if (!mbx::mixdown_form_ok(form)) {
-        return refuse(who, mbx::mixdown_refusal_text(mbx::kMixdownForm));
-    }
     mbx::MixdownPlan plan;
-    const mbx::MixdownRefusal why = mbx::plan_mixdown(n_buses, bus_offset, src_row, 0, &plan);
-    if (why != mbx::kMixdownOk) {
-        return refuse(who, mbx::mixdown_refusal_text(why));
-    }
-    if (!out || (!pcm16 && plan.rows_needed > 0)) {
-        return refuse(who, "pcm16 and out are needed");
-    }
-    if (nrows < (size_t)plan.rows_needed) {
-        return refuse(who, mbx::mixdown_refusal_text(mbx::kMixdownRows));
+    if (const char* const why = mbx::mixdown_host_refused(form, n_buses, bus_offset, src_row, pcm16, nrows, out, &plan)) {
+        return refuse(who, why);
     }
     std::vector<uint64_t> keys;
     for (int b = 0; b < n_buses; ++b) {
@@ -387,13 +333,7 @@ int mbx_mixdown_gated_host(int form, const mbx_mixdown_gate* gate, int n_buses, 
                 acc[n] += mbx::mixdown_term(x[n], g);
             }
         }
-        for (int n = 0; n < 160; ++n) {
-            if (form == MBX_MIXDOWN_PCM16) {
-                static_cast<int16_t*>(out)[(size_t)b * 160u + n] = mbx::mixdown_clamp(acc[n]);
-            } else {
-                static_cast<uint8_t*>(out)[(size_t)b * 160u + n] = mbx::mixdown_byte(form, acc[n]);
-            }
-        }
+        mbx::mixdown_put_row(form, acc, b, out);
     }
     return 0;
 }
@@ -407,24 +347,24 @@ int mbx_mixdown_gated(const mbx_mixdown_plan* plan, const mbx_mixdown_gate* gate
     if (why != mbx::kLevelsOk) {
         return refuse(who, why, mix);
     }
-    int dev = -1;
-    const int rc = ready_device(&dev);
+    mbx::MixdownTables t;
+    const int rc = mbx::mixdown_tables(who, plan, &t);
     if (rc < 0) {
         return rc;
     }
-    if (dev != plan->device) {
-        char text[160];
-        snprintf(text, sizeof(text), "the plan was made on device %d, the current device is %d", plan->device, dev);
-        return refuse(who, text);
-    }
-    const hipStream_t strm = (hipStream_t)stream;
-    if (form == MBX_MIXDOWN_PCM16) {
-        launch_gated<mbx::kMixdownPcm16>(plan, *gate, d_pcm16, d_levels, d_out, strm);
-    } else if (form == MBX_MIXDOWN_ULAW) {
-        launch_gated<mbx::kMixdownUlaw>(plan, *gate, d_pcm16, d_levels, d_out, strm);
-    } else {
-        launch_gated<mbx::kMixdownAlaw>(plan, *gate, d_pcm16, d_levels, d_out, strm);
-    }
+    const mbx::MixdownPlan& p = plan->plan;
+    const uint32_t open_peak = gate->open_peak;
+    const int loudest_n = gate->loudest_n;
+    mbx::mixdown_by_form(form, [&](auto k) {
+        if (p.short_grid) {
+            hipLaunchKernelGGL(mbx::mixdown_gated_kernel<k()>, dim3(p.short_grid), dim3(mbx::kMixdownBlock), 0, (hipStream_t)stream, d_pcm16, d_levels,
+                               t.bus_offset, t.short_bus, t.input, p.n_short, open_peak, loudest_n, d_out);
+        }
+        if (p.long_grid) {
+            hipLaunchKernelGGL(mbx::mixdown_gated_long_kernel<k()>, dim3(p.long_grid), dim3(mbx::kMixdownBlock), 0, (hipStream_t)stream, d_pcm16,
+                               d_levels, t.bus_offset, t.long_bus, t.input, open_peak, loudest_n, d_out);
+        }
+    });
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : mbx::hip_failed("", "mixdown_gated_kernel", e);
 }

@@ -1,6 +1,9 @@
 // mbx_mixdown.hip -- mix-down out (include/mbx_mixdown.h): the int16 rows a step wrote -> talkgroup BUSES, each the saturated sum of
 // its input rows times their Q12 gains, as int16 or G.711 bytes, in one or two launches BEHIND the step.  The arithmetic is
-// mbx_mixdown.h, shared with the host definition below; the checks, the split and the tables are mbx_mixdown_plan.h, host-only.
+// mbx_mixdown.h, shared with the host definition below; the checks, the split and the tables are mbx_mixdown_plan.h, host-only, and so
+// is what this unit shares with mbx_levels.hip and mbx_hold.hip on the host: the way from the plan handle to a launch (the device
+// check, the tables, the dispatch over the forms) and the prelude and the row store of the three host definitions.  What a lane does
+// -- its bus, one input's piece, the walk, the tail of a long bus, the store -- is mbx_mixdown_lanes.h, shared with the same two.
 //
 // Both kernels share one piece shape: a lane owns a PIECE of 8 samples of one bus, loads 16 B per input and stores 16 B (int16) or
 // 8 B (bytes) once; 20 adjacent lanes read one 320-byte row contiguously; the sums are eight int32 per lane.  The clamp and the
@@ -20,7 +23,7 @@
 #include "mbx_mixdown.h"    // the arithmetic: the private header of this directory
 #include <mbx_mixdown.h>    // the public header of the same name: include/, first on the include path
 #include "mbx_mixdown_plan.h"
-#include "mbx_mixdown_lanes.h"   // the lane's add, walk and store, shared with mbx_levels.hip
+#include "mbx_mixdown_lanes.h"   // a lane's bus, add, walk, tail and store, shared with mbx_levels.hip and mbx_hold.hip
 
 namespace mbx {
 
@@ -29,14 +32,11 @@ template <int kOut>
 __global__ void __launch_bounds__(256)
 mixdown_kernel(const int16_t* __restrict__ pcm16, const int32_t* __restrict__ bus_offset, const int32_t* __restrict__ short_bus,
                const MixdownInput* __restrict__ input, int n_short, void* __restrict__ out) {
-    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t slot = g / kMixdownPieces;
+    const auto [slot, piece] = mixdown_short_slot();
     if (slot >= (size_t)n_short) {
         return;
     }
-    const int piece = (int)(g - slot * kMixdownPieces);
-    const int bus = short_bus[slot];
-    const int32_t lo = bus_offset[bus], count = bus_offset[bus + 1] - lo;
+    const auto [bus, lo, count] = mixdown_bus_at(bus_offset, short_bus, slot);
     int32_t acc[kMixdownPiece] = {0, 0, 0, 0, 0, 0, 0, 0};
     mixdown_sum<1>(pcm16, input + lo, 0, count, piece, acc);
     mixdown_store<kOut>(out, bus, piece, acc);
@@ -50,25 +50,20 @@ template <int kOut>
 __global__ void __launch_bounds__(256)
 mixdown_long_kernel(const int16_t* __restrict__ pcm16, const int32_t* __restrict__ bus_offset, const int32_t* __restrict__ long_bus,
                     const MixdownInput* __restrict__ input, void* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) int32_t part[kMixdownSlices][160];
-    const int bus = long_bus[blockIdx.x];
-    const int32_t lo = bus_offset[bus], count = bus_offset[bus + 1] - lo;
+    __shared__ __attribute__((aligned(16))) MixdownPart part;
+    const auto [bus, lo, count] = mixdown_bus_at(bus_offset, long_bus, blockIdx.x);
     const int slice = (int)threadIdx.x / kMixdownPieces, piece = (int)threadIdx.x - slice * kMixdownPieces;
     if (slice < kMixdownSlices) {   // (lanes 240 .. 255 only keep the barrier company)
         int32_t acc[kMixdownPiece] = {0, 0, 0, 0, 0, 0, 0, 0};
         mixdown_sum<kMixdownSlices>(pcm16, input + lo, slice, count, piece, acc);
-        int4* const to = reinterpret_cast<int4*>(&part[slice][piece * kMixdownPiece]);
-        to[0] = int4{acc[0], acc[1], acc[2], acc[3]};
-        to[1] = int4{acc[4], acc[5], acc[6], acc[7]};
+        mixdown_part_put(part, slice, piece, acc);
     }
     __syncthreads();
     if (threadIdx.x < kMixdownPieces) {
         int32_t acc[kMixdownPiece] = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int j = 0; j < kMixdownSlices; ++j) {
-            const int4* const from = reinterpret_cast<const int4*>(&part[j][(int)threadIdx.x * kMixdownPiece]);
-            const int4 a = from[0], b = from[1];
-            acc[0] += a.x, acc[1] += a.y, acc[2] += a.z, acc[3] += a.w, acc[4] += b.x, acc[5] += b.y, acc[6] += b.z, acc[7] += b.w;
+            mixdown_part_add(part, j, (int)threadIdx.x, acc);
         }
         mixdown_store<kOut>(out, bus, (int)threadIdx.x, acc);
     }
@@ -80,46 +75,15 @@ template __global__ void mixdown_long_kernel<kMixdownAlaw>(const int16_t*, const
 }  // namespace mbx
 
 // ---- the plan (host) ---------------------------------------------------------------------------------------------------------------
-// (struct mbx_mixdown_plan, the handle: mbx_mixdown_plan.h -- mbx_levels.hip launches from it too)
+// (struct mbx_mixdown_plan, the handle, and mixdown_tables, its way to a launch: mbx_mixdown_plan.h -- mbx_levels.hip and mbx_hold.hip
+// launch from it too)
 namespace mbx {
 int mixdown_plan_device(const mbx_mixdown_plan* plan) { return plan ? plan->device : -1; }
 }  // namespace mbx
 
 namespace {
 
-int refuse(const char* who, mbx::MixdownRefusal why) {
-    char text[200];
-    snprintf(text, sizeof(text), "%s: %s", who, mbx::mixdown_refusal_text(why));
-    mbx_set_error_text(text);
-    return MBE_STATUS_INVALID_ARGUMENT;
-}
-
-// the current device, after mbx_init() for it
-int ready_device(int* dev) {
-    const hipError_t e = hipGetDevice(dev);
-    if (e != hipSuccess) {
-        return mbx::hip_failed("", "hipGetDevice", e);
-    }
-    if (!mbx_device_ready(*dev)) {
-        mbx_set_error_text("mbx_init() has not been called for the current device");
-        return MBX_ENOTINIT;
-    }
-    return 0;
-}
-
-template <int kOut>
-void launch(const mbx_mixdown_plan* p, const int16_t* d_pcm16, void* d_out, hipStream_t strm) {
-    const mbx::MixdownPlan& plan = p->plan;
-    const mbx::MixdownInput* const input = reinterpret_cast<const mbx::MixdownInput*>(p->d_words + plan.at_inputs);
-    if (plan.short_grid) {
-        hipLaunchKernelGGL(mbx::mixdown_kernel<kOut>, dim3(plan.short_grid), dim3(mbx::kMixdownBlock), 0, strm, d_pcm16, p->d_words,
-                           p->d_words + plan.at_short, input, plan.n_short, d_out);
-    }
-    if (plan.long_grid) {
-        hipLaunchKernelGGL(mbx::mixdown_long_kernel<kOut>, dim3(plan.long_grid), dim3(mbx::kMixdownBlock), 0, strm, d_pcm16, p->d_words,
-                           p->d_words + plan.at_long, input, d_out);
-    }
-}
+int refuse(const char* who, mbx::MixdownRefusal why) { return mbx::refuse(who, mbx::mixdown_refusal_text(why)); }
 
 }  // namespace
 
@@ -144,7 +108,7 @@ int mbx_mixdown_plan_create_split(mbx_mixdown_plan** out, int n_buses, const int
         return refuse(who, why);
     }
     int dev = -1;
-    const int rc = ready_device(&dev);
+    const int rc = mbx::ready_device(&dev);
     if (rc < 0) {
         return rc;
     }
@@ -190,20 +154,9 @@ int mbx_mixdown_plan_long_buses(const mbx_mixdown_plan* plan) { return plan ? pl
 int mbx_mixdown_host(int form, int n_buses, const int32_t* bus_offset, const int32_t* src_row, const int16_t* gain_q12, const int16_t* pcm16,
                      size_t nrows, void* out) {
     const char* const who = "mbx_mixdown_host";
-    if (!mbx::mixdown_form_ok(form)) {
-        return refuse(who, mbx::kMixdownForm);
-    }
     mbx::MixdownPlan plan;
-    const mbx::MixdownRefusal why = mbx::plan_mixdown(n_buses, bus_offset, src_row, 0, &plan);
-    if (why != mbx::kMixdownOk) {
-        return refuse(who, why);
-    }
-    if (!out || (!pcm16 && plan.rows_needed > 0)) {
-        mbx_set_error_text("mbx_mixdown_host: pcm16 and out are needed");
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (nrows < (size_t)plan.rows_needed) {
-        return refuse(who, mbx::kMixdownRows);
+    if (const char* const why = mbx::mixdown_host_refused(form, n_buses, bus_offset, src_row, pcm16, nrows, out, &plan)) {
+        return mbx::refuse(who, why);
     }
     for (int b = 0; b < n_buses; ++b) {
         int32_t acc[160] = {0};
@@ -214,13 +167,7 @@ int mbx_mixdown_host(int form, int n_buses, const int32_t* bus_offset, const int
                 acc[n] += mbx::mixdown_term(x[n], g);
             }
         }
-        for (int n = 0; n < 160; ++n) {
-            if (form == MBX_MIXDOWN_PCM16) {
-                static_cast<int16_t*>(out)[(size_t)b * 160u + n] = mbx::mixdown_clamp(acc[n]);
-            } else {
-                static_cast<uint8_t*>(out)[(size_t)b * 160u + n] = mbx::mixdown_byte(form, acc[n]);
-            }
-        }
+        mbx::mixdown_put_row(form, acc, b, out);
     }
     return 0;
 }
@@ -231,25 +178,22 @@ int mbx_mixdown(const mbx_mixdown_plan* plan, int form, const int16_t* d_pcm16, 
     if (why != mbx::kMixdownOk) {
         return why == mbx::kMixdownAlign ? mbx::misaligned(who, "mbx_mixdown.h") : refuse(who, why);
     }
-    int dev = -1;
-    const int rc = ready_device(&dev);
+    mbx::MixdownTables t;
+    const int rc = mbx::mixdown_tables(who, plan, &t);
     if (rc < 0) {
         return rc;
     }
-    if (dev != plan->device) {
-        char text[160];
-        snprintf(text, sizeof(text), "%s: the plan was made on device %d, the current device is %d", who, plan->device, dev);
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    const hipStream_t strm = (hipStream_t)stream;
-    if (form == MBX_MIXDOWN_PCM16) {
-        launch<mbx::kMixdownPcm16>(plan, d_pcm16, d_out, strm);
-    } else if (form == MBX_MIXDOWN_ULAW) {
-        launch<mbx::kMixdownUlaw>(plan, d_pcm16, d_out, strm);
-    } else {
-        launch<mbx::kMixdownAlaw>(plan, d_pcm16, d_out, strm);
-    }
+    const mbx::MixdownPlan& p = plan->plan;
+    mbx::mixdown_by_form(form, [&](auto k) {
+        if (p.short_grid) {
+            hipLaunchKernelGGL(mbx::mixdown_kernel<k()>, dim3(p.short_grid), dim3(mbx::kMixdownBlock), 0, (hipStream_t)stream, d_pcm16, t.bus_offset,
+                               t.short_bus, t.input, p.n_short, d_out);
+        }
+        if (p.long_grid) {
+            hipLaunchKernelGGL(mbx::mixdown_long_kernel<k()>, dim3(p.long_grid), dim3(mbx::kMixdownBlock), 0, (hipStream_t)stream, d_pcm16, t.bus_offset,
+                               t.long_bus, t.input, d_out);
+        }
+    });
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : mbx::hip_failed("", "mixdown_kernel", e);
 }

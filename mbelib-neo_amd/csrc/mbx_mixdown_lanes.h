@@ -1,6 +1,8 @@
-// mbx_mixdown_lanes.h -- what a lane of the mix-down kernels does with its PIECE of 8 samples of one bus: add one input's 16 bytes times
-// its gain, walk the inputs of a bus four at a time, store the piece in the form of the instance.  Device code, shared as it is by
-// the kernels of mbx_mixdown.hip and by their gated twins in mbx_levels.hip (include/mbx_levels.h); the arithmetic is mbx_mixdown.h.
+// mbx_mixdown_lanes.h -- what a lane of the bus kernels does with its PIECE of 8 samples of one bus: find its bus, load one input's 16
+// bytes and add them times the gain, walk the inputs of a bus four at a time, pass the piece through the 12 slices of a long bus, store
+// it in the form of the instance; and how the keys of a long bus lie over a workgroup.  Device code, stated once for the kernels
+// of THREE units: mbx_mixdown.hip, their gated twins in mbx_levels.hip (include/mbx_levels.h) and the held ones in mbx_hold.hip
+// (include/mbx_hold.h).  The arithmetic is mbx_mixdown.h.
 #pragma once
 
 #include "mbx_device.h"
@@ -9,11 +11,42 @@
 
 namespace mbx {
 
-// one input's piece: the 16 bytes of the row at the lane's piece, times the gain, into the lane's sums
-__device__ __forceinline__ void mixdown_add_input(const int16_t* __restrict__ pcm16, const MixdownInput in, int piece, int32_t acc[kMixdownPiece]) {
+// ---- the bus of a lane or of a workgroup --------------------------------------------------------------------------------------------
+struct MixdownBus {
+    int     bus;         // in the caller's order
+    int32_t lo, count;   // its inputs: input[lo .. lo + count)
+};
+// bus_of: short_bus[] or long_bus[] of the plan's tables; at: the slot of a short launch, the workgroup of a long one
+__device__ __forceinline__ MixdownBus mixdown_bus_at(const int32_t* __restrict__ bus_offset, const int32_t* __restrict__ bus_of, size_t at) {
+    const int bus = bus_of[at];
+    const int32_t lo = bus_offset[bus], count = bus_offset[bus + 1] - lo;
+    return MixdownBus{bus, lo, count};
+}
+
+// a lane of a short launch: lane = slot * 20 + piece, flat over the grid.  Slots from n_short on are not live: their lanes leave, and
+// only a live lane asks for the bus of its slot.
+struct MixdownSlot {
+    size_t slot;
+    int    piece;
+};
+__device__ __forceinline__ MixdownSlot mixdown_short_slot() {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t slot = g / kMixdownPieces;
+    return MixdownSlot{slot, (int)(g - slot * kMixdownPieces)};
+}
+
+// ---- one input ----------------------------------------------------------------------------------------------------------------------
+// the 16 bytes of the input's row at the lane's piece, as eight samples
+__device__ __forceinline__ void mixdown_load_piece(const int16_t* __restrict__ pcm16, const MixdownInput in, int piece, int16_t x[kMixdownPiece]) {
     const uint4 v = *reinterpret_cast<const uint4*>(pcm16 + (size_t)in.row * 160u + (size_t)(piece * kMixdownPiece));
-    const int16_t x[kMixdownPiece] = {(int16_t)(v.x & 0xFFFFu), (int16_t)(v.x >> 16), (int16_t)(v.y & 0xFFFFu), (int16_t)(v.y >> 16),
-                                      (int16_t)(v.z & 0xFFFFu), (int16_t)(v.z >> 16), (int16_t)(v.w & 0xFFFFu), (int16_t)(v.w >> 16)};
+    x[0] = (int16_t)(v.x & 0xFFFFu), x[1] = (int16_t)(v.x >> 16), x[2] = (int16_t)(v.y & 0xFFFFu), x[3] = (int16_t)(v.y >> 16);
+    x[4] = (int16_t)(v.z & 0xFFFFu), x[5] = (int16_t)(v.z >> 16), x[6] = (int16_t)(v.w & 0xFFFFu), x[7] = (int16_t)(v.w >> 16);
+}
+
+// one input's piece times the gain, into the lane's sums
+__device__ __forceinline__ void mixdown_add_input(const int16_t* __restrict__ pcm16, const MixdownInput in, int piece, int32_t acc[kMixdownPiece]) {
+    int16_t x[kMixdownPiece];
+    mixdown_load_piece(pcm16, in, piece, x);
     mixdown_add_piece(x, (int16_t)in.gain, acc);
 }
 
@@ -54,5 +87,34 @@ __device__ __forceinline__ void mixdown_store(void* __restrict__ out, int bus, i
         *reinterpret_cast<uint2*>(static_cast<uint8_t*>(out) + at) = uint2{four(0), four(4)};
     }
 }
+
+// ---- the tail of a long bus ---------------------------------------------------------------------------------------------------------
+// A workgroup of 256 is 12 input SLICES x 20 pieces (lanes 240 .. 255 only keep the barriers company).  A kernel declares
+//     __shared__ __attribute__((aligned(16))) MixdownPart part;
+// has every lane of a slice PUT its sums into its slice's row, reaches __syncthreads(), and has its first 20 lanes ADD the 12 rows of
+// their piece to sums that start at zero, and store.  The loop over the rows stays in the kernel: a helper that holds it reaches the
+// kernel unrolled, and the compiler then orders the operands of the adds another way than it does for the kernel's own loop.
+typedef int32_t MixdownPart[kMixdownSlices][160];
+
+__device__ __forceinline__ void mixdown_part_put(MixdownPart& part, int slice, int piece, const int32_t acc[kMixdownPiece]) {
+    int4* const to = reinterpret_cast<int4*>(&part[slice][piece * kMixdownPiece]);
+    to[0] = int4{acc[0], acc[1], acc[2], acc[3]};
+    to[1] = int4{acc[4], acc[5], acc[6], acc[7]};
+}
+
+__device__ __forceinline__ void mixdown_part_add(const MixdownPart& part, int slice, int piece, int32_t acc[kMixdownPiece]) {
+    const int4* const from = reinterpret_cast<const int4*>(&part[slice][piece * kMixdownPiece]);
+    const int4 a = from[0], b = from[1];
+    acc[0] += a.x, acc[1] += a.y, acc[2] += a.z, acc[3] += a.w, acc[4] += b.x, acc[5] += b.y, acc[6] += b.z, acc[7] += b.w;
+}
+
+// ---- the keys of a long bus ---------------------------------------------------------------------------------------------------------
+// The 256 lanes of a workgroup hold the keys of a bus, lane tid those of inputs tid, tid + 256, ...: at most 16, in registers; a
+// workgroup-wide maximum over them is a 64-lane reduction per wave and one word per wave through LDS.  (The N rounds themselves are
+// written out in mixdown_gated_long_kernel and in hold_long_kernel: behind a shared helper, whole or in parts, the compiler states the
+// branch conditions of the rounds another way in both, and a kernel whose code changes keeps its own body.)
+constexpr int kGateKeysPerLane = kMixdownMaxInputs / kMixdownBlock;   // 16
+constexpr int kGateWaves = kMixdownBlock / 64;                        // 4: the kernels of this library are built for 64-lane waves
+static_assert(kGateKeysPerLane * kMixdownBlock == kMixdownMaxInputs, "the lanes of a workgroup hold the keys of a full bus");
 
 }  // namespace mbx

@@ -1,13 +1,15 @@
 // mbx_mixdown_plan.h -- what a mix-down plan (include/mbx_mixdown.h) is before it reaches a device: the caller's CSR arrays checked,
 // rows_needed, the split of the buses into SHORT ones (flat lanes, mixdown_kernel) and LONG ones (one workgroup each,
-// mixdown_long_kernel), the two grid sizes, the words of the tables the kernels read, and what mbx_mixdown refuses of its arguments.
-// Integer work on the host alone: no HIP, no locks, no globals -- so that a CPU program can check it under a sanitizer
-// (tests/mixdown_check.cpp), in the manner of mbx_group_plan.h, mbx_launch_plan.h and mbe_flush_plan.h.  Private to mbx_mixdown.hip;
+// mixdown_long_kernel), the two grid sizes, the words of the tables the kernels read, what mbx_mixdown refuses of its arguments, and
+// what the three host definitions share.  Integer work on the host alone: no HIP, no locks, no globals -- so that a CPU program can
+// check it under a sanitizer (tests/mixdown_check.cpp), in the manner of mbx_group_plan.h, mbx_launch_plan.h and mbe_flush_plan.h.
+// At its end, for hipcc alone: the handle's way to a launch, shared by mbx_mixdown.hip, mbx_levels.hip and mbx_hold.hip.  Private;
 // nothing here is exported.
 #pragma once
 
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include "mbx_mixdown.h"
 
@@ -189,12 +191,87 @@ static inline MixdownRefusal mixdown_launch_refused(const MixdownPlan* plan, int
     return kMixdownOk;
 }
 
+// ---- the host definitions (mbx_mixdown_host, mbx_mixdown_gated_host, mbx_mixdown_held_host) -----------------------------------------
+// what all three refuse of these arguments, in this order, behind what each refuses of its gate or hold: the form, the plan's own, the
+// pointers, rows short of the plan.  nullptr: nothing, and *plan is the plan of the arrays.
+static inline const char* mixdown_host_refused(int form, int n_buses, const int32_t* bus_offset, const int32_t* src_row, const int16_t* pcm16,
+                                               size_t nrows, const void* out, MixdownPlan* plan) {
+    if (!mixdown_form_ok(form)) {
+        return mixdown_refusal_text(kMixdownForm);
+    }
+    const MixdownRefusal why = plan_mixdown(n_buses, bus_offset, src_row, 0, plan);
+    if (why != kMixdownOk) {
+        return mixdown_refusal_text(why);
+    }
+    if (!out || (!pcm16 && plan->rows_needed > 0)) {
+        return "pcm16 and out are needed";
+    }
+    return nrows < (size_t)plan->rows_needed ? mixdown_refusal_text(kMixdownRows) : nullptr;
+}
+
+// the 160 sums of bus b into row b of out, in `form`: the clamp, or the byte
+static inline void mixdown_put_row(int form, const int32_t acc[160], int b, void* out) {
+    for (int n = 0; n < 160; ++n) {
+        if (form == kMixdownPcm16) {
+            static_cast<int16_t*>(out)[(size_t)b * 160u + n] = mixdown_clamp(acc[n]);
+        } else {
+            static_cast<uint8_t*>(out)[(size_t)b * 160u + n] = mixdown_byte(form, acc[n]);
+        }
+    }
+}
+
+// f(k) with k() the form as a constant, for the kernel instance of that form
+template <class F>
+static inline void mixdown_by_form(int form, F f) {
+    if (form == kMixdownPcm16) {
+        f(std::integral_constant<int, kMixdownPcm16>());
+    } else if (form == kMixdownUlaw) {
+        f(std::integral_constant<int, kMixdownUlaw>());
+    } else {
+        f(std::integral_constant<int, kMixdownAlaw>());
+    }
+}
+
 }  // namespace mbx
 
-// the handle of the public header: the plan and where its tables are.  Made and destroyed by mbx_mixdown.hip; mbx_levels.hip launches
-// the gated kernels from the same tables.
+// the handle of the public header: the plan and where its tables are.  Made and destroyed by mbx_mixdown.hip; mbx_levels.hip and
+// mbx_hold.hip launch their kernels from the same tables.
 struct mbx_mixdown_plan {
     mbx::MixdownPlan plan;
     int      device = -1;
     int32_t* d_words = nullptr;   // the tables, one allocation on `device`
 };
+
+#ifdef __HIPCC__   // the launch side of the handle: for the units that launch from it, not for the CPU programs that check the plan
+#include "mbx_host.h"
+
+namespace mbx {
+
+// what the kernels of a launch read of the plan's tables
+struct MixdownTables {
+    const int32_t *bus_offset, *short_bus, *long_bus;
+    const MixdownInput* input;
+};
+
+// the handle -> its tables, for a launch on the current device: that device ready (mbx_init), and the plan made on it or refused
+// (t may be NULL: mbx_gate_state_create wants the check alone)
+static inline int mixdown_tables(const char* who, const mbx_mixdown_plan* p, MixdownTables* t) {
+    int dev = -1;
+    const int rc = ready_device(&dev);
+    if (rc < 0) {
+        return rc;
+    }
+    if (dev != p->device) {
+        char text[160];
+        snprintf(text, sizeof(text), "the plan was made on device %d, the current device is %d", p->device, dev);
+        return refuse(who, text);
+    }
+    if (t) {
+        *t = MixdownTables{p->d_words, p->d_words + p->plan.at_short, p->d_words + p->plan.at_long,
+                           reinterpret_cast<const MixdownInput*>(p->d_words + p->plan.at_inputs)};
+    }
+    return 0;
+}
+
+}  // namespace mbx
+#endif

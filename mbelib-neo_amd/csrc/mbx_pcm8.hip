@@ -60,8 +60,7 @@ static_assert(MBX_LAW_ULAW == mbx::kLawUlaw && MBX_LAW_ALAW == mbx::kLawAlaw, "o
 
 int mbx_pcm_compand_host(int law, const int16_t* pcm16, size_t nsamples, uint8_t* pcm8) {
     if (!pcm16 || !pcm8 || (law != MBX_LAW_ULAW && law != MBX_LAW_ALAW)) {
-        mbx_set_error_text("mbx_pcm_compand_host: pcm16 and pcm8 are needed, law is MBX_LAW_ULAW or MBX_LAW_ALAW");
-        return MBE_STATUS_INVALID_ARGUMENT;
+        return mbx::refuse("mbx_pcm_compand_host", "pcm16 and pcm8 are needed, law is MBX_LAW_ULAW or MBX_LAW_ALAW");
     }
     for (size_t i = 0; i < nsamples; ++i) {
         pcm8[i] = mbx::pcm16_compand(law, pcm16[i]);
@@ -71,8 +70,7 @@ int mbx_pcm_compand_host(int law, const int16_t* pcm16, size_t nsamples, uint8_t
 
 int mbx_pcm_compand(int law, const int16_t* d_pcm16, size_t nframes, uint8_t* d_pcm8, void* stream) {
     if (!d_pcm16 || !d_pcm8 || (law != MBX_LAW_ULAW && law != MBX_LAW_ALAW)) {
-        mbx_set_error_text("mbx_pcm_compand: d_pcm16 and d_pcm8 are needed, law is MBX_LAW_ULAW or MBX_LAW_ALAW");
-        return MBE_STATUS_INVALID_ARGUMENT;
+        return mbx::refuse("mbx_pcm_compand", "d_pcm16 and d_pcm8 are needed, law is MBX_LAW_ULAW or MBX_LAW_ALAW");
     }
     if (!mbx::aligned_to(d_pcm16, 2)) {
         return mbx::misaligned("mbx_pcm_compand", "mbx_pcm8.h");
@@ -81,17 +79,12 @@ int mbx_pcm_compand(int law, const int16_t* d_pcm16, size_t nframes, uint8_t* d_
         return 0;
     }
     if (nframes > ((size_t)1 << 40)) {   // (the grid below stays under 2^31 workgroups)
-        mbx_set_error_text("mbx_pcm_compand: more than 2^40 frames in one launch");
-        return MBE_STATUS_INVALID_ARGUMENT;
+        return mbx::refuse("mbx_pcm_compand", "more than 2^40 frames in one launch");
     }
     int dev = -1;
-    const hipError_t eg = hipGetDevice(&dev);
-    if (eg != hipSuccess) {
-        return mbx::hip_failed("", "hipGetDevice", eg);
-    }
-    if (!mbx_device_ready(dev)) {
-        mbx_set_error_text("mbx_init() has not been called for the current device");
-        return MBX_ENOTINIT;
+    const int rc = mbx::ready_device(&dev);
+    if (rc < 0) {
+        return rc;
     }
     // the phase of the launch: the first sample whose byte is 8-byte aligned; its piece is one 16-byte load where the sample is
     // 16-byte aligned too

@@ -146,14 +146,13 @@ class BatchDecoder:
         [n, 160] a decode returned (a contiguous device tensor) -> uint8 [n, 160], G.711 mu-law (pcm8.LAW_ULAW) or A-law
         (pcm8.LAW_ALAW), the bytes pcm8.ulaw / pcm8.alaw give on the host.  out: a contiguous uint8 tensor of as many elements."""
         torch = _torch()
-        if pcm16.dtype != torch.int16 or not pcm16.is_contiguous() or pcm16.numel() % 160:
-            raise ValueError("pcm16 must be a contiguous int16 tensor of rows of 160 samples")
+        n = _pcm16_rows(pcm16)
         if out is None:
             out = torch.empty(tuple(pcm16.shape), dtype=torch.uint8, device=pcm16.device)
         elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != pcm16.numel() or out.device != pcm16.device:
             raise ValueError("out must be a contiguous uint8 tensor of one byte per sample on the device of pcm16")
         with torch.cuda.device(pcm16.device):
-            rc = _native.lib().mbx_pcm_compand(int(law), pcm16.data_ptr(), pcm16.numel() // 160, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            rc = _native.lib().mbx_pcm_compand(int(law), pcm16.data_ptr(), n, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(rc, "mbx_pcm_compand")
         return out
 
@@ -163,15 +162,10 @@ class BatchDecoder:
         int16 (mixdown.PCM16) or G.711 bytes (mixdown.ULAW, mixdown.ALAW), the values mixdown.mix gives on the host.  out: a contiguous
         tensor of that shape's element count and dtype."""
         torch = _torch()
-        if pcm16.dtype != torch.int16 or not pcm16.is_contiguous() or pcm16.numel() % 160:
-            raise ValueError("pcm16 must be a contiguous int16 tensor of rows of 160 samples")
-        dtype = torch.int16 if int(form) == 0 else torch.uint8
-        if out is None:
-            out = torch.empty((plan.buses, 160), dtype=dtype, device=pcm16.device)
-        elif out.dtype != dtype or not out.is_contiguous() or out.numel() != plan.buses * 160 or out.device != pcm16.device:
-            raise ValueError("out must be a contiguous tensor of 160 samples per bus, int16 or uint8 by the form, on the device of pcm16")
+        n = _pcm16_rows(pcm16)
+        out = _bus_out(pcm16, plan, form, out)
         with torch.cuda.device(pcm16.device):
-            rc = _native.lib().mbx_mixdown(plan.handle, int(form), pcm16.data_ptr(), pcm16.numel() // 160, out.data_ptr(),
+            rc = _native.lib().mbx_mixdown(plan.handle, int(form), pcm16.data_ptr(), n, out.data_ptr(),
                                            torch.cuda.current_stream().cuda_stream)
         _native.check(rc, "mbx_mixdown")
         return out
@@ -181,9 +175,7 @@ class BatchDecoder:
         decode returned (a contiguous device tensor) -> their level records as uint8 [n, 16]; ``.cpu().numpy().view(levels.LEVEL_DTYPE)``
         gives the records levels.measure gives on the host.  out: a contiguous uint8 tensor of 16 bytes per row."""
         torch = _torch()
-        if pcm16.dtype != torch.int16 or not pcm16.is_contiguous() or pcm16.numel() % 160:
-            raise ValueError("pcm16 must be a contiguous int16 tensor of rows of 160 samples")
-        n = pcm16.numel() // 160
+        n = _pcm16_rows(pcm16)
         if out is None:
             out = torch.empty((n, 16), dtype=torch.uint8, device=pcm16.device)
         elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != n * 16 or out.device != pcm16.device:
@@ -192,6 +184,16 @@ class BatchDecoder:
             rc = _native.lib().mbx_pcm_levels(pcm16.data_ptr(), n, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(rc, "mbx_pcm_levels")
         return out
+
+    def _levels_for(self, pcm16, levels):
+        """the levels tensor of a gated or held call and the rows of pcm16: what the caller got from self.levels(pcm16), or measured here"""
+        torch = _torch()
+        if levels is None:
+            levels = self.levels(pcm16)
+        n = pcm16.numel() // 160
+        if levels.dtype != torch.uint8 or not levels.is_contiguous() or levels.numel() != n * 16 or levels.device != pcm16.device:
+            raise ValueError("levels must be the contiguous uint8 tensor of 16 bytes per row that levels() returns for pcm16")
+        return levels, n
 
     def mixdown_gated(self, pcm16, plan, form=0, open_peak=0, loudest_n=0, levels=None, out=None):
         """The gated mix-down (include/mbx_levels.h): mbx_mixdown_gated on the current torch stream -- the buses of `plan` summing only
@@ -202,16 +204,8 @@ class BatchDecoder:
         from . import levels as _levels
 
         torch = _torch()
-        if levels is None:
-            levels = self.levels(pcm16)
-        n = pcm16.numel() // 160
-        if levels.dtype != torch.uint8 or not levels.is_contiguous() or levels.numel() != n * 16 or levels.device != pcm16.device:
-            raise ValueError("levels must be the contiguous uint8 tensor of 16 bytes per row that levels() returns for pcm16")
-        dtype = torch.int16 if int(form) == 0 else torch.uint8
-        if out is None:
-            out = torch.empty((plan.buses, 160), dtype=dtype, device=pcm16.device)
-        elif out.dtype != dtype or not out.is_contiguous() or out.numel() != plan.buses * 160 or out.device != pcm16.device:
-            raise ValueError("out must be a contiguous tensor of 160 samples per bus, int16 or uint8 by the form, on the device of pcm16")
+        levels, n = self._levels_for(pcm16, levels)
+        out = _bus_out(pcm16, plan, form, out)
         if not (0 <= int(open_peak) <= 0xFFFF and 0 <= int(loudest_n) <= 0xFFFF):
             raise ValueError("open_peak and loudest_n are uint16 fields of the gate")
         gate = _levels.Gate(int(open_peak), int(loudest_n))
@@ -228,16 +222,8 @@ class BatchDecoder:
         import ctypes
 
         torch = _torch()
-        if levels is None:
-            levels = self.levels(pcm16)
-        n = pcm16.numel() // 160
-        if levels.dtype != torch.uint8 or not levels.is_contiguous() or levels.numel() != n * 16 or levels.device != pcm16.device:
-            raise ValueError("levels must be the contiguous uint8 tensor of 16 bytes per row that levels() returns for pcm16")
-        dtype = torch.int16 if int(form) == 0 else torch.uint8
-        if out is None:
-            out = torch.empty((plan.buses, 160), dtype=dtype, device=pcm16.device)
-        elif out.dtype != dtype or not out.is_contiguous() or out.numel() != plan.buses * 160 or out.device != pcm16.device:
-            raise ValueError("out must be a contiguous tensor of 160 samples per bus, int16 or uint8 by the form, on the device of pcm16")
+        levels, n = self._levels_for(pcm16, levels)
+        out = _bus_out(pcm16, plan, form, out)
         with torch.cuda.device(pcm16.device):
             rc = _native.lib().mbx_mixdown_held(plan.handle, ctypes.addressof(hold), state.handle, int(form), pcm16.data_ptr(), n, levels.data_ptr(),
                                                 out.data_ptr(), torch.cuda.current_stream().cuda_stream)
@@ -638,6 +624,24 @@ def pack_mixed_rows(codec, counts, frames, soft=False):
         rows[at:at + k, :own] = f.reshape(k, own)
         at += k
     return rows.reshape(-1, MIXED_ROW_CELLS, 2) if soft else rows
+
+
+def _pcm16_rows(pcm16):
+    """the rows of the int16 tensor a decode returned"""
+    if pcm16.dtype != _torch().int16 or not pcm16.is_contiguous() or pcm16.numel() % 160:
+        raise ValueError("pcm16 must be a contiguous int16 tensor of rows of 160 samples")
+    return pcm16.numel() // 160
+
+
+def _bus_out(pcm16, plan, form, out):
+    """the bus rows of `plan` in `form` on the device of pcm16: a new tensor, or the caller's, checked"""
+    torch = _torch()
+    dtype = torch.int16 if int(form) == 0 else torch.uint8
+    if out is None:
+        return torch.empty((plan.buses, 160), dtype=dtype, device=pcm16.device)
+    if out.dtype != dtype or not out.is_contiguous() or out.numel() != plan.buses * 160 or out.device != pcm16.device:
+        raise ValueError("out must be a contiguous tensor of 160 samples per bus, int16 or uint8 by the form, on the device of pcm16")
+    return out
 
 
 def _soft_array(codec, soft, n):

@@ -289,7 +289,21 @@ def test_the_host_call_and_the_launchers_refuse_their_arguments_before_they_ask_
         wrong = np.array([record], dtype=hold.STATE_DTYPE)
         assert b"state record" in hh(*but(8, wrong.ctypes.data))
         assert wrong[0].tolist() == record
-    assert not out.any() and not st.view(np.uint32).any()
+    # their order: everything wrong at once, then one thing fewer each time -- the hold, the form, the plan's own, the pointers, the
+    # rows, the missing state, the bad record
+    wrong = np.array([(0, 0, 1)], dtype=hold.STATE_DTYPE)
+    worst = [3, C.addressof(bad_holds[0][0]), 0, off.ctypes.data, row.ctypes.data, None, None, 4, None, None]
+    for at, value, part in ((None, None, bad_holds[0][1]), (1, g, b"form"), (0, 0, b"n_buses"), (2, 1, b"pcm16 and out"),
+                            (6, x.ctypes.data, b"pcm16 and out"), (9, out.ctypes.data, b"nrows"), (7, 5, b"state is needed"),
+                            (8, wrong.ctypes.data, b"state record")):
+        if at is not None:
+            worst[at] = value
+        text = hh(*worst)
+        assert text.startswith(b"mbx_mixdown_held_host: ") and part in text, text
+    worst[1] = None   # no hold at all, in front of a bad record and of everything else
+    worst[0], worst[2], worst[6], worst[7] = 3, 0, None, 4
+    assert b"hold is needed" in hh(*worst)
+    assert not out.any() and not st.view(np.uint32).any() and wrong[0].tolist() == (0, 0, 1)
     assert L.mbx_mixdown_held_host(*good) == 0, L.mbx_last_error()
 
     # the launcher: a zeroed stand-in for a state (never reached: no plan can be made without a device, and "no plan" is refused first)

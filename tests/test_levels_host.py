@@ -233,6 +233,18 @@ def test_the_host_functions_are_the_numpy_definition_in_all_three_forms():
         assert L.mbx_mixdown_gated_host(*args) == INVALID, args
         assert b"mbx_mixdown_gated_host" in L.mbx_last_error() and part in L.mbx_last_error(), L.mbx_last_error()
     assert not out.any()
+    # their order: everything wrong at once, then one thing fewer each time -- the gate, the form, the plan's own, the pointers, the rows
+    both = [(3, None, 0, off.ctypes.data, row.ctypes.data, None, None, 4, None, b"gate is needed"),
+            (3, C.addressof(nine), 0, off.ctypes.data, row.ctypes.data, None, None, 4, None, b"MBX_GATE_MAX_LOUDEST"),
+            (3, C.addressof(ok), 0, off.ctypes.data, row.ctypes.data, None, None, 4, None, b"form"),
+            (0, C.addressof(ok), 0, off.ctypes.data, row.ctypes.data, None, None, 4, None, b"n_buses"),
+            (0, C.addressof(ok), 1, off.ctypes.data, row.ctypes.data, None, None, 4, None, b"pcm16 and out"),
+            (0, C.addressof(ok), 1, off.ctypes.data, row.ctypes.data, None, x.ctypes.data, 4, None, b"pcm16 and out"),
+            (0, C.addressof(ok), 1, off.ctypes.data, row.ctypes.data, None, x.ctypes.data, 4, out.ctypes.data, b"nrows")]
+    for *args, part in both:
+        assert L.mbx_mixdown_gated_host(*args) == INVALID, args
+        assert L.mbx_last_error().startswith(b"mbx_mixdown_gated_host: ") and part in L.mbx_last_error(), L.mbx_last_error()
+    assert not out.any()
 
 
 def test_the_launchers_and_the_session_calls_refuse_their_arguments_before_they_ask_for_a_device():

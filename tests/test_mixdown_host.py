@@ -196,6 +196,16 @@ def test_the_host_function_is_the_numpy_definition_in_all_three_forms():
         assert L.mbx_mixdown_host(*args) == INVALID, args
         assert b"mbx_mixdown_host" in L.mbx_last_error() and part in L.mbx_last_error(), L.mbx_last_error()
     assert not out.any()
+    # their order: everything wrong at once, then one thing fewer each time -- the form, the plan's own, the pointers, the rows
+    both = [(3, 0, off.ctypes.data, row.ctypes.data, None, None, 4, None, b"form"),
+            (0, 0, off.ctypes.data, row.ctypes.data, None, None, 4, None, b"n_buses"),
+            (0, 1, off.ctypes.data, row.ctypes.data, None, None, 4, None, b"pcm16 and out"),
+            (0, 1, off.ctypes.data, row.ctypes.data, None, x.ctypes.data, 4, None, b"pcm16 and out"),
+            (0, 1, off.ctypes.data, row.ctypes.data, None, x.ctypes.data, 4, out.ctypes.data, b"nrows")]
+    for *args, part in both:
+        assert L.mbx_mixdown_host(*args) == INVALID, args
+        assert L.mbx_last_error().startswith(b"mbx_mixdown_host: ") and part in L.mbx_last_error(), L.mbx_last_error()
+    assert not out.any()
 
 
 def test_a_plan_is_checked_on_the_host_before_a_device_is_asked_for():
