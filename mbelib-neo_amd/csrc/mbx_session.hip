@@ -18,7 +18,8 @@
 // Host buffers that are pinned (mbx_host_alloc / hipHostMalloc / hipHostRegister) are DMA targets as they are; pageable
 // buffers are staged through pinned memory owned by the slot (one extra host memcpy each way).
 //
-// Host code only; every number is computed by the kernels of mbx_fec.hip / mbx_stream.hip.
+// Host code only; every number is computed by the kernels of mbx_fec.hip / mbx_stream.hip, and every decision that is integers
+// alone -- what a submit is refused for, which buffers a session owns, where a group's bursts lie -- is made in mbx_session_plan.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -42,10 +43,12 @@
 #include "mbx_hold_plan.h"     // (what a hold is refused for, and the plan a state is tied to)
 #include <mbx_mixdown.h>   // (the public header: include/ is first on the include path; "mbx_mixdown.h" would be this directory's)
 #include "mbx_pcm8.h"
+#include "mbx_session_plan.h"
 
 namespace {
 
 constexpr int kDepth = 3;
+static_assert(mbx::kMaxBurstGroups == MBX_BURST_MAX_GROUPS, "mbx_session_plan.h lays out as many groups as a call may have");
 
 #define S_TRY(expr)                        \
     do {                                   \
@@ -65,45 +68,49 @@ bool is_pinned(const void* p) {
     return a.type == hipMemoryTypeHost;
 }
 
-struct CopyOut {   // a staged output still to be handed to the caller's pageable buffer
-    void*       dst = nullptr;
-    const void* src = nullptr;
-    size_t      bytes = 0;
+struct CopyOut { void* dst; const void* src; size_t bytes; };   // a staged output still to be handed to the caller's pageable buffer
+
+// A buffer of a slot, on the device or pinned on the host: made by the first need() and made anew by one that asks for more (the
+// slot's earlier batch is finished: nothing reads the old one).  A need() of the size it has is free.
+template <bool kHost>
+struct Grown {
+    uint8_t* p = nullptr;
+    size_t   cap = 0;
+    int need(size_t bytes) {
+        if (cap >= bytes) {
+            return 0;
+        }
+        release();
+        S_TRY(kHost ? hipHostMalloc(reinterpret_cast<void**>(&p), bytes, hipHostMallocDefault) : hipMalloc(reinterpret_cast<void**>(&p), bytes));
+        cap = bytes;
+        return 0;
+    }
+    void release() {
+        if (p) {
+            (void)(kHost ? hipHostFree(p) : hipFree(p));
+        }
+        p = nullptr;
+        cap = 0;
+    }
 };
+struct Pair { Grown<false> d; Grown<true> h; };   // a device buffer and its pinned staging, the staging made on first need
+
+// The inputs of a slot.  Wire frames and the index words are made with the session.  Soft frames are 368 / 336 / 192 B each against
+// 18 / 9: their device buffer and their staging belong to the slot's first soft submit, so a session that never sees one pays for
+// neither; the keystream rows (include/mbx_keystream.h) likewise to its first keyed submit.  Bursts (hard or soft) belong to the burst
+// submits and grow with them.
+enum In { kInFrames = 0, kInSoft, kInBursts, kInKeystream, kInIndex, kInCount };
 
 struct Slot {
-    uint8_t*            d_frames = nullptr;
-    mbe_soft_bit*       d_soft = nullptr;   // soft frames, allocated (as h_soft) by the slot's first soft submit
-    mbx_param_record*   d_records = nullptr;
-    int16_t*            d_pcm16 = nullptr;
-    float*              d_pcmf = nullptr;
-    mbe_process_result* d_results = nullptr;
-    uint8_t*            d_pcm8 = nullptr;   // companded bytes (include/mbx_pcm8.h): a session created with MBX_SESSION_PCM8
-    uint8_t*            d_mix = nullptr;    // bus rows (include/mbx_mixdown.h), max_frames of 320 B: a session created with MBX_SESSION_MIXDOWN
-    mbx_row_level*      d_levels = nullptr; // level records (include/mbx_levels.h), max_frames of them: a session created with MBX_SESSION_LEVELS
-    int32_t*            d_index = nullptr;
-    void*               d_workspace = nullptr;
-    uint8_t*            d_bursts = nullptr;   // bursts (hard or soft), grown by the burst submits that need more
-    size_t              bursts_cap = 0;
-    uint8_t*            d_keystream = nullptr;   // keystream rows (include/mbx_keystream.h), allocated (as h_keystream) by the slot's first keyed submit
-    // pinned staging, allocated on first need
-    uint8_t*            h_in = nullptr;
-    uint8_t*            h_soft = nullptr;
-    uint8_t*            h_bursts = nullptr;   // ... and their pinned staging
-    size_t              h_bursts_cap = 0;
-    uint8_t*            h_keystream = nullptr;
-    int32_t*            h_index = nullptr;
-    int16_t*            h_pcm16 = nullptr;
-    float*              h_pcmf = nullptr;
-    uint8_t*            h_pcm8 = nullptr;
-    uint8_t*            h_mix = nullptr;
-    mbx_row_level*      h_levels = nullptr;
-    mbe_process_result* h_results = nullptr;
-    mbx_param_record*   h_records = nullptr;
-    hipEvent_t          comp = nullptr, done = nullptr;
-    bool                busy = false;
-    CopyOut             out[7];
-    int                 nout = 0;
+    Pair       in[kInCount];
+    Pair       out[mbx::kOutCount];   // (mbx_session_plan.h: which of them a session owns, and their sizes)
+    void*      d_workspace = nullptr;
+    hipEvent_t comp = nullptr, done = nullptr;
+    bool       busy = false;
+    CopyOut    staged[mbx::kOutCount];
+    int        nout = 0;
+    template <class U> U* din(int which) { return reinterpret_cast<U*>(in[which].d.p); }
+    template <class U> U* dout(int which) { return reinterpret_cast<U*>(out[which].d.p); }
 };
 
 }  // namespace
@@ -135,18 +142,10 @@ int finish_slot(Slot& sl) {   // wait for the slot's batch and hand staged outpu
     }
     S_TRY(hipEventSynchronize(sl.done));
     for (int i = 0; i < sl.nout; ++i) {
-        memcpy(sl.out[i].dst, sl.out[i].src, sl.out[i].bytes);
+        memcpy(sl.staged[i].dst, sl.staged[i].src, sl.staged[i].bytes);
     }
     sl.nout = 0;
     sl.busy = false;
-    return 0;
-}
-
-template <class U>
-int pinned(U*& p, size_t count) {
-    if (!p) {
-        S_TRY(hipHostMalloc(reinterpret_cast<void**>(&p), count * sizeof(U), hipHostMallocDefault));
-    }
     return 0;
 }
 
@@ -186,18 +185,23 @@ void default_parms(mbe_parms& p) {   // ref mbe_initMbeParms, src/core/mbelib.c:
 // by the session's ADDRESS, out of a table beside the sessions: a submit refuses some arguments before it looks at its session, and
 // must not dereference a pointer it has not checked to use the attachment up.
 // mbx_session_next_mixdown (include/mbx_mixdown.h) attaches the buses of a plan in the same way, in the same record: one submit uses both up.
+enum MixKind { kMixPlain = 0, kMixGated, kMixHeld };
 struct NextOut {
-    uint8_t* dst = nullptr;   // host memory, rows * 160 bytes; nullptr: nothing attached
+    void*    dst = nullptr;   // host memory, rows * 160 bytes; nullptr: nothing attached
     int      law = 0;         // MBX_LAW_*
     void*                   buses = nullptr;   // host memory, the plan's buses * 160 samples of `form`; nullptr: nothing attached
     const mbx_mixdown_plan* plan = nullptr;
     int                     form = 0;          // MBX_MIXDOWN_*
-    bool                    gated = false;     // the buses under `gate` (mbx_session_next_mixdown_gated, include/mbx_levels.h): the same slot, whichever call came last
+    // the buses as they are, under `gate` (mbx_session_next_mixdown_gated, include/mbx_levels.h) or under `hold` with the caller's
+    // `state` (mbx_session_next_mixdown_held, include/mbx_hold.h): the same slot, whichever call came last
+    MixKind                 kind = kMixPlain;
     mbx_mixdown_gate        gate = {0, 0};
-    mbx_gate_state*         held = nullptr;    // the buses under `hold` with this state (mbx_session_next_mixdown_held, include/mbx_hold.h): the same slot again
     mbx_mixdown_hold        hold = {0, 0, 0, 0, 0};
-    mbx_row_level*          levels = nullptr;  // host memory, one record per row (mbx_session_next_levels); nullptr: nothing attached
-    bool wants_levels() const { return levels || (buses && (gated || held)); }
+    mbx_gate_state*         state = nullptr;
+    void*                   levels = nullptr;  // host memory, one mbx_row_level per row (mbx_session_next_levels); nullptr: nothing attached
+    bool wants_levels() const { return levels || (buses && kind != kMixPlain); }
+    // the step is handed the slot's int16 rows: for the caller, or for the compand, the levels and the mix-down behind the step
+    bool wants_pcm16(const void* callers) const { return callers || dst || buses || levels; }
 };
 std::mutex g_next_mu;
 std::unordered_map<const mbx_session*, NextOut> g_next;
@@ -213,6 +217,27 @@ NextOut take_next(const mbx_session* s) {
     return out;
 }
 
+// One attach call: a NULL destination clears `field` of what is attached and leaves the rest; else `why` (the call's own checks, which
+// may look at the session) names a refusal or nullptr, and `set` stores into the record.
+template <class Why, class Set>
+int next_attach(const char* who, const mbx_session* s, const void* out, void* NextOut::*field, Why why, Set set) {
+    if (!s) {
+        return mbx::refuse(who, "no session");
+    }
+    if (out) {
+        if (const char* text = why()) {
+            return mbx::refuse(who, text);
+        }
+    }
+    std::lock_guard<std::mutex> lock(g_next_mu);
+    if (out) {
+        set(g_next[s]);
+    } else if (const auto it = g_next.find(s); it != g_next.end()) {
+        it->second.*field = nullptr;
+    }
+    return 0;
+}
+
 bool range_ok(const mbx_session* s, int first, int count) {
     return s && first >= 0 && count >= 0 && (long long)first + count <= s->streams;
 }
@@ -224,106 +249,135 @@ struct BurstIn {
     size_t                    bytes;    // one burst in the input: burst_stride, or mbx_burst_schedule_soft_bytes()
 };
 
-// `soft`: frames are mbe_soft_bit cells (soft_bytes per frame) instead of wire frames (frame_bytes)
-int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst, const uint8_t* keystream, const NextOut& next);
+// One submit, as its public entry point fills it in.  A group submit uses the kind, the outputs and the attachment.
+struct Submit {
+    int            n = 0, T = 0;       // n streams of T frames each
+    const int32_t* index = nullptr;
+    const void*    frames = nullptr;   // wire frames (frame_bytes each); soft: mbe_soft_bit cells (soft_bytes per frame); burst: bursts
+    bool           soft = false;
+    const BurstIn* burst = nullptr;
+    const uint8_t* keystream = nullptr;
+    void*          user[mbx::kOutCount] = {};   // where each output goes: the caller's four, and the three of `next`
+    NextOut        next;                         // taken for this call
+    Submit(const NextOut& nx, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records) : next(nx) {
+        user[mbx::kOutPcm16] = pcm16, user[mbx::kOutPcmf] = pcmf, user[mbx::kOutResults] = results, user[mbx::kOutRecords] = records;
+        user[mbx::kOutPcm8] = nx.dst, user[mbx::kOutMix] = nx.buses, user[mbx::kOutLevels] = nx.levels;
+    }
+    Submit& rows(int n_, int T_, const int32_t* index_, const void* frames_, bool soft_) {
+        n = n_, T = T_, index = index_, frames = frames_, soft = soft_;
+        return *this;
+    }
+};
 
-int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records, const NextOut& next);
-
-// behind the step of a submit of nf frames that has a destination attached: the slot's int16 rows -> its bytes, on the compute stream
-int compand_step(mbx_session* s, Slot& sl, size_t nf, const NextOut& next) {
-    return next.dst ? mbx_pcm_compand(next.law, sl.d_pcm16, nf, sl.d_pcm8, s->s_comp) : 0;
+// what the plan header holds a submit to (s may be NULL: then nothing of it is looked at)
+mbx::SessionShape shape_of(const mbx_session* s, const Submit& c) {
+    mbx::SessionShape sh;
+    sh.session = s != nullptr;
+    if (s) {
+        sh.mixed = s->mixed(), sh.streams = s->streams, sh.max_frames = s->max_frames, sh.flags = s->outputs;
+    }
+    sh.requested = mbx::requested_outputs(c.user[mbx::kOutPcm16], c.user[mbx::kOutPcmf], c.user[mbx::kOutResults]);
+    sh.plan_rows = c.next.buses ? mbx_mixdown_plan_rows(c.next.plan) : 0;   // (every row the plan names must be among the submit's)
+    return sh;
 }
 
-// ... the level records of those rows, once per submit, for the caller or for the gate of its buses or both
-int levels_step(mbx_session* s, Slot& sl, size_t nf, const NextOut& next) {
-    return next.wants_levels() ? mbx_pcm_levels(sl.d_pcm16, nf, sl.d_levels, s->s_comp) : 0;
+// what mbx_session_plan.h says of a submit goes back: nothing to do is 0; a refusal with "<who>: <its text>", or with no text where it has none
+int refused(const char* who, mbx::SessionRefusal why, const Submit& c, size_t rows) {
+    const char* const text = mbx::session_refusal_text(why);
+    if (why == mbx::kSessionRowsShort) {
+        char numbers[200];
+        snprintf(numbers, sizeof(numbers), text, rows, mbx_mixdown_plan_rows(c.next.plan));
+        return mbx::refuse("session", numbers);
+    }
+    return why == mbx::kSessionNothing ? 0 : (text[0] ? mbx::refuse(who, text) : MBE_STATUS_INVALID_ARGUMENT);
 }
 
-// ... and the plan's buses of those rows, nf of them: one or two more launches on the compute stream
-int mixdown_step(mbx_session* s, Slot& sl, size_t nf, const NextOut& next) {
-    if (next.buses && next.held) {
-        return mbx_mixdown_held(next.plan, &next.hold, next.held, next.form, sl.d_pcm16, nf, sl.d_levels, sl.d_mix, s->s_comp);
-    }
-    if (next.buses && next.gated) {
-        return mbx_mixdown_gated(next.plan, &next.gate, next.form, sl.d_pcm16, nf, sl.d_levels, sl.d_mix, s->s_comp);
-    }
-    return next.buses ? mbx_mixdown(next.plan, next.form, sl.d_pcm16, nf, sl.d_mix, s->s_comp) : 0;
-}
-
-// a submit of `rows` rows with buses attached: every row the plan names must be among them, or nothing is queued
-int refuse_rows_short_of_the_plan(const NextOut& next, size_t rows) {
-    if (next.buses && rows < (size_t)mbx_mixdown_plan_rows(next.plan)) {
-        char text[200];
-        snprintf(text, sizeof(text), "session: the submit has %zu rows, the mix-down plan attached to it needs %d (mbx_session_next_mixdown)", rows,
-                 mbx_mixdown_plan_rows(next.plan));
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    return 0;
-}
-
-// a mixed session takes burst groups only
-int refuse_mixed(const mbx_session* s, const char* who) {
-    if (s && s->mixed()) {
-        char text[160];
-        snprintf(text, sizeof(text), "%s: a mixed session takes burst groups only (mbx_session_submit_burst_groups)", who);
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    return 0;
-}
-
-int submit(const NextOut& next, mbx_session* s, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-           mbe_process_result* results, mbx_param_record* records, const BurstIn* burst = nullptr, const uint8_t* keystream = nullptr) {
-    if (refuse_mixed(s, "mbx_session_submit") < 0) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (!s || !frames || n < 0 || T < 0 || n > s->streams || (size_t)n * (size_t)T > s->max_frames) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if ((pcm16 && !(s->outputs & MBX_SESSION_PCM16)) || (pcmf && !(s->outputs & MBX_SESSION_PCMF))
-        || (results && !(s->outputs & MBX_SESSION_RESULTS))) {
-        return MBE_STATUS_INVALID_ARGUMENT;   // an output the session was not created for
-    }
-    if (refuse_rows_short_of_the_plan(next, (size_t)n * (size_t)T) < 0) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (n == 0 || T == 0) {
-        return 0;
-    }
-    if (burst && mbx::burst_shape(burst->sched).llr()) {
-        // every LLR is a valid one: nothing to check
-    } else if (burst) {   // bursts of a form that can be invalid: a bit byte > 1, a dibit > 3, a soft hard decision > 1 (mbx_burst_validate)
-        const int rc = mbx_burst_validate(burst->sched, frames, burst->stride, (size_t)n, soft ? 1 : 0);
-        if (rc < 0) {
+// Host bytes to a device address.  They are fetched by a kernel on the COMPUTE stream, not by a DMA copy: see stage_in_kernel
+// (mbx_fec.hip).  Pinned 16-byte aligned bytes are read in place; others -- pageable, or pinned and not aligned -- go through the
+// buffer's pinned staging (`room` bytes of it, made here on first need) at the offset `at` they have on the device.
+int carry_in(mbx_session* s, Pair& buf, size_t at, const void* host, size_t bytes, size_t room) {
+    const uint8_t* src = static_cast<const uint8_t*>(host);
+    if (!is_pinned(src) || !mbx::aligned_to(src, 16)) {
+        if (const int rc = buf.h.need(room); rc < 0) {
             return rc;
         }
-    } else if (soft) {   // a hard decision > 1 is refused before anything is queued (ref mbe_validate_soft_bits, src/internal/mbe_result.h:31-42)
-        const int rc = mbx_validate_soft_bits(static_cast<const mbe_soft_bit*>(frames), (size_t)n * (size_t)T * (s->soft_bytes / sizeof(mbe_soft_bit)));
-        if (rc < 0) {
-            return rc;
-        }
+        memcpy(buf.h.p + at, src, bytes);
+        src = buf.h.p + at;
     }
-    if (index) {   // every row must name its own stream: two rows on one stream would race on its state
-        s->seen.assign((size_t)s->streams, 0);
-        for (int i = 0; i < n; ++i) {
-            if (index[i] < 0 || index[i] >= s->streams || s->seen[(size_t)index[i]]) {
-                mbx_set_error_text("session: stream index out of range or listed twice");
-                return MBE_STATUS_INVALID_ARGUMENT;
+    const void* dev_view = src;   // what the GPU dereferences: the same address for hipHostMalloc memory, possibly another one for
+    void* mapped = nullptr;       // memory the host registered itself (hipHostRegister)
+    if (hipHostGetDevicePointer(&mapped, const_cast<uint8_t*>(src), 0) == hipSuccess && mapped) {
+        dev_view = mapped;
+    } else {
+        (void)hipGetLastError();
+    }
+    return mbx_stage_in(buf.d.p + at, dev_view, bytes, s->s_comp);
+}
+
+// ---- out ----: behind the compute stream's launches of a submit of nf frames, the outputs to the caller (or to the slot's staging,
+// made on the output's first pageable destination)
+int copy_out(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
+    S_TRY(hipEventRecord(sl.comp, s->s_comp));
+    S_TRY(hipStreamWaitEvent(s->s_out, sl.comp, 0));
+    sl.nout = 0;
+    const size_t buses = c.next.buses ? (size_t)mbx_mixdown_plan_buses(c.next.plan) : 0;
+    for (int k = 0; k < mbx::kOutCount; ++k) {
+        if (!c.user[k]) {
+            continue;
+        }
+        const size_t bytes = mbx::out_bytes(k, nf, buses, c.next.form);
+        void* dst = c.user[k];
+        if (!is_pinned(dst)) {
+            if (const int rc = sl.out[k].h.need(mbx::out_capacity(k, s->max_frames)); rc < 0) {
+                return rc;
             }
-            s->seen[(size_t)index[i]] = 1;
+            dst = sl.out[k].h.p;
+            sl.staged[sl.nout++] = CopyOut{c.user[k], dst, bytes};
+        }
+        const hipError_t e = hipMemcpyAsync(dst, sl.out[k].d.p, bytes, hipMemcpyDeviceToHost, s->s_out);
+        if (e != hipSuccess) {
+            return mbx::hip_failed("session: ", "hipMemcpyAsync (device to host)", e);
         }
     }
+    S_TRY(hipEventRecord(sl.done, s->s_out));
+    return 0;
+}
+
+// Behind the step of a submit of nf frames, on the compute stream: the slot's int16 rows -> companded bytes where a destination is
+// attached; their level records, once per submit, for the caller or for the gate of its buses or both; the plan's buses of those rows
+// (one or two more launches); then the outputs out.
+int behind_step(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
+    const NextOut& next = c.next;
+    const int16_t* const d16 = sl.dout<int16_t>(mbx::kOutPcm16);
+    mbx_row_level* const dlev = sl.dout<mbx_row_level>(mbx::kOutLevels);
+    uint8_t* const dmix = sl.dout<uint8_t>(mbx::kOutMix);
+    int rc = 0;
+    if ((next.dst && (rc = mbx_pcm_compand(next.law, d16, nf, sl.dout<uint8_t>(mbx::kOutPcm8), s->s_comp)) < 0)
+        || (next.wants_levels() && (rc = mbx_pcm_levels(d16, nf, dlev, s->s_comp)) < 0)) {
+        return rc;
+    }
+    if (next.buses && next.kind == kMixHeld) {
+        rc = mbx_mixdown_held(next.plan, &next.hold, next.state, next.form, d16, nf, dlev, dmix, s->s_comp);
+    } else if (next.buses && next.kind == kMixGated) {
+        rc = mbx_mixdown_gated(next.plan, &next.gate, next.form, d16, nf, dlev, dmix, s->s_comp);
+    } else if (next.buses) {
+        rc = mbx_mixdown(next.plan, next.form, d16, nf, dmix, s->s_comp);
+    }
+    return rc < 0 ? rc : copy_out(s, sl, c, nf);
+}
+
+// The slot of the next batch, with the batch that used it kDepth submissions ago finished, and `enqueue` run on it.  From there on
+// work is queued on the two streams against this slot's buffers.  If anything fails halfway the slot is NOT marked busy, so before
+// the error goes back the streams are drained: the next submit may reuse the slot at once.
+template <class Enqueue>
+int on_next_slot(mbx_session* s, Enqueue enqueue) {
     DeviceGuard guard(s->device);
     Slot& sl = s->slot[s->submitted % kDepth];
-    int rc = finish_slot(sl);   // the batch that used this slot kDepth submissions ago
+    int rc = finish_slot(sl);
     if (rc < 0) {
         return rc;
     }
-    // From here on work is queued on the three streams against this slot's buffers.  If anything fails halfway the slot is
-    // NOT marked busy, so before the error goes back the streams are drained: the next submit may reuse the slot at once.
-    rc = enqueue(s, sl, n, T, index, frames, soft, pcm16, pcmf, results, records, burst, keystream, next);
+    rc = enqueue(sl);
     if (rc < 0) {
         (void)hipStreamSynchronize(s->s_comp);
         (void)hipStreamSynchronize(s->s_out);
@@ -336,164 +390,88 @@ int submit(const NextOut& next, mbx_session* s, int n, int T, const int32_t* ind
     return 0;
 }
 
-int enqueue(mbx_session* s, Slot& sl, int n, int T, const int32_t* index, const void* frames, bool soft, int16_t* pcm16, float* pcmf,
-            mbe_process_result* results, mbx_param_record* records, const BurstIn* burst, const uint8_t* keystream, const NextOut& next) {
-    int rc = 0;
-    const size_t nf = (size_t)n * (size_t)T;
-    // ---- in ----
-    // Soft frames are 368 / 336 / 192 B each against 18 / 9: their device buffer and their pinned staging belong to the slot's
-    // first soft submit, so a session that never sees one pays for neither.  Bursts likewise: their buffers belong to the burst
-    // submits and grow with them (the slot's earlier batch is finished: nothing reads the old ones).
+int enqueue(mbx_session* s, Slot& sl, const Submit& c) {
+    const int      n = c.n, T = c.T;
+    const bool     soft = c.soft;
+    const BurstIn* burst = c.burst;
+    const size_t   nf = (size_t)n * (size_t)T;
+    // ---- in ----: the frames or bursts, the stream index, the keystream rows
     const size_t in_bytes = soft ? s->soft_bytes : s->frame_bytes;
     const size_t in_total = burst ? (size_t)n * burst->bytes : nf * in_bytes;
-    uint8_t*& stage = burst ? sl.h_bursts : (soft ? sl.h_soft : sl.h_in);
-    if (burst && sl.bursts_cap < in_total) {
-        (void)hipFree(sl.d_bursts);
-        sl.d_bursts = nullptr;
-        sl.bursts_cap = 0;
-        S_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_bursts), in_total));
-        sl.bursts_cap = in_total;
-    }
-    if (!burst && soft && !sl.d_soft) {
-        S_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_soft), s->max_frames * s->soft_bytes));
-    }
-    const uint8_t* src = static_cast<const uint8_t*>(frames);
-    // The frames (and the stream index) are fetched by a kernel on the COMPUTE stream, not by a DMA copy: see stage_in_kernel
-    // (mbx_fec.hip).  A pinned buffer that is not 16-byte aligned goes through the slot's own pinned staging like a pageable one.
-    if (!is_pinned(frames) || (reinterpret_cast<uintptr_t>(src) & 15u)) {
-        if (burst) {
-            if (sl.h_bursts_cap < in_total) {
-                (void)hipHostFree(sl.h_bursts);
-                sl.h_bursts = nullptr;
-                sl.h_bursts_cap = 0;
-                S_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.h_bursts), in_total, hipHostMallocDefault));
-                sl.h_bursts_cap = in_total;
-            }
-        } else {
-            rc = pinned(stage, s->max_frames * in_bytes);
-            if (rc < 0) {
-                return rc;
-            }
-        }
-        memcpy(stage, frames, in_total);
-        src = stage;
-    }
-    const void* dev_view = src;   // what the GPU dereferences: the same address for hipHostMalloc memory, possibly another one for
-    void* mapped = nullptr;       // memory the host registered itself (hipHostRegister)
-    if (hipHostGetDevicePointer(&mapped, const_cast<uint8_t*>(src), 0) == hipSuccess && mapped) {
-        dev_view = mapped;
-    } else {
-        (void)hipGetLastError();
-    }
-    void* const d_in = burst ? static_cast<void*>(sl.d_bursts) : (soft ? static_cast<void*>(sl.d_soft) : static_cast<void*>(sl.d_frames));
-    rc = mbx_stage_in(d_in, dev_view, in_total, s->s_comp);
-    if (rc < 0) {
+    const size_t in_room = burst ? in_total : s->max_frames * in_bytes;
+    Pair& in = sl.in[burst ? kInBursts : (soft ? kInSoft : kInFrames)];
+    int rc = 0;
+    if ((rc = in.d.need(in_room)) < 0 || (rc = carry_in(s, in, 0, c.frames, in_total, in_room)) < 0) {
         return rc;
     }
-    if (index) {
-        rc = pinned(sl.h_index, (size_t)s->streams);   // always staged: 4 B per stream, and the caller may reuse its array at once
-        if (rc < 0) {
+    int32_t* const d_index = c.index ? sl.din<int32_t>(kInIndex) : nullptr;
+    if (c.index) {   // always staged: 4 B per stream, and the caller may reuse its array at once
+        Grown<true>& h_index = sl.in[kInIndex].h;
+        if ((rc = h_index.need((size_t)s->streams * sizeof(int32_t))) < 0) {
             return rc;
         }
-        memcpy(sl.h_index, index, (size_t)n * sizeof(int32_t));
-        rc = mbx_stage_in(sl.d_index, sl.h_index, (size_t)n * sizeof(int32_t), s->s_comp);
-        if (rc < 0) {
+        memcpy(h_index.p, c.index, (size_t)n * sizeof(int32_t));
+        if ((rc = mbx_stage_in(d_index, h_index.p, (size_t)n * sizeof(int32_t), s->s_comp)) < 0) {
             return rc;
         }
     }
-    if (keystream) {   // the keystream rows take the road the frames take: pinned 16-byte aligned rows in place, others staged
-        const size_t ks_total = nf * (size_t)MBX_KEYSTREAM_ROW_BYTES;
-        if (!sl.d_keystream) {
-            S_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_keystream), s->max_frames * (size_t)MBX_KEYSTREAM_ROW_BYTES));
-        }
-        const uint8_t* ks = keystream;
-        if (!is_pinned(keystream) || (reinterpret_cast<uintptr_t>(ks) & 15u)) {
-            rc = pinned(sl.h_keystream, s->max_frames * (size_t)MBX_KEYSTREAM_ROW_BYTES);
-            if (rc < 0) {
-                return rc;
-            }
-            memcpy(sl.h_keystream, keystream, ks_total);
-            ks = sl.h_keystream;
-        }
-        const void* ks_view = ks;
-        void* ks_mapped = nullptr;
-        if (hipHostGetDevicePointer(&ks_mapped, const_cast<uint8_t*>(ks), 0) == hipSuccess && ks_mapped) {
-            ks_view = ks_mapped;
-        } else {
-            (void)hipGetLastError();
-        }
-        rc = mbx_stage_in(sl.d_keystream, ks_view, ks_total, s->s_comp);
-        if (rc < 0) {
+    if (c.keystream) {   // the keystream rows take the road the frames take
+        const size_t ks_room = s->max_frames * (size_t)MBX_KEYSTREAM_ROW_BYTES;
+        Pair& ks = sl.in[kInKeystream];
+        if ((rc = ks.d.need(ks_room)) < 0 || (rc = carry_in(s, ks, 0, c.keystream, nf * (size_t)MBX_KEYSTREAM_ROW_BYTES, ks_room)) < 0) {
             return rc;
         }
     }
     // ---- compute ----
-    int16_t* d16 = pcm16 || next.dst || next.buses || next.levels ? sl.d_pcm16 : nullptr;   // (the compand, the levels and the mix-down behind the step read the int16 rows)
-    float*   dfl = pcmf ? sl.d_pcmf : nullptr;
-    mbe_process_result* dres = results ? sl.d_results : nullptr;
-    if (keystream) {   // the keyed call takes every form: hard or soft, index or none, resident words or plain triplets
-        rc = mbx_process_batch_keyed(s->codec, n, T, index ? sl.d_index : nullptr, soft ? nullptr : sl.d_frames, soft ? sl.d_soft : nullptr,
-                                     sl.d_keystream, s->d_state, s->d_resident, s->d_rng, d16, dfl, dres, sl.d_records, s->s_comp);
+    int16_t* d16 = c.next.wants_pcm16(c.user[mbx::kOutPcm16]) ? sl.dout<int16_t>(mbx::kOutPcm16) : nullptr;
+    float*   dfl = c.user[mbx::kOutPcmf] ? sl.dout<float>(mbx::kOutPcmf) : nullptr;
+    mbe_process_result* dres = c.user[mbx::kOutResults] ? sl.dout<mbe_process_result>(mbx::kOutResults) : nullptr;
+    mbx_param_record* const drec = sl.dout<mbx_param_record>(mbx::kOutRecords);
+    uint8_t* const      d_frames = sl.din<uint8_t>(kInFrames);
+    mbe_soft_bit* const d_soft = sl.din<mbe_soft_bit>(kInSoft);
+    if (c.keystream) {   // the keyed call takes every form: hard or soft, index or none, resident words or plain triplets
+        rc = mbx_process_batch_keyed(s->codec, n, T, d_index, soft ? nullptr : d_frames, soft ? d_soft : nullptr, sl.din<uint8_t>(kInKeystream),
+                                     s->d_state, s->d_resident, s->d_rng, d16, dfl, dres, drec, s->s_comp);
     } else if (burst && soft) {   // the gather in front of the step the frames submits run: resident words or plain triplets, index or none
-        rc = mbx_process_bursts_soft(burst->sched, n, index ? sl.d_index : nullptr, reinterpret_cast<const mbe_soft_bit*>(sl.d_bursts), s->d_state,
-                                     s->d_resident, s->d_rng, d16, dfl, dres, sl.d_records, s->s_comp);
+        rc = mbx_process_bursts_soft(burst->sched, n, d_index, sl.din<mbe_soft_bit>(kInBursts), s->d_state, s->d_resident, s->d_rng, d16, dfl, dres,
+                                     drec, s->s_comp);
     } else if (burst) {
-        rc = mbx_process_bursts(burst->sched, n, index ? sl.d_index : nullptr, sl.d_bursts, burst->stride, s->d_state, s->d_resident, s->d_rng, d16,
-                                dfl, dres, sl.d_records, s->s_comp);
+        rc = mbx_process_bursts(burst->sched, n, d_index, sl.din<uint8_t>(kInBursts), burst->stride, s->d_state, s->d_resident, s->d_rng, d16, dfl,
+                                dres, drec, s->s_comp);
     } else if (soft) {   // the soft twin of the resident launcher takes every form: index or none, resident words or plain triplets
-        rc = mbx_process_batch_soft_resident(s->codec, n, T, index ? sl.d_index : nullptr, sl.d_soft, s->d_state, s->d_resident, s->d_rng,
-                                             d16, dfl, dres, sl.d_records, s->s_comp);
+        rc = mbx_process_batch_soft_resident(s->codec, n, T, d_index, d_soft, s->d_state, s->d_resident, s->d_rng, d16, dfl, dres, drec, s->s_comp);
     } else if (s->d_resident) {   // the session owns the state between submits: the resident form (no prev_mp_enhanced traffic, lazy prev_mp)
-        rc = mbx_process_batch_resident(s->codec, n, T, index ? sl.d_index : nullptr, sl.d_frames, s->d_state, s->d_resident, s->d_rng,
-                                        d16, dfl, dres, sl.d_records, s->s_comp);
-    } else if (index) {
-        rc = mbx_process_batch_indexed(s->codec, n, T, sl.d_index, sl.d_frames, s->d_state, s->d_rng, d16, dfl, dres, sl.d_records,
-                                       s->s_comp);
+        rc = mbx_process_batch_resident(s->codec, n, T, d_index, d_frames, s->d_state, s->d_resident, s->d_rng, d16, dfl, dres, drec, s->s_comp);
+    } else if (c.index) {
+        rc = mbx_process_batch_indexed(s->codec, n, T, d_index, d_frames, s->d_state, s->d_rng, d16, dfl, dres, drec, s->s_comp);
     } else {
-        rc = mbx_process_batch_ws(s->codec, n, T, sl.d_frames, s->d_state, s->d_rng, d16, dfl, dres, sl.d_records, sl.d_workspace,
+        rc = mbx_process_batch_ws(s->codec, n, T, d_frames, s->d_state, s->d_rng, d16, dfl, dres, drec, sl.d_workspace,
                                   mbx_workspace_bytes(s->max_frames), s->s_comp);
     }
-    if (rc < 0 || (rc = compand_step(s, sl, nf, next)) < 0 || (rc = levels_step(s, sl, nf, next)) < 0 || (rc = mixdown_step(s, sl, nf, next)) < 0) {
-        return rc;
-    }
-    return copy_out(s, sl, nf, pcm16, pcmf, results, records, next);
+    return rc < 0 ? rc : behind_step(s, sl, c, nf);
 }
 
-// ---- out ----: behind the compute stream's launches of a submit of nf frames, the outputs to the caller (or to the slot's staging)
-int copy_out(mbx_session* s, Slot& sl, size_t nf, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records, const NextOut& next) {
+int submit(mbx_session* s, const Submit& c) {
+    const mbx::SessionRefusal why = mbx::frames_submit_refused(shape_of(s, c), c.frames != nullptr, c.n, c.T);
+    if (why != mbx::kSessionOk) {
+        return refused("mbx_session_submit", why, c, (size_t)c.n * (size_t)c.T);
+    }
     int rc = 0;
-    S_TRY(hipEventRecord(sl.comp, s->s_comp));
-    S_TRY(hipStreamWaitEvent(s->s_out, sl.comp, 0));
-    sl.nout = 0;
-    // per_frame elements of *stage per row (the staging, made on first need, holds most_per_frame); rows: nf, but the buses of a mix-down
-    // plan (at most max_frames of them)
-    auto out = [&](void* user, const void* dev, auto*& stage, size_t per_frame, size_t rows, size_t most_per_frame) -> int {
-        if (!user) {
-            return 0;
-        }
-        const size_t bytes = rows * per_frame * sizeof(*stage);
-        void* dst = user;
-        if (!is_pinned(user)) {
-            int r = pinned(stage, s->max_frames * most_per_frame);
-            if (r < 0) {
-                return r;
-            }
-            dst = stage;
-            sl.out[sl.nout++] = CopyOut{user, stage, bytes};
-        }
-        hipError_t e = hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, s->s_out);
-        return e == hipSuccess ? 0 : mbx::hip_failed("session: ", "hipMemcpyAsync (device to host)", e);
-    };
-    const size_t buses = next.buses ? (size_t)mbx_mixdown_plan_buses(next.plan) : 0;
-    if ((rc = out(pcm16, sl.d_pcm16, sl.h_pcm16, 160, nf, 160)) < 0 || (rc = out(pcmf, sl.d_pcmf, sl.h_pcmf, 160, nf, 160)) < 0
-        || (rc = out(results, sl.d_results, sl.h_results, 1, nf, 1)) < 0 || (rc = out(records, sl.d_records, sl.h_records, 1, nf, 1)) < 0
-        || (rc = out(next.dst, sl.d_pcm8, sl.h_pcm8, 160, nf, 160)) < 0
-        || (rc = out(next.buses, sl.d_mix, sl.h_mix, next.form == MBX_MIXDOWN_PCM16 ? 320 : 160, buses, 320)) < 0
-        || (rc = out(next.levels, sl.d_levels, sl.h_levels, 1, nf, 1)) < 0) {
+    if (c.burst) {   // bursts of a form that can be invalid: a bit byte > 1, a dibit > 3, a soft hard decision > 1 (mbx_burst_validate); every LLR is a valid one
+        rc = mbx::burst_shape(c.burst->sched).llr() ? 0 : mbx_burst_validate(c.burst->sched, c.frames, c.burst->stride, (size_t)c.n, c.soft ? 1 : 0);
+    } else if (c.soft) {   // a hard decision > 1 is refused before anything is queued (ref mbe_validate_soft_bits, src/internal/mbe_result.h:31-42)
+        rc = mbx_validate_soft_bits(static_cast<const mbe_soft_bit*>(c.frames), (size_t)c.n * (size_t)c.T * (s->soft_bytes / sizeof(mbe_soft_bit)));
+    }
+    if (rc < 0) {
         return rc;
     }
-    S_TRY(hipEventRecord(sl.done, s->s_out));
-    return 0;
+    if (c.index) {
+        s->seen.assign((size_t)s->streams, 0);
+        if (mbx::mark_streams(s->seen.data(), s->streams, c.index, c.n) != mbx::kSessionOk) {
+            return refused("session", mbx::kSessionIndex, c, 0);
+        }
+    }
+    return on_next_slot(s, [&](Slot& sl) { return enqueue(s, sl, c); });
 }
 
 }  // namespace
@@ -511,6 +489,40 @@ void mbx_host_free(void* p) {
     }
 }
 
+// the device side of a new session whose sizes are set: state, streams, the slots' buffers and events, the streams' state at its defaults
+static int session_buffers(mbx_session* s) {
+    const size_t streams = (size_t)s->streams, mf = s->max_frames;
+    S_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_state), streams * 3 * sizeof(mbe_parms)));
+    S_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_rng), streams * sizeof(mbx_stream_rng)));
+    if (!getenv("MBX_SESSION_ABI_STATE")) {   // (development switch: keep the ABI triplets whole after every submit, for A/B timing)
+        S_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_resident), streams * sizeof(uint32_t)));
+        S_TRY(hipMemset(s->d_resident, 0, streams * sizeof(uint32_t)));
+    }
+    S_TRY(hipStreamCreateWithFlags(&s->s_comp, hipStreamNonBlocking));
+    S_TRY(hipStreamCreateWithFlags(&s->s_out, hipStreamNonBlocking));
+    int rc = 0;
+    for (Slot& sl : s->slot) {
+        if ((rc = sl.in[kInFrames].d.need(mf * s->frame_bytes)) < 0 || (rc = sl.in[kInIndex].d.need(streams * sizeof(int32_t))) < 0) {
+            return rc;
+        }
+        if (!s->d_resident) {   // (the resident entry point uses the workspace the launcher keeps for the compute stream, reserved below)
+            S_TRY(hipMalloc(&sl.d_workspace, mbx_workspace_bytes(mf)));
+        }
+        for (int k = 0; k < mbx::kOutCount; ++k) {
+            if (mbx::out_owned(k, s->outputs) && (rc = sl.out[k].d.need(mbx::out_capacity(k, mf))) < 0) {
+                return rc;
+            }
+        }
+        S_TRY(hipEventCreateWithFlags(&sl.comp, hipEventDisableTiming));
+        // (a blocking wait -- hipEventBlockingSync -- was measured here and costs more than it saves: the wake-up latency of every
+        // submit that has to wait is exposed, 155 -> 113 M frames/s with two session threads, 117 -> 78 M with four)
+        S_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
+    }
+    // the indexed launches size the compute stream's own workspace once, here, not in the first submit
+    rc = mbx_reserve_stream(s->s_comp, mf);
+    return rc < 0 ? rc : mbx_session_reset(s, 0, s->streams);
+}
+
 // (stream_codec: a mixed session -- `codec` is then none (-1), and the slot buffers are sized for mixed rows)
 static int create_session(mbx_session** out, int codec, const uint8_t* stream_codec, int streams, size_t max_frames_per_submit, unsigned outputs) {
     const mbx::CodecShape* shape = mbx::codec_shape(codec);
@@ -520,8 +532,7 @@ static int create_session(mbx_session** out, int codec, const uint8_t* stream_co
     }
     for (int i = 0; stream_codec && i < streams; ++i) {
         if (!mbx::codec_shape(stream_codec[i])) {
-            mbx_set_error_text("mbx_session_create_mixed: a stream_codec byte is not one of MBX_CODEC_*");
-            return MBE_STATUS_INVALID_ARGUMENT;
+            return mbx::refuse("mbx_session_create_mixed", "a stream_codec byte is not one of MBX_CODEC_*");
         }
     }
     int dev = -1;
@@ -545,65 +556,12 @@ static int create_session(mbx_session** out, int codec, const uint8_t* stream_co
         s->stream_codec.assign(stream_codec, stream_codec + streams);
     }
     *out = s;
-    auto bail = [&](int rc) {
+    const int rc = session_buffers(s);
+    if (rc < 0) {
         mbx_session_destroy(s);
         *out = nullptr;
-        return rc;
-    };
-#define C_TRY(expr)                          \
-    do {                                     \
-        hipError_t e_ = (expr);              \
-        if (e_ != hipSuccess) {              \
-            return bail(mbx::hip_failed("session: ", #expr, e_));   \
-        }                                    \
-    } while (0)
-    C_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_state), (size_t)streams * 3 * sizeof(mbe_parms)));
-    C_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_rng), (size_t)streams * sizeof(mbx_stream_rng)));
-    if (!getenv("MBX_SESSION_ABI_STATE")) {   // (development switch: keep the ABI triplets whole after every submit, for A/B timing)
-        C_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_resident), (size_t)streams * sizeof(uint32_t)));
-        C_TRY(hipMemset(s->d_resident, 0, (size_t)streams * sizeof(uint32_t)));
     }
-    C_TRY(hipStreamCreateWithFlags(&s->s_comp, hipStreamNonBlocking));
-    C_TRY(hipStreamCreateWithFlags(&s->s_out, hipStreamNonBlocking));
-    const size_t mf = s->max_frames;
-    for (Slot& sl : s->slot) {
-        C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_frames), mf * s->frame_bytes));
-        C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_records), mf * sizeof(mbx_param_record)));
-        C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_index), (size_t)streams * sizeof(int32_t)));
-        if (!s->d_resident) {   // (the resident entry point uses the workspace the launcher keeps for the compute stream, reserved below)
-            C_TRY(hipMalloc(&sl.d_workspace, mbx_workspace_bytes(mf)));
-        }
-        if (s->outputs & (MBX_SESSION_PCM16 | MBX_SESSION_PCM8 | MBX_SESSION_MIXDOWN | MBX_SESSION_LEVELS)) {   // (the step writes int16; the compand, the mix-down and the levels read it)
-            C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_pcm16), mf * 160 * sizeof(int16_t)));
-        }
-        if (s->outputs & MBX_SESSION_PCM8) {
-            C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_pcm8), mf * 160));
-        }
-        if (s->outputs & MBX_SESSION_MIXDOWN) {
-            C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_mix), mf * 160 * sizeof(int16_t)));
-        }
-        if (s->outputs & MBX_SESSION_LEVELS) {
-            C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_levels), mf * sizeof(mbx_row_level)));
-        }
-        if (s->outputs & MBX_SESSION_PCMF) {
-            C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_pcmf), mf * 160 * sizeof(float)));
-        }
-        if (s->outputs & MBX_SESSION_RESULTS) {
-            C_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_results), mf * sizeof(mbe_process_result)));
-        }
-        C_TRY(hipEventCreateWithFlags(&sl.comp, hipEventDisableTiming));
-        // (a blocking wait -- hipEventBlockingSync -- was measured here and costs more than it saves: the wake-up latency of every
-        // submit that has to wait is exposed, 155 -> 113 M frames/s with two session threads, 117 -> 78 M with four)
-        C_TRY(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    }
-#undef C_TRY
-    // the indexed launches size the compute stream's own workspace once, here, not in the first submit
-    int rc = mbx_reserve_stream(s->s_comp, mf);
-    if (rc < 0) {
-        return bail(rc);
-    }
-    rc = mbx_session_reset(s, 0, streams);
-    return rc < 0 ? bail(rc) : 0;
+    return rc;
 }
 
 int mbx_session_create(mbx_session** out, int codec, int streams, size_t max_frames_per_submit, unsigned outputs) {
@@ -612,8 +570,7 @@ int mbx_session_create(mbx_session** out, int codec, int streams, size_t max_fra
 
 int mbx_session_create_mixed(mbx_session** out, int streams, const uint8_t* stream_codec, size_t max_frames_per_submit, unsigned outputs) {
     if (!stream_codec) {
-        mbx_set_error_text("mbx_session_create_mixed: stream_codec is NULL");
-        return MBE_STATUS_INVALID_ARGUMENT;
+        return mbx::refuse("mbx_session_create_mixed", "stream_codec is NULL");
     }
     return create_session(out, -1, stream_codec, streams, max_frames_per_submit, outputs);
 }
@@ -632,31 +589,13 @@ int mbx_session_destroy(mbx_session* s) {
         (void)hipStreamSynchronize(s->s_out);
     }
     for (Slot& sl : s->slot) {
-        (void)hipFree(sl.d_frames);
-        (void)hipFree(sl.d_soft);
-        (void)hipFree(sl.d_records);
-        (void)hipFree(sl.d_pcm16);
-        (void)hipFree(sl.d_pcmf);
-        (void)hipFree(sl.d_results);
-        (void)hipFree(sl.d_pcm8);
-        (void)hipFree(sl.d_mix);
-        (void)hipFree(sl.d_levels);
-        (void)hipFree(sl.d_index);
+        for (Pair& b : sl.in) {
+            b.d.release(), b.h.release();
+        }
+        for (Pair& b : sl.out) {
+            b.d.release(), b.h.release();
+        }
         (void)hipFree(sl.d_workspace);
-        (void)hipFree(sl.d_bursts);
-        (void)hipFree(sl.d_keystream);
-        (void)hipHostFree(sl.h_keystream);
-        (void)hipHostFree(sl.h_bursts);
-        (void)hipHostFree(sl.h_in);
-        (void)hipHostFree(sl.h_soft);
-        (void)hipHostFree(sl.h_index);
-        (void)hipHostFree(sl.h_pcm16);
-        (void)hipHostFree(sl.h_pcmf);
-        (void)hipHostFree(sl.h_pcm8);
-        (void)hipHostFree(sl.h_mix);
-        (void)hipHostFree(sl.h_levels);
-        (void)hipHostFree(sl.h_results);
-        (void)hipHostFree(sl.h_records);
         if (sl.comp) {
             (void)hipEventDestroy(sl.comp);
         }
@@ -777,356 +716,234 @@ int mbx_session_seed(mbx_session* s, int first, int count, const uint32_t* seeds
 }
 
 int mbx_session_submit(mbx_session* s, int T, const uint8_t* frames, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
-    return submit(take_next(s), s, s ? s->streams : 0, T, nullptr, frames, false, pcm16, pcmf, results, nullptr);
+    return submit(s, Submit(take_next(s), pcm16, pcmf, results, nullptr).rows(s ? s->streams : 0, T, nullptr, frames, false));
 }
 
 int mbx_session_submit_indexed(mbx_session* s, int n, int T, const int32_t* stream_index, const uint8_t* frames, int16_t* pcm16,
                                float* pcmf, mbe_process_result* results, mbx_param_record* records) {
-    const NextOut next = take_next(s);
-    if (!stream_index) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    return submit(next, s, n, T, stream_index, frames, false, pcm16, pcmf, results, records);
+    Submit c(take_next(s), pcm16, pcmf, results, records);
+    return stream_index ? submit(s, c.rows(n, T, stream_index, frames, false)) : MBE_STATUS_INVALID_ARGUMENT;
 }
 
 int mbx_session_submit_soft(mbx_session* s, int T, const mbe_soft_bit* soft, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
-    return submit(take_next(s), s, s ? s->streams : 0, T, nullptr, soft, true, pcm16, pcmf, results, nullptr);
+    return submit(s, Submit(take_next(s), pcm16, pcmf, results, nullptr).rows(s ? s->streams : 0, T, nullptr, soft, true));
 }
 
 int mbx_session_submit_soft_indexed(mbx_session* s, int n, int T, const int32_t* stream_index, const mbe_soft_bit* soft, int16_t* pcm16,
                                     float* pcmf, mbe_process_result* results, mbx_param_record* records) {
-    const NextOut next = take_next(s);
-    if (!stream_index) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    return submit(next, s, n, T, stream_index, soft, true, pcm16, pcmf, results, records);
+    Submit c(take_next(s), pcm16, pcmf, results, records);
+    return stream_index ? submit(s, c.rows(n, T, stream_index, soft, true)) : MBE_STATUS_INVALID_ARGUMENT;
 }
 
 // ---- companded bytes out (include/mbx_pcm8.h): the destination of the next submit ----------------------------------------------------
 int mbx_session_next_pcm8(mbx_session* s, int law, uint8_t* pcm8) {
-    if (!s) {
-        mbx_set_error_text("mbx_session_next_pcm8: no session");
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (!pcm8) {
-        std::lock_guard<std::mutex> lock(g_next_mu);
-        const auto it = g_next.find(s);
-        if (it != g_next.end()) {
-            it->second.dst = nullptr;   // (buses attached beside it stay)
+    const auto why = [&]() -> const char* {
+        if (!(s->outputs & MBX_SESSION_PCM8)) {
+            return "the session was created without MBX_SESSION_PCM8";
         }
-        return 0;
-    }
-    if (!(s->outputs & MBX_SESSION_PCM8)) {
-        mbx_set_error_text("mbx_session_next_pcm8: the session was created without MBX_SESSION_PCM8");
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (law != MBX_LAW_ULAW && law != MBX_LAW_ALAW) {
-        mbx_set_error_text("mbx_session_next_pcm8: law is MBX_LAW_ULAW or MBX_LAW_ALAW");
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    std::lock_guard<std::mutex> lock(g_next_mu);
-    NextOut& next = g_next[s];
-    next.dst = pcm8;
-    next.law = law;
-    return 0;
+        return law != MBX_LAW_ULAW && law != MBX_LAW_ALAW ? "law is MBX_LAW_ULAW or MBX_LAW_ALAW" : nullptr;
+    };
+    return next_attach("mbx_session_next_pcm8", s, pcm8, &NextOut::dst, why, [&](NextOut& next) { next.dst = pcm8, next.law = law; });
 }
 
 // ---- mix-down out (include/mbx_mixdown.h): the buses of the next submit -----------------------------------------------------------------
-// (gate: the gated call of include/mbx_levels.h, which shares the buses slot of the record; nullptr: mbx_session_next_mixdown itself.
-// held: the held call of include/mbx_hold.h, the same slot again, with its hold and its state)
-static int next_mixdown(const char* who, mbx_session* s, const mbx_mixdown_plan* plan, int form, const mbx_mixdown_gate* gate, bool gated, void* out,
-                        bool held = false, const mbx_mixdown_hold* hold = nullptr, mbx_gate_state* state = nullptr) {
-    const auto refused = [who](const char* why) {
-        char text[200];
-        snprintf(text, sizeof(text), "%s: %s", who, why);
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
+// how the buses are attached: as they are (mbx_session_next_mixdown), under a gate (the gated call of include/mbx_levels.h) or under a
+// hold with the caller's state (the held call of include/mbx_hold.h).  The three share the buses of the record.
+struct MixHow {
+    MixKind                 kind;
+    const mbx_mixdown_gate* gate;
+    const mbx_mixdown_hold* hold;
+    mbx_gate_state*         state;
+};
+static int next_mixdown(const char* who, mbx_session* s, const mbx_mixdown_plan* plan, int form, void* out, const MixHow& how) {
+    const auto why = [&]() -> const char* {
+        if (!(s->outputs & MBX_SESSION_MIXDOWN)) {
+            return "the session was created without MBX_SESSION_MIXDOWN";
+        }
+        if (how.kind != kMixPlain && !(s->outputs & MBX_SESSION_LEVELS)) {
+            return "the session was created without MBX_SESSION_LEVELS";
+        }
+        if (!plan) {
+            return "no plan";
+        }
+        if (how.kind == kMixGated) {
+            const mbx_mixdown_gate* gate = how.gate;
+            const mbx::LevelsRefusal bad = mbx::gate_refused(gate != nullptr, gate ? gate->open_peak : 0u, gate ? gate->loudest_n : 0u);
+            if (bad != mbx::kLevelsOk) {
+                return mbx::levels_refusal_text(bad);
+            }
+        }
+        if (how.kind == kMixHeld) {
+            const mbx_mixdown_hold* hold = how.hold;
+            mbx::HoldRefusal bad = mbx::hold_refused(hold != nullptr, hold ? hold->open_peak : 0u, hold ? hold->close_peak : 0u, hold ? hold->loudest_n : 0u,
+                                                     hold ? hold->ramp_log2 : 0u);
+            if (bad == mbx::kHoldOk) {
+                bad = mbx::hold_state_refused(how.state != nullptr, how.state ? how.state->plan : nullptr, plan);
+            }
+            if (bad != mbx::kHoldOk) {
+                return mbx::hold_refusal_text(bad);
+            }
+        }
+        if (form != MBX_MIXDOWN_PCM16 && form != MBX_MIXDOWN_ULAW && form != MBX_MIXDOWN_ALAW) {
+            return "form is MBX_MIXDOWN_PCM16, MBX_MIXDOWN_ULAW or MBX_MIXDOWN_ALAW";
+        }
+        if ((size_t)mbx_mixdown_plan_buses(plan) > s->max_frames) {
+            return "the plan has more buses than max_frames_per_submit";
+        }
+        return mbx::mixdown_plan_device(plan) != s->device ? "a plan of another device than the session" : nullptr;
     };
-    if (!s) {
-        return refused("no session");
-    }
-    if (!out) {
-        std::lock_guard<std::mutex> lock(g_next_mu);
-        const auto it = g_next.find(s);
-        if (it != g_next.end()) {
-            it->second.buses = nullptr;   // (bytes attached beside it stay)
-        }
-        return 0;
-    }
-    if (!(s->outputs & MBX_SESSION_MIXDOWN)) {
-        return refused("the session was created without MBX_SESSION_MIXDOWN");
-    }
-    if ((gated || held) && !(s->outputs & MBX_SESSION_LEVELS)) {
-        return refused("the session was created without MBX_SESSION_LEVELS");
-    }
-    if (!plan) {
-        return refused("no plan");
-    }
-    if (gated) {
-        const mbx::LevelsRefusal why = mbx::gate_refused(gate != nullptr, gate ? gate->open_peak : 0u, gate ? gate->loudest_n : 0u);
-        if (why != mbx::kLevelsOk) {
-            return refused(mbx::levels_refusal_text(why));
-        }
-    }
-    if (held) {
-        mbx::HoldRefusal why = mbx::hold_refused(hold != nullptr, hold ? hold->open_peak : 0u, hold ? hold->close_peak : 0u, hold ? hold->loudest_n : 0u,
-                                                 hold ? hold->ramp_log2 : 0u);
-        if (why == mbx::kHoldOk) {
-            why = mbx::hold_state_refused(state != nullptr, state ? state->plan : nullptr, plan);
-        }
-        if (why != mbx::kHoldOk) {
-            return refused(mbx::hold_refusal_text(why));
-        }
-    }
-    if (form != MBX_MIXDOWN_PCM16 && form != MBX_MIXDOWN_ULAW && form != MBX_MIXDOWN_ALAW) {
-        return refused("form is MBX_MIXDOWN_PCM16, MBX_MIXDOWN_ULAW or MBX_MIXDOWN_ALAW");
-    }
-    if ((size_t)mbx_mixdown_plan_buses(plan) > s->max_frames) {
-        return refused("the plan has more buses than max_frames_per_submit");
-    }
-    if (mbx::mixdown_plan_device(plan) != s->device) {
-        return refused("a plan of another device than the session");
-    }
-    std::lock_guard<std::mutex> lock(g_next_mu);
-    NextOut& next = g_next[s];
-    next.buses = out;
-    next.plan = plan;
-    next.form = form;
-    next.gated = gated;
-    next.gate = gated ? *gate : mbx_mixdown_gate{0, 0};
-    next.held = held ? state : nullptr;
-    next.hold = held ? *hold : mbx_mixdown_hold{0, 0, 0, 0, 0};
-    return 0;
+    return next_attach(who, s, out, &NextOut::buses, why, [&](NextOut& next) {
+        next.buses = out, next.plan = plan, next.form = form, next.kind = how.kind;
+        next.gate = how.kind == kMixGated ? *how.gate : mbx_mixdown_gate{0, 0};
+        next.hold = how.kind == kMixHeld ? *how.hold : mbx_mixdown_hold{0, 0, 0, 0, 0};
+        next.state = how.kind == kMixHeld ? how.state : nullptr;
+    });
 }
 
 int mbx_session_next_mixdown(mbx_session* s, const mbx_mixdown_plan* plan, int form, void* out) {
-    return next_mixdown("mbx_session_next_mixdown", s, plan, form, nullptr, false, out);
+    return next_mixdown("mbx_session_next_mixdown", s, plan, form, out, MixHow{kMixPlain, nullptr, nullptr, nullptr});
 }
 
 // ---- levels out and the gated mix-down (include/mbx_levels.h): the records and the gated buses of the next submit ------------------------
 int mbx_session_next_mixdown_gated(mbx_session* s, const mbx_mixdown_plan* plan, int form, const mbx_mixdown_gate* gate, void* out) {
-    return next_mixdown("mbx_session_next_mixdown_gated", s, plan, form, gate, true, out);
+    return next_mixdown("mbx_session_next_mixdown_gated", s, plan, form, out, MixHow{kMixGated, gate, nullptr, nullptr});
 }
 
 // ---- the held gate (include/mbx_hold.h): the buses of the next submit under a hold, the caller's state advanced by one frame ------------
 int mbx_session_next_mixdown_held(mbx_session* s, const mbx_mixdown_plan* plan, int form, const mbx_mixdown_hold* hold, mbx_gate_state* state, void* out) {
-    return next_mixdown("mbx_session_next_mixdown_held", s, plan, form, nullptr, false, out, true, hold, state);
+    return next_mixdown("mbx_session_next_mixdown_held", s, plan, form, out, MixHow{kMixHeld, nullptr, hold, state});
 }
 
 int mbx_session_next_levels(mbx_session* s, mbx_row_level* out) {
-    if (!s) {
-        mbx_set_error_text("mbx_session_next_levels: no session");
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (!out) {
-        std::lock_guard<std::mutex> lock(g_next_mu);
-        const auto it = g_next.find(s);
-        if (it != g_next.end()) {
-            it->second.levels = nullptr;   // (bytes and buses attached beside it stay)
-        }
-        return 0;
-    }
-    if (!(s->outputs & MBX_SESSION_LEVELS)) {
-        mbx_set_error_text("mbx_session_next_levels: the session was created without MBX_SESSION_LEVELS");
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    std::lock_guard<std::mutex> lock(g_next_mu);
-    g_next[s].levels = out;
-    return 0;
+    const auto why = [&]() -> const char* { return s->outputs & MBX_SESSION_LEVELS ? nullptr : "the session was created without MBX_SESSION_LEVELS"; };
+    return next_attach("mbx_session_next_levels", s, out, &NextOut::levels, why, [&](NextOut& next) { next.levels = out; });
 }
 
 // ---- keyed submits (include/mbx_keystream.h): a frames submit of either kind with a keystream row per frame ---------------------------
 int mbx_session_submit_keyed(mbx_session* s, int n, int T, const int32_t* stream_index, const uint8_t* frames, const mbe_soft_bit* soft,
                              const uint8_t* keystream, int16_t* pcm16, float* pcmf, mbe_process_result* results, mbx_param_record* records) {
-    const NextOut next = take_next(s);
-    if (refuse_mixed(s, "mbx_session_submit_keyed") < 0) {
-        return MBE_STATUS_INVALID_ARGUMENT;
+    const char* const who = "mbx_session_submit_keyed";
+    Submit c(take_next(s), pcm16, pcmf, results, records);
+    if (s && s->mixed()) {
+        return refused(who, mbx::kSessionMixed, c, 0);
     }
     if (!s || (frames != nullptr) == (soft != nullptr) || (!stream_index && n != s->streams)) {
-        mbx_set_error_text("mbx_session_submit_keyed: a session, exactly one of frames and soft, and without an index n = the session's stream count");
-        return MBE_STATUS_INVALID_ARGUMENT;
+        return mbx::refuse(who, "a session, exactly one of frames and soft, and without an index n = the session's stream count");
     }
-    return submit(next, s, n, T, stream_index, soft ? static_cast<const void*>(soft) : frames, soft != nullptr, pcm16, pcmf, results, records, nullptr, keystream);
+    c.keystream = keystream;
+    return submit(s, c.rows(n, T, stream_index, soft ? static_cast<const void*>(soft) : frames, soft != nullptr));
 }
 
 // ---- burst submits (include/mbx_burst.h) ---------------------------------------------------------------------------------------------
-static int submit_bursts(const char* who, mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index, const void* bursts,
-                         size_t burst_stride, bool soft, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
-    const NextOut next = take_next(s);
-    char text[160];
-    if (!s || !sched || !bursts || n < 0 || refuse_mixed(s, who) < 0) {
-        return MBE_STATUS_INVALID_ARGUMENT;
+// (bursts: hard bursts of burst_stride bytes each, or soft ones of the schedule's own size)
+static int submit_bursts(const char* who, mbx_session* s, const mbx_burst_schedule* sched, Submit& c, size_t burst_stride) {
+    const mbx::BurstShape sh = sched ? mbx::burst_shape(sched) : mbx::BurstShape{};
+    mbx::BurstsShape b;
+    b.sched = sched != nullptr, b.bursts = c.frames != nullptr, b.soft = c.soft, b.llr = sched && sh.llr(), b.indexed = c.index != nullptr;
+    b.n = c.n, b.frames = sh.frames, b.codec = sh.codec, b.device = sh.device, b.stride = burst_stride, b.sched_bytes = sh.bytes;
+    b.session_codec = s ? s->codec : 0, b.session_device = s ? s->device : 0;
+    const mbx::SessionRefusal why = mbx::bursts_submit_refused(shape_of(s, c), b);
+    if (why != mbx::kSessionOk) {
+        return refused(who, why, c, 0);
     }
-    const mbx::BurstShape sh = mbx::burst_shape(sched);
-    if (sh.codec != s->codec || sh.device != s->device) {
-        snprintf(text, sizeof(text), "%s: the schedule is of another codec or device than the session", who);
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (!soft && sh.llr()) {
-        snprintf(text, sizeof(text), "%s: an LLR schedule has soft bursts only", who);
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if (!soft && burst_stride < sh.bytes) {
-        snprintf(text, sizeof(text), "%s: burst_stride is below mbx_burst_schedule_bytes()", who);
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    if ((!stream_index && n != s->streams) || (size_t)n * (size_t)sh.frames > s->max_frames) {
-        snprintf(text, sizeof(text), "%s: without an index n is the session's stream count; n * frames_per_burst <= max_frames_per_submit", who);
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    const BurstIn in{sched, burst_stride, soft ? mbx_burst_schedule_soft_bytes(sched) : burst_stride};
-    return submit(next, s, n, sh.frames, stream_index, bursts, soft, pcm16, pcmf, results, nullptr, &in);
+    const BurstIn in{sched, burst_stride, c.soft ? mbx_burst_schedule_soft_bytes(sched) : burst_stride};
+    c.T = sh.frames, c.burst = &in;
+    return submit(s, c);
 }
 
 int mbx_session_submit_bursts(mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index, const uint8_t* bursts,
                               size_t burst_stride, int16_t* pcm16, float* pcmf, mbe_process_result* results) {
-    return submit_bursts("mbx_session_submit_bursts", s, sched, n, stream_index, bursts, burst_stride, false, pcm16, pcmf, results);
+    Submit c(take_next(s), pcm16, pcmf, results, nullptr);
+    return submit_bursts("mbx_session_submit_bursts", s, sched, c.rows(n, 0, stream_index, bursts, false), burst_stride);
 }
 
 int mbx_session_submit_bursts_soft(mbx_session* s, const mbx_burst_schedule* sched, int n, const int32_t* stream_index, const mbe_soft_bit* soft,
                                    int16_t* pcm16, float* pcmf, mbe_process_result* results) {
-    return submit_bursts("mbx_session_submit_bursts_soft", s, sched, n, stream_index, soft, 0, true, pcm16, pcmf, results);
+    Submit c(take_next(s), pcm16, pcmf, results, nullptr);
+    return submit_bursts("mbx_session_submit_bursts_soft", s, sched, c.rows(n, 0, stream_index, soft, true), 0);
 }
 
 // ---- burst groups (include/mbx_burst_groups.h) --------------------------------------------------------------------------------------
 // The groups' bursts into the slot's burst buffer, each group at a 16-byte aligned offset (pinned 16-byte aligned buffers read in
 // place, others through the slot's pinned staging at the same offsets), their indices into the slot's index words, then
 // mbx_process_burst_groups on the compute stream with the groups rewritten to those device addresses, and the outputs out.
-static int enqueue_groups(mbx_session* s, Slot& sl, const mbx_burst_group* groups, int n_groups, bool soft, const mbx::GroupPlan& gp,
-                          int16_t* pcm16, float* pcmf, mbe_process_result* results, const NextOut& next) {
-    size_t at[MBX_BURST_MAX_GROUPS], bytes[MBX_BURST_MAX_GROUPS], total = 0;
-    bool staged = false, indexed = false;
-    for (int i = 0; i < n_groups; ++i) {
-        const size_t per = soft ? mbx_burst_schedule_soft_bytes(groups[i].sched) : groups[i].burst_stride;
-        at[i] = total;
-        // (of the last hard burst only the schedule's bytes are there to read, not its whole stride)
-        bytes[i] = gp.place[i].bursts ? ((size_t)gp.place[i].bursts - 1) * per + (soft ? per : mbx_burst_schedule_bytes(groups[i].sched)) : 0;
-        total = (total + bytes[i] + 15) & ~(size_t)15;
-        if (bytes[i] && (!is_pinned(groups[i].bursts) || (reinterpret_cast<uintptr_t>(groups[i].bursts) & 15u))) {
-            staged = true;
-        }
-        indexed = indexed || (gp.place[i].bursts && groups[i].stream_index);
+static int enqueue_groups(mbx_session* s, Slot& sl, const Submit& c, const mbx_burst_group* groups, const mbx::GroupPlan& gp) {
+    mbx::GroupIn in[MBX_BURST_MAX_GROUPS];
+    for (int i = 0; i < gp.n_groups; ++i) {
+        const mbx_burst_group& g = groups[i];
+        in[i].bursts = gp.place[i].bursts;
+        in[i].per = c.soft ? mbx_burst_schedule_soft_bytes(g.sched) : g.burst_stride;
+        in[i].sched_bytes = c.soft ? 0 : mbx_burst_schedule_bytes(g.sched);
+        in[i].in_place = in[i].bursts && is_pinned(g.bursts) && mbx::aligned_to(g.bursts, 16);   // (of a group without bursts the pointer is not looked at)
+        in[i].has_index = g.stream_index != nullptr;
     }
-    if (sl.bursts_cap < total) {
-        (void)hipFree(sl.d_bursts);
-        sl.d_bursts = nullptr;
-        sl.bursts_cap = 0;
-        S_TRY(hipMalloc(reinterpret_cast<void**>(&sl.d_bursts), total));
-        sl.bursts_cap = total;
-    }
-    if (staged && sl.h_bursts_cap < total) {
-        (void)hipHostFree(sl.h_bursts);
-        sl.h_bursts = nullptr;
-        sl.h_bursts_cap = 0;
-        S_TRY(hipHostMalloc(reinterpret_cast<void**>(&sl.h_bursts), total, hipHostMallocDefault));
-        sl.h_bursts_cap = total;
-    }
+    const mbx::GroupBytes lay = mbx::group_bytes(in, gp.n_groups, c.soft);
+    Pair&          bursts = sl.in[kInBursts];
+    Grown<true>&   h_index = sl.in[kInIndex].h;
+    int32_t* const d_index = sl.din<int32_t>(kInIndex);
     int rc = 0;
-    if (indexed) {
-        rc = pinned(sl.h_index, (size_t)s->streams);
-        if (rc < 0) {
-            return rc;
-        }
+    if ((rc = bursts.d.need(lay.total)) < 0 || (lay.staged && (rc = bursts.h.need(lay.total)) < 0)
+        || (lay.indexed && (rc = h_index.need((size_t)s->streams * sizeof(int32_t))) < 0)) {
+        return rc;
     }
     mbx_burst_group dev[MBX_BURST_MAX_GROUPS];
-    for (int i = 0; i < n_groups; ++i) {
+    for (int i = 0; i < gp.n_groups; ++i) {
         dev[i] = groups[i];
-        dev[i].bursts = sl.d_bursts + at[i];
+        dev[i].bursts = bursts.d.p + lay.at[i];
         dev[i].stream_index = nullptr;
-        if (!bytes[i]) {
+        if (!lay.bytes[i]) {
             continue;
         }
-        const uint8_t* src = static_cast<const uint8_t*>(groups[i].bursts);
-        if (!is_pinned(src) || (reinterpret_cast<uintptr_t>(src) & 15u)) {
-            memcpy(sl.h_bursts + at[i], src, bytes[i]);
-            src = sl.h_bursts + at[i];
-        }
-        const void* dev_view = src;
-        void* mapped = nullptr;
-        if (hipHostGetDevicePointer(&mapped, const_cast<uint8_t*>(src), 0) == hipSuccess && mapped) {
-            dev_view = mapped;
-        } else {
-            (void)hipGetLastError();
-        }
-        rc = mbx_stage_in(sl.d_bursts + at[i], dev_view, bytes[i], s->s_comp);
-        if (rc < 0) {
+        if ((rc = carry_in(s, bursts, lay.at[i], groups[i].bursts, lay.bytes[i], lay.total)) < 0) {
             return rc;
         }
         if (groups[i].stream_index) {   // (the groups name every stream once: their indices fit the slot's `streams` words, at their stream rows)
-            memcpy(sl.h_index + gp.place[i].first_stream, groups[i].stream_index, (size_t)groups[i].n_streams * sizeof(int32_t));
-            dev[i].stream_index = sl.d_index + gp.place[i].first_stream;
+            memcpy(reinterpret_cast<int32_t*>(h_index.p) + gp.place[i].first_stream, groups[i].stream_index, (size_t)groups[i].n_streams * sizeof(int32_t));
+            dev[i].stream_index = d_index + gp.place[i].first_stream;
         }
     }
-    if (indexed) {
-        rc = mbx_stage_in(sl.d_index, sl.h_index, (size_t)gp.total_streams * sizeof(int32_t), s->s_comp);
-        if (rc < 0) {
-            return rc;
-        }
-    }
-    rc = mbx_process_burst_groups(dev, n_groups, soft ? 1 : 0, s->d_state, s->d_resident, s->d_rng, pcm16 || next.dst || next.buses || next.levels ? sl.d_pcm16 : nullptr,
-                                  pcmf ? sl.d_pcmf : nullptr, results ? sl.d_results : nullptr, sl.d_records, s->s_comp);
-    if (rc < 0 || (rc = compand_step(s, sl, (size_t)gp.total_rows, next)) < 0 || (rc = levels_step(s, sl, (size_t)gp.total_rows, next)) < 0
-        || (rc = mixdown_step(s, sl, (size_t)gp.total_rows, next)) < 0) {
+    if (lay.indexed && (rc = mbx_stage_in(d_index, h_index.p, (size_t)gp.total_streams * sizeof(int32_t), s->s_comp)) < 0) {
         return rc;
     }
-    return copy_out(s, sl, (size_t)gp.total_rows, pcm16, pcmf, results, nullptr, next);
+    rc = mbx_process_burst_groups(dev, gp.n_groups, c.soft ? 1 : 0, s->d_state, s->d_resident, s->d_rng,
+                                  c.next.wants_pcm16(c.user[mbx::kOutPcm16]) ? sl.dout<int16_t>(mbx::kOutPcm16) : nullptr,
+                                  c.user[mbx::kOutPcmf] ? sl.dout<float>(mbx::kOutPcmf) : nullptr,
+                                  c.user[mbx::kOutResults] ? sl.dout<mbe_process_result>(mbx::kOutResults) : nullptr,
+                                  sl.dout<mbx_param_record>(mbx::kOutRecords), s->s_comp);
+    return rc < 0 ? rc : behind_step(s, sl, c, (size_t)gp.total_rows);
 }
 
 int mbx_session_submit_burst_groups(mbx_session* s, const mbx_burst_group* groups, int n_groups, int soft_in, int16_t* pcm16, float* pcmf,
                                     mbe_process_result* results) {
     const char* const who = "mbx_session_submit_burst_groups";
-    const NextOut next = take_next(s);
-    const bool soft = soft_in != 0;
-    char text[200];
-    const auto refused = [&](const char* why) {
-        snprintf(text, sizeof(text), "%s: %s", who, why);
-        mbx_set_error_text(text);
-        return MBE_STATUS_INVALID_ARGUMENT;
-    };
+    Submit c(take_next(s), pcm16, pcmf, results, nullptr);
+    c.soft = soft_in != 0;
     if (!s) {
-        return refused("no session");
+        return refused(who, mbx::kSessionNoSession, c, 0);
     }
     mbx::GroupShape shapes[MBX_BURST_MAX_GROUPS];
     mbx::GroupPlan gp;
-    int rc = mbx::burst_groups_plan(who, groups, n_groups, soft, shapes, &gp);
+    int rc = mbx::burst_groups_plan(who, groups, n_groups, c.soft, shapes, &gp);
     if (rc < 0) {
         return rc;
     }
-    if ((pcm16 && !(s->outputs & MBX_SESSION_PCM16)) || (pcmf && !(s->outputs & MBX_SESSION_PCMF)) || (results && !(s->outputs & MBX_SESSION_RESULTS))) {
-        return refused("an output the session was not created for");
-    }
-    if ((size_t)gp.total_rows > s->max_frames) {
-        return refused("more frames than max_frames_per_submit");
-    }
-    if (refuse_rows_short_of_the_plan(next, (size_t)gp.total_rows) < 0) {
-        return MBE_STATUS_INVALID_ARGUMENT;
-    }
-    // every group's schedule is of the codec of every stream the group names; slots in range, none named twice across the groups
+    // the session's sizes; then every group's schedule is of the session's device and of the codec of every stream the group names,
+    // slots in range, none named twice across the groups
+    mbx::SessionRefusal why = mbx::groups_submit_refused(shape_of(s, c), gp.total_rows);
     s->seen.assign((size_t)s->streams, 0);
-    for (int i = 0; i < n_groups; ++i) {
+    for (int i = 0; i < n_groups && why == mbx::kSessionOk; ++i) {
         const mbx_burst_group& g = groups[i];
         const mbx::BurstShape sh = mbx::burst_shape(g.sched);
-        if (sh.device != s->device) {
-            return refused("a schedule of another device than the session");
-        }
-        for (int j = 0; j < g.n_streams; ++j) {
-            const long long slot = g.stream_index ? (long long)g.stream_index[j] : (long long)g.first_slot + j;
-            if (slot < 0 || slot >= s->streams || s->seen[(size_t)slot]) {
-                return refused("stream index out of range or listed twice");
-            }
-            s->seen[(size_t)slot] = 1;
-            if ((s->mixed() ? (int)s->stream_codec[(size_t)slot] : s->codec) != sh.codec) {
-                return refused("a schedule of another codec than a stream its group names");
-            }
-        }
+        why = sh.device != s->device ? mbx::kGroupsDevice
+                                     : mbx::mark_group(s->seen.data(), s->streams, g.stream_index, g.first_slot, g.n_streams,
+                                                       s->mixed() ? s->stream_codec.data() : nullptr, s->codec, sh.codec);
+    }
+    if (why != mbx::kSessionOk) {
+        return refused(who, why, c, (size_t)gp.total_rows);
     }
     for (int i = 0; i < n_groups; ++i) {   // bursts of a form that can be invalid (mbx_burst_validate)
         if (gp.place[i].bursts && !mbx::burst_shape(groups[i].sched).llr()) {
-            rc = mbx_burst_validate(groups[i].sched, groups[i].bursts, groups[i].burst_stride, (size_t)gp.place[i].bursts, soft ? 1 : 0);
+            rc = mbx_burst_validate(groups[i].sched, groups[i].bursts, groups[i].burst_stride, (size_t)gp.place[i].bursts, c.soft ? 1 : 0);
             if (rc < 0) {
                 return rc;
             }
@@ -1135,23 +952,7 @@ int mbx_session_submit_burst_groups(mbx_session* s, const mbx_burst_group* group
     if (gp.total_rows == 0) {
         return 0;
     }
-    DeviceGuard guard(s->device);
-    Slot& sl = s->slot[s->submitted % kDepth];
-    rc = finish_slot(sl);
-    if (rc < 0) {
-        return rc;
-    }
-    rc = enqueue_groups(s, sl, groups, n_groups, soft, gp, pcm16, pcmf, results, next);
-    if (rc < 0) {   // (as submit: drain, so that the next submit may reuse the slot at once)
-        (void)hipStreamSynchronize(s->s_comp);
-        (void)hipStreamSynchronize(s->s_out);
-        (void)hipGetLastError();
-        sl.nout = 0;
-        return rc;
-    }
-    sl.busy = true;
-    ++s->submitted;
-    return 0;
+    return on_next_slot(s, [&](Slot& sl) { return enqueue_groups(s, sl, c, groups, gp); });
 }
 
 }  // extern "C"
