@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h,
-include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h, include/mbx_hold.h).  Fails loudly when the library
+include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h, include/mbx_hold.h, include/mbx_agc.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -208,6 +208,19 @@ _HOLD_SIGNATURES = {
     "mbx_session_next_mixdown_held": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, _vp]),
 }
 HOLD_SYMBOLS = tuple(_HOLD_SIGNATURES)
+# levelled rows (include/mbx_agc.h): a per-stream automatic gain over the int16 rows, a state record per stream on the device
+_AGC_SIGNATURES = {
+    "mbx_agc_state_create": (C.c_int, [_vp, C.c_int]),
+    "mbx_agc_state_destroy": (C.c_int, [_vp]),
+    "mbx_agc_state_streams": (C.c_int, [_vp]),
+    "mbx_agc_state_reset": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "mbx_agc_state_get": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "mbx_agc_state_set": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "mbx_pcm_agc": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "mbx_pcm_agc_host": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "mbx_session_next_agc": (C.c_int, [_vp, _vp, _vp]),
+}
+AGC_SYMBOLS = tuple(_AGC_SIGNATURES)
 
 
 class BurstGroupStruct(C.Structure):
@@ -237,7 +250,7 @@ def lib():
         except OSError as e:  # e.g. libamdhip64 not found
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
         for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES, **_KEYSTREAM_SIGNATURES, **_PCM8_SIGNATURES,
-                                   **_MIXDOWN_SIGNATURES, **_LEVELS_SIGNATURES, **_HOLD_SIGNATURES}.items():
+                                   **_MIXDOWN_SIGNATURES, **_LEVELS_SIGNATURES, **_HOLD_SIGNATURES, **_AGC_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

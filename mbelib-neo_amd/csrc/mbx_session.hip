@@ -31,6 +31,8 @@
 #include <vector>
 
 #include "mbx.h"
+#include <mbx_agc.h>       // (levelled rows: the public header)
+#include "mbx_agc_plan.h"      // (what an agc is refused for, and the device and the size of a state)
 #include "mbx_burst.h"
 #include "mbx_burst_groups.h"
 #include "mbx_codec.h"
@@ -199,9 +201,14 @@ struct NextOut {
     mbx_mixdown_hold        hold = {0, 0, 0, 0, 0};
     mbx_gate_state*         state = nullptr;
     void*                   levels = nullptr;  // host memory, one mbx_row_level per row (mbx_session_next_levels); nullptr: nothing attached
+    // the slot's int16 rows levelled in place under `agc` with the caller's `agc_state` (mbx_session_next_agc, include/mbx_agc.h), in
+    // front of every other launch behind the step; nullptr: nothing attached
+    void*                   agc_state = nullptr;
+    mbx_agc                 agc = {0, 0, 0, 0, 0, 0, 0, 0};
     bool wants_levels() const { return levels || (buses && kind != kMixPlain); }
-    // the step is handed the slot's int16 rows: for the caller, or for the compand, the levels and the mix-down behind the step
-    bool wants_pcm16(const void* callers) const { return callers || dst || buses || levels; }
+    // the step is handed the slot's int16 rows: for the caller, or for the compand, the levels and the mix-down behind the step; an
+    // attached AGC advances its state whether or not anybody takes the rows
+    bool wants_pcm16(const void* callers) const { return callers || dst || buses || levels || agc_state; }
 };
 std::mutex g_next_mu;
 std::unordered_map<const mbx_session*, NextOut> g_next;
@@ -343,15 +350,20 @@ int copy_out(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
     return 0;
 }
 
-// Behind the step of a submit of nf frames, on the compute stream: the slot's int16 rows -> companded bytes where a destination is
-// attached; their level records, once per submit, for the caller or for the gate of its buses or both; the plan's buses of those rows
+// Behind the step of a submit of nf frames, on the compute stream: FIRST the slot's int16 rows levelled in place where an AGC is
+// attached (the records of the submit's streams: its index on the device, or 0 .. n-1); then those rows -> companded bytes where a
+// destination is attached; their level records, once per submit, for the caller or for the gate of its buses or both; the plan's buses of those rows
 // (one or two more launches); then the outputs out.
 int behind_step(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
     const NextOut& next = c.next;
-    const int16_t* const d16 = sl.dout<int16_t>(mbx::kOutPcm16);
+    int16_t* const d16 = sl.dout<int16_t>(mbx::kOutPcm16);
     mbx_row_level* const dlev = sl.dout<mbx_row_level>(mbx::kOutLevels);
     uint8_t* const dmix = sl.dout<uint8_t>(mbx::kOutMix);
     int rc = 0;
+    if (next.agc_state
+        && (rc = mbx_pcm_agc(&next.agc, static_cast<mbx_agc_state*>(next.agc_state), c.index ? sl.din<int32_t>(kInIndex) : nullptr, c.n, c.T, d16, d16, s->s_comp)) < 0) {
+        return rc;
+    }
     if ((next.dst && (rc = mbx_pcm_compand(next.law, d16, nf, sl.dout<uint8_t>(mbx::kOutPcm8), s->s_comp)) < 0)
         || (next.wants_levels() && (rc = mbx_pcm_levels(d16, nf, dlev, s->s_comp)) < 0)) {
         return rc;
@@ -814,6 +826,25 @@ int mbx_session_next_mixdown_held(mbx_session* s, const mbx_mixdown_plan* plan, 
     return next_mixdown("mbx_session_next_mixdown_held", s, plan, form, out, MixHow{kMixHeld, nullptr, hold, state});
 }
 
+// ---- levelled rows (include/mbx_agc.h): the int16 rows of the next submit under an AGC, the caller's state advanced by its frames ------
+int mbx_session_next_agc(mbx_session* s, const mbx_agc* agc, mbx_agc_state* state) {
+    const auto why = [&]() -> const char* {
+        const mbx::AgcRefusal bad = mbx::agc_refused(agc != nullptr, agc ? agc->target_peak : 0u, agc ? agc->floor_peak : 0u, agc ? agc->min_gain_q10 : 0u,
+                                                     agc ? agc->max_gain_q10 : 0u, agc ? agc->ramp_log2 : 0u, agc ? agc->zero : 0u);
+        if (bad != mbx::kAgcOk) {
+            return mbx::agc_refusal_text(bad);
+        }
+        if (!mbx::out_owned(mbx::kOutPcm16, s->outputs)) {
+            return "the session was created without an output that has int16 rows";
+        }
+        if (state->streams < s->streams) {
+            return "the state holds fewer records than the session has streams";
+        }
+        return state->device != s->device ? "a state of another device than the session" : nullptr;
+    };
+    return next_attach("mbx_session_next_agc", s, state, &NextOut::agc_state, why, [&](NextOut& next) { next.agc_state = state, next.agc = *agc; });
+}
+
 int mbx_session_next_levels(mbx_session* s, mbx_row_level* out) {
     const auto why = [&]() -> const char* { return s->outputs & MBX_SESSION_LEVELS ? nullptr : "the session was created without MBX_SESSION_LEVELS"; };
     return next_attach("mbx_session_next_levels", s, out, &NextOut::levels, why, [&](NextOut& next) { next.levels = out; });
@@ -920,6 +951,9 @@ int mbx_session_submit_burst_groups(mbx_session* s, const mbx_burst_group* group
     c.soft = soft_in != 0;
     if (!s) {
         return refused(who, mbx::kSessionNoSession, c, 0);
+    }
+    if (c.next.agc_state) {   // (the groups have different frame counts: one launch of mbx_pcm_agc has one T)
+        return mbx::refuse(who, "an AGC is attached (mbx_session_next_agc): burst groups take none");
     }
     mbx::GroupShape shapes[MBX_BURST_MAX_GROUPS];
     mbx::GroupPlan gp;

@@ -14,7 +14,8 @@ Beyond the reference: compand(pcm16, law) -- the int16 rows of a decode as G.711
 mixdown(pcm16, plan, form) -- the rows summed into talkgroup buses, a gain per input (include/mbx_mixdown.h);
 levels(pcm16) -- a level record per row, and mixdown_gated(pcm16, plan, form, open_peak, loudest_n) -- the buses of the open / the N
 loudest inputs (include/mbx_levels.h); mixdown_held(pcm16, plan, state, hold, form) -- the same with hysteresis, hang time and ramps,
-a state record per input kept on the device (include/mbx_hold.h).
+a state record per input kept on the device (include/mbx_hold.h); agc(pcm16, T, state, agc) -- the rows levelled by a per-stream
+automatic gain, a state record per stream kept on the device (include/mbx_agc.h).
 """
 import numpy as np
 
@@ -228,6 +229,30 @@ class BatchDecoder:
             rc = _native.lib().mbx_mixdown_held(plan.handle, ctypes.addressof(hold), state.handle, int(form), pcm16.data_ptr(), n, levels.data_ptr(),
                                                 out.data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(rc, "mbx_mixdown_held")
+        return out
+
+    def agc(self, pcm16, T, state, agc, stream_index=None, out=None):
+        """Levelled rows (include/mbx_agc.h): mbx_pcm_agc on the current torch stream -- the int16 rows [n * T, 160] a decode returned
+        (a contiguous device tensor, stream-major) under `agc` (an agc.Agc) and `state` (an agc.AgcState) advanced by T frames, the
+        values agc.step gives on the host.  stream_index (int32 device tensor [n]): entry i uses record stream_index[i]; without it
+        record i.  out: a contiguous int16 tensor of as many elements, or pcm16 itself (in place); None: a new tensor."""
+        import ctypes
+
+        torch = _torch()
+        rows, T = _pcm16_rows(pcm16), int(T)
+        if T <= 0 or rows % T:
+            raise ValueError("pcm16 must hold n * T rows")
+        if stream_index is not None and (stream_index.dtype != torch.int32 or not stream_index.is_contiguous() or stream_index.numel() != rows // T
+                                         or stream_index.device != pcm16.device):
+            raise ValueError("stream_index must be a contiguous int32 tensor of one entry per stream on the device of pcm16")
+        if out is None:
+            out = torch.empty(tuple(pcm16.shape), dtype=torch.int16, device=pcm16.device)
+        elif out.dtype != torch.int16 or not out.is_contiguous() or out.numel() != pcm16.numel() or out.device != pcm16.device:
+            raise ValueError("out must be a contiguous int16 tensor of one element per sample on the device of pcm16")
+        with torch.cuda.device(pcm16.device):
+            rc = _native.lib().mbx_pcm_agc(ctypes.addressof(agc), state.handle, None if stream_index is None else stream_index.data_ptr(), rows // T, T,
+                                           pcm16.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_pcm_agc")
         return out
 
     def decode_soft(self, soft, T, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None, keystream=None):
