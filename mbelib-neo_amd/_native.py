@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h,
-include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h, include/mbx_hold.h, include/mbx_agc.h).  Fails loudly when the library
+include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h, include/mbx_hold.h, include/mbx_agc.h, include/mbx_limit.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -221,6 +221,26 @@ _AGC_SIGNATURES = {
     "mbx_session_next_agc": (C.c_int, [_vp, _vp, _vp]),
 }
 AGC_SYMBOLS = tuple(_AGC_SIGNATURES)
+# limited buses (include/mbx_limit.h): the int32 sums of the bus launches and a look-ahead peak limiter behind them, a state record per bus
+_LIMIT_SIGNATURES = {
+    "mbx_limit_state_create": (C.c_int, [_vp, C.c_int]),
+    "mbx_limit_state_destroy": (C.c_int, [_vp]),
+    "mbx_limit_state_buses": (C.c_int, [_vp]),
+    "mbx_limit_state_reset": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "mbx_limit_state_get": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "mbx_limit_state_set": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "mbx_limit_state_sums": (_vp, [_vp]),
+    "mbx_bus_limit": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
+    "mbx_bus_limit_host": (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp]),
+    "mbx_mixdown_sums": (C.c_int, [_vp, _vp, _sz, _vp, _vp]),
+    "mbx_mixdown_sums_host": (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mbx_mixdown_gated_sums": (C.c_int, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "mbx_mixdown_gated_sums_host": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mbx_mixdown_held_sums": (C.c_int, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "mbx_mixdown_held_sums_host": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "mbx_session_next_limit": (C.c_int, [_vp, _vp, _vp]),
+}
+LIMIT_SYMBOLS = tuple(_LIMIT_SIGNATURES)
 
 
 class BurstGroupStruct(C.Structure):
@@ -250,7 +270,7 @@ def lib():
         except OSError as e:  # e.g. libamdhip64 not found
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
         for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES, **_KEYSTREAM_SIGNATURES, **_PCM8_SIGNATURES,
-                                   **_MIXDOWN_SIGNATURES, **_LEVELS_SIGNATURES, **_HOLD_SIGNATURES, **_AGC_SIGNATURES}.items():
+                                   **_MIXDOWN_SIGNATURES, **_LEVELS_SIGNATURES, **_HOLD_SIGNATURES, **_AGC_SIGNATURES, **_LIMIT_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

@@ -33,6 +33,7 @@
 #include "mbx_kernels.h"
 #include "mbx_levels.h"    // the arithmetic: the private header of this directory
 #include <mbx_hold.h>      // the public header: include/, first on the include path
+#include <mbx_limit.h>     // (mbx_mixdown_held_sums and its host twin are declared there)
 #include "mbx_hold_plan.h"
 #include "mbx_mixdown_lanes.h"
 
@@ -161,6 +162,7 @@ hold_sum_kernel(const int16_t* __restrict__ pcm16, const int32_t* __restrict__ b
 template __global__ void hold_sum_kernel<kMixdownPcm16>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, const uint8_t*, int, void*);
 template __global__ void hold_sum_kernel<kMixdownUlaw>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, const uint8_t*, int, void*);
 template __global__ void hold_sum_kernel<kMixdownAlaw>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, const uint8_t*, int, void*);
+template __global__ void hold_sum_kernel<kMixdownSums>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, const uint8_t*, int, void*);
 
 static_assert(kMixdownMaxInputs <= (1 << 12) && kHoldFalling < 4, "a list entry, position | code << 12, fits 16 bits");
 
@@ -288,6 +290,7 @@ hold_long_kernel(const int16_t* __restrict__ pcm16, const mbx_row_level* __restr
 template __global__ void hold_long_kernel<kMixdownPcm16>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, HoldParams, uint32_t*, void*);
 template __global__ void hold_long_kernel<kMixdownUlaw>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, HoldParams, uint32_t*, void*);
 template __global__ void hold_long_kernel<kMixdownAlaw>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, HoldParams, uint32_t*, void*);
+template __global__ void hold_long_kernel<kMixdownSums>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, HoldParams, uint32_t*, void*);
 
 }  // namespace mbx
 
@@ -316,6 +319,90 @@ mbx::HoldRefusal records_refused(const mbx_gate_input_state* r, int32_t n) {
         words[(size_t)k] = mbx::hold_state_word(r[k].hang_left, r[k].open, r[k].on);
     }
     return mbx::hold_records_refused(words.data(), words.size());
+}
+
+// mbx_mixdown_held_host and its sums twin: `out_kind` is the caller's form, or kMixdownSums
+int held_host(const char* who, int out_kind, const mbx_mixdown_hold* hold, int n_buses, const int32_t* bus_offset, const int32_t* src_row,
+              const int16_t* gain_q12, const int16_t* pcm16, size_t nrows, mbx_gate_input_state* state, void* out) {
+    const mbx::HoldRefusal bad_hold = mbx::hold_refused(hold != nullptr, hold ? hold->open_peak : 0u, hold ? hold->close_peak : 0u,
+                                                        hold ? hold->loudest_n : 0u, hold ? hold->ramp_log2 : 0u);
+    if (bad_hold != mbx::kHoldOk) {
+        return refuse(who, bad_hold);
+    }
+    mbx::MixdownPlan plan;
+    if (const char* const why = mbx::mixdown_host_out_refused(out_kind, n_buses, bus_offset, src_row, pcm16, nrows, out, &plan)) {
+        return refuse(who, why);
+    }
+    if (!state && plan.inputs > 0) {
+        return refuse(who, mbx::kHoldNoState);
+    }
+    if (records_refused(state, plan.inputs) != mbx::kHoldOk) {
+        return refuse(who, mbx::kHoldRecord);
+    }
+    const mbx::HoldParams hp = params_of(*hold);
+    std::vector<uint64_t> keys;
+    std::vector<mbx::HoldDecision> decided;
+    for (int b = 0; b < n_buses; ++b) {
+        const int32_t lo = bus_offset[b], count = bus_offset[b + 1] - lo;
+        keys.resize((size_t)count);
+        decided.resize((size_t)count);
+        for (int32_t k = 0; k < count; ++k) {   // (the levels of the rows as they are, before the gain)
+            const mbx::Level l = mbx::level_of_row(pcm16 + (size_t)src_row[lo + k] * 160u);
+            const mbx_gate_input_state& was = state[lo + k];
+            decided[(size_t)k] = mbx::hold_decide(l.peak, was.open, was.hang_left, hp.open_peak, hp.close_peak, hp.hang_frames);
+            keys[(size_t)k] = mbx::hold_key(decided[(size_t)k], l.energy, k);
+        }
+        const uint64_t threshold = mbx::gate_threshold(keys.data(), count, hp.loudest_n);
+        int32_t acc[160] = {0};
+        for (int32_t k = 0; k < count; ++k) {
+            const int16_t* const x = pcm16 + (size_t)src_row[lo + k] * 160u;
+            const int16_t g = gain_q12 ? gain_q12[lo + k] : (int16_t)mbx::kMixdownUnity;
+            const uint32_t on = keys[(size_t)k] >= threshold ? 1u : 0u;
+            const uint32_t code = mbx::hold_code(state[lo + k].on, on);
+            for (int n = 0; n < 160; ++n) {   // THE definition: every term under its weight, whatever the code
+                acc[n] += mbx::hold_ramped(mbx::mixdown_term(x[n], g), mbx::hold_weight(code, n, hp.ramp_log2), hp.ramp_log2);
+            }
+            state[lo + k] = mbx_gate_input_state{(uint16_t)decided[(size_t)k].hang, (uint8_t)decided[(size_t)k].open, (uint8_t)on};
+        }
+        mbx::mixdown_put_row(out_kind, acc, b, out);
+    }
+    return 0;
+}
+
+// mbx_mixdown_held and its sums twin, down ONE launch path: `out` is the caller's form (mixdown_out_of_form), or kMixdownSums
+int held_launch(const char* who, const mbx_mixdown_plan* plan, const mbx_mixdown_hold* hold, mbx_gate_state* state, int out, const int16_t* d_pcm16,
+                size_t nrows, const mbx_row_level* d_levels, void* d_out, void* stream) {
+    mbx::LevelsRefusal levels = mbx::kLevelsOk;
+    mbx::MixdownRefusal mix = mbx::kMixdownOk;
+    const mbx::HoldRefusal why = mbx::held_launch_refused(plan ? &plan->plan : nullptr, plan, hold != nullptr, hold ? hold->open_peak : 0u,
+                                                          hold ? hold->close_peak : 0u, hold ? hold->loudest_n : 0u, hold ? hold->ramp_log2 : 0u,
+                                                          state != nullptr, state ? state->plan : nullptr, out, d_pcm16, nrows, d_levels, d_out,
+                                                          &levels, &mix, out == mbx::kMixdownSums);
+    if (why != mbx::kHoldOk) {
+        return refuse(who, why, levels, mix);
+    }
+    mbx::MixdownTables t;
+    const int rc = mbx::mixdown_tables(who, plan, &t);
+    if (rc < 0) {
+        return rc;
+    }
+    const mbx::MixdownPlan& p = plan->plan;
+    const mbx::HoldParams hp = params_of(*hold);
+    const hipStream_t strm = (hipStream_t)stream;
+    mbx::mixdown_by_out(out, [&](auto k) {
+        if (p.short_grid) {
+            hipLaunchKernelGGL(mbx::hold_decide_kernel, dim3(mbx::hold_decide_grid(p)), dim3(mbx::kHoldDecideBlock), 0, strm, d_levels, t.bus_offset,
+                               t.short_bus, t.input, p.n_short, hp, state->d_state, state->d_code);
+            hipLaunchKernelGGL(mbx::hold_sum_kernel<k()>, dim3(p.short_grid), dim3(mbx::kMixdownBlock), 0, strm, d_pcm16, t.bus_offset, t.short_bus,
+                               t.input, p.n_short, state->d_code, hp.ramp_log2, d_out);
+        }
+        if (p.long_grid) {
+            hipLaunchKernelGGL(mbx::hold_long_kernel<k()>, dim3(p.long_grid), dim3(mbx::kMixdownBlock), 0, strm, d_pcm16, d_levels, t.bus_offset,
+                               t.long_bus, t.input, hp, state->d_state, d_out);
+        }
+    });
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : mbx::hip_failed("", "hold kernels", e);
 }
 
 }  // namespace
@@ -420,86 +507,22 @@ int mbx_gate_state_set(mbx_gate_state* st, const mbx_gate_input_state* host, voi
 
 int mbx_mixdown_held_host(int form, const mbx_mixdown_hold* hold, int n_buses, const int32_t* bus_offset, const int32_t* src_row,
                           const int16_t* gain_q12, const int16_t* pcm16, size_t nrows, mbx_gate_input_state* state, void* out) {
-    const char* const who = "mbx_mixdown_held_host";
-    const mbx::HoldRefusal bad_hold = mbx::hold_refused(hold != nullptr, hold ? hold->open_peak : 0u, hold ? hold->close_peak : 0u,
-                                                        hold ? hold->loudest_n : 0u, hold ? hold->ramp_log2 : 0u);
-    if (bad_hold != mbx::kHoldOk) {
-        return refuse(who, bad_hold);
-    }
-    mbx::MixdownPlan plan;
-    if (const char* const why = mbx::mixdown_host_refused(form, n_buses, bus_offset, src_row, pcm16, nrows, out, &plan)) {
-        return refuse(who, why);
-    }
-    if (!state && plan.inputs > 0) {
-        return refuse(who, mbx::kHoldNoState);
-    }
-    if (records_refused(state, plan.inputs) != mbx::kHoldOk) {
-        return refuse(who, mbx::kHoldRecord);
-    }
-    const mbx::HoldParams hp = params_of(*hold);
-    std::vector<uint64_t> keys;
-    std::vector<mbx::HoldDecision> decided;
-    for (int b = 0; b < n_buses; ++b) {
-        const int32_t lo = bus_offset[b], count = bus_offset[b + 1] - lo;
-        keys.resize((size_t)count);
-        decided.resize((size_t)count);
-        for (int32_t k = 0; k < count; ++k) {   // (the levels of the rows as they are, before the gain)
-            const mbx::Level l = mbx::level_of_row(pcm16 + (size_t)src_row[lo + k] * 160u);
-            const mbx_gate_input_state& was = state[lo + k];
-            decided[(size_t)k] = mbx::hold_decide(l.peak, was.open, was.hang_left, hp.open_peak, hp.close_peak, hp.hang_frames);
-            keys[(size_t)k] = mbx::hold_key(decided[(size_t)k], l.energy, k);
-        }
-        const uint64_t threshold = mbx::gate_threshold(keys.data(), count, hp.loudest_n);
-        int32_t acc[160] = {0};
-        for (int32_t k = 0; k < count; ++k) {
-            const int16_t* const x = pcm16 + (size_t)src_row[lo + k] * 160u;
-            const int16_t g = gain_q12 ? gain_q12[lo + k] : (int16_t)mbx::kMixdownUnity;
-            const uint32_t on = keys[(size_t)k] >= threshold ? 1u : 0u;
-            const uint32_t code = mbx::hold_code(state[lo + k].on, on);
-            for (int n = 0; n < 160; ++n) {   // THE definition: every term under its weight, whatever the code
-                acc[n] += mbx::hold_ramped(mbx::mixdown_term(x[n], g), mbx::hold_weight(code, n, hp.ramp_log2), hp.ramp_log2);
-            }
-            state[lo + k] = mbx_gate_input_state{(uint16_t)decided[(size_t)k].hang, (uint8_t)decided[(size_t)k].open, (uint8_t)on};
-        }
-        mbx::mixdown_put_row(form, acc, b, out);
-    }
-    return 0;
+    return held_host("mbx_mixdown_held_host", mbx::mixdown_out_of_form(form), hold, n_buses, bus_offset, src_row, gain_q12, pcm16, nrows, state, out);
+}
+
+int mbx_mixdown_held_sums_host(const mbx_mixdown_hold* hold, int n_buses, const int32_t* bus_offset, const int32_t* src_row,
+                               const int16_t* gain_q12, const int16_t* pcm16, size_t nrows, mbx_gate_input_state* state, int32_t* out) {
+    return held_host("mbx_mixdown_held_sums_host", mbx::kMixdownSums, hold, n_buses, bus_offset, src_row, gain_q12, pcm16, nrows, state, out);
 }
 
 int mbx_mixdown_held(const mbx_mixdown_plan* plan, const mbx_mixdown_hold* hold, mbx_gate_state* state, int form, const int16_t* d_pcm16,
                      size_t nrows, const mbx_row_level* d_levels, void* d_out, void* stream) {
-    const char* const who = "mbx_mixdown_held";
-    mbx::LevelsRefusal levels = mbx::kLevelsOk;
-    mbx::MixdownRefusal mix = mbx::kMixdownOk;
-    const mbx::HoldRefusal why = mbx::held_launch_refused(plan ? &plan->plan : nullptr, plan, hold != nullptr, hold ? hold->open_peak : 0u,
-                                                          hold ? hold->close_peak : 0u, hold ? hold->loudest_n : 0u, hold ? hold->ramp_log2 : 0u,
-                                                          state != nullptr, state ? state->plan : nullptr, form, d_pcm16, nrows, d_levels, d_out,
-                                                          &levels, &mix);
-    if (why != mbx::kHoldOk) {
-        return refuse(who, why, levels, mix);
-    }
-    mbx::MixdownTables t;
-    const int rc = mbx::mixdown_tables(who, plan, &t);
-    if (rc < 0) {
-        return rc;
-    }
-    const mbx::MixdownPlan& p = plan->plan;
-    const mbx::HoldParams hp = params_of(*hold);
-    const hipStream_t strm = (hipStream_t)stream;
-    mbx::mixdown_by_form(form, [&](auto k) {
-        if (p.short_grid) {
-            hipLaunchKernelGGL(mbx::hold_decide_kernel, dim3(mbx::hold_decide_grid(p)), dim3(mbx::kHoldDecideBlock), 0, strm, d_levels, t.bus_offset,
-                               t.short_bus, t.input, p.n_short, hp, state->d_state, state->d_code);
-            hipLaunchKernelGGL(mbx::hold_sum_kernel<k()>, dim3(p.short_grid), dim3(mbx::kMixdownBlock), 0, strm, d_pcm16, t.bus_offset, t.short_bus,
-                               t.input, p.n_short, state->d_code, hp.ramp_log2, d_out);
-        }
-        if (p.long_grid) {
-            hipLaunchKernelGGL(mbx::hold_long_kernel<k()>, dim3(p.long_grid), dim3(mbx::kMixdownBlock), 0, strm, d_pcm16, d_levels, t.bus_offset,
-                               t.long_bus, t.input, hp, state->d_state, d_out);
-        }
-    });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : mbx::hip_failed("", "hold kernels", e);
+    return held_launch("mbx_mixdown_held", plan, hold, state, mbx::mixdown_out_of_form(form), d_pcm16, nrows, d_levels, d_out, stream);
+}
+
+int mbx_mixdown_held_sums(const mbx_mixdown_plan* plan, const mbx_mixdown_hold* hold, mbx_gate_state* state, const int16_t* d_pcm16,
+                          size_t nrows, const mbx_row_level* d_levels, int32_t* d_out, void* stream) {
+    return held_launch("mbx_mixdown_held_sums", plan, hold, state, mbx::kMixdownSums, d_pcm16, nrows, d_levels, d_out, stream);
 }
 
 }  // extern "C"

@@ -140,11 +140,11 @@ static inline HoldRefusal hold_records_refused(const uint32_t* words, size_t n) 
 }
 
 // mbx_mixdown_held: the hold, the state, then everything mbx_mixdown_gated refuses under the gate {open_peak, loudest_n}
-// (*levels and *mix say what when kHoldGated comes back)
+// (*levels and *mix say what when kHoldGated comes back; sums: as gated_launch_refused has it)
 static inline HoldRefusal held_launch_refused(const MixdownPlan* plan, const void* plan_handle, bool have_hold, unsigned open_peak, unsigned close_peak,
                                               unsigned loudest_n, unsigned ramp_log2, bool have_state, const void* state_plan, int form,
                                               const void* d_pcm16, size_t nrows, const void* d_levels, const void* d_out, LevelsRefusal* levels,
-                                              MixdownRefusal* mix) {
+                                              MixdownRefusal* mix, bool sums = false) {
     *levels = kLevelsOk;
     *mix = kMixdownOk;
     const HoldRefusal hold = hold_refused(have_hold, open_peak, close_peak, loudest_n, ramp_log2);
@@ -154,7 +154,7 @@ static inline HoldRefusal held_launch_refused(const MixdownPlan* plan, const voi
     if (!have_state) {
         return kHoldNoState;
     }
-    *levels = gated_launch_refused(plan, true, open_peak, loudest_n, form, d_pcm16, nrows, d_levels, d_out, mix);
+    *levels = gated_launch_refused(plan, true, open_peak, loudest_n, form, d_pcm16, nrows, d_levels, d_out, mix, sums);
     if (*levels != kLevelsOk) {
         return kHoldGated;
     }

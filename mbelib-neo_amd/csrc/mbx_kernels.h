@@ -1,6 +1,6 @@
 // mbx_kernels.h -- every __global__ kernel of libmbx_hip.so, declared exactly once.
-// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
-// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip and mbx_agc.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
+// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
+// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip and mbx_limit.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
 // overload at the launch site or in the instance table), not an unresolved symbol when the library is loaded.
 // A new kernel: declare it here, define it, and -- a stream-stage instance -- give it its row in kInstances (mbx_api.hip).
 #pragma once
@@ -166,6 +166,13 @@ __global__ void hold_long_kernel(const int16_t*, const ::mbx_row_level*, const i
 // frames per entry, rows in, rows out (which may be the rows in) ---------------------------------------------------------------------
 struct AgcParams;
 __global__ void pcm_agc_kernel(AgcParams, uint32_t*, int, const int32_t*, int, int, const int16_t*, int16_t*);
+
+// ---- mbx_limit.hip: limited buses (include/mbx_limit.h) -- behind the sums instances of the bus kernels above (kOut = kMixdownSums,
+// mbx_mixdown.h: acc itself as int32), a look-ahead peak limiter per bus in one of the three output forms: the parameters
+// (mbx_limit_plan.h), the state in place, buses, frames per bus, sums in, rows out ------------------------------------------------------
+struct LimitParams;
+template <int kOut>
+__global__ void bus_limit_kernel(LimitParams, uint32_t*, int, int, const int32_t*, void*);
 
 // ---- mbx_expand.hip ------------------------------------------------------------------------------------------------------------
 __global__ void expand_imbe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);

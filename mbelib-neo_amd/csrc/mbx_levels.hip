@@ -32,6 +32,7 @@
 #include "mbx_kernels.h"
 #include "mbx_levels.h"    // the arithmetic: the private header of this directory
 #include <mbx_levels.h>    // the public header of the same name: include/, first on the include path
+#include <mbx_limit.h>     // (mbx_mixdown_gated_sums and its host twin are declared there)
 #include "mbx_levels_plan.h"
 #include "mbx_mixdown_lanes.h"
 
@@ -165,6 +166,7 @@ mixdown_gated_kernel(const int16_t* __restrict__ pcm16, const mbx_row_level* __r
 template __global__ void mixdown_gated_kernel<kMixdownPcm16>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, int, uint32_t, int, void*);
 template __global__ void mixdown_gated_kernel<kMixdownUlaw>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, int, uint32_t, int, void*);
 template __global__ void mixdown_gated_kernel<kMixdownAlaw>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, int, uint32_t, int, void*);
+template __global__ void mixdown_gated_kernel<kMixdownSums>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, int, uint32_t, int, void*);
 
 // one workgroup per long bus: long_bus[blockIdx.x] is its bus
 template <int kOut>
@@ -254,6 +256,7 @@ mixdown_gated_long_kernel(const int16_t* __restrict__ pcm16, const mbx_row_level
 template __global__ void mixdown_gated_long_kernel<kMixdownPcm16>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, uint32_t, int, void*);
 template __global__ void mixdown_gated_long_kernel<kMixdownUlaw>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, uint32_t, int, void*);
 template __global__ void mixdown_gated_long_kernel<kMixdownAlaw>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, uint32_t, int, void*);
+template __global__ void mixdown_gated_long_kernel<kMixdownSums>(const int16_t*, const mbx_row_level*, const int32_t*, const int32_t*, const MixdownInput*, uint32_t, int, void*);
 
 }  // namespace mbx
 
@@ -266,6 +269,72 @@ int refuse(const char* who, mbx::LevelsRefusal why, mbx::MixdownRefusal mix = mb
         return mbx::misaligned(who, "mbx_levels.h");
     }
     return refuse(who, why == mbx::kGateMixdown ? mbx::mixdown_refusal_text(mix) : mbx::levels_refusal_text(why));
+}
+
+// mbx_mixdown_gated_host and its sums twin: `out_kind` is the caller's form, or kMixdownSums
+int gated_host(const char* who, int out_kind, const mbx_mixdown_gate* gate, int n_buses, const int32_t* bus_offset, const int32_t* src_row,
+               const int16_t* gain_q12, const int16_t* pcm16, size_t nrows, void* out) {
+    const mbx::LevelsRefusal bad_gate = mbx::gate_refused(gate != nullptr, gate ? gate->open_peak : 0u, gate ? gate->loudest_n : 0u);
+    if (bad_gate != mbx::kLevelsOk) {
+        return refuse(who, bad_gate);
+    }
+    mbx::MixdownPlan plan;
+    if (const char* const why = mbx::mixdown_host_out_refused(out_kind, n_buses, bus_offset, src_row, pcm16, nrows, out, &plan)) {
+        return refuse(who, why);
+    }
+    std::vector<uint64_t> keys;
+    for (int b = 0; b < n_buses; ++b) {
+        const int32_t lo = bus_offset[b], count = bus_offset[b + 1] - lo;
+        keys.resize((size_t)count);
+        for (int32_t k = 0; k < count; ++k) {   // (the levels of the rows as they are, before the gain)
+            const mbx::Level l = mbx::level_of_row(pcm16 + (size_t)src_row[lo + k] * 160u);
+            keys[(size_t)k] = mbx::gate_key(l.energy, l.peak, k, gate->open_peak);
+        }
+        const uint64_t threshold = mbx::gate_threshold(keys.data(), count, gate->loudest_n);
+        int32_t acc[160] = {0};
+        for (int32_t k = 0; k < count; ++k) {
+            const int16_t* const x = pcm16 + (size_t)src_row[lo + k] * 160u;
+            // THE definition: an input that is not chosen has the gain 0
+            const int16_t g = keys[(size_t)k] >= threshold ? (gain_q12 ? gain_q12[lo + k] : (int16_t)mbx::kMixdownUnity) : (int16_t)0;
+            for (int n = 0; n < 160; ++n) {
+                acc[n] += mbx::mixdown_term(x[n], g);
+            }
+        }
+        mbx::mixdown_put_row(out_kind, acc, b, out);
+    }
+    return 0;
+}
+
+// mbx_mixdown_gated and its sums twin, down ONE launch path: `out` is the caller's form (mixdown_out_of_form), or kMixdownSums
+int gated_launch(const char* who, const mbx_mixdown_plan* plan, const mbx_mixdown_gate* gate, int out, const int16_t* d_pcm16, size_t nrows,
+                 const mbx_row_level* d_levels, void* d_out, void* stream) {
+    mbx::MixdownRefusal mix = mbx::kMixdownOk;
+    const mbx::LevelsRefusal why = mbx::gated_launch_refused(plan ? &plan->plan : nullptr, gate != nullptr, gate ? gate->open_peak : 0u,
+                                                             gate ? gate->loudest_n : 0u, out, d_pcm16, nrows, d_levels, d_out, &mix,
+                                                             out == mbx::kMixdownSums);
+    if (why != mbx::kLevelsOk) {
+        return refuse(who, why, mix);
+    }
+    mbx::MixdownTables t;
+    const int rc = mbx::mixdown_tables(who, plan, &t);
+    if (rc < 0) {
+        return rc;
+    }
+    const mbx::MixdownPlan& p = plan->plan;
+    const uint32_t open_peak = gate->open_peak;
+    const int loudest_n = gate->loudest_n;
+    mbx::mixdown_by_out(out, [&](auto k) {
+        if (p.short_grid) {
+            hipLaunchKernelGGL(mbx::mixdown_gated_kernel<k()>, dim3(p.short_grid), dim3(mbx::kMixdownBlock), 0, (hipStream_t)stream, d_pcm16, d_levels,
+                               t.bus_offset, t.short_bus, t.input, p.n_short, open_peak, loudest_n, d_out);
+        }
+        if (p.long_grid) {
+            hipLaunchKernelGGL(mbx::mixdown_gated_long_kernel<k()>, dim3(p.long_grid), dim3(mbx::kMixdownBlock), 0, (hipStream_t)stream, d_pcm16,
+                               d_levels, t.bus_offset, t.long_bus, t.input, open_peak, loudest_n, d_out);
+        }
+    });
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : mbx::hip_failed("", "mixdown_gated_kernel", e);
 }
 
 }  // namespace
@@ -306,67 +375,22 @@ int mbx_pcm_levels(const int16_t* d_pcm16, size_t nrows, mbx_row_level* d_levels
 
 int mbx_mixdown_gated_host(int form, const mbx_mixdown_gate* gate, int n_buses, const int32_t* bus_offset, const int32_t* src_row,
                            const int16_t* gain_q12, const int16_t* pcm16, size_t nrows, void* out) {
-    const char* const who = "mbx_mixdown_gated_host";
-    const mbx::LevelsRefusal bad_gate = mbx::gate_refused(gate != nullptr, gate ? gate->open_peak : 0u, gate ? gate->loudest_n : 0u);
-    if (bad_gate != mbx::kLevelsOk) {
-        return refuse(who, bad_gate);
-    }
-    mbx::MixdownPlan plan;
-    if (const char* const why = mbx::mixdown_host_refused(form, n_buses, bus_offset, src_row, pcm16, nrows, out, &plan)) {
-        return refuse(who, why);
-    }
-    std::vector<uint64_t> keys;
-    for (int b = 0; b < n_buses; ++b) {
-        const int32_t lo = bus_offset[b], count = bus_offset[b + 1] - lo;
-        keys.resize((size_t)count);
-        for (int32_t k = 0; k < count; ++k) {   // (the levels of the rows as they are, before the gain)
-            const mbx::Level l = mbx::level_of_row(pcm16 + (size_t)src_row[lo + k] * 160u);
-            keys[(size_t)k] = mbx::gate_key(l.energy, l.peak, k, gate->open_peak);
-        }
-        const uint64_t threshold = mbx::gate_threshold(keys.data(), count, gate->loudest_n);
-        int32_t acc[160] = {0};
-        for (int32_t k = 0; k < count; ++k) {
-            const int16_t* const x = pcm16 + (size_t)src_row[lo + k] * 160u;
-            // THE definition: an input that is not chosen has the gain 0
-            const int16_t g = keys[(size_t)k] >= threshold ? (gain_q12 ? gain_q12[lo + k] : (int16_t)mbx::kMixdownUnity) : (int16_t)0;
-            for (int n = 0; n < 160; ++n) {
-                acc[n] += mbx::mixdown_term(x[n], g);
-            }
-        }
-        mbx::mixdown_put_row(form, acc, b, out);
-    }
-    return 0;
+    return gated_host("mbx_mixdown_gated_host", mbx::mixdown_out_of_form(form), gate, n_buses, bus_offset, src_row, gain_q12, pcm16, nrows, out);
+}
+
+int mbx_mixdown_gated_sums_host(const mbx_mixdown_gate* gate, int n_buses, const int32_t* bus_offset, const int32_t* src_row,
+                                const int16_t* gain_q12, const int16_t* pcm16, size_t nrows, int32_t* out) {
+    return gated_host("mbx_mixdown_gated_sums_host", mbx::kMixdownSums, gate, n_buses, bus_offset, src_row, gain_q12, pcm16, nrows, out);
 }
 
 int mbx_mixdown_gated(const mbx_mixdown_plan* plan, const mbx_mixdown_gate* gate, int form, const int16_t* d_pcm16, size_t nrows,
                       const mbx_row_level* d_levels, void* d_out, void* stream) {
-    const char* const who = "mbx_mixdown_gated";
-    mbx::MixdownRefusal mix = mbx::kMixdownOk;
-    const mbx::LevelsRefusal why = mbx::gated_launch_refused(plan ? &plan->plan : nullptr, gate != nullptr, gate ? gate->open_peak : 0u,
-                                                             gate ? gate->loudest_n : 0u, form, d_pcm16, nrows, d_levels, d_out, &mix);
-    if (why != mbx::kLevelsOk) {
-        return refuse(who, why, mix);
-    }
-    mbx::MixdownTables t;
-    const int rc = mbx::mixdown_tables(who, plan, &t);
-    if (rc < 0) {
-        return rc;
-    }
-    const mbx::MixdownPlan& p = plan->plan;
-    const uint32_t open_peak = gate->open_peak;
-    const int loudest_n = gate->loudest_n;
-    mbx::mixdown_by_form(form, [&](auto k) {
-        if (p.short_grid) {
-            hipLaunchKernelGGL(mbx::mixdown_gated_kernel<k()>, dim3(p.short_grid), dim3(mbx::kMixdownBlock), 0, (hipStream_t)stream, d_pcm16, d_levels,
-                               t.bus_offset, t.short_bus, t.input, p.n_short, open_peak, loudest_n, d_out);
-        }
-        if (p.long_grid) {
-            hipLaunchKernelGGL(mbx::mixdown_gated_long_kernel<k()>, dim3(p.long_grid), dim3(mbx::kMixdownBlock), 0, (hipStream_t)stream, d_pcm16,
-                               d_levels, t.bus_offset, t.long_bus, t.input, open_peak, loudest_n, d_out);
-        }
-    });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : mbx::hip_failed("", "mixdown_gated_kernel", e);
+    return gated_launch("mbx_mixdown_gated", plan, gate, mbx::mixdown_out_of_form(form), d_pcm16, nrows, d_levels, d_out, stream);
+}
+
+int mbx_mixdown_gated_sums(const mbx_mixdown_plan* plan, const mbx_mixdown_gate* gate, const int16_t* d_pcm16, size_t nrows,
+                           const mbx_row_level* d_levels, int32_t* d_out, void* stream) {
+    return gated_launch("mbx_mixdown_gated_sums", plan, gate, mbx::kMixdownSums, d_pcm16, nrows, d_levels, d_out, stream);
 }
 
 }  // extern "C"

@@ -77,10 +77,12 @@ static inline LevelsRefusal gate_refused(bool have_gate, unsigned open_peak, uns
 }
 
 // mbx_mixdown_gated: the gate, d_levels by itself, then everything mbx_mixdown refuses (*mix says what when kGateMixdown comes back),
-// then d_levels against the two arrays of that launch
+// then d_levels against the two arrays of that launch.  sums: the sums twin (include/mbx_limit.h) -- `form` is not looked at, d_out is int32
 static inline LevelsRefusal gated_launch_refused(const MixdownPlan* plan, bool have_gate, unsigned open_peak, unsigned loudest_n, int form,
-                                                 const void* d_pcm16, size_t nrows, const void* d_levels, const void* d_out, MixdownRefusal* mix) {
+                                                 const void* d_pcm16, size_t nrows, const void* d_levels, const void* d_out, MixdownRefusal* mix,
+                                                 bool sums = false) {
     *mix = kMixdownOk;
+    const int out = sums ? kMixdownSums : mixdown_out_of_form(form);
     const LevelsRefusal gate = gate_refused(have_gate, open_peak, loudest_n);
     if (gate != kLevelsOk) {
         return gate;
@@ -92,7 +94,7 @@ static inline LevelsRefusal gated_launch_refused(const MixdownPlan* plan, bool h
     if ((lv & 15u) != 0) {
         return kLevelsAlign;
     }
-    *mix = mixdown_launch_refused(plan, form, d_pcm16, nrows, d_out);
+    *mix = mixdown_out_refused(plan, out, d_pcm16, nrows, d_out);
     if (*mix != kMixdownOk) {
         return kGateMixdown;
     }
@@ -101,7 +103,7 @@ static inline LevelsRefusal gated_launch_refused(const MixdownPlan* plan, bool h
     }
     const uintptr_t lv_bytes = (uintptr_t)nrows * kLevelBytes;
     if (ranges_overlap(lv, lv_bytes, reinterpret_cast<uintptr_t>(d_pcm16), (uintptr_t)nrows * 320u)
-        || ranges_overlap(lv, lv_bytes, reinterpret_cast<uintptr_t>(d_out), (uintptr_t)plan->n_buses * 160u * mixdown_sample_bytes(form))) {
+        || ranges_overlap(lv, lv_bytes, reinterpret_cast<uintptr_t>(d_out), (uintptr_t)plan->n_buses * 160u * mixdown_sample_bytes(out))) {
         return kLevelsOverlap;
     }
     return kLevelsOk;

@@ -26,6 +26,10 @@ static_assert((long long)kMixdownMaxInputs * ((1ll << 18) + 1) < (1ll << 31), "t
 
 MBX_COMPAND_FN bool mixdown_form_ok(int form) { return form == kMixdownPcm16 || form == kMixdownUlaw || form == kMixdownAlaw; }
 
+// NOT a form, and no public number: what the sums instances of the bus kernels write (include/mbx_limit.h) -- acc itself as int32, in
+// front of the clamp.  The sums launches name it beside the forms (mixdown_by_out, mbx_mixdown_plan.h); mixdown_form_ok stays as it is.
+constexpr int kMixdownSums = 3;
+
 MBX_COMPAND_FN int32_t mixdown_term(int16_t x, int16_t gain_q12) { return ((int32_t)x * (int32_t)gain_q12 + 2048) >> 12; }
 
 MBX_COMPAND_FN int16_t mixdown_clamp(int32_t acc) { return (int16_t)(acc < -32768 ? -32768 : (acc > 32767 ? 32767 : acc)); }

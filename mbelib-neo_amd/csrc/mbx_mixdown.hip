@@ -22,6 +22,7 @@
 #include "mbx_kernels.h"
 #include "mbx_mixdown.h"    // the arithmetic: the private header of this directory
 #include <mbx_mixdown.h>    // the public header of the same name: include/, first on the include path
+#include <mbx_limit.h>      // (mbx_mixdown_sums and its host twin are declared there)
 #include "mbx_mixdown_plan.h"
 #include "mbx_mixdown_lanes.h"   // a lane's bus, add, walk, tail and store, shared with mbx_levels.hip and mbx_hold.hip
 
@@ -44,6 +45,7 @@ mixdown_kernel(const int16_t* __restrict__ pcm16, const int32_t* __restrict__ bu
 template __global__ void mixdown_kernel<kMixdownPcm16>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, void*);
 template __global__ void mixdown_kernel<kMixdownUlaw>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, void*);
 template __global__ void mixdown_kernel<kMixdownAlaw>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, void*);
+template __global__ void mixdown_kernel<kMixdownSums>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, int, void*);
 
 // one workgroup per long bus: long_bus[blockIdx.x] is its bus
 template <int kOut>
@@ -71,6 +73,7 @@ mixdown_long_kernel(const int16_t* __restrict__ pcm16, const int32_t* __restrict
 template __global__ void mixdown_long_kernel<kMixdownPcm16>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, void*);
 template __global__ void mixdown_long_kernel<kMixdownUlaw>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, void*);
 template __global__ void mixdown_long_kernel<kMixdownAlaw>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, void*);
+template __global__ void mixdown_long_kernel<kMixdownSums>(const int16_t*, const int32_t*, const int32_t*, const MixdownInput*, void*);
 
 }  // namespace mbx
 
@@ -84,6 +87,53 @@ int mixdown_plan_device(const mbx_mixdown_plan* plan) { return plan ? plan->devi
 namespace {
 
 int refuse(const char* who, mbx::MixdownRefusal why) { return mbx::refuse(who, mbx::mixdown_refusal_text(why)); }
+
+// mbx_mixdown_host and its sums twin: `out_kind` is the caller's form, or kMixdownSums
+int mixdown_host(const char* who, int out_kind, int n_buses, const int32_t* bus_offset, const int32_t* src_row, const int16_t* gain_q12,
+                 const int16_t* pcm16, size_t nrows, void* out) {
+    mbx::MixdownPlan plan;
+    if (const char* const why = mbx::mixdown_host_out_refused(out_kind, n_buses, bus_offset, src_row, pcm16, nrows, out, &plan)) {
+        return mbx::refuse(who, why);
+    }
+    for (int b = 0; b < n_buses; ++b) {
+        int32_t acc[160] = {0};
+        for (int32_t k = bus_offset[b]; k < bus_offset[b + 1]; ++k) {
+            const int16_t* const x = pcm16 + (size_t)src_row[k] * 160u;
+            const int16_t g = gain_q12 ? gain_q12[k] : (int16_t)mbx::kMixdownUnity;
+            for (int n = 0; n < 160; ++n) {
+                acc[n] += mbx::mixdown_term(x[n], g);
+            }
+        }
+        mbx::mixdown_put_row(out_kind, acc, b, out);
+    }
+    return 0;
+}
+
+// mbx_mixdown and its sums twin, down ONE launch path: `out` is the caller's form (mixdown_out_of_form), or kMixdownSums
+int mixdown_launch(const char* who, const mbx_mixdown_plan* plan, int out, const int16_t* d_pcm16, size_t nrows, void* d_out, void* stream) {
+    const mbx::MixdownRefusal why = mbx::mixdown_out_refused(plan ? &plan->plan : nullptr, out, d_pcm16, nrows, d_out);
+    if (why != mbx::kMixdownOk) {
+        return why == mbx::kMixdownAlign ? mbx::misaligned(who, "mbx_mixdown.h") : refuse(who, why);
+    }
+    mbx::MixdownTables t;
+    const int rc = mbx::mixdown_tables(who, plan, &t);
+    if (rc < 0) {
+        return rc;
+    }
+    const mbx::MixdownPlan& p = plan->plan;
+    mbx::mixdown_by_out(out, [&](auto k) {
+        if (p.short_grid) {
+            hipLaunchKernelGGL(mbx::mixdown_kernel<k()>, dim3(p.short_grid), dim3(mbx::kMixdownBlock), 0, (hipStream_t)stream, d_pcm16, t.bus_offset,
+                               t.short_bus, t.input, p.n_short, d_out);
+        }
+        if (p.long_grid) {
+            hipLaunchKernelGGL(mbx::mixdown_long_kernel<k()>, dim3(p.long_grid), dim3(mbx::kMixdownBlock), 0, (hipStream_t)stream, d_pcm16, t.bus_offset,
+                               t.long_bus, t.input, d_out);
+        }
+    });
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : mbx::hip_failed("", "mixdown_kernel", e);
+}
 
 }  // namespace
 
@@ -153,49 +203,20 @@ int mbx_mixdown_plan_long_buses(const mbx_mixdown_plan* plan) { return plan ? pl
 
 int mbx_mixdown_host(int form, int n_buses, const int32_t* bus_offset, const int32_t* src_row, const int16_t* gain_q12, const int16_t* pcm16,
                      size_t nrows, void* out) {
-    const char* const who = "mbx_mixdown_host";
-    mbx::MixdownPlan plan;
-    if (const char* const why = mbx::mixdown_host_refused(form, n_buses, bus_offset, src_row, pcm16, nrows, out, &plan)) {
-        return mbx::refuse(who, why);
-    }
-    for (int b = 0; b < n_buses; ++b) {
-        int32_t acc[160] = {0};
-        for (int32_t k = bus_offset[b]; k < bus_offset[b + 1]; ++k) {
-            const int16_t* const x = pcm16 + (size_t)src_row[k] * 160u;
-            const int16_t g = gain_q12 ? gain_q12[k] : (int16_t)mbx::kMixdownUnity;
-            for (int n = 0; n < 160; ++n) {
-                acc[n] += mbx::mixdown_term(x[n], g);
-            }
-        }
-        mbx::mixdown_put_row(form, acc, b, out);
-    }
-    return 0;
+    return mixdown_host("mbx_mixdown_host", mbx::mixdown_out_of_form(form), n_buses, bus_offset, src_row, gain_q12, pcm16, nrows, out);
+}
+
+int mbx_mixdown_sums_host(int n_buses, const int32_t* bus_offset, const int32_t* src_row, const int16_t* gain_q12, const int16_t* pcm16, size_t nrows,
+                          int32_t* out) {
+    return mixdown_host("mbx_mixdown_sums_host", mbx::kMixdownSums, n_buses, bus_offset, src_row, gain_q12, pcm16, nrows, out);
 }
 
 int mbx_mixdown(const mbx_mixdown_plan* plan, int form, const int16_t* d_pcm16, size_t nrows, void* d_out, void* stream) {
-    const char* const who = "mbx_mixdown";
-    const mbx::MixdownRefusal why = mbx::mixdown_launch_refused(plan ? &plan->plan : nullptr, form, d_pcm16, nrows, d_out);
-    if (why != mbx::kMixdownOk) {
-        return why == mbx::kMixdownAlign ? mbx::misaligned(who, "mbx_mixdown.h") : refuse(who, why);
-    }
-    mbx::MixdownTables t;
-    const int rc = mbx::mixdown_tables(who, plan, &t);
-    if (rc < 0) {
-        return rc;
-    }
-    const mbx::MixdownPlan& p = plan->plan;
-    mbx::mixdown_by_form(form, [&](auto k) {
-        if (p.short_grid) {
-            hipLaunchKernelGGL(mbx::mixdown_kernel<k()>, dim3(p.short_grid), dim3(mbx::kMixdownBlock), 0, (hipStream_t)stream, d_pcm16, t.bus_offset,
-                               t.short_bus, t.input, p.n_short, d_out);
-        }
-        if (p.long_grid) {
-            hipLaunchKernelGGL(mbx::mixdown_long_kernel<k()>, dim3(p.long_grid), dim3(mbx::kMixdownBlock), 0, (hipStream_t)stream, d_pcm16, t.bus_offset,
-                               t.long_bus, t.input, d_out);
-        }
-    });
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : mbx::hip_failed("", "mixdown_kernel", e);
+    return mixdown_launch("mbx_mixdown", plan, mbx::mixdown_out_of_form(form), d_pcm16, nrows, d_out, stream);
+}
+
+int mbx_mixdown_sums(const mbx_mixdown_plan* plan, const int16_t* d_pcm16, size_t nrows, int32_t* d_out, void* stream) {
+    return mixdown_launch("mbx_mixdown_sums", plan, mbx::kMixdownSums, d_pcm16, nrows, d_out, stream);
 }
 
 }  // extern "C"

@@ -72,11 +72,16 @@ __device__ __forceinline__ void mixdown_sum(const int16_t* __restrict__ pcm16, c
     }
 }
 
-// the lane's eight sums -> the piece of the bus row, in the form of the instance: one 16-byte or one 8-byte store
+// the lane's eight sums -> the piece of the bus row, in the form of the instance: one 16-byte or one 8-byte store; a sums instance
+// (kMixdownSums, include/mbx_limit.h) stores the eight sums themselves, two 16-byte stores
 template <int kOut>
 __device__ __forceinline__ void mixdown_store(void* __restrict__ out, int bus, int piece, const int32_t acc[kMixdownPiece]) {
     const size_t at = (size_t)bus * 160u + (size_t)(piece * kMixdownPiece);
-    if constexpr (kOut == kMixdownPcm16) {
+    if constexpr (kOut == kMixdownSums) {
+        int4* const to = reinterpret_cast<int4*>(static_cast<int32_t*>(out) + at);
+        to[0] = int4{acc[0], acc[1], acc[2], acc[3]};
+        to[1] = int4{acc[4], acc[5], acc[6], acc[7]};
+    } else if constexpr (kOut == kMixdownPcm16) {
         const auto pair = [&](int i) { return (uint32_t)(uint16_t)mixdown_clamp(acc[i]) | ((uint32_t)(uint16_t)mixdown_clamp(acc[i + 1]) << 16); };
         *reinterpret_cast<uint4*>(static_cast<int16_t*>(out) + at) = uint4{pair(0), pair(2), pair(4), pair(6)};
     } else {

@@ -162,19 +162,18 @@ static inline void fill_mixdown_tables(const MixdownPlan& plan, const int32_t* b
     }
 }
 
-static inline size_t mixdown_sample_bytes(int form) { return form == kMixdownPcm16 ? 2 : 1; }
+// bytes of a sample out: of a form, or of the sums (kMixdownSums, include/mbx_limit.h)
+static inline size_t mixdown_sample_bytes(int out) { return out == kMixdownSums ? 4 : out == kMixdownPcm16 ? 2 : 1; }
 
-// what mbx_mixdown refuses of its arguments, before a device is asked for.  The pointers are never dereferenced.
-// Alignment: d_pcm16 16 (a piece of 8 samples is one 16-byte load), d_out 16 as int16 and 8 as bytes (a piece is one store).
-static inline MixdownRefusal mixdown_launch_refused(const MixdownPlan* plan, int form, const void* d_pcm16, size_t nrows, const void* d_out) {
-    if (!mixdown_form_ok(form)) {
-        return kMixdownForm;
-    }
+// what a bus launch refuses of its buffers, before a device is asked for: `out` is a form that was checked, or kMixdownSums.  The
+// pointers are never dereferenced.
+// Alignment: d_pcm16 16 (a piece of 8 samples is one 16-byte load), d_out 16 as int16 or int32 and 8 as bytes (a piece is one store, or two).
+static inline MixdownRefusal mixdown_buffers_refused(const MixdownPlan* plan, int out, const void* d_pcm16, size_t nrows, const void* d_out) {
     if (!d_pcm16 || !d_out) {
         return kMixdownPointers;
     }
     const uintptr_t in = reinterpret_cast<uintptr_t>(d_pcm16), to = reinterpret_cast<uintptr_t>(d_out);
-    if ((in & 15u) != 0 || (to & (form == kMixdownPcm16 ? 15u : 7u)) != 0) {
+    if ((in & 15u) != 0 || (to & (mixdown_sample_bytes(out) > 1 ? 15u : 7u)) != 0) {
         return kMixdownAlign;
     }
     if (!plan) {   // (behind the pointers' own checks: those need no plan, and a host without a device can make none)
@@ -184,21 +183,30 @@ static inline MixdownRefusal mixdown_launch_refused(const MixdownPlan* plan, int
         return kMixdownRows;
     }
     // (the caller's nrows rows, whether the plan reads them all or not, and the output as far as it is written)
-    const uintptr_t in_bytes = (uintptr_t)nrows * 320u, to_bytes = (uintptr_t)plan->n_buses * 160u * mixdown_sample_bytes(form);
+    const uintptr_t in_bytes = (uintptr_t)nrows * 320u, to_bytes = (uintptr_t)plan->n_buses * 160u * mixdown_sample_bytes(out);
     if (in < to + to_bytes && to < in + in_bytes) {
         return kMixdownOverlap;
     }
     return kMixdownOk;
 }
 
+// what mbx_mixdown refuses of its arguments: the form, then the buffers
+static inline MixdownRefusal mixdown_launch_refused(const MixdownPlan* plan, int form, const void* d_pcm16, size_t nrows, const void* d_out) {
+    return mixdown_form_ok(form) ? mixdown_buffers_refused(plan, form, d_pcm16, nrows, d_out) : kMixdownForm;
+}
+// a caller's form as the `out` of a path a launch shares with its sums twin: never kMixdownSums, whatever number the caller gave
+static inline int mixdown_out_of_form(int form) { return mixdown_form_ok(form) ? form : -1; }
+// a public launch (a form, checked) or its sums twin (kMixdownSums, which no caller can give: the twins have no form argument)
+static inline MixdownRefusal mixdown_out_refused(const MixdownPlan* plan, int out, const void* d_pcm16, size_t nrows, const void* d_out) {
+    return out == kMixdownSums ? mixdown_buffers_refused(plan, out, d_pcm16, nrows, d_out) : mixdown_launch_refused(plan, out, d_pcm16, nrows, d_out);
+}
+
 // ---- the host definitions (mbx_mixdown_host, mbx_mixdown_gated_host, mbx_mixdown_held_host) -----------------------------------------
 // what all three refuse of these arguments, in this order, behind what each refuses of its gate or hold: the form, the plan's own, the
 // pointers, rows short of the plan.  nullptr: nothing, and *plan is the plan of the arrays.
-static inline const char* mixdown_host_refused(int form, int n_buses, const int32_t* bus_offset, const int32_t* src_row, const int16_t* pcm16,
-                                               size_t nrows, const void* out, MixdownPlan* plan) {
-    if (!mixdown_form_ok(form)) {
-        return mixdown_refusal_text(kMixdownForm);
-    }
+// (mixdown_host_arrays_refused: all of it but the form, for the sums twins of include/mbx_limit.h, whose callers give no form)
+static inline const char* mixdown_host_arrays_refused(int n_buses, const int32_t* bus_offset, const int32_t* src_row, const int16_t* pcm16, size_t nrows,
+                                                      const void* out, MixdownPlan* plan) {
     const MixdownRefusal why = plan_mixdown(n_buses, bus_offset, src_row, 0, plan);
     if (why != kMixdownOk) {
         return mixdown_refusal_text(why);
@@ -208,11 +216,23 @@ static inline const char* mixdown_host_refused(int form, int n_buses, const int3
     }
     return nrows < (size_t)plan->rows_needed ? mixdown_refusal_text(kMixdownRows) : nullptr;
 }
+static inline const char* mixdown_host_refused(int form, int n_buses, const int32_t* bus_offset, const int32_t* src_row, const int16_t* pcm16,
+                                               size_t nrows, const void* out, MixdownPlan* plan) {
+    return mixdown_form_ok(form) ? mixdown_host_arrays_refused(n_buses, bus_offset, src_row, pcm16, nrows, out, plan) : mixdown_refusal_text(kMixdownForm);
+}
+// a public host definition (a form) or its sums twin (kMixdownSums)
+static inline const char* mixdown_host_out_refused(int out_kind, int n_buses, const int32_t* bus_offset, const int32_t* src_row, const int16_t* pcm16,
+                                                   size_t nrows, const void* out, MixdownPlan* plan) {
+    return out_kind == kMixdownSums ? mixdown_host_arrays_refused(n_buses, bus_offset, src_row, pcm16, nrows, out, plan)
+                                    : mixdown_host_refused(out_kind, n_buses, bus_offset, src_row, pcm16, nrows, out, plan);
+}
 
-// the 160 sums of bus b into row b of out, in `form`: the clamp, or the byte
+// the 160 sums of bus b into row b of out, in `form`: the clamp, or the byte; or (kMixdownSums) as they are
 static inline void mixdown_put_row(int form, const int32_t acc[160], int b, void* out) {
     for (int n = 0; n < 160; ++n) {
-        if (form == kMixdownPcm16) {
+        if (form == kMixdownSums) {
+            static_cast<int32_t*>(out)[(size_t)b * 160u + n] = acc[n];
+        } else if (form == kMixdownPcm16) {
             static_cast<int16_t*>(out)[(size_t)b * 160u + n] = mixdown_clamp(acc[n]);
         } else {
             static_cast<uint8_t*>(out)[(size_t)b * 160u + n] = mixdown_byte(form, acc[n]);
@@ -229,6 +249,15 @@ static inline void mixdown_by_form(int form, F f) {
         f(std::integral_constant<int, kMixdownUlaw>());
     } else {
         f(std::integral_constant<int, kMixdownAlaw>());
+    }
+}
+// the same for what a launch writes: a form, or -- BESIDE the forms, not among them -- the sums
+template <class F>
+static inline void mixdown_by_out(int out, F f) {
+    if (out == kMixdownSums) {
+        f(std::integral_constant<int, kMixdownSums>());
+    } else {
+        mixdown_by_form(out, f);
     }
 }
 

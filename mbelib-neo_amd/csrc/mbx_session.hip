@@ -33,6 +33,8 @@
 #include "mbx.h"
 #include <mbx_agc.h>       // (levelled rows: the public header)
 #include "mbx_agc_plan.h"      // (what an agc is refused for, and the device and the size of a state)
+#include <mbx_limit.h>     // (limited buses: the public header)
+#include "mbx_limit_plan.h"    // (what a limit is refused for, and the device, the size and the scratch of a state)
 #include "mbx_burst.h"
 #include "mbx_burst_groups.h"
 #include "mbx_codec.h"
@@ -205,6 +207,10 @@ struct NextOut {
     // front of every other launch behind the step; nullptr: nothing attached
     void*                   agc_state = nullptr;
     mbx_agc                 agc = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the buses limited under `limit` with the caller's `limit_state` (mbx_session_next_limit, include/mbx_limit.h): their sums into the
+    // state's scratch, then the limiter into the slot's bus buffer in `form`; nullptr: nothing attached
+    void*                   limit_state = nullptr;
+    mbx_limit               limit = {0, 0, 0, 0, {0, 0, 0}};
     bool wants_levels() const { return levels || (buses && kind != kMixPlain); }
     // the step is handed the slot's int16 rows: for the caller, or for the compand, the levels and the mix-down behind the step; an
     // attached AGC advances its state whether or not anybody takes the rows
@@ -350,10 +356,25 @@ int copy_out(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
     return 0;
 }
 
+// a limiter attached to a submit (mbx_session_next_limit): what the submit refuses of it, before anything is queued -- no buses to
+// limit, or a plan of more buses than the state has records and scratch for; nullptr: nothing
+const char* limit_refused_text(const NextOut& next) {
+    if (!next.limit_state) {
+        return nullptr;
+    }
+    if (!next.buses) {
+        return "a limiter is attached (mbx_session_next_limit) and no buses are";
+    }
+    return mbx_mixdown_plan_buses(next.plan) > static_cast<const mbx_limit_state*>(next.limit_state)->buses
+               ? "the plan has more buses than the limiter's state (mbx_limit_state_buses)"
+               : nullptr;
+}
+
 // Behind the step of a submit of nf frames, on the compute stream: FIRST the slot's int16 rows levelled in place where an AGC is
 // attached (the records of the submit's streams: its index on the device, or 0 .. n-1); then those rows -> companded bytes where a
 // destination is attached; their level records, once per submit, for the caller or for the gate of its buses or both; the plan's buses of those rows
-// (one or two more launches); then the outputs out.
+// (one or two more launches) -- under an attached limiter their sums into the limiter's scratch and the limited rows from there, one
+// launch more; then the outputs out.
 int behind_step(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
     const NextOut& next = c.next;
     int16_t* const d16 = sl.dout<int16_t>(mbx::kOutPcm16);
@@ -368,7 +389,16 @@ int behind_step(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
         || (next.wants_levels() && (rc = mbx_pcm_levels(d16, nf, dlev, s->s_comp)) < 0)) {
         return rc;
     }
-    if (next.buses && next.kind == kMixHeld) {
+    if (next.buses && next.limit_state) {
+        mbx_limit_state* const lim = static_cast<mbx_limit_state*>(next.limit_state);
+        int32_t* const dsums = mbx_limit_state_sums(lim);
+        rc = next.kind == kMixHeld    ? mbx_mixdown_held_sums(next.plan, &next.hold, next.state, d16, nf, dlev, dsums, s->s_comp)
+             : next.kind == kMixGated ? mbx_mixdown_gated_sums(next.plan, &next.gate, d16, nf, dlev, dsums, s->s_comp)
+                                      : mbx_mixdown_sums(next.plan, d16, nf, dsums, s->s_comp);
+        if (rc >= 0) {
+            rc = mbx_bus_limit(&next.limit, lim, mbx_mixdown_plan_buses(next.plan), 1, dsums, next.form, dmix, s->s_comp);
+        }
+    } else if (next.buses && next.kind == kMixHeld) {
         rc = mbx_mixdown_held(next.plan, &next.hold, next.state, next.form, d16, nf, dlev, dmix, s->s_comp);
     } else if (next.buses && next.kind == kMixGated) {
         rc = mbx_mixdown_gated(next.plan, &next.gate, next.form, d16, nf, dlev, dmix, s->s_comp);
@@ -467,6 +497,9 @@ int submit(mbx_session* s, const Submit& c) {
     const mbx::SessionRefusal why = mbx::frames_submit_refused(shape_of(s, c), c.frames != nullptr, c.n, c.T);
     if (why != mbx::kSessionOk) {
         return refused("mbx_session_submit", why, c, (size_t)c.n * (size_t)c.T);
+    }
+    if (const char* const text = limit_refused_text(c.next)) {
+        return mbx::refuse("mbx_session_submit", text);
     }
     int rc = 0;
     if (c.burst) {   // bursts of a form that can be invalid: a bit byte > 1, a dibit > 3, a soft hard decision > 1 (mbx_burst_validate); every LLR is a valid one
@@ -845,6 +878,19 @@ int mbx_session_next_agc(mbx_session* s, const mbx_agc* agc, mbx_agc_state* stat
     return next_attach("mbx_session_next_agc", s, state, &NextOut::agc_state, why, [&](NextOut& next) { next.agc_state = state, next.agc = *agc; });
 }
 
+// ---- limited buses (include/mbx_limit.h): the buses of the next submit under a limiter, the caller's state advanced by one frame ------
+int mbx_session_next_limit(mbx_session* s, const mbx_limit* limit, mbx_limit_state* state) {
+    const auto why = [&]() -> const char* {
+        const mbx::LimitRefusal bad = mbx::limit_refused(limit != nullptr, limit ? limit->ceiling : 0u, limit ? limit->ramp_log2 : 0u,
+                                                         limit ? (unsigned)(limit->zero[0] | limit->zero[1] | limit->zero[2]) : 0u);
+        if (bad != mbx::kLimitOk) {
+            return mbx::limit_refusal_text(bad);
+        }
+        return state->device != s->device ? "a state of another device than the session" : nullptr;
+    };
+    return next_attach("mbx_session_next_limit", s, state, &NextOut::limit_state, why, [&](NextOut& next) { next.limit_state = state, next.limit = *limit; });
+}
+
 int mbx_session_next_levels(mbx_session* s, mbx_row_level* out) {
     const auto why = [&]() -> const char* { return s->outputs & MBX_SESSION_LEVELS ? nullptr : "the session was created without MBX_SESSION_LEVELS"; };
     return next_attach("mbx_session_next_levels", s, out, &NextOut::levels, why, [&](NextOut& next) { next.levels = out; });
@@ -954,6 +1000,9 @@ int mbx_session_submit_burst_groups(mbx_session* s, const mbx_burst_group* group
     }
     if (c.next.agc_state) {   // (the groups have different frame counts: one launch of mbx_pcm_agc has one T)
         return mbx::refuse(who, "an AGC is attached (mbx_session_next_agc): burst groups take none");
+    }
+    if (const char* const text = limit_refused_text(c.next)) {   // (a limiter they may take: buses have no T)
+        return mbx::refuse(who, text);
     }
     mbx::GroupShape shapes[MBX_BURST_MAX_GROUPS];
     mbx::GroupPlan gp;

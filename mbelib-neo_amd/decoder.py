@@ -15,7 +15,9 @@ mixdown(pcm16, plan, form) -- the rows summed into talkgroup buses, a gain per i
 levels(pcm16) -- a level record per row, and mixdown_gated(pcm16, plan, form, open_peak, loudest_n) -- the buses of the open / the N
 loudest inputs (include/mbx_levels.h); mixdown_held(pcm16, plan, state, hold, form) -- the same with hysteresis, hang time and ramps,
 a state record per input kept on the device (include/mbx_hold.h); agc(pcm16, T, state, agc) -- the rows levelled by a per-stream
-automatic gain, a state record per stream kept on the device (include/mbx_agc.h).
+automatic gain, a state record per stream kept on the device (include/mbx_agc.h); mixdown_sums / mixdown_gated_sums /
+mixdown_held_sums -- the buses as int32 sums in front of the clamp, and bus_limit(sums, T, state, limit, form) -- those sums under a
+look-ahead peak limiter, a state record per bus kept on the device (include/mbx_limit.h).
 """
 import numpy as np
 
@@ -253,6 +255,76 @@ class BatchDecoder:
             rc = _native.lib().mbx_pcm_agc(ctypes.addressof(agc), state.handle, None if stream_index is None else stream_index.data_ptr(), rows // T, T,
                                            pcm16.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(rc, "mbx_pcm_agc")
+        return out
+
+    def mixdown_sums(self, pcm16, plan, out=None):
+        """The sums of mixdown (include/mbx_limit.h): mbx_mixdown_sums on the current torch stream -- the buses of `plan` as int32
+        [plan.buses, 160], the sum in front of the clamp, the values limit.sums gives on the host.  out: a contiguous int32 tensor of
+        that element count."""
+        torch = _torch()
+        n = _pcm16_rows(pcm16)
+        out = _sums_out(pcm16, plan, out)
+        with torch.cuda.device(pcm16.device):
+            rc = _native.lib().mbx_mixdown_sums(plan.handle, pcm16.data_ptr(), n, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_mixdown_sums")
+        return out
+
+    def mixdown_gated_sums(self, pcm16, plan, open_peak=0, loudest_n=0, levels=None, out=None):
+        """The sums of mixdown_gated (include/mbx_limit.h): mbx_mixdown_gated_sums on the current torch stream, the values
+        limit.sums_gated gives on the host.  levels and out: as for mixdown_gated and mixdown_sums."""
+        import ctypes
+
+        from . import levels as _levels
+
+        torch = _torch()
+        levels, n = self._levels_for(pcm16, levels)
+        out = _sums_out(pcm16, plan, out)
+        if not (0 <= int(open_peak) <= 0xFFFF and 0 <= int(loudest_n) <= 0xFFFF):
+            raise ValueError("open_peak and loudest_n are uint16 fields of the gate")
+        gate = _levels.Gate(int(open_peak), int(loudest_n))
+        with torch.cuda.device(pcm16.device):
+            rc = _native.lib().mbx_mixdown_gated_sums(plan.handle, ctypes.addressof(gate), pcm16.data_ptr(), n, levels.data_ptr(), out.data_ptr(),
+                                                      torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_mixdown_gated_sums")
+        return out
+
+    def mixdown_held_sums(self, pcm16, plan, state, hold, levels=None, out=None):
+        """The sums of mixdown_held (include/mbx_limit.h): mbx_mixdown_held_sums on the current torch stream, `state` advanced by one
+        frame, the values limit.sums_held gives on the host.  levels and out: as for mixdown_held and mixdown_sums."""
+        import ctypes
+
+        torch = _torch()
+        levels, n = self._levels_for(pcm16, levels)
+        out = _sums_out(pcm16, plan, out)
+        with torch.cuda.device(pcm16.device):
+            rc = _native.lib().mbx_mixdown_held_sums(plan.handle, ctypes.addressof(hold), state.handle, pcm16.data_ptr(), n, levels.data_ptr(),
+                                                     out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_mixdown_held_sums")
+        return out
+
+    def bus_limit(self, sums, T, state, limit, form=0, out=None):
+        """Limited buses (include/mbx_limit.h): mbx_bus_limit on the current torch stream -- the int32 sums [n * T, 160] of a sums call
+        (a contiguous device tensor, bus-major) under `limit` (a limit.Limit) and `state` (a limit.LimitState) advanced by T frames ->
+        [n * T, 160] int16 (mixdown.PCM16) or G.711 bytes (mixdown.ULAW, mixdown.ALAW), the values limit.step gives on the host.
+        out: a contiguous tensor of that element count and dtype."""
+        import ctypes
+
+        torch = _torch()
+        T = int(T)
+        if sums.dtype != torch.int32 or not sums.is_contiguous() or sums.numel() % 160:
+            raise ValueError("sums must be a contiguous int32 tensor of rows of 160 samples")
+        rows = sums.numel() // 160
+        if T <= 0 or rows % T:
+            raise ValueError("sums must hold n * T rows")
+        dtype = torch.int16 if int(form) == 0 else torch.uint8
+        if out is None:
+            out = torch.empty((rows, 160), dtype=dtype, device=sums.device)
+        elif out.dtype != dtype or not out.is_contiguous() or out.numel() != rows * 160 or out.device != sums.device:
+            raise ValueError("out must be a contiguous tensor of 160 samples per row, int16 or uint8 by the form, on the device of sums")
+        with torch.cuda.device(sums.device):
+            rc = _native.lib().mbx_bus_limit(ctypes.addressof(limit), state.handle, rows // T, T, sums.data_ptr(), int(form), out.data_ptr(),
+                                             torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_bus_limit")
         return out
 
     def decode_soft(self, soft, T, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None, keystream=None):
@@ -666,6 +738,16 @@ def _bus_out(pcm16, plan, form, out):
         return torch.empty((plan.buses, 160), dtype=dtype, device=pcm16.device)
     if out.dtype != dtype or not out.is_contiguous() or out.numel() != plan.buses * 160 or out.device != pcm16.device:
         raise ValueError("out must be a contiguous tensor of 160 samples per bus, int16 or uint8 by the form, on the device of pcm16")
+    return out
+
+
+def _sums_out(pcm16, plan, out):
+    """the int32 sums of the buses of `plan` on the device of pcm16: a new tensor, or the caller's, checked"""
+    torch = _torch()
+    if out is None:
+        return torch.empty((plan.buses, 160), dtype=torch.int32, device=pcm16.device)
+    if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != plan.buses * 160 or out.device != pcm16.device:
+        raise ValueError("out must be a contiguous int32 tensor of 160 sums per bus on the device of pcm16")
     return out
 
 
