@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h,
-include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h, include/mbx_hold.h, include/mbx_agc.h, include/mbx_limit.h).  Fails loudly when the library
+include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h, include/mbx_hold.h, include/mbx_agc.h, include/mbx_limit.h, include/mbx_resample.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -241,6 +241,19 @@ _LIMIT_SIGNATURES = {
     "mbx_session_next_limit": (C.c_int, [_vp, _vp, _vp]),
 }
 LIMIT_SYMBOLS = tuple(_LIMIT_SIGNATURES)
+# wide rows (include/mbx_resample.h): int16 rows upsampled by a polyphase FIR interpolator, a 64-byte history record per row on the device
+_RESAMPLE_SIGNATURES = {
+    "mbx_resample_state_create": (C.c_int, [_vp, C.c_int]),
+    "mbx_resample_state_destroy": (C.c_int, [_vp]),
+    "mbx_resample_state_streams": (C.c_int, [_vp]),
+    "mbx_resample_state_reset": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "mbx_resample_state_get": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "mbx_resample_state_set": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "mbx_pcm_resample": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "mbx_pcm_resample_host": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "mbx_session_next_resample": (C.c_int, [_vp, _vp, _vp, _vp]),
+}
+RESAMPLE_SYMBOLS = tuple(_RESAMPLE_SIGNATURES)
 
 
 class BurstGroupStruct(C.Structure):
@@ -270,7 +283,8 @@ def lib():
         except OSError as e:  # e.g. libamdhip64 not found
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
         for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES, **_KEYSTREAM_SIGNATURES, **_PCM8_SIGNATURES,
-                                   **_MIXDOWN_SIGNATURES, **_LEVELS_SIGNATURES, **_HOLD_SIGNATURES, **_AGC_SIGNATURES, **_LIMIT_SIGNATURES}.items():
+                                   **_MIXDOWN_SIGNATURES, **_LEVELS_SIGNATURES, **_HOLD_SIGNATURES, **_AGC_SIGNATURES, **_LIMIT_SIGNATURES,
+                                   **_RESAMPLE_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

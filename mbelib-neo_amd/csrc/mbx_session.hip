@@ -35,6 +35,8 @@
 #include "mbx_agc_plan.h"      // (what an agc is refused for, and the device and the size of a state)
 #include <mbx_limit.h>     // (limited buses: the public header)
 #include "mbx_limit_plan.h"    // (what a limit is refused for, and the device, the size and the scratch of a state)
+#include <mbx_resample.h>  // (wide rows: the public header)
+#include "mbx_resample_plan.h" // (what a resampler is refused for, and the device and the size of a state)
 #include "mbx_burst.h"
 #include "mbx_burst_groups.h"
 #include "mbx_codec.h"
@@ -111,7 +113,10 @@ struct Slot {
     void*      d_workspace = nullptr;
     hipEvent_t comp = nullptr, done = nullptr;
     bool       busy = false;
-    CopyOut    staged[mbx::kOutCount];
+    // the buses of a submit resampled (mbx_session_next_resample, include/mbx_resample.h): made by the slot's first resampled submit,
+    // and made anew by one that needs more, so a session that never sees one pays for neither the buffer nor its staging
+    Pair       wide;
+    CopyOut    staged[mbx::kOutCount + 1];   // (the outputs of the table, and the wide buses)
     int        nout = 0;
     template <class U> U* din(int which) { return reinterpret_cast<U*>(in[which].d.p); }
     template <class U> U* dout(int which) { return reinterpret_cast<U*>(out[which].d.p); }
@@ -211,6 +216,12 @@ struct NextOut {
     // state's scratch, then the limiter into the slot's bus buffer in `form`; nullptr: nothing attached
     void*                   limit_state = nullptr;
     mbx_limit               limit = {0, 0, 0, 0, {0, 0, 0}};
+    // the buses resampled under `resample` with the caller's `resample_state` into `wide` (mbx_session_next_resample,
+    // include/mbx_resample.h): one launch behind the bus launches, from the slot's bus buffer into the slot's wide buffer; nullptr:
+    // nothing attached
+    void*                   resample_state = nullptr;
+    void*                   wide = nullptr;    // host memory, the plan's buses * 160 * L int16
+    mbx_resample            resample = {};
     bool wants_levels() const { return levels || (buses && kind != kMixPlain); }
     // the step is handed the slot's int16 rows: for the caller, or for the compand, the levels and the mix-down behind the step; an
     // attached AGC advances its state whether or not anybody takes the rows
@@ -352,6 +363,21 @@ int copy_out(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
             return mbx::hip_failed("session: ", "hipMemcpyAsync (device to host)", e);
         }
     }
+    if (c.next.resample_state && buses > 0) {   // the wide buses, on the road every output takes: a pinned destination in place, a pageable one staged
+        const size_t bytes = mbx::wide_bytes(buses, c.next.resample.L);
+        void* dst = c.next.wide;
+        if (!is_pinned(dst)) {
+            if (const int rc = sl.wide.h.need(bytes); rc < 0) {
+                return rc;
+            }
+            dst = sl.wide.h.p;
+            sl.staged[sl.nout++] = CopyOut{c.next.wide, dst, bytes};
+        }
+        const hipError_t e = hipMemcpyAsync(dst, sl.wide.d.p, bytes, hipMemcpyDeviceToHost, s->s_out);
+        if (e != hipSuccess) {
+            return mbx::hip_failed("session: ", "hipMemcpyAsync (device to host)", e);
+        }
+    }
     S_TRY(hipEventRecord(sl.done, s->s_out));
     return 0;
 }
@@ -370,11 +396,30 @@ const char* limit_refused_text(const NextOut& next) {
                : nullptr;
 }
 
+// a resampler attached to a submit (mbx_session_next_resample): what the submit refuses of it, before anything is queued -- no buses to
+// resample, buses that are not int16, a plan of more buses than the state has records, or a state of another device; nullptr: nothing
+const char* resample_refused_text(const mbx_session* s, const NextOut& next) {
+    if (!next.resample_state) {
+        return nullptr;
+    }
+    if (!next.buses) {
+        return "a resampler is attached (mbx_session_next_resample) and no buses are";
+    }
+    if (next.form != MBX_MIXDOWN_PCM16) {
+        return "a resampler is attached (mbx_session_next_resample) and the buses are not MBX_MIXDOWN_PCM16";
+    }
+    const mbx_resample_state* const st = static_cast<const mbx_resample_state*>(next.resample_state);
+    if (mbx_mixdown_plan_buses(next.plan) > st->streams) {
+        return "the plan has more buses than the resampler's state (mbx_resample_state_streams)";
+    }
+    return st->device != s->device ? "a resampler's state of another device than the session" : nullptr;
+}
+
 // Behind the step of a submit of nf frames, on the compute stream: FIRST the slot's int16 rows levelled in place where an AGC is
 // attached (the records of the submit's streams: its index on the device, or 0 .. n-1); then those rows -> companded bytes where a
 // destination is attached; their level records, once per submit, for the caller or for the gate of its buses or both; the plan's buses of those rows
 // (one or two more launches) -- under an attached limiter their sums into the limiter's scratch and the limited rows from there, one
-// launch more; then the outputs out.
+// launch more; the buses resampled into the slot's wide buffer where a resampler is attached, one launch behind them; then the outputs out.
 int behind_step(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
     const NextOut& next = c.next;
     int16_t* const d16 = sl.dout<int16_t>(mbx::kOutPcm16);
@@ -404,6 +449,13 @@ int behind_step(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
         rc = mbx_mixdown_gated(next.plan, &next.gate, next.form, d16, nf, dlev, dmix, s->s_comp);
     } else if (next.buses) {
         rc = mbx_mixdown(next.plan, next.form, d16, nf, dmix, s->s_comp);
+    }
+    if (rc >= 0 && next.resample_state) {   // (resample_refused_text: there are buses, and they are int16)
+        const int buses = mbx_mixdown_plan_buses(next.plan);
+        if (buses > 0 && (rc = sl.wide.d.need(mbx::wide_bytes((size_t)buses, next.resample.L))) >= 0) {
+            rc = mbx_pcm_resample(&next.resample, static_cast<mbx_resample_state*>(next.resample_state), nullptr, buses, 1, reinterpret_cast<const int16_t*>(dmix),
+                                  reinterpret_cast<int16_t*>(sl.wide.d.p), s->s_comp);
+        }
     }
     return rc < 0 ? rc : copy_out(s, sl, c, nf);
 }
@@ -499,6 +551,9 @@ int submit(mbx_session* s, const Submit& c) {
         return refused("mbx_session_submit", why, c, (size_t)c.n * (size_t)c.T);
     }
     if (const char* const text = limit_refused_text(c.next)) {
+        return mbx::refuse("mbx_session_submit", text);
+    }
+    if (const char* const text = resample_refused_text(s, c.next)) {
         return mbx::refuse("mbx_session_submit", text);
     }
     int rc = 0;
@@ -640,6 +695,7 @@ int mbx_session_destroy(mbx_session* s) {
         for (Pair& b : sl.out) {
             b.d.release(), b.h.release();
         }
+        sl.wide.d.release(), sl.wide.h.release();
         (void)hipFree(sl.d_workspace);
         if (sl.comp) {
             (void)hipEventDestroy(sl.comp);
@@ -891,6 +947,23 @@ int mbx_session_next_limit(mbx_session* s, const mbx_limit* limit, mbx_limit_sta
     return next_attach("mbx_session_next_limit", s, state, &NextOut::limit_state, why, [&](NextOut& next) { next.limit_state = state, next.limit = *limit; });
 }
 
+// ---- wide rows (include/mbx_resample.h): the buses of the next submit resampled as well, the caller's state advanced by one frame ------
+int mbx_session_next_resample(mbx_session* s, const mbx_resample* rs, mbx_resample_state* state, int16_t* out) {
+    const auto why = [&]() -> const char* {
+        const mbx::ResampleRefusal bad = mbx::resample_refused(rs != nullptr, rs ? rs->L : 0u, rs ? rs->K : 0u, rs ? (unsigned)(rs->zero[0] | rs->zero[1]) : 0u,
+                                                               rs ? rs->taps : nullptr);
+        if (bad != mbx::kResampleOk) {
+            return mbx::resample_refusal_text(bad);
+        }
+        if (!out) {
+            return "no place for the wide buses";
+        }
+        return state->device != s->device ? "a state of another device than the session" : nullptr;
+    };
+    return next_attach("mbx_session_next_resample", s, state, &NextOut::resample_state, why,
+                       [&](NextOut& next) { next.resample_state = state, next.resample = *rs, next.wide = out; });
+}
+
 int mbx_session_next_levels(mbx_session* s, mbx_row_level* out) {
     const auto why = [&]() -> const char* { return s->outputs & MBX_SESSION_LEVELS ? nullptr : "the session was created without MBX_SESSION_LEVELS"; };
     return next_attach("mbx_session_next_levels", s, out, &NextOut::levels, why, [&](NextOut& next) { next.levels = out; });
@@ -1002,6 +1075,9 @@ int mbx_session_submit_burst_groups(mbx_session* s, const mbx_burst_group* group
         return mbx::refuse(who, "an AGC is attached (mbx_session_next_agc): burst groups take none");
     }
     if (const char* const text = limit_refused_text(c.next)) {   // (a limiter they may take: buses have no T)
+        return mbx::refuse(who, text);
+    }
+    if (const char* const text = resample_refused_text(s, c.next)) {   // (and a resampler, for the same reason)
         return mbx::refuse(who, text);
     }
     mbx::GroupShape shapes[MBX_BURST_MAX_GROUPS];

@@ -42,6 +42,9 @@ static inline size_t out_bytes(int which, size_t nf, size_t buses, int mix_form)
     }
     return nf * kOutFacts[which].row_bytes;
 }
+// the wide buses of a submit (mbx_session_next_resample, include/mbx_resample.h) are no entry of the table: their buffer belongs to the
+// slot's first resampled submit and is sized by that submit -- `buses` rows of 160 * L int16, on the device and in the pinned staging
+static inline size_t wide_bytes(size_t buses, unsigned L) { return buses * 160u * (size_t)L * sizeof(int16_t); }
 // the outputs a caller may name in a submit, as the session flags they need
 static inline unsigned requested_outputs(bool pcm16, bool pcmf, bool results) {
     return (pcm16 ? MBX_SESSION_PCM16 : 0u) | (pcmf ? MBX_SESSION_PCMF : 0u) | (results ? MBX_SESSION_RESULTS : 0u);

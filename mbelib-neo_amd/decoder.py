@@ -17,7 +17,10 @@ loudest inputs (include/mbx_levels.h); mixdown_held(pcm16, plan, state, hold, fo
 a state record per input kept on the device (include/mbx_hold.h); agc(pcm16, T, state, agc) -- the rows levelled by a per-stream
 automatic gain, a state record per stream kept on the device (include/mbx_agc.h); mixdown_sums / mixdown_gated_sums /
 mixdown_held_sums -- the buses as int32 sums in front of the clamp, and bus_limit(sums, T, state, limit, form) -- those sums under a
-look-ahead peak limiter, a state record per bus kept on the device (include/mbx_limit.h).
+look-ahead peak limiter, a state record per bus kept on the device (include/mbx_limit.h); resample(pcm16, T, state, rs) -- int16 rows
+upsampled to 16, 24, 32 or 48 kHz by a polyphase FIR interpolator with the caller's taps, a history record per row kept on the device
+(include/mbx_resample.h).  Sessions are not wrapped here: mbx_session_next_resample is called through _native.lib(), as every
+mbx_session_* call is.
 """
 import numpy as np
 
@@ -325,6 +328,31 @@ class BatchDecoder:
             rc = _native.lib().mbx_bus_limit(ctypes.addressof(limit), state.handle, rows // T, T, sums.data_ptr(), int(form), out.data_ptr(),
                                              torch.cuda.current_stream().cuda_stream)
         _native.check(rc, "mbx_bus_limit")
+        return out
+
+    def resample(self, pcm16, T, state, rs, stream_index=None, out=None):
+        """Wide rows (include/mbx_resample.h): mbx_pcm_resample on the current torch stream -- the int16 rows [n * T, 160] of a decode
+        or of a mix-down (a contiguous device tensor, stream-major) under `rs` (a resample.Resample) and `state` (a
+        resample.ResampleState) advanced by T frames -> int16 [n * T, 160 * L], the values resample.step gives on the host.
+        stream_index (int32 device tensor [n]): entry i uses record stream_index[i]; without it record i.  out: a contiguous int16
+        tensor of L times as many elements, apart from pcm16; None: a new tensor."""
+        import ctypes
+
+        torch = _torch()
+        rows, T, L = _pcm16_rows(pcm16), int(T), int(rs.L)
+        if T <= 0 or rows % T:
+            raise ValueError("pcm16 must hold n * T rows")
+        if stream_index is not None and (stream_index.dtype != torch.int32 or not stream_index.is_contiguous() or stream_index.numel() != rows // T
+                                         or stream_index.device != pcm16.device):
+            raise ValueError("stream_index must be a contiguous int32 tensor of one entry per stream on the device of pcm16")
+        if out is None:
+            out = torch.empty((rows, 160 * L), dtype=torch.int16, device=pcm16.device)
+        elif out.dtype != torch.int16 or not out.is_contiguous() or out.numel() != pcm16.numel() * L or out.device != pcm16.device:
+            raise ValueError("out must be a contiguous int16 tensor of L elements per sample on the device of pcm16")
+        with torch.cuda.device(pcm16.device):
+            rc = _native.lib().mbx_pcm_resample(ctypes.addressof(rs), state.handle, None if stream_index is None else stream_index.data_ptr(), rows // T, T,
+                                                pcm16.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_pcm_resample")
         return out
 
     def decode_soft(self, soft, T, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None, keystream=None):
