@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h,
-include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h, include/mbx_hold.h, include/mbx_agc.h, include/mbx_limit.h, include/mbx_resample.h).  Fails loudly when the library
+include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h, include/mbx_hold.h, include/mbx_agc.h, include/mbx_limit.h, include/mbx_resample.h, include/mbx_filter.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -254,6 +254,19 @@ _RESAMPLE_SIGNATURES = {
     "mbx_session_next_resample": (C.c_int, [_vp, _vp, _vp, _vp]),
 }
 RESAMPLE_SYMBOLS = tuple(_RESAMPLE_SIGNATURES)
+# filtered rows (include/mbx_filter.h): a per-stream biquad cascade over the int16 rows, a 32-byte state record per stream on the device
+_FILTER_SIGNATURES = {
+    "mbx_filter_state_create": (C.c_int, [_vp, C.c_int]),
+    "mbx_filter_state_destroy": (C.c_int, [_vp]),
+    "mbx_filter_state_streams": (C.c_int, [_vp]),
+    "mbx_filter_state_reset": (C.c_int, [_vp, C.c_int, C.c_int, _vp]),
+    "mbx_filter_state_get": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "mbx_filter_state_set": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    "mbx_pcm_filter": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp]),
+    "mbx_pcm_filter_host": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
+    "mbx_session_next_filter": (C.c_int, [_vp, _vp, _vp]),
+}
+FILTER_SYMBOLS = tuple(_FILTER_SIGNATURES)
 
 
 class BurstGroupStruct(C.Structure):
@@ -284,7 +297,7 @@ def lib():
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
         for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES, **_KEYSTREAM_SIGNATURES, **_PCM8_SIGNATURES,
                                    **_MIXDOWN_SIGNATURES, **_LEVELS_SIGNATURES, **_HOLD_SIGNATURES, **_AGC_SIGNATURES, **_LIMIT_SIGNATURES,
-                                   **_RESAMPLE_SIGNATURES}.items():
+                                   **_RESAMPLE_SIGNATURES, **_FILTER_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

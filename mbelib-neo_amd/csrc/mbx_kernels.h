@@ -1,6 +1,6 @@
 // mbx_kernels.h -- every __global__ kernel of libmbx_hip.so, declared exactly once.
-// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_resample.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
-// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip and mbx_resample.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
+// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_resample.hip, mbx_filter.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
+// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_resample.hip and mbx_filter.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
 // overload at the launch site or in the instance table), not an unresolved symbol when the library is loaded.
 // A new kernel: declare it here, define it, and -- a stream-stage instance -- give it its row in kInstances (mbx_api.hip).
 #pragma once
@@ -180,6 +180,13 @@ __global__ void bus_limit_kernel(LimitParams, uint32_t*, int, int, const int32_t
 struct ResampleTaps;
 template <int L>
 __global__ void pcm_resample_kernel(ResampleTaps, uint32_t*, int, const int32_t*, uint32_t, uint32_t, const int16_t*, int16_t*);
+
+// ---- mbx_filter.hip: filtered rows (include/mbx_filter.h) -- behind a step and in front of the AGC, its int16 rows through a cascade
+// of S second-order sections per stream: the coefficients by value (mbx_filter_plan.h), the state in place and its size, the record of
+// every entry (or nullptr), entries, frames per entry, rows in, rows out (which may be the rows in) --------------------------------------
+struct FilterParams;
+template <int S>
+__global__ void pcm_filter_kernel(FilterParams, uint32_t*, int, const int32_t*, int, int, const int16_t*, int16_t*);
 
 // ---- mbx_expand.hip ------------------------------------------------------------------------------------------------------------
 __global__ void expand_imbe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);

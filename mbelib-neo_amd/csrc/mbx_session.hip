@@ -33,6 +33,8 @@
 #include "mbx.h"
 #include <mbx_agc.h>       // (levelled rows: the public header)
 #include "mbx_agc_plan.h"      // (what an agc is refused for, and the device and the size of a state)
+#include <mbx_filter.h>    // (filtered rows: the public header)
+#include "mbx_filter_plan.h"   // (what a filter is refused for, and the device and the size of a state)
 #include <mbx_limit.h>     // (limited buses: the public header)
 #include "mbx_limit_plan.h"    // (what a limit is refused for, and the device, the size and the scratch of a state)
 #include <mbx_resample.h>  // (wide rows: the public header)
@@ -212,6 +214,10 @@ struct NextOut {
     // front of every other launch behind the step; nullptr: nothing attached
     void*                   agc_state = nullptr;
     mbx_agc                 agc = {0, 0, 0, 0, 0, 0, 0, 0};
+    // the slot's int16 rows filtered in place under `filter` with the caller's `filter_state` (mbx_session_next_filter,
+    // include/mbx_filter.h), in front of the AGC and so of every launch behind the step; nullptr: nothing attached
+    void*                   filter_state = nullptr;
+    mbx_filter              filter = {};
     // the buses limited under `limit` with the caller's `limit_state` (mbx_session_next_limit, include/mbx_limit.h): their sums into the
     // state's scratch, then the limiter into the slot's bus buffer in `form`; nullptr: nothing attached
     void*                   limit_state = nullptr;
@@ -224,8 +230,8 @@ struct NextOut {
     mbx_resample            resample = {};
     bool wants_levels() const { return levels || (buses && kind != kMixPlain); }
     // the step is handed the slot's int16 rows: for the caller, or for the compand, the levels and the mix-down behind the step; an
-    // attached AGC advances its state whether or not anybody takes the rows
-    bool wants_pcm16(const void* callers) const { return callers || dst || buses || levels || agc_state; }
+    // attached AGC or filter advances its state whether or not anybody takes the rows
+    bool wants_pcm16(const void* callers) const { return callers || dst || buses || levels || agc_state || filter_state; }
 };
 std::mutex g_next_mu;
 std::unordered_map<const mbx_session*, NextOut> g_next;
@@ -415,8 +421,8 @@ const char* resample_refused_text(const mbx_session* s, const NextOut& next) {
     return st->device != s->device ? "a resampler's state of another device than the session" : nullptr;
 }
 
-// Behind the step of a submit of nf frames, on the compute stream: FIRST the slot's int16 rows levelled in place where an AGC is
-// attached (the records of the submit's streams: its index on the device, or 0 .. n-1); then those rows -> companded bytes where a
+// Behind the step of a submit of nf frames, on the compute stream: FIRST the slot's int16 rows filtered in place where a filter is
+// attached, THEN levelled in place where an AGC is (the records of the submit's streams: its index on the device, or 0 .. n-1); then those rows -> companded bytes where a
 // destination is attached; their level records, once per submit, for the caller or for the gate of its buses or both; the plan's buses of those rows
 // (one or two more launches) -- under an attached limiter their sums into the limiter's scratch and the limited rows from there, one
 // launch more; the buses resampled into the slot's wide buffer where a resampler is attached, one launch behind them; then the outputs out.
@@ -426,8 +432,13 @@ int behind_step(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
     mbx_row_level* const dlev = sl.dout<mbx_row_level>(mbx::kOutLevels);
     uint8_t* const dmix = sl.dout<uint8_t>(mbx::kOutMix);
     int rc = 0;
+    const int32_t* const dindex = c.index ? sl.din<int32_t>(kInIndex) : nullptr;
+    if (next.filter_state
+        && (rc = mbx_pcm_filter(&next.filter, static_cast<mbx_filter_state*>(next.filter_state), dindex, c.n, c.T, d16, d16, s->s_comp)) < 0) {
+        return rc;
+    }
     if (next.agc_state
-        && (rc = mbx_pcm_agc(&next.agc, static_cast<mbx_agc_state*>(next.agc_state), c.index ? sl.din<int32_t>(kInIndex) : nullptr, c.n, c.T, d16, d16, s->s_comp)) < 0) {
+        && (rc = mbx_pcm_agc(&next.agc, static_cast<mbx_agc_state*>(next.agc_state), dindex, c.n, c.T, d16, d16, s->s_comp)) < 0) {
         return rc;
     }
     if ((next.dst && (rc = mbx_pcm_compand(next.law, d16, nf, sl.dout<uint8_t>(mbx::kOutPcm8), s->s_comp)) < 0)
@@ -934,6 +945,26 @@ int mbx_session_next_agc(mbx_session* s, const mbx_agc* agc, mbx_agc_state* stat
     return next_attach("mbx_session_next_agc", s, state, &NextOut::agc_state, why, [&](NextOut& next) { next.agc_state = state, next.agc = *agc; });
 }
 
+// ---- filtered rows (include/mbx_filter.h): the int16 rows of the next submit through a cascade, the caller's state advanced by its frames
+int mbx_session_next_filter(mbx_session* s, const mbx_filter* filter, mbx_filter_state* state) {
+    const auto why = [&]() -> const char* {
+        const mbx::FilterRefusal bad = mbx::filter_refused(filter != nullptr, filter ? filter->sections : 0u,
+                                                           filter ? (unsigned)(filter->zero[0] | filter->zero[1] | filter->zero[2]) : 0u,
+                                                           filter ? &filter->sec[0].b0 : nullptr);
+        if (bad != mbx::kFilterOk) {
+            return mbx::filter_refusal_text(bad);
+        }
+        if (!mbx::out_owned(mbx::kOutPcm16, s->outputs)) {
+            return "the session was created without an output that has int16 rows";
+        }
+        if (state->streams < s->streams) {
+            return "the state holds fewer records than the session has streams";
+        }
+        return state->device != s->device ? "a state of another device than the session" : nullptr;
+    };
+    return next_attach("mbx_session_next_filter", s, state, &NextOut::filter_state, why, [&](NextOut& next) { next.filter_state = state, next.filter = *filter; });
+}
+
 // ---- limited buses (include/mbx_limit.h): the buses of the next submit under a limiter, the caller's state advanced by one frame ------
 int mbx_session_next_limit(mbx_session* s, const mbx_limit* limit, mbx_limit_state* state) {
     const auto why = [&]() -> const char* {
@@ -1070,6 +1101,9 @@ int mbx_session_submit_burst_groups(mbx_session* s, const mbx_burst_group* group
     c.soft = soft_in != 0;
     if (!s) {
         return refused(who, mbx::kSessionNoSession, c, 0);
+    }
+    if (c.next.filter_state) {   // (the groups have different frame counts: one launch of mbx_pcm_filter has one T)
+        return mbx::refuse(who, "a filter is attached (mbx_session_next_filter): burst groups take none");
     }
     if (c.next.agc_state) {   // (the groups have different frame counts: one launch of mbx_pcm_agc has one T)
         return mbx::refuse(who, "an AGC is attached (mbx_session_next_agc): burst groups take none");

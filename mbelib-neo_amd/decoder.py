@@ -19,7 +19,8 @@ automatic gain, a state record per stream kept on the device (include/mbx_agc.h)
 mixdown_held_sums -- the buses as int32 sums in front of the clamp, and bus_limit(sums, T, state, limit, form) -- those sums under a
 look-ahead peak limiter, a state record per bus kept on the device (include/mbx_limit.h); resample(pcm16, T, state, rs) -- int16 rows
 upsampled to 16, 24, 32 or 48 kHz by a polyphase FIR interpolator with the caller's taps, a history record per row kept on the device
-(include/mbx_resample.h).  Sessions are not wrapped here: mbx_session_next_resample is called through _native.lib(), as every
+(include/mbx_resample.h); filter(pcm16, T, state, filt) -- int16 rows through a per-stream cascade of 1-4 biquads in front of the
+gain, a state record per stream kept on the device (include/mbx_filter.h).  Sessions are not wrapped here: mbx_session_next_resample is called through _native.lib(), as every
 mbx_session_* call is.
 """
 import numpy as np
@@ -353,6 +354,31 @@ class BatchDecoder:
             rc = _native.lib().mbx_pcm_resample(ctypes.addressof(rs), state.handle, None if stream_index is None else stream_index.data_ptr(), rows // T, T,
                                                 pcm16.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(rc, "mbx_pcm_resample")
+        return out
+
+    def filter(self, pcm16, T, state, filt, stream_index=None, out=None):
+        """Filtered rows (include/mbx_filter.h): mbx_pcm_filter on the current torch stream -- the int16 rows [n * T, 160] a decode
+        returned (a contiguous device tensor, stream-major) through the cascade `filt` (a filters.Filter) with `state` (a
+        filters.FilterState) advanced by T frames, the values filters.step gives on the host.  stream_index (int32 device tensor [n]):
+        entry i uses record stream_index[i]; without it record i.  out: a contiguous int16 tensor of as many elements, or pcm16 itself
+        (in place); None: a new tensor."""
+        import ctypes
+
+        torch = _torch()
+        rows, T = _pcm16_rows(pcm16), int(T)
+        if T <= 0 or rows % T:
+            raise ValueError("pcm16 must hold n * T rows")
+        if stream_index is not None and (stream_index.dtype != torch.int32 or not stream_index.is_contiguous() or stream_index.numel() != rows // T
+                                         or stream_index.device != pcm16.device):
+            raise ValueError("stream_index must be a contiguous int32 tensor of one entry per stream on the device of pcm16")
+        if out is None:
+            out = torch.empty(tuple(pcm16.shape), dtype=torch.int16, device=pcm16.device)
+        elif out.dtype != torch.int16 or not out.is_contiguous() or out.numel() != pcm16.numel() or out.device != pcm16.device:
+            raise ValueError("out must be a contiguous int16 tensor of one element per sample on the device of pcm16")
+        with torch.cuda.device(pcm16.device):
+            rc = _native.lib().mbx_pcm_filter(ctypes.addressof(filt), state.handle, None if stream_index is None else stream_index.data_ptr(), rows // T, T,
+                                              pcm16.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_pcm_filter")
         return out
 
     def decode_soft(self, soft, T, want_pcm16=True, want_float=False, want_results=True, out=None, stream_index=None, keystream=None):
