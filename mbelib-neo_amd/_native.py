@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h,
-include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h, include/mbx_hold.h, include/mbx_agc.h, include/mbx_limit.h, include/mbx_resample.h, include/mbx_filter.h).  Fails loudly when the library
+include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h, include/mbx_hold.h, include/mbx_agc.h, include/mbx_limit.h, include/mbx_resample.h, include/mbx_filter.h, include/mbx_bands.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -267,6 +267,16 @@ _FILTER_SIGNATURES = {
     "mbx_session_next_filter": (C.c_int, [_vp, _vp, _vp]),
 }
 FILTER_SYMBOLS = tuple(_FILTER_SIGNATURES)
+# band records (include/mbx_bands.h): the int16 rows against a caller's bank of probes, K small records per row; the bank on the device
+_BANDS_SIGNATURES = {
+    "mbx_band_bank_create": (C.c_int, [_vp, _vp, C.c_int]),
+    "mbx_band_bank_destroy": (C.c_int, [_vp]),
+    "mbx_band_bank_probes": (C.c_int, [_vp]),
+    "mbx_pcm_bands": (C.c_int, [_vp, C.c_int, _vp, _sz, _vp, _vp]),
+    "mbx_pcm_bands_host": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _sz, _vp]),
+    "mbx_session_next_bands": (C.c_int, [_vp, _vp, C.c_int, _vp]),
+}
+BANDS_SYMBOLS = tuple(_BANDS_SIGNATURES)
 
 
 class BurstGroupStruct(C.Structure):
@@ -297,7 +307,7 @@ def lib():
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
         for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES, **_KEYSTREAM_SIGNATURES, **_PCM8_SIGNATURES,
                                    **_MIXDOWN_SIGNATURES, **_LEVELS_SIGNATURES, **_HOLD_SIGNATURES, **_AGC_SIGNATURES, **_LIMIT_SIGNATURES,
-                                   **_RESAMPLE_SIGNATURES, **_FILTER_SIGNATURES}.items():
+                                   **_RESAMPLE_SIGNATURES, **_FILTER_SIGNATURES, **_BANDS_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

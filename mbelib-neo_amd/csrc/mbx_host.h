@@ -1,5 +1,5 @@
 // mbx_host.h -- what the host units of libmbx_hip.so (mbx_api.hip, mbx_session.hip, mbx_burst.hip, mbx_collective.hip, mbx_pcm8.hip,
-// mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip) share to refuse a call: the per-thread text behind mbx_last_error(), the "who: why"
+// mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_bands.hip) share to refuse a call: the per-thread text behind mbx_last_error(), the "who: why"
 // refusal, the failed-HIP-call text, the alignment refusal, the current device after mbx_init().  Host-only and private; the inlines
 // have internal linkage, nothing here is exported.  Only what at least two units use belongs here.
 #pragma once

@@ -1,6 +1,6 @@
 // mbx_kernels.h -- every __global__ kernel of libmbx_hip.so, declared exactly once.
-// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_resample.hip, mbx_filter.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
-// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_resample.hip and mbx_filter.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
+// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_resample.hip, mbx_filter.hip, mbx_bands.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
+// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_resample.hip, mbx_filter.hip and mbx_bands.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
 // overload at the launch site or in the instance table), not an unresolved symbol when the library is loaded.
 // A new kernel: declare it here, define it, and -- a stream-stage instance -- give it its row in kInstances (mbx_api.hip).
 #pragma once
@@ -187,6 +187,11 @@ __global__ void pcm_resample_kernel(ResampleTaps, uint32_t*, int, const int32_t*
 struct FilterParams;
 template <int S>
 __global__ void pcm_filter_kernel(FilterParams, uint32_t*, int, const int32_t*, int, int, const int16_t*, int16_t*);
+
+// ---- mbx_bands.hip: band records (include/mbx_bands.h) -- behind a step, its int16 rows against a bank of K probes: the bank on the
+// device (K x 160 dwords), K, rows in, their number, K records per row out, of the form kForm (mbx_bands_plan.h) -------------------------
+template <int kForm>
+__global__ void pcm_bands_kernel(const uint32_t*, int, const int16_t*, size_t, void*);
 
 // ---- mbx_expand.hip ------------------------------------------------------------------------------------------------------------
 __global__ void expand_imbe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);

@@ -39,6 +39,8 @@
 #include "mbx_limit_plan.h"    // (what a limit is refused for, and the device, the size and the scratch of a state)
 #include <mbx_resample.h>  // (wide rows: the public header)
 #include "mbx_resample_plan.h" // (what a resampler is refused for, and the device and the size of a state)
+#include <mbx_bands.h>     // (band records: the public header)
+#include "mbx_bands_plan.h"    // (the forms, and the device and the probes of a bank)
 #include "mbx_burst.h"
 #include "mbx_burst_groups.h"
 #include "mbx_codec.h"
@@ -118,7 +120,10 @@ struct Slot {
     // the buses of a submit resampled (mbx_session_next_resample, include/mbx_resample.h): made by the slot's first resampled submit,
     // and made anew by one that needs more, so a session that never sees one pays for neither the buffer nor its staging
     Pair       wide;
-    CopyOut    staged[mbx::kOutCount + 1];   // (the outputs of the table, and the wide buses)
+    // the band records of a submit (mbx_session_next_bands, include/mbx_bands.h): made by the slot's first submit with a bank, for
+    // max_frames_per_submit rows of that bank and form, and made anew by a bank that needs more
+    Pair       bands;
+    CopyOut    staged[mbx::kOutCount + 2];   // (the outputs of the table, the wide buses and the band records)
     int        nout = 0;
     template <class U> U* din(int which) { return reinterpret_cast<U*>(in[which].d.p); }
     template <class U> U* dout(int which) { return reinterpret_cast<U*>(out[which].d.p); }
@@ -228,10 +233,15 @@ struct NextOut {
     void*                   resample_state = nullptr;
     void*                   wide = nullptr;    // host memory, the plan's buses * 160 * L int16
     mbx_resample            resample = {};
+    // the records of the slot's int16 rows against `bank` in `band_form` (mbx_session_next_bands, include/mbx_bands.h): one launch
+    // beside the levels launch, into the slot's band buffer; nullptr: nothing attached
+    void*                   bands = nullptr;   // host memory, rows * K records
+    const mbx_band_bank*    bank = nullptr;
+    int                     band_form = 0;     // MBX_BANDS_*
     bool wants_levels() const { return levels || (buses && kind != kMixPlain); }
     // the step is handed the slot's int16 rows: for the caller, or for the compand, the levels and the mix-down behind the step; an
     // attached AGC or filter advances its state whether or not anybody takes the rows
-    bool wants_pcm16(const void* callers) const { return callers || dst || buses || levels || agc_state || filter_state; }
+    bool wants_pcm16(const void* callers) const { return callers || dst || buses || levels || agc_state || filter_state || bands; }
 };
 std::mutex g_next_mu;
 std::unordered_map<const mbx_session*, NextOut> g_next;
@@ -384,6 +394,21 @@ int copy_out(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
             return mbx::hip_failed("session: ", "hipMemcpyAsync (device to host)", e);
         }
     }
+    if (c.next.bands) {   // the band records, on the same road
+        const size_t bytes = mbx::band_bytes(nf, c.next.bank->K, c.next.band_form);
+        void* dst = c.next.bands;
+        if (!is_pinned(dst)) {
+            if (const int rc = sl.bands.h.need(mbx::band_bytes(s->max_frames, c.next.bank->K, c.next.band_form)); rc < 0) {
+                return rc;
+            }
+            dst = sl.bands.h.p;
+            sl.staged[sl.nout++] = CopyOut{c.next.bands, dst, bytes};
+        }
+        const hipError_t e = hipMemcpyAsync(dst, sl.bands.d.p, bytes, hipMemcpyDeviceToHost, s->s_out);
+        if (e != hipSuccess) {
+            return mbx::hip_failed("session: ", "hipMemcpyAsync (device to host)", e);
+        }
+    }
     S_TRY(hipEventRecord(sl.done, s->s_out));
     return 0;
 }
@@ -423,7 +448,8 @@ const char* resample_refused_text(const mbx_session* s, const NextOut& next) {
 
 // Behind the step of a submit of nf frames, on the compute stream: FIRST the slot's int16 rows filtered in place where a filter is
 // attached, THEN levelled in place where an AGC is (the records of the submit's streams: its index on the device, or 0 .. n-1); then those rows -> companded bytes where a
-// destination is attached; their level records, once per submit, for the caller or for the gate of its buses or both; the plan's buses of those rows
+// destination is attached; their level records, once per submit, for the caller or for the gate of its buses or both; beside them the band records of those
+// rows where a bank is attached, into the slot's band buffer; the plan's buses of those rows
 // (one or two more launches) -- under an attached limiter their sums into the limiter's scratch and the limited rows from there, one
 // launch more; the buses resampled into the slot's wide buffer where a resampler is attached, one launch behind them; then the outputs out.
 int behind_step(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
@@ -443,6 +469,11 @@ int behind_step(mbx_session* s, Slot& sl, const Submit& c, size_t nf) {
     }
     if ((next.dst && (rc = mbx_pcm_compand(next.law, d16, nf, sl.dout<uint8_t>(mbx::kOutPcm8), s->s_comp)) < 0)
         || (next.wants_levels() && (rc = mbx_pcm_levels(d16, nf, dlev, s->s_comp)) < 0)) {
+        return rc;
+    }
+    if (next.bands
+        && ((rc = sl.bands.d.need(mbx::band_bytes(s->max_frames, next.bank->K, next.band_form))) < 0
+            || (rc = mbx_pcm_bands(next.bank, next.band_form, d16, nf, sl.bands.d.p, s->s_comp)) < 0)) {
         return rc;
     }
     if (next.buses && next.limit_state) {
@@ -707,6 +738,7 @@ int mbx_session_destroy(mbx_session* s) {
             b.d.release(), b.h.release();
         }
         sl.wide.d.release(), sl.wide.h.release();
+        sl.bands.d.release(), sl.bands.h.release();
         (void)hipFree(sl.d_workspace);
         if (sl.comp) {
             (void)hipEventDestroy(sl.comp);
@@ -993,6 +1025,23 @@ int mbx_session_next_resample(mbx_session* s, const mbx_resample* rs, mbx_resamp
     };
     return next_attach("mbx_session_next_resample", s, state, &NextOut::resample_state, why,
                        [&](NextOut& next) { next.resample_state = state, next.resample = *rs, next.wide = out; });
+}
+
+// ---- band records (include/mbx_bands.h): the records of the next submit's int16 rows against a caller's bank ----------------------------
+int mbx_session_next_bands(mbx_session* s, const mbx_band_bank* b, int form, void* out) {
+    const auto why = [&]() -> const char* {
+        if (!b) {
+            return "no bank";
+        }
+        if (!mbx::bands_form_ok(form)) {
+            return mbx::bands_refusal_text(mbx::kBandsForm);
+        }
+        if (!mbx::out_owned(mbx::kOutPcm16, s->outputs)) {
+            return "the session was created without an output that has int16 rows";
+        }
+        return b->device != s->device ? "a bank of another device than the session" : nullptr;
+    };
+    return next_attach("mbx_session_next_bands", s, out, &NextOut::bands, why, [&](NextOut& next) { next.bands = out, next.bank = b, next.band_form = form; });
 }
 
 int mbx_session_next_levels(mbx_session* s, mbx_row_level* out) {

@@ -9,6 +9,7 @@
 #include <cstdint>
 
 #include <mbx.h>           // (the public headers: the session flags and the records the outputs are made of)
+#include <mbx_bands.h>
 #include <mbx_levels.h>
 #include <mbx_mixdown.h>
 #include <mbx_pcm8.h>
@@ -45,6 +46,10 @@ static inline size_t out_bytes(int which, size_t nf, size_t buses, int mix_form)
 // the wide buses of a submit (mbx_session_next_resample, include/mbx_resample.h) are no entry of the table: their buffer belongs to the
 // slot's first resampled submit and is sized by that submit -- `buses` rows of 160 * L int16, on the device and in the pinned staging
 static inline size_t wide_bytes(size_t buses, unsigned L) { return buses * 160u * (size_t)L * sizeof(int16_t); }
+// the band records of a submit (mbx_session_next_bands, include/mbx_bands.h) are no entry of the table either: their buffer belongs to
+// the slot's first submit with a bank, is sized by max_frames_per_submit rows of that bank and form -- band_bytes(max_frames, K, form),
+// on the device and in the pinned staging -- and is made anew when a later bank needs more; band_bytes(nf, K, form) of it go out
+static inline size_t band_bytes(size_t nf, int K, int form) { return nf * (size_t)K * (form == MBX_BANDS_COMPLEX ? sizeof(mbx_band_record) : sizeof(uint32_t)); }
 // the outputs a caller may name in a submit, as the session flags they need
 static inline unsigned requested_outputs(bool pcm16, bool pcmf, bool results) {
     return (pcm16 ? MBX_SESSION_PCM16 : 0u) | (pcmf ? MBX_SESSION_PCMF : 0u) | (results ? MBX_SESSION_RESULTS : 0u);

@@ -20,7 +20,8 @@ mixdown_held_sums -- the buses as int32 sums in front of the clamp, and bus_limi
 look-ahead peak limiter, a state record per bus kept on the device (include/mbx_limit.h); resample(pcm16, T, state, rs) -- int16 rows
 upsampled to 16, 24, 32 or 48 kHz by a polyphase FIR interpolator with the caller's taps, a history record per row kept on the device
 (include/mbx_resample.h); filter(pcm16, T, state, filt) -- int16 rows through a per-stream cascade of 1-4 biquads in front of the
-gain, a state record per stream kept on the device (include/mbx_filter.h).  Sessions are not wrapped here: mbx_session_next_resample is called through _native.lib(), as every
+gain, a state record per stream kept on the device (include/mbx_filter.h); bands(pcm16, bank, form) -- the rows against a caller's
+bank of probes (a Bank, below), K small records per row (include/mbx_bands.h).  Sessions are not wrapped here: mbx_session_next_resample is called through _native.lib(), as every
 mbx_session_* call is.
 """
 import numpy as np
@@ -62,6 +63,40 @@ def _torch():
     if not torch.cuda.is_available():
         raise _native.NativeLibraryError("no HIP device visible to torch; mbelib-neo_amd has no CPU fallback")
     return torch
+
+
+class Bank:
+    """A native bank of probes (mbx_band_bank_create, include/mbx_bands.h) on the current device: `probes` is int16 [K, 2, 160] as
+    bands.tone / bands.dtmf make them, K x { c[160], s[160] }.  Immutable; usable from several streams.  Owns the native handle."""
+
+    def __init__(self, probes):
+        import ctypes
+
+        self.handle = None
+        p = np.ascontiguousarray(probes)
+        if p.dtype != np.int16 or p.size % 320:
+            raise ValueError("probes are int16 [K, 2, 160]")
+        h = ctypes.c_void_p()
+        _native.check(_native.lib().mbx_band_bank_create(ctypes.byref(h), p.ctypes.data if p.size else None, p.size // 320), "mbx_band_bank_create")
+        self.handle = h
+        self.probes = _native.lib().mbx_band_bank_probes(h)
+
+    def close(self):
+        if self.handle is not None:
+            _native.lib().mbx_band_bank_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class BatchDecoder:
@@ -190,6 +225,25 @@ class BatchDecoder:
         with torch.cuda.device(pcm16.device):
             rc = _native.lib().mbx_pcm_levels(pcm16.data_ptr(), n, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
         _native.check(rc, "mbx_pcm_levels")
+        return out
+
+    def bands(self, pcm16, bank, form=0, out=None):
+        """Band records (include/mbx_bands.h): mbx_pcm_bands behind a decode on the current torch stream -- the int16 rows [n, 160] a
+        decode returned (a contiguous device tensor) against `bank` (a Bank) -> their records as uint8 [n, K * record_bytes], 8 bytes
+        per probe for form 0 (MBX_BANDS_COMPLEX) and 4 for form 1 (MBX_BANDS_POWER); ``.cpu().numpy().view(bands.out_dtype(form))``
+        gives the records bands.measure gives on the host.  out: a contiguous uint8 tensor of that size."""
+        torch = _torch()
+        n, form = _pcm16_rows(pcm16), int(form)
+        if form not in (0, 1):
+            raise ValueError("form is MBX_BANDS_COMPLEX (0) or MBX_BANDS_POWER (1)")
+        per_row = bank.probes * (8 if form == 0 else 4)
+        if out is None:
+            out = torch.empty((n, per_row), dtype=torch.uint8, device=pcm16.device)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != n * per_row or out.device != pcm16.device:
+            raise ValueError("out must be a contiguous uint8 tensor of K * record_bytes bytes per row on the device of pcm16")
+        with torch.cuda.device(pcm16.device):
+            rc = _native.lib().mbx_pcm_bands(bank.handle, form, pcm16.data_ptr(), n, out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        _native.check(rc, "mbx_pcm_bands")
         return out
 
     def _levels_for(self, pcm16, levels):
