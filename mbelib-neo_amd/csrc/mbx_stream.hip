@@ -102,7 +102,7 @@ namespace mbx { __device__ unsigned long long g_frame_stamps[16]; }
 #define MBX_PARK_N 8   // how many per-lane values wait in LDS across the unvoiced transform pair (synth_core)
 #endif
 #ifndef MBX_STREAM_WAVES_PER_SIMD
-#define MBX_STREAM_WAVES_PER_SIMD 7   // occupancy target of the IMBE stream kernel (caps VGPRs at 72; 4,624 B of LDS per wave)
+#define MBX_STREAM_WAVES_PER_SIMD 7   // occupancy target of the IMBE stream kernel (caps VGPRs at 72; 4,672 B of LDS per wave; the IMBE one-frame instances 4,928 B)
 #endif
 
 namespace mbx {
@@ -156,6 +156,19 @@ __device__ __forceinline__ uint32_t load_header(const mbe_parms* __restrict__ p,
     const int idx = (j < 3) ? j : ((j < 13) ? (O_GAMMA - H_GAMMA) + j : O_NOISESEED);
     static_assert(O_MUTETHR - O_GAMMA == H_MUTETHR - H_GAMMA, "fields 3..12 of the header are contiguous in mbe_parms");
     return reinterpret_cast<const uint32_t*>(p)[idx];
+}
+// The header of a VIEW (kNoSeed: the lean views of the IMBE one-frame instances, kLeanPrevView): noiseSeed sits 1 KB behind the other
+// thirteen fields, on a line of its own; the decode's view of prev_mp and the synthesiser's view of prev_mp_enhanced never read it,
+// so their gathers leave it out (lanes 13..15 repeat mutingThreshold: hdr_*(h, H_NOISESEED) of such a header is NOT the seed).
+template <bool kNoSeed>
+__device__ __forceinline__ uint32_t load_view_header(const mbe_parms* __restrict__ p, int lane) {
+    if constexpr (kNoSeed) {
+        const int j = lane & 15;
+        const int idx = (j < 3) ? j : (O_GAMMA - H_GAMMA) + (j < 13 ? j : H_MUTETHR);
+        return reinterpret_cast<const uint32_t*>(p)[idx];
+    } else {
+        return load_header(p, lane);
+    }
 }
 __device__ __forceinline__ int hdr_i(uint32_t h, int k) { return __builtin_amdgcn_readlane((int)h, k); }
 __device__ __forceinline__ float hdr_f(uint32_t h, int k) { return __int_as_float(__builtin_amdgcn_readlane((int)h, k)); }
@@ -350,11 +363,18 @@ __device__ __forceinline__ void store_parms(const Parms& r, mbe_parms* __restric
 //   * synthesis reads from prev_mp_enhanced only w0, L, Vl, Ml, PHIl, PSIl, the second half of
 //     previousUw and the two smoothing memories.
 // Unread fields stay zero and are optimised away: fewer registers, and ~40 % less state read traffic.
-template <bool kFlat = false>
+// kLog2Only (kLeanPrevView): the IMBE decode predicts from log2Ml alone; Ml is carried only by a repeat, which reloads the whole
+// struct from the slot anyway and takes Ml from there (pad_prediction_memory) -- 228 B per stream less.
+template <bool kFlat = false, bool kLog2Only = false>
 __device__ __forceinline__ void load_prev_arrays(Parms& r, const mbe_parms* __restrict__ p, int lane) {
     const float* f = reinterpret_cast<const float*>(p);
     const bool band = lane < MBX_BAND_SLOTS;
     r = Parms{};
+    if constexpr (kLog2Only) {
+        const float l2 = f[O_LOG2ML + lane];   // (lanes past the band slots read PHIl's first dwords, same struct, and drop them)
+        r.log2Ml = band ? l2 : 0.0f;
+        return;
+    }
     if constexpr (kFlat) {
         const float ml = f[O_ML + lane], l2 = f[O_LOG2ML + lane], ph = f[O_PHI + lane];
         r.Ml = band ? ml : 0.0f;
@@ -473,9 +493,14 @@ __device__ __forceinline__ void load_continuity(Parms& r, const mbe_parms* __res
 typedef float v2f __attribute__((ext_vector_type(2)));   // two samples per lane: v_pk_{mul,fma}_f32
 __device__ __forceinline__ v2f splat(float x) { return v2f{x, x}; }
 
-template <int kParkColsT>
+// kKeepColsT: further columns of the same kind behind the parked ones, for per-lane values that cross the WHOLE synthesiser
+// (park[kParkCols + k]; the IMBE one-frame instances keep log2Ml there, kLeanKeepLog2).  8 + 1 columns: 4,928 B per wave,
+// inside the four 1,280-B granules (5,120 B) that seven waves per SIMD leave a wave.
+template <int kParkColsT, int kKeepColsT = 0>
 struct WaveScratchT {
     static constexpr int kParkCols = kParkColsT;
+    static constexpr int kKeepCols = kKeepColsT;
+    static constexpr int kCols = kParkColsT + kKeepColsT;
     union {
         struct {                       // voiced bank, harmonic l: g (cos psi, sin psi) and d g (sin psi, cos psi),
             alignas(16) float4 coef_amp[64];     //   each as (prev, cur) pairs = the operands of the packed FMAs
@@ -495,7 +520,7 @@ struct WaveScratchT {
     };
     // per-lane values that only cross the unvoiced transform pair (see synth_core); none in the LDS-resident kernel
     // instances: they run at the occupancy LDS allows and have the registers to carry those values themselves
-    float park[kParkColsT > 0 ? kParkColsT : 1][kParkColsT > 0 ? 64 : 4];
+    float park[kCols > 0 ? kCols : 1][kCols > 0 ? 64 : 4];
 };
 using WaveScratch = WaveScratchT<MBX_PARK_N>;
 
@@ -780,6 +805,23 @@ __device__ __forceinline__ int rec_bit(const uint32_t w[3], int i) { return (int
 // Frame parameters from the expand stage (mbx_expand.hip): v[1..56] prediction residuals T_l,
 // v[57..58] voicing bits, v[59] w0, v[60] L, v[61] K (IMBE) / mean residual (AMBE), v[62] error
 // context word, v[63] frame class, v[0] AMBE gain increment.  AMBE rows: v[60] = 0.2046 / sqrt(w0), v[63] = class | L << 8.
+// The padding the decode applies to the previous frame's prediction memory (ref src/imbe/imbe7200x4400.c, log-magnitude prediction): harmonics
+// prev_L + 1 .. cur_L take harmonic prev_L's value, harmonic 0 takes harmonic 1's.  One helper for the decode and for a repeat that
+// takes Ml from the struct it reloads (kLeanPrevView): the same lanes, the same order.  prev_L: already clamped to 1..56.
+__device__ __forceinline__ void pad_prediction_memory(float& Ml, float& log2Ml, int prev_L, int cur_L, int lane) {
+    const float padM = lane_read(Ml, prev_L), padL = lane_read(log2Ml, prev_L);   // wave-uniform index: v_readlane, no LDS trip
+    if (lane > prev_L && lane <= cur_L) {
+        Ml = padM;
+        log2Ml = padL;
+    }
+    const float m1 = lane_read(Ml, 1), l1 = lane_read(log2Ml, 1);
+    if (lane == 0) {
+        Ml = m1;
+        log2Ml = l1;
+    }
+}
+__device__ __forceinline__ int clamp_prev_L(int L) { return L < 1 ? 1 : (L > 56 ? 56 : L); }
+
 __device__ int decode_imbe(const float* __restrict__ fp, Parms& cur, Parms& prev, const DerivedTables* Dg, int lane, float* tmp) {
     const int bad = uni(__float_as_int(fp[63]));
     if (bad != 0) {
@@ -802,19 +844,8 @@ __device__ int decode_imbe(const float* __restrict__ fp, Parms& cur, Parms& prev
     // log-magnitude prediction
     const float rho = (L <= 15) ? 0.4f : ((L <= 24) ? ((0.03f * (float)L) - 0.05f) : 0.7f);
     const int cur_L = L;   // 9..56
-    const int prev_L = prev.L < 1 ? 1 : (prev.L > 56 ? 56 : prev.L);
-    {
-        const float padM = lane_read(prev.Ml, prev_L), padL = lane_read(prev.log2Ml, prev_L);   // wave-uniform index: v_readlane, no LDS trip
-        if (lane > prev_L && lane <= cur_L) {
-            prev.Ml = padM;
-            prev.log2Ml = padL;
-        }
-        const float m1 = lane_read(prev.Ml, 1), l1 = lane_read(prev.log2Ml, 1);
-        if (lane == 0) {
-            prev.Ml = m1;
-            prev.log2Ml = l1;
-        }
-    }
+    const int prev_L = clamp_prev_L(prev.L);
+    pad_prediction_memory(prev.Ml, prev.log2Ml, prev_L, cur_L, lane);
     const ConstDerived D = (ConstDerived)Dg;   // scalar loads
     const float pos = D->l_ratio[uni(prev_L)][cur_L] * (float)lane;
     int lo = (int)pos;
@@ -1929,6 +1960,14 @@ __device__ __forceinline__ void load_rng(StreamRng& r, const mbx_stream_rng* p) 
     r.unv_override = p->unvoiced_seed_override;
 }
 
+// Silent rng store (kLeanSilentRng): the record changes only on a cold start, a pending seed or a comfort-noise frame; every other
+// frame would store the 20 bytes it loaded, a partial-line write per stream.  Compared as bits, wave-uniform: a scalar branch.
+__device__ __forceinline__ bool rng_same_bits(const StreamRng& a, const StreamRng& b) {
+    const unsigned long long d48 = a.cn_seed48 ^ b.cn_seed48;
+    const uint32_t d = ((uint32_t)d48 | (uint32_t)(d48 >> 32)) | (a.cn_seeded ^ b.cn_seeded) | (a.unv_state ^ b.unv_state)
+                       | (a.unv_override ^ b.unv_override);
+    return uni(d) == 0u;
+}
 __device__ __forceinline__ void store_rng(const StreamRng& r, mbx_stream_rng* p, int lane) {
     if (lane == 0) {
         p->cn_seed48 = r.cn_seed48;
@@ -2181,14 +2220,29 @@ struct ParkedLds {
 #ifndef MBX_FRONT_SPIN
 #define MBX_FRONT_SPIN 160   // polls, ~0.25 us apart (s_sleep 8 = 512 cycles), before a stream block gives up on its front block and
 #endif                       // expands its frame itself: ~40 us, four times a front block's life
-template <bool kPark, bool kFrame = false, bool kRes = false, bool kOne = false, int kFuse = 0, bool kLdsIn = false>
+// kLean (with kOne; EXPERIMENTS.md "Lean state I/O"): reads and stores of a one-frame wave that no output needs, one bit per piece,
+// 0 = the code every other instance runs.
+//   kLeanPrevView:  of prev_mp only log2Ml and the five header fields the decode reads are requested, of prev_mp_enhanced's header
+//                   the four the synthesiser reads (no noiseSeed line for either); a repeat takes Ml from the struct it reloads.
+//   kLeanKeepLog2:  log2Ml crosses the synthesiser in the wave's own LDS column (WaveScratchT, kKeepColsT) instead of being read back
+//                   from the snapshot in prev_mp's slot: no dependent memory round trip in the tail of a synthesised frame.
+//   kLeanSilentRng: the rng record is stored only when it differs from what the wave loaded (rng_same_bits).
+enum : int { kLeanPrevView = 1, kLeanKeepLog2 = 2, kLeanSilentRng = 4 };
+#ifndef MBX_LEAN_ONE
+#define MBX_LEAN_ONE (kLeanPrevView | kLeanKeepLog2 | kLeanSilentRng)   // what the IMBE one-frame instances are built with
+#endif
+template <int kLean>
+using ImbeScratchT = WaveScratchT<MBX_PARK_N, (kLean & kLeanKeepLog2) ? 1 : 0>;
+template <bool kPark, bool kFrame = false, bool kRes = false, bool kOne = false, int kFuse = 0, bool kLdsIn = false, int kLean = 0>
 __device__ __forceinline__ void
 imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, const FrameParams* __restrict__ params,
                  mbe_parms* __restrict__ state,
                  mbx_stream_rng* __restrict__ rngs, int16_t* __restrict__ pcm16, float* __restrict__ pcmf,
                  mbe_process_result* __restrict__ results, DeviceTables tabs_in, const uint8_t* frame_in = nullptr,
                  int fec_codec = 0, FrameShadow shadow = FrameShadow{}, FrontLink link = FrontLink{}, FrameSlice slice = FrameSlice{}) {
-    using ScratchT = WaveScratchT<kPark ? 0 : MBX_PARK_N>;
+    static_assert(kLean == 0 || (kOne && !kPark), "the lean pieces belong to the one-frame HBM-slot instances");
+    constexpr bool kLeanPrev = (kLean & kLeanPrevView) != 0, kKeepLog2 = (kLean & kLeanKeepLog2) != 0, kSilentRng = (kLean & kLeanSilentRng) != 0;
+    using ScratchT = std::conditional_t<kPark, WaveScratchT<0>, ImbeScratchT<kLean>>;
     ScratchT* scratch_ptr;
     static_assert(!kLdsIn || (kPark && kFuse == 0), "a ParkedLds is the LDS of an LDS-parked body");
     std::conditional_t<kPark, ParkedPrevOnly, ParkedState<false>>* park_ptr;
@@ -2241,6 +2295,7 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
     Parms enh_keep;   // kPark: the fields of prev_mp_enhanced that synthesis reads, carried from frame to frame in registers
     Parms cur;
     StreamRng rng;
+    StreamRng rng_loaded = {};   // kLeanSilentRng: the record as the wave found it
     // resident launches (DeviceTables::resident): prev_mp_enhanced elided while it equals cur_mp, prev_mp fetched lazily
     uint32_t* const res = (kPark && kRes) ? tabs_in.resident : nullptr;   // (kRes: own kernel instances, the others carry none of this)
     // kRes without kPark: the HBM-slot instance for resident launches of ONE frame per stream.  It reads of prev_mp only the
@@ -2329,17 +2384,17 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         constexpr bool kFlat = kFuse != 0;   // the fused and one-launch T = 1 instances: unconditional struct loads (see load_parms_arrays)
         const uint32_t h_cur = load_header(slot_cur, lane_in);
         if constexpr (!kRes) {
-            h_prev_first = load_header(slot_prev, lane_in);
-            h_enh_first = load_header(enh_src, lane_in);
+            h_prev_first = load_view_header<kLeanPrev>(slot_prev, lane_in);
+            h_enh_first = load_view_header<kLeanPrev>(enh_src, lane_in);
         }
         load_rng(rng, &rngs[slot]);
-        load_prev_arrays<kFlat>(prev_first, slot_prev, lane_in);
+        load_prev_arrays<kFlat, kLeanPrev>(prev_first, slot_prev, lane_in);
         load_parms_arrays<kFlat>(cur, slot_cur, lane_in);
         if constexpr (kRes) {
             asm volatile("" ::: "memory");   // (everything above is requested before the flag is looked at)
             if (!elided1) {   // (elided: both come from cur_mp's registers where the frame loop starts, see enh_view_of / prev_header_of)
-                h_prev_first = load_header(slot_prev, lane_in);
-                h_enh_first = load_header(slot_enh, lane_in);
+                h_prev_first = load_view_header<kLeanPrev>(slot_prev, lane_in);
+                h_enh_first = load_view_header<kLeanPrev>(slot_enh, lane_in);
                 load_enh_arrays<kFlat>(enh_first, slot_enh, lane_in);
             }
         } else {
@@ -2414,6 +2469,12 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         }
         set_parms_header(cur, h_cur);
         MBX_TS(1);   // cur_mp's scalars are there (first round trip)
+        if constexpr (kSilentRng) {   // what the record holds, in SGPRs to the end of the wave (requested with the headers: it is there)
+            rng_loaded.cn_seed48 = ((unsigned long long)uni((uint32_t)(rng.cn_seed48 >> 32)) << 32) | uni((uint32_t)rng.cn_seed48);
+            rng_loaded.cn_seeded = uni(rng.cn_seeded);
+            rng_loaded.unv_state = uni(rng.unv_state);
+            rng_loaded.unv_override = uni(rng.unv_override);
+        }
     } else {
         slot_prev = home_prev;
         slot_enh = home_enh;
@@ -2521,8 +2582,16 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
                         copy_parms<kOne>(slot_prev, home_prev, lane);
                         slot_fence<kPark>();
                     }
+                    const int decoded_L = cur.L;   // (the padding's upper end, should the decode have got that far)
                     load_parms<kOne>(cur, slot_prev, lane);
-                    cur.Ml = prev.Ml;
+                    if constexpr (kLeanPrev) {   // Ml of prev_mp was not requested at the start: it has just come with the whole struct, and
+                        if (bad == 0) {          // gets the padding a good decode gave the view (an invalid fundamental returns before it)
+                            float log2_unused = 0.0f;
+                            pad_prediction_memory(cur.Ml, log2_unused, clamp_prev_L(prev.L), decoded_L, lane);
+                        }
+                    } else {
+                        cur.Ml = prev.Ml;
+                    }
                     cur.log2Ml = prev.log2Ml;
                     cur.repeatCount++;
                 }
@@ -2535,6 +2604,10 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
         MBX_STAMP(4, false);
         if constexpr (kOne) { MBX_TS(3); }   // decoded, policy applied
         if (!MBX_ABL(tabs, 256)) store_parms<kOne>(cur, slot_prev, lane);
+        if constexpr (kKeepLog2) {   // the lane's own column, written and read by the same lane: no synchronisation (cf. synth_core's park)
+            scratch.park[ScratchT::kParkCols][lane] = cur.log2Ml;
+            asm volatile("" ::: "memory");   // (a real ds_read behind the synthesiser, not the register carried across it)
+        }
         prev_partial = false;
         // Register diet for the synthesiser: what the snapshot holds and the synthesiser does not change (log2Ml) or
         // replaces only at its end (previousUw, the noise overlap) is dropped here and read back from the snapshot
@@ -2553,7 +2626,23 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
             MBX_STAMP(6, false);
             if constexpr (kOne) { MBX_TS(12); }   // synthesised (soft clip)
         }
-        {
+        if constexpr (kKeepLog2) {   // log2Ml from the wave's LDS column; the slot is read only by a frame that was not synthesised
+            asm volatile("" ::: "memory");
+            if (lane < MBX_BAND_SLOTS) {
+                cur.log2Ml = scratch.park[ScratchT::kParkCols][lane];
+            }
+            if (!fresh) {   // silence / comfort noise (rare): previousUw and the noise overlap are unchanged, read back as before
+                slot_fence<kPark>();
+                const float* f = reinterpret_cast<const float*>(slot_prev);
+                asm volatile("" : "+s"(f));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    cur.uw[j] = slot_read<kPark>(f, O_UW + lane + 64 * j);
+                }
+                cur.ov[0] = slot_read<kPark>(f, O_OVERLAP + lane);
+                cur.ov[1] = (lane < 32) ? slot_read<kPark>(f, O_OVERLAP + 64 + lane) : 0.0f;
+            }
+        } else {
             slot_fence<kPark>();
             const float* f = reinterpret_cast<const float*>(slot_prev);
             if constexpr (!kPark) {
@@ -2616,7 +2705,9 @@ imbe_stream_body(int S, int Tn, const mbx_param_record* __restrict__ records, co
     }
 
     if (!MBX_ABL(tabs_in, 1024)) store_parms<kOne, kOne, kOne>(cur, slot_cur, lane_in, skip_cur);
-    store_rng(rng, &rngs[slot], lane_in);
+    if (!kSilentRng || !rng_same_bits(rng, rng_loaded)) {
+        store_rng(rng, &rngs[slot], lane_in);
+    }
     if constexpr (kPark) {   // prev_mp goes home from LDS; prev_mp_enhanced IS cur_mp after the last frame
         if (res) {
             if (Tn > 0 && lane_in == 0) {
@@ -2717,7 +2808,7 @@ __device__ __forceinline__ void imbe_one_launch_body(int S, int lead, const uint
             pos = 8 * G + (q - 9 * G);
         }
     }
-    constexpr size_t kFrontLds = 8 * 65 * 4 + 8 * 64 * 4 + 8 * 8 * 4, kStreamLds = sizeof(WaveScratchT<MBX_PARK_N>);
+    constexpr size_t kFrontLds = 8 * 65 * 4 + 8 * 64 * 4 + 8 * 8 * 4, kStreamLds = sizeof(ImbeScratchT<MBX_LEAN_ONE>);
     __shared__ alignas(16) char lds[kFrontLds > kStreamLds ? kFrontLds : kStreamLds];   // ONE block of LDS for either kind of workgroup
     if (chunk >= 0) {
 #ifdef MBX_TESTING   // libmbx_hip_testing.so only (mbx_testing_set_front_skip): this chunk's stream blocks will not find their rows
@@ -2734,7 +2825,7 @@ __device__ __forceinline__ void imbe_one_launch_body(int S, int lead, const uint
     link.flag = &flags[pos >> 3];
     link.epoch = epoch;
     link.pos = pos;
-    imbe_stream_body<false, false, kRes, true, 3>(S, 1, records, rows, state, rngs, pcm16, pcmf, results, tabs_in, frames, MBX_CODEC_IMBE7200X4400,
+    imbe_stream_body<false, false, kRes, true, 3, false, MBX_LEAN_ONE>(S, 1, records, rows, state, rngs, pcm16, pcmf, results, tabs_in, frames, MBX_CODEC_IMBE7200X4400,
                                                   FrameShadow{}, link);
 }
 
@@ -3946,13 +4037,16 @@ state_copy_kernel(int S, mbe_parms* __restrict__ state) {
 // (parameter lists: mbx_kernels.h; which instance a launch takes: mbx_api.hip, kInstances / select_instance).
 // One stream per 64-lane workgroup; the second number of the launch bounds is the instance's waves per SIMD.
 // ------------------------------------------------------------------------------------------
-// The body templates' arguments by name: imbe_stream_body<kPark, kFrame, kRes, kOne, kFuse>, ambe_stream_body<k2400, kPark, ...>
+// The body templates' arguments by name: imbe_stream_body<kPark, kFrame, kRes, kOne, kFuse, kLdsIn, kLean>, ambe_stream_body<k2400, kPark, ...>
 constexpr bool kAmbe2450 = false, kAmbe2400 = true;   // k2400: AMBE+2 3600x2450 | AMBE 3600x2400 (D-STAR)
 constexpr bool kSlots = false, kLds = true;           // kPark: prev_mp parked in its HBM slot every frame | in LDS for the whole launch
 constexpr bool kBatch = false;                        // kFrame (true: the single-frame kernels above)
 constexpr bool kPlain = false, kResident = true;      // kRes: DeviceTables::resident honoured (prev_mp_enhanced elided while it equals cur_mp)
 constexpr bool kOneFrame = true;                      // kOne: no frame loop, every request of the frame issued before the first wait
 constexpr int kFrontImbe = 1, kFront7100 = 2;         // kFuse: the front end in the stream's own wave (3, front blocks: the *_one_launch_body)
+constexpr int kNoFront = 0;
+constexpr bool kOwnLds = false;                       // kLdsIn (true: the mixed-codec kernels)
+constexpr int kLeanOne = MBX_LEAN_ONE;                // kLean: the IMBE one-frame instances, all of them
 #define MBX_OUT_ARGS state, rngs, pcm16, pcmf, results, tabs_in
 #define MBX_STREAM_KERNEL(name, waves, ...) \
     __global__ void __launch_bounds__(64, waves) name(MBX_STREAM_PARAMS) { __VA_ARGS__; }
@@ -3978,7 +4072,7 @@ MBX_STREAM_KERNEL(ambe2400_stream_kernel, MBX_AMBE2400_WAVES_PER_SIMD, ambe_stre
                                         // interpolated branch stopped holding n^2 across its loop: 65,536 x 1 AMBE+2 -1.7 %, resident -2.5 %
                                         // (profiles/r06/ab_ambe_seven_waves.log; round 5 forced seven with 44 B of scratch: +7.8 %)
 MBX_STREAM_KERNEL(imbe_stream_kernel_one, MBX_STREAM_WAVES_PER_SIMD,
-                  imbe_stream_body<kSlots, kBatch, kPlain, kOneFrame>(S, Tn > 1 ? 1 : Tn, records, params, MBX_OUT_ARGS))
+                  imbe_stream_body<kSlots, kBatch, kPlain, kOneFrame, kNoFront, kOwnLds, kLeanOne>(S, Tn > 1 ? 1 : Tn, records, params, MBX_OUT_ARGS))
 MBX_STREAM_KERNEL(ambe_stream_kernel_one, MBX_AMBE_ONE_WAVES_PER_SIMD,
                   ambe_stream_body<kAmbe2450, kSlots, kBatch, kPlain, kOneFrame>(S, Tn, records, params, MBX_OUT_ARGS))
 MBX_STREAM_KERNEL(ambe2400_stream_kernel_one, MBX_AMBE2400_WAVES_PER_SIMD,
@@ -4003,7 +4097,7 @@ MBX_STREAM_KERNEL(ambe2400_stream_kernel_res, MBX_AMBE_LDS_WAVES_PER_SIMD,
                   ambe_stream_body<kAmbe2400, kLds, kBatch, kResident>(S, Tn, records, params, MBX_OUT_ARGS))
 // one frame per stream on resident state: the HBM-slot bodies with the elision (IMBE: seven waves per SIMD, no LDS copy of prev_mp)
 MBX_STREAM_KERNEL(imbe_stream_kernel_res1, MBX_STREAM_WAVES_PER_SIMD,
-                  imbe_stream_body<kSlots, kBatch, kResident, kOneFrame>(S, Tn > 1 ? 1 : Tn, records, params, MBX_OUT_ARGS))
+                  imbe_stream_body<kSlots, kBatch, kResident, kOneFrame, kNoFront, kOwnLds, kLeanOne>(S, Tn > 1 ? 1 : Tn, records, params, MBX_OUT_ARGS))
 MBX_STREAM_KERNEL(ambe_stream_kernel_res1, MBX_AMBE_ONE_WAVES_PER_SIMD,
                   ambe_stream_body<kAmbe2450, kSlots, kBatch, kResident, kOneFrame>(S, Tn > 1 ? 1 : Tn, records, params, MBX_OUT_ARGS))
 MBX_STREAM_KERNEL(ambe2400_stream_kernel_res1, MBX_AMBE2400_WAVES_PER_SIMD,
@@ -4170,14 +4264,14 @@ mixed_row_codec_kernel(int S, int total, const int32_t* __restrict__ frame_offse
 // ---- fused family: the whole T = 1 step as ONE launch with the front end in the stream's own wave (kFuse) -- wire frames in,
 // PCM / results / records / state out.  fec_codec: MBX_CODEC_IMBE7200X4400 or MBX_CODEC_IMBE7100X4400. ----
 MBX_FUSED_KERNEL(imbe_stream_kernel_one_fused, MBX_STREAM_WAVES_PER_SIMD,
-                 imbe_stream_body<kSlots, kBatch, kPlain, kOneFrame, kFrontImbe>(S, 1, records, nullptr, MBX_OUT_ARGS, frames, fec_codec))
+                 imbe_stream_body<kSlots, kBatch, kPlain, kOneFrame, kFrontImbe, kOwnLds, kLeanOne>(S, 1, records, nullptr, MBX_OUT_ARGS, frames, fec_codec))
 MBX_FUSED_KERNEL(imbe_stream_kernel_res1_fused, MBX_STREAM_WAVES_PER_SIMD,
-                 imbe_stream_body<kSlots, kBatch, kResident, kOneFrame, kFrontImbe>(S, 1, records, nullptr, MBX_OUT_ARGS, frames, fec_codec))
+                 imbe_stream_body<kSlots, kBatch, kResident, kOneFrame, kFrontImbe, kOwnLds, kLeanOne>(S, 1, records, nullptr, MBX_OUT_ARGS, frames, fec_codec))
 // IMBE 7100x4400 frames: own front end (whole, then the expansion's requests), the same stream stage
 MBX_FUSED_KERNEL(imbe7100_stream_kernel_one_fused, MBX_STREAM_WAVES_PER_SIMD,
-                 imbe_stream_body<kSlots, kBatch, kPlain, kOneFrame, kFront7100>(S, 1, records, nullptr, MBX_OUT_ARGS, frames, fec_codec))
+                 imbe_stream_body<kSlots, kBatch, kPlain, kOneFrame, kFront7100, kOwnLds, kLeanOne>(S, 1, records, nullptr, MBX_OUT_ARGS, frames, fec_codec))
 MBX_FUSED_KERNEL(imbe7100_stream_kernel_res1_fused, MBX_STREAM_WAVES_PER_SIMD,
-                 imbe_stream_body<kSlots, kBatch, kResident, kOneFrame, kFront7100>(S, 1, records, nullptr, MBX_OUT_ARGS, frames, fec_codec))
+                 imbe_stream_body<kSlots, kBatch, kResident, kOneFrame, kFront7100, kOwnLds, kLeanOne>(S, 1, records, nullptr, MBX_OUT_ARGS, frames, fec_codec))
 
 // ---- one-launch family: front blocks and stream blocks in one grid (imbe_one_launch_body / ambe_one_launch_body<k2400, kRes>) ----
 #ifndef MBX_AMBE_ONE_RES_WAVES_PER_SIMD
