@@ -1,5 +1,5 @@
 """ctypes binding of the C-ABI HIP launcher (include/mbx.h, include/mbx_burst.h, include/mbx_llr.h,
-include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h, include/mbx_hold.h, include/mbx_agc.h, include/mbx_limit.h, include/mbx_resample.h, include/mbx_filter.h, include/mbx_bands.h).  Fails loudly when the library
+include/mbx_burst_groups.h, include/mbx_keystream.h, include/mbx_pcm8.h, include/mbx_mixdown.h, include/mbx_levels.h, include/mbx_hold.h, include/mbx_agc.h, include/mbx_limit.h, include/mbx_resample.h, include/mbx_filter.h, include/mbx_bands.h, include/mbx_vote.h).  Fails loudly when the library
 is missing or cannot be initialised: there is no Python/CPU stand-in."""
 import ctypes as C
 import os
@@ -277,6 +277,21 @@ _BANDS_SIGNATURES = {
     "mbx_session_next_bands": (C.c_int, [_vp, _vp, C.c_int, _vp]),
 }
 BANDS_SYMBOLS = tuple(_BANDS_SIGNATURES)
+# voted streams (include/mbx_vote.h): several receivers' copies of a frame picked on their records or combined on their cells; the grouping on the device
+_VOTE_SIGNATURES = {
+    "mbx_vote_plan_create": (C.c_int, [_vp, _vp, C.c_int]),
+    "mbx_vote_plan_destroy": (C.c_int, [_vp]),
+    "mbx_vote_plan_streams": (C.c_int, [_vp]),
+    "mbx_vote_plan_candidates": (C.c_int, [_vp]),
+    "mbx_vote_select": (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "mbx_vote_combine": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "mbx_vote_select_host": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "mbx_vote_combine_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
+    "mbx_vote_workspace_frames": (_sz, [_vp, C.c_int, C.c_int, C.c_int]),
+    "mbx_process_batch_voted": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mbx_process_batch_soft_voted": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+}
+VOTE_SYMBOLS = tuple(_VOTE_SIGNATURES)
 
 
 class BurstGroupStruct(C.Structure):
@@ -307,7 +322,7 @@ def lib():
             raise NativeLibraryError(f"cannot load {path}: {e}") from e
         for name, (res, args) in {**_SIGNATURES, **_BURST_SIGNATURES, **_LLR_SIGNATURES, **_GROUP_SIGNATURES, **_KEYSTREAM_SIGNATURES, **_PCM8_SIGNATURES,
                                    **_MIXDOWN_SIGNATURES, **_LEVELS_SIGNATURES, **_HOLD_SIGNATURES, **_AGC_SIGNATURES, **_LIMIT_SIGNATURES,
-                                   **_RESAMPLE_SIGNATURES, **_FILTER_SIGNATURES, **_BANDS_SIGNATURES}.items():
+                                   **_RESAMPLE_SIGNATURES, **_FILTER_SIGNATURES, **_BANDS_SIGNATURES, **_VOTE_SIGNATURES}.items():
             try:
                 fn = getattr(handle, name)
             except AttributeError as e:

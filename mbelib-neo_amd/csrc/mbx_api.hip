@@ -25,6 +25,8 @@
 #include "mbx_launch_plan.h"
 #include "mbx_llr.h"
 #include "mbx_llr_cell.h"
+#include "mbx_vote.h"
+#include "mbx_vote_plan.h"
 
 namespace {
 
@@ -1716,6 +1718,111 @@ int mbx_process_batch_ragged_keyed(int codec, const uint8_t* d_stream_codec, int
     return process_batch_ragged("mbx_process_batch_ragged_keyed", d_soft ? kSoft : kFrames, d_stream_codec != nullptr, d_stream_codec ? 0 : codec, S,
                                 d_stream_codec, d_frame_offset, total_frames, d_stream_index, d_soft ? static_cast<const void*>(d_soft) : d_frames,
                                 d_state_pool, d_resident, d_rng_pool, d_pcm16, d_pcmf, d_results, d_records, stream, d_keystream);
+}
+
+// ---- voted streams (include/mbx_vote.h): the vote launch of mbx_vote.hip between the front launch and the records step -----------------
+// One entry for the hard and the soft step: what plan_step says of a StepShape with `vote` set -- the frames the front launch runs
+// over, where in the stream's workspace the candidates' records (select) or the combined cells (combine) sit behind the rows, and the
+// stream stage of the records step of the same S x T -- issued as a linear chain on the caller's stream under c->mu.
+static StepShape voted_shape(const mbx_vote_plan* plan, int codec, int mode, bool soft, int T, bool resident, const void* d_cand) {
+    StepShape q;
+    q.codec = codec, q.S = plan->S, q.T = T;
+    q.kind = soft ? kSoft : kFrames;
+    q.resident = resident;
+    q.aligned = (reinterpret_cast<uintptr_t>(d_cand) & 3u) == 0;
+    q.own_workspace = true;
+    q.vote = mode == mbx::kVoteCombine ? mbx::kCombineVote : mbx::kSelectVote;
+    q.candidates = plan->C;
+    q.row_cells = mbx::kCodecs[codec].cells;
+    return q;
+}
+static int process_batch_voted(const char* who, const mbx_vote_plan* plan, int codec, int mode, bool soft, int T, const int32_t* d_stream_index,
+                               const void* d_cand, const uint8_t* d_present, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool,
+                               int16_t* d_pcm16, float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, mbx_vote_record* d_votes,
+                               void* stream) {
+    if (!plan || !d_cand || !d_state_pool || !d_rng_pool || !d_records) {
+        return mbx::refuse(who, "a plan, the candidates, the state pool, the RNG pool and a place for the voted records are needed");
+    }
+    const mbx::CodecShape* sh = mbx::codec_shape(codec);
+    if (!sh) {
+        return mbx::refuse(who, "codec is one of MBX_CODEC_*");
+    }
+    if (!mbx::vote_mode_ok(mode) || (mode == mbx::kVoteCombine && !soft)) {
+        return mbx::refuse(who, "mode is MBX_VOTE_SELECT or MBX_VOTE_COMBINE");
+    }
+    const mbx::VoteRefusal shape = mbx::vote_shape_refused(plan->C, T);
+    if (shape != mbx::kVoteOk) {
+        return mbx::refuse(who, mbx::vote_refusal_text(shape));
+    }
+    if (!aligned_to(d_votes, 8) || (soft && !aligned_to(d_cand, 16))) {
+        return mbx::misaligned(who, "mbx_vote.h");
+    }
+    if (!batch_pointers_aligned(d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, d_stream_index, d_resident, nullptr) ||
+        (!soft && !frames_aligned(d_cand, imbe_codec(codec)))) {
+        return misaligned(who);
+    }
+    REQUIRE_CTX(c);
+    if (plan->device != (int)(c - g_ctx)) {
+        return mbx::refuse(who, "a plan of another device than the current one");
+    }
+    if (T == 0) {
+        return 0;
+    }
+    const BatchCall b{codec, plan->S, T, d_records, d_state_pool, d_rng_pool, d_pcm16, d_pcmf, d_results, stream, d_stream_index, d_resident};
+    const StepShape q = voted_shape(plan, codec, mode, soft, T, d_resident != nullptr, d_cand);
+    const StepPlan vp = plan_of(c, q);   // (never one that holds outside capture only: see plan_step)
+    if (vp.form != mbx::kStagedStep) {
+        return MBE_STATUS_INVALID_ARGUMENT;
+    }
+    std::lock_guard<std::mutex> lock(c->mu);
+    StreamSlot& slot = c->slots[stream];
+    int rc = ensure_workspace(c, slot, vp.workspace_frames, stream);
+    if (rc < 0) {
+        return rc;
+    }
+    slot.exp_codec = -1;   // the rows of an earlier mbx_expand_records() are about to be replaced
+    const unsigned order = slot.launches++;
+    void* const behind = slot.workspace + vp.vote_offset;
+    if (vp.vote == mbx::kCombineVote) {
+        mbe_soft_bit* const cells = static_cast<mbe_soft_bit*>(behind);
+        rc = mbx::vote_combine_launch(plan, sh->cells, T, static_cast<const mbe_soft_bit*>(d_cand), d_present, cells, d_votes, stream);
+        if (rc >= 0) {
+            rc = launch_soft_fec(c, codec, true, cells, vp.front_frames, d_records, stream);
+        }
+    } else {
+        mbx_param_record* const cand_records = static_cast<mbx_param_record*>(behind);
+        rc = soft ? launch_soft_fec(c, codec, true, static_cast<const mbe_soft_bit*>(d_cand), vp.front_frames, cand_records, stream)
+                  : launch_fec(c, codec, static_cast<const uint8_t*>(d_cand), vp.front_frames, cand_records, stream);
+        if (rc >= 0) {
+            rc = mbx::vote_select_launch(plan, T, cand_records, d_present, d_records, d_votes, stream);
+        }
+    }
+    if (rc < 0) {
+        return rc;
+    }
+    StepPlan rest = vp;   // behind the vote: the records step's expand launch and stream kernel
+    rest.front = mbx::kNoFront;
+    return run_stages(c, order, b, q, rest, d_records, slot.workspace, nullptr);
+}
+
+size_t mbx_vote_workspace_frames(const mbx_vote_plan* plan, int codec, int mode, int T) {
+    if (!plan || !mbx::codec_shape(codec) || !mbx::vote_mode_ok(mode) || T < 0) {
+        return 0;
+    }
+    return plan_of(nullptr, voted_shape(plan, codec, mode, true, T, false, nullptr)).workspace_frames;
+}
+
+int mbx_process_batch_voted(const mbx_vote_plan* plan, int codec, int T, const int32_t* d_stream_index, const uint8_t* d_cand_frames,
+                            const uint8_t* d_present, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16,
+                            float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, mbx_vote_record* d_votes, void* stream) {
+    return process_batch_voted("mbx_process_batch_voted", plan, codec, MBX_VOTE_SELECT, false, T, d_stream_index, d_cand_frames, d_present, d_state_pool,
+                               d_resident, d_rng_pool, d_pcm16, d_pcmf, d_results, d_records, d_votes, stream);
+}
+int mbx_process_batch_soft_voted(const mbx_vote_plan* plan, int codec, int mode, int T, const int32_t* d_stream_index, const mbe_soft_bit* d_cand_soft,
+                                 const uint8_t* d_present, mbe_parms* d_state_pool, uint32_t* d_resident, mbx_stream_rng* d_rng_pool, int16_t* d_pcm16,
+                                 float* d_pcmf, mbe_process_result* d_results, mbx_param_record* d_records, mbx_vote_record* d_votes, void* stream) {
+    return process_batch_voted("mbx_process_batch_soft_voted", plan, codec, mode, true, T, d_stream_index, d_cand_soft, d_present, d_state_pool, d_resident,
+                               d_rng_pool, d_pcm16, d_pcmf, d_results, d_records, d_votes, stream);
 }
 
 int mbx_synthesize_speech(int S, mbe_parms* d_cur, mbe_parms* d_prev, mbx_stream_rng* d_rng, float* d_pcmf,

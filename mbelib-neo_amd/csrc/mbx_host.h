@@ -1,5 +1,5 @@
 // mbx_host.h -- what the host units of libmbx_hip.so (mbx_api.hip, mbx_session.hip, mbx_burst.hip, mbx_collective.hip, mbx_pcm8.hip,
-// mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_bands.hip) share to refuse a call: the per-thread text behind mbx_last_error(), the "who: why"
+// mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_bands.hip, mbx_vote.hip) share to refuse a call: the per-thread text behind mbx_last_error(), the "who: why"
 // refusal, the failed-HIP-call text, the alignment refusal, the current device after mbx_init().  Host-only and private; the inlines
 // have internal linkage, nothing here is exported.  Only what at least two units use belongs here.
 #pragma once
@@ -14,10 +14,19 @@
 void mbx_set_error_text(const char* text);   // mbx_api.hip: sets the calling thread's mbx_last_error()
 
 struct mbx_mixdown_plan;
+struct mbx_vote_plan;
+struct mbx_vote_record;
 
 namespace mbx {
 
 int mixdown_plan_device(const mbx_mixdown_plan* plan);   // mbx_mixdown.hip: the device a plan's tables are on (-1: no plan)
+
+// mbx_vote.hip: the two launches of include/mbx_vote.h, for its own entry points and for the voted steps of mbx_api.hip (the caller has
+// made the refusals, T > 0, and has the plan's device current)
+int vote_select_launch(const mbx_vote_plan* plan, int T, const mbx_param_record* d_cand, const uint8_t* d_present, mbx_param_record* d_records,
+                       mbx_vote_record* d_votes, void* stream);
+int vote_combine_launch(const mbx_vote_plan* plan, int row_cells, int T, const mbe_soft_bit* d_cand, const uint8_t* d_present, mbe_soft_bit* d_soft,
+                        mbx_vote_record* d_votes, void* stream);
 
 static inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1u)) == 0; }
 

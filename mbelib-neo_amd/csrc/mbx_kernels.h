@@ -1,12 +1,13 @@
 // mbx_kernels.h -- every __global__ kernel of libmbx_hip.so, declared exactly once.
-// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_resample.hip, mbx_filter.hip, mbx_bands.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
-// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_resample.hip, mbx_filter.hip and mbx_bands.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
+// Included by the translation unit that defines a kernel (mbx_fec.hip, mbx_soft_front.hip, mbx_keystream.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_resample.hip, mbx_filter.hip, mbx_bands.hip, mbx_vote.hip, mbx_expand.hip, mbx_stream.hip, mbx_burst.hip, mbx_api.hip) and by the
+// one that launches it (mbx_api.hip; mbx_burst.hip, mbx_pcm8.hip, mbx_mixdown.hip, mbx_levels.hip, mbx_hold.hip, mbx_agc.hip, mbx_limit.hip, mbx_resample.hip, mbx_filter.hip, mbx_bands.hip and mbx_vote.hip launch their own), so a parameter list that drifts from its definition is a compile error (an unmatched
 // overload at the launch site or in the instance table), not an unresolved symbol when the library is loaded.
 // A new kernel: declare it here, define it, and -- a stream-stage instance -- give it its row in kInstances (mbx_api.hip).
 #pragma once
 #include "mbx_device.h"
 
 struct mbx_row_level;   // include/mbx_levels.h
+struct mbx_vote_record; // include/mbx_vote.h
 
 // The four argument families of the stream-stage instances, written once: the declarations below, the definitions
 // (mbx_stream.hip, MBX_*_KERNEL) and the launcher's function pointer types (mbx_api.hip, Instance) all take them from here.
@@ -192,6 +193,12 @@ __global__ void pcm_filter_kernel(FilterParams, uint32_t*, int, const int32_t*, 
 // device (K x 160 dwords), K, rows in, their number, K records per row out, of the form kForm (mbx_bands_plan.h) -------------------------
 template <int kForm>
 __global__ void pcm_bands_kernel(const uint32_t*, int, const int16_t*, size_t, void*);
+
+// ---- mbx_vote.hip: voted streams (include/mbx_vote.h) -- between the front and the stream stage, the candidates of every voted frame
+// picked on their records or combined on their cells: the plan's offsets, T, (pieces of a row,) the C x T candidates, their present
+// bytes or nullptr, the S x T voted array, the vote records or nullptr, the voted frames (combine: the pieces) of the launch -------------
+__global__ void vote_select_kernel(const int32_t*, int, const mbx_param_record*, const uint8_t*, mbx_param_record*, ::mbx_vote_record*, size_t);
+__global__ void vote_combine_kernel(const int32_t*, int, int, const mbe_soft_bit*, const uint8_t*, mbe_soft_bit*, ::mbx_vote_record*, size_t);
 
 // ---- mbx_expand.hip ------------------------------------------------------------------------------------------------------------
 __global__ void expand_imbe_kernel(const mbx_param_record*, size_t, FrameParams*, DeviceTables);

@@ -91,6 +91,10 @@ struct DeviceFacts {
 //   kSoft: soft cells, a soft front launch (one wave per frame) in front.  Codec 2 records come out in 7200x4400 order; codec 3 frames
 //   take the AMBE front end and are expanded by the 3600x2400 rules.
 enum InputKind { kRecords, kFrames, kSoft };
+//   A VOTED step (include/mbx_vote.h): `kind` is the form of the CANDIDATES, `candidates` rows of T of them for the S voted streams.
+//   kSelectVote: the front launch over candidates * T frames, the select launch, the stream stage of S * T records;  kCombineVote
+//   (kSoft only): the combine launch, the soft front over S * T frames, the stream stage.
+enum VoteKind { kNoVote, kSelectVote, kCombineVote };
 struct StepShape {
     int       codec = 0, S = 0, T = 0;   // T: unused by a ragged step; codec: unused by a mixed one
     size_t    total = 0;                 // rows of a ragged step
@@ -103,6 +107,9 @@ struct StepShape {
     bool      slices_allowed = false;    // the launch may be issued slice by slice on the slot's side streams
     bool      capturing = false;         // the stream is being captured into a graph
     bool      keyed = false;             // a keystream row per frame is XORed onto the record by the front launch (mbx_keystream.hip)
+    VoteKind  vote = kNoVote;            // a voted step, with ...
+    int       candidates = 0;            // ... this many candidate rows (C) and ...
+    int       row_cells = 0;             // ... soft candidates of this many cells a frame
 };
 
 // ---- ... and everything the launcher then does without asking again -----------------------------------------------------------------
@@ -130,6 +137,9 @@ struct StepPlan {
     size_t      order_offset = 0;       // ... the order words of a ragged step (S of them) and ...
     size_t      codec_offset = 0;       // ... the codec bytes of a mixed one (one per row) behind the rows, at these rows
     bool        outside_capture_only = false;   // needs the slot's flag words or side streams: ask whether the stream is being captured, plan again if so
+    VoteKind    vote = kNoVote;         // a voted step: the vote launch behind (select) or in front of (combine) the front launch, which runs over ...
+    size_t      front_frames = 0;       // ... so many frames, and ...
+    size_t      vote_offset = 0;        // ... the candidates' records (select) or the combined cells (combine) behind the rows, at this row
 };
 
 constexpr int kSmallBatchFrames = 256;
@@ -181,6 +191,29 @@ static inline StepPlan plan_step(const StepShape& q, const LaunchSwitches& sw, c
     StepPlan p;
     p.front = q.kind == kFrames ? kFecFront : (q.kind == kSoft ? kSoftFront : kNoFront);
     p.front_lead = sw.front_lead;
+
+    if (q.vote != kNoVote) {
+        // A voted step: behind the vote its stream stage is that of the RECORDS step of the same S x T -- the expand launch where
+        // that has one, its instance -- on the caller's stream alone: never sliced (side streams and events), never a one-launch
+        // form (those start from the wire frames of the streams themselves), so it can be captured as it is.  What the vote hands on
+        // sits behind the rows of the stream stage in the same workspace: candidates * T records of 16 bytes, or S * T rows of cells.
+        StepShape r = q;
+        r.vote = kNoVote;
+        r.kind = kRecords;
+        r.slices_allowed = false;
+        r.ragged = r.mixed = r.keyed = false;   // (no such voted steps)
+        StepPlan v = plan_step(r, sw, dev);
+        const bool combine = q.vote == kCombineVote;
+        const size_t st = (size_t)q.S * (size_t)q.T, ct = (size_t)q.candidates * (size_t)q.T;
+        const size_t bytes = combine ? st * (size_t)q.row_cells * 2u : ct * 16u;
+        v.form = (v.form == kNoLaunch || (combine && q.kind != kSoft) || q.kind == kRecords) ? kNoLaunch : kStagedStep;
+        v.front = p.front;
+        v.vote = q.vote;
+        v.front_frames = combine ? st : ct;
+        v.vote_offset = v.workspace_frames;
+        v.workspace_frames += dev.row_bytes ? (bytes + dev.row_bytes - 1) / dev.row_bytes : 0;
+        return v;
+    }
     const bool known = sh || q.mixed;   // (a mixed step brings its codecs: q.codec is not looked at)
 
     if (q.ragged || q.mixed) {
